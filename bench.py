@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- trust-region steps/sec (fp64) of the dog-leg hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR]
 
 A "step" is one full trial step of the hot path on an operating point whose x
 and Jacobian values are already resident in HBM: K1 (Jt*x, |x|^2) -> K3 (Cauchy)
@@ -50,6 +50,31 @@ WORKLOADS = {
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 MFMA_F64_PEAK_TFLOPS = 78.6    # public datasheet; a register-only v_mfma_f64_16x16x4_f64 loop sustains 72 - 78 here (profiles/r04_probe.txt)
+DUMP_LIMIT_BYTES = 64 << 20
+
+# --dump-outputs: the last timed step's results, read back from the device after the timed region.  From slot 1 (the trial
+# point the step went to): p_new (what the caller receives on the host) and the step; from slot 0 (the point the step was
+# taken from): Jt*x, the Cauchy and the Gauss-Newton steps it was formed from.  `scalars` holds the step's scalars as
+# dlg_run_steps returns them, in the order of SCALAR_NAMES.
+DUMP_VECTORS = [("p_new", 1, "VEC_P"), ("step", 1, "VEC_STEP"), ("jtx", 0, "VEC_JTX"),
+                ("cauchy", 0, "VEC_CAUCHY"), ("gauss_newton", 0, "VEC_GN")]
+SCALAR_NAMES = ["norm2_x", "norm2_cauchy", "norm2_gn", "k_cauchy_to_gn", "norm2_step", "expected_improvement",
+                "absmax_jtx", "absmax_step", "lambda"]
+
+
+def dump_outputs(out_dir, be, res):
+    """write DUMP_VECTORS and the scalars `res` of the last timed step as out_dir/<name>.npy (float64); returns the names"""
+    import numpy as np
+    from libdogleg_amd import capi
+    arrays = {name: be.download(slot, getattr(capi, which)) for name, slot, which in DUMP_VECTORS}
+    arrays["scalars"] = np.array(res, dtype=np.float64)
+    assert arrays["scalars"].shape == (len(SCALAR_NAMES),)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 def main():
@@ -66,7 +91,11 @@ def main():
     ap.add_argument("--logical-ranks", type=int, default=1)
     ap.add_argument("--rank", type=int, default=0)
     ap.add_argument("--lambda0", type=float, default=None, help="lambda of every step (logical ranks: 1.0, the partial top of the tree must stay positive definite)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -238,6 +267,7 @@ def main():
     res = run_steps(args.steps) or res
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, be, res) if (args.dump_outputs and rank == 0) else None
     prof_k4 = be.profile()
     be.set_profiling(True)
     run_steps(args.steps)
@@ -463,6 +493,8 @@ def main():
                            "bytes_panel_buffer": 8 * part["panel_doubles"]} if part else None),
             "check": {"norm2_x": res[0], "norm2_step": res[4], "expected_improvement": res[5], "lambda": res[8]},
         }
+        if dumped:
+            out["outputs_dumped"] = {"dir": os.path.abspath(args.dump_outputs), "names": dumped, "scalars": SCALAR_NAMES}
 
     # ---- CPU baseline: the oracle's restatement of the same step, host cores, bounded sample
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not logical:

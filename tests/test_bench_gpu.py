@@ -40,3 +40,33 @@ def test_bench_line_keeps_its_contract(gpu, workload, dtype_bound):
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_the_last_timed_step_computed(gpu, tmp_path):
+    """--dump-outputs: the last timed step's vectors and scalars as float64 .npy files; --steps sets the timed steps and the
+    inputs are fixed, so two runs of different lengths dump the same numbers"""
+    import numpy as np
+    runs = []
+    for steps in (3, 7):
+        d = _run(["--workload", "sparse-tiny", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline",
+                  "--dump-outputs", str(tmp_path / str(steps))])
+        assert d["steps"] == steps and abs(d["value"] * d["ms_per_step"] - 1e3) <= 1e-6 * 1e3
+        names = d["outputs_dumped"]["names"]
+        assert set(names) == {"p_new", "step", "jtx", "cauchy", "gauss_newton", "scalars"}
+        a = {n: np.load(tmp_path / str(steps) / (n + ".npy")) for n in names}
+        assert sum(v.nbytes for v in a.values()) <= 64 << 20
+        N = d["config"]["Nstate"]
+        for n in names:
+            assert a[n].dtype == np.float64 and np.all(np.isfinite(a[n])), n
+            assert a[n].shape == ((len(d["outputs_dumped"]["scalars"]),) if n == "scalars" else (N,)), n
+        s = dict(zip(d["outputs_dumped"]["scalars"], a["scalars"]))
+        assert s["norm2_step"] == d["check"]["norm2_step"] and s["norm2_x"] == d["check"]["norm2_x"]
+        assert abs(s["norm2_step"] - a["step"] @ a["step"]) <= 1e-9 * s["norm2_step"]
+        assert abs(s["norm2_cauchy"] - a["cauchy"] @ a["cauchy"]) <= 1e-9 * s["norm2_cauchy"]
+        assert abs(s["norm2_gn"] - a["gauss_newton"] @ a["gauss_newton"]) <= 1e-9 * s["norm2_gn"]
+        assert abs(s["absmax_step"] - np.max(np.abs(a["step"]))) <= 1e-12 * s["absmax_step"]
+        assert abs(s["absmax_jtx"] - np.max(np.abs(a["jtx"]))) <= 1e-12 * s["absmax_jtx"]
+        runs.append(a)
+    for n in runs[0]:
+        assert np.max(np.abs(runs[0][n] - runs[1][n])) <= 1e-10 * np.max(np.abs(runs[0][n])), n
