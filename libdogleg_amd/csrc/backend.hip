@@ -673,10 +673,11 @@ static void invalidate(DlgSlot& S)
 // kappa^2 |J g|^2, K3's own scalar.  The Gauss-Newton step b solves (JtJ + lambda I) b = -g, so
 // |J b|^2 = b' JtJ b = -<g, b> - lambda |b|^2 and <J a, J b> = a' JtJ b = -<a, g> - lambda <a, b> = -kappa |g|^2 - lambda <a, b>;
 // the interpolated step is (1 - k) a + k b (dogleg.c:964-987).  The error of the last two against the pass over J is b' r
-// with r the residual of the solve, i.e. eps * cond(JtJ + lambda I) relative to <g, b>: the caller uses them only where the
-// (damped) factor's pivot ratio says cond is small (k_part_take_step) -- the value agrees with
-// computeExpectedImprovement (dogleg.c:1085-1165) to rounding there.  (lambda > 0: -<g, b> and lambda |b|^2 may cancel in
-// |J b|^2 alone, but not in the expected improvement, which carries -2 <g, step> beside it.)
+// with r the residual of the solve, i.e. eps * cond(JtJ + lambda I) along b relative to <g, b> -- first order in the
+// factor's backward error, where computeExpectedImprovement's pass over J (dogleg.c:1085-1165) has a second-order one.  The
+// caller uses them only where the step kernel's estimate of that error is small (k_part_take_step, dlg_backend::
+// IDENT_ERR_MAX): the value is then within about 2e-12 (relative) of the exact one.  (lambda > 0: -<g, b> and
+// lambda |b|^2 may cancel in |J b|^2 alone, but not in the expected improvement, which carries -2 <g, step> beside it.)
 static double ident_norm2_Jstep(int kind, double k, double trustregion, double g2, double Jg2, double n2c, double g_dot_gn,
                                 double lambda, double n2g, double a_dot_gn)
 {
@@ -1633,7 +1634,7 @@ extern "C" int dlg_take_step(dlg_backend_t* b, int from, int to, double trustreg
                                   b->d_scal, b->d_scal + 8, F.Jt_x, b->d_scal + 11,
                                   ident_try ? b->d_scal + dlg_backend::GB_SLOT : (double*)nullptr,
                                   ident_try ? b->d_scal + dlg_backend::IDENT_SLOT : (double*)nullptr,
-                                  ident_mm != nullptr, true, dlg_backend::IDENT_RATIO_MAX);
+                                  ident_mm != nullptr, true, dlg_backend::IDENT_RATIO_MAX, F.norm2_jtx, dlg_backend::IDENT_ERR_MAX);
       b->fold_scal_k7 = 0; b->attach_stop = nullptr;
       DLG_CHECK(rc7);
     }
@@ -1789,7 +1790,7 @@ extern "C" int dlg_take_step(dlg_backend_t* b, int from, int to, double trustreg
   b->pivot_ratio = b->ident_launched ? b->h_scal[dlg_backend::IDENT_SLOT + 1] : NAN;
   // (a retry from the cached vectors of this point, dlg_step, takes the same route: <Jt x, gn> and the factor's verdict)
   F.g_dot_gn = b->h_scal[dlg_backend::GB_SLOT];
-  F.ident_ok = b->ident_launched && ident_mm != nullptr && b->h_scal[dlg_backend::IDENT_SLOT + 1] <= dlg_backend::IDENT_RATIO_MAX;
+  F.ident_ok = b->ident_launched && ident_mm != nullptr && b->h_scal[dlg_backend::IDENT_SLOT] == 1.0;      // (the factor's verdict, not the Cauchy step's)
   F.ident_lam = lam; F.a_dot_gn = F.norm2_cauchy - b->h_scal[dlg_backend::IDENT_SLOT + 4];
   return DLG_OK;
 }

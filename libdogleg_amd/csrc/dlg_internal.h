@@ -106,11 +106,20 @@ struct dlg_backend
   bool kout_host = false;     // (dlg_step behind the decision point: k_interpolate's k straight into the page-locked scalars)
   // The expected improvement WITHOUT its pass over J (K8): with (JtJ + lambda I) gn = -Jt_x solved, |J step|^2 of all three
   // kinds of step is a combination of N-vector dot products (ident_norm2_Jstep).  The step kernel decides on the device
-  // (the factor's pivot ratio small enough -- d_scal[IDENT_SLOT] = 1, [IDENT_SLOT + 1] = the ratio, [IDENT_SLOT + 4] = <cauchy - gn, cauchy>) and the
-  // pass over J that is on the stream behind it returns at once (k8_skip); the host reads the same word and forms the value.
-  // DOGLEG_AMD_EI_JPASS=1: always the pass over J.
+  // (d_scal[IDENT_SLOT] = 1: the factor allows it, 2: the step is the Cauchy step, which needs no factor, 0: neither;
+  // [IDENT_SLOT + 1] = the pivot ratio, [IDENT_SLOT + 4] = <cauchy - gn, cauchy>) and the pass over J that is on the stream
+  // behind it returns at once (k8_skip); the host reads the same word and forms the value, and a retry from the cached
+  // vectors (dlg_step) takes the word's 1 along (DlgSlot::ident_ok).  DOGLEG_AMD_EI_JPASS=1: always the pass over J.
+  // The factor allows it where its pivot ratio is at most IDENT_RATIO_MAX AND the estimate of the value's relative error,
+  // eps (max L_ii)^2 |gn|^2 / -<Jt x, gn>, is at most IDENT_ERR_MAX.  The error is gn' r with r the residual of the solve:
+  // eps times cond(JtJ + lambda I) along gn, first order in the backward error of the factor, where the pass over J has
+  // a second-order one.  The pivot ratio bounds cond only from below (a factor with unit pivots can have cond 1e14), so it
+  // does not bound the error by itself; the estimate came out at no less than about half the measured error on fixtures
+  // built to defeat the ratio (tests/exact_ei.py) and at 1e-15 and below on the bundle-adjustment shapes.  With
+  // IDENT_ERR_MAX = 1e-12 the value from the solved system is within about 2e-12 of the exact one.
   static constexpr int IDENT_SLOT = 3, GB_SLOT = 13;     // free slots of dlg_take_step's scalar block
-  static constexpr double IDENT_RATIO_MAX = 212.0;       // (max L_ii / min L_ii)^2 * 2.2e-16 <= 1e-11
+  static constexpr double IDENT_RATIO_MAX = 212.0;
+  static constexpr double IDENT_ERR_MAX = 1e-12;
   bool ident_launched = false, ident_predict = false; const double* k8_skip = nullptr;      // ident_predict: the last step's pass over J was let go by the device
   bool ei_from_system = false; double pivot_ratio = NAN;   // dlg_backend_ei_source: how the last value handed out was formed
   int ei_flip = 0, ei_count = 0;                           // DOGLEG_AMD_DEBUG_EI_FLIP (test hook)
@@ -139,7 +148,7 @@ struct dlg_backend
   // reduction partials
   double* d_part = nullptr;
   size_t  part_cap = 0;       // in doubles
-  double* d_gnpart = nullptr; // [1024] partials of |gn|^2 kept on the device (dlg_take_step)
+  double* d_gnpart = nullptr; // [4096]: [0, 1024) partials of |gn|^2 kept on the device (dlg_take_step), [2048, 4096) the pivots' partial minima / maxima
   // Reductions whose result only the host reads skip their one-workgroup second stage: the
   // partials are written straight into page-locked host memory and summed (in index order) by
   // dlg_resolve_pending() after the synchronisation that the host needs anyway.  Off when an
@@ -312,7 +321,8 @@ int k_negate_interp1(dlg_backend* b, double* gn, const double* cauchy, int n, do
 int k_take_step(dlg_backend* b, const double* cauchy, const double* gn, const double* gnpart, int nbg,
                 const double* n2c_dev, double trustregion, const double* p, double* step, double* p_new, int n,
                 double* out_n2_max, double* out3, const double* Jtx, double* out_inner,
-                double* out_gb = nullptr, double* ident_out = nullptr, bool have_mm = false, bool ident_gn = false, double ratio_max = 0.0);
+                double* out_gb = nullptr, double* ident_out = nullptr, bool have_mm = false, bool ident_gn = false, double ratio_max = 0.0,
+                double g2 = 0.0, double err_max = 0.0);
 // generic deterministic final reduction of `np` partials (sum) into out[0]
 int k_reduce_sum(dlg_backend* b, const double* partials, int np, double* out);
 // region of b->h_part for (nsum + nmax) x nb partials whose results go to h_scal[out - d_scal + k*stride],

@@ -8,6 +8,7 @@
 // Reference loops replaced: norm2 (dogleg.c:190-196), inner (197-203),
 // vec_copy_scaled (221-226), vec_add (228-233), vec_negate (241-245), the
 // interpolation loops (964-987), the threshold scans (1073-1078, 1289-1291).
+#include <cfloat>
 #include "dlg_internal.h"
 
 namespace {
@@ -255,22 +256,26 @@ __global__ void __launch_bounds__(TPB) k_part_take_step(const double* __restrict
                                                         double* __restrict__ gpart,
                                                         const double* __restrict__ dsc, double* __restrict__ hsc, int nsc,
                                                         double* __restrict__ gbpart, const double* __restrict__ mmpart, int nbm,
-                                                        int ident_enable, double ratio_max, double* __restrict__ ident_out)
+                                                        int ident_enable, double ratio_max, double g2, double err_max,
+                                                        double* __restrict__ ident_out)
 {
   __shared__ double sh[16];
   __shared__ double s_l2, s_negc, s_n2g, s_skip, s_ratio;
   __shared__ double s_gn[MAXB];
-  // The expected improvement from the solved system (K8 without its pass over J, backend.hip: ident_value): allowed by
-  // the host (lambda == 0, one rank) and by the factor itself -- the ratio of its largest to its smallest pivot, from
-  // the pairs the backward solve left per supernode (mmpart: their partial minima / maxima, k_part_negate_interp1).
-  // ident_out[0] = 1: the pass over J that follows on the stream returns at once (k_norm2_Jv: skipf); [1] = the ratio.
-  double ratio = 0.0;
+  // The expected improvement from the solved system (K8 without its pass over J, backend.hip: ident_norm2_Jstep): allowed
+  // by the host (one rank) and by the factor itself, from the pairs of pivots the backward solve left per supernode
+  // (mmpart: their partial minima / maxima, k_part_negate_interp1): the ratio of its largest to its smallest pivot, and
+  // the estimate of the value's relative error below (dlg_backend::IDENT_ERR_MAX).
+  // ident_out[0] != 0: the pass over J that follows on the stream returns at once (k_norm2_Jv: skipf) -- 1: the factor
+  // allows the value from the solved system for any kind of step, 2: the step is the Cauchy step, which needs no factor;
+  // [1] = the ratio.
+  double ratio = 0.0, piv_hi = 0.0;
   if(ident_out && blockIdx.x == 0)
   {
     double lo = 1e300, hi = 0.0;
     for(int i = threadIdx.x; i < nbm; i += TPB) { lo = fmin(lo, mmpart[i]); hi = fmax(hi, mmpart[nbm + i]); }
     { double r2[2] = { lo, hi }; block_reduce<2, 1>(r2, sh); lo = r2[0]; hi = r2[1]; }
-    if(threadIdx.x == 0) { ratio = (nbm > 0 && lo > 0.0) ? hi/lo : INFINITY; s_ratio = ratio; }
+    if(threadIdx.x == 0) { ratio = (nbm > 0 && lo > 0.0) ? hi/lo : INFINITY; s_ratio = ratio; piv_hi = hi; }
     __syncthreads();
   }
   {
@@ -327,8 +332,19 @@ __global__ void __launch_bounds__(TPB) k_part_take_step(const double* __restrict
     out3[0] = (double)kind; out3[1] = (kind == 2) ? k : NAN; out3[2] = n2g;
     if(ident_out)
     {
+      // The value from the solved system is off by gn' r, r the residual of the solve: relative to -<Jt x, gn> =
+      // gn' (JtJ + lambda I) gn, about eps |L|^2 |gn|^2 / -<Jt x, gn> -- eps times cond(JtJ + lambda I) along gn, which
+      // the pivot ratio alone does not bound (unit pivots and cond 1e14 go together).  (max L_ii)^2 stands in for |L|^2.
+      // -<Jt x, gn> = <cauchy, gn> / |kappa| with cauchy = kappa Jt x, kappa^2 = |cauchy|^2 / |Jt x|^2 (dogleg.c:605),
+      // and <cauchy, gn> = |cauchy|^2 - <cauchy - gn, cauchy>: no sum over the workgroups' partials of <Jt x, gn>.
+      bool allowed = false;
+      if(ident_enable && ratio <= ratio_max && g2 > 0.0 && n2c > 0.0)
+      {
+        const double minus_g_gn = (n2c - s_negc)*sqrt(g2/n2c);
+        allowed = minus_g_gn > 0.0 && DBL_EPSILON*piv_hi*piv_hi*n2g <= err_max*minus_g_gn;
+      }
       // (the Cauchy step to the edge needs no factor: its |J step|^2 is a multiple of K3's own scalar)
-      const double skip = (kind == 0 || (ident_enable && ratio <= ratio_max)) ? 1.0 : 0.0;
+      const double skip = allowed ? 1.0 : (kind == 0 ? 2.0 : 0.0);
       ident_out[0] = skip; ident_out[1] = ratio; s_skip = skip;
       ident_out[4] = s_negc;                                     // <cauchy - gn, cauchy>: with lambda > 0 the identity needs <cauchy, gn>
     }
@@ -586,12 +602,13 @@ int k_negate_interp1(dlg_backend* b, double* gn, const double* cauchy, int n, do
   return DLG_OK;
 }
 // after k_negate_interp1: the step (kind chosen on the device) and <Jtx, step> -> out_inner
-// out_gb: <Jt x, gn>; ident_out (two device scalars inside d_scal, or null): {the pass over J may be skipped, pivot ratio},
-// ident_gn: the Gauss-Newton system was solved at lambda = 0 (its identity holds), ratio_max: the largest pivot ratio trusted
+// out_gb: <Jt x, gn>; ident_out (device scalars inside d_scal, or null): {the pass over J may be skipped, pivot ratio, ...},
+// ident_gn: the value from the solved system may be used at all, ratio_max: the largest pivot ratio trusted, g2: |Jt x|^2,
+// err_max: the largest estimated relative error of the value from the solved system trusted (k_part_take_step)
 int k_take_step(dlg_backend* b, const double* cauchy, const double* gn, const double* gnpart, int nbg,
                 const double* n2c_dev, double trustregion, const double* p, double* step, double* p_new, int n,
                 double* out_n2_max, double* out3, const double* Jtx, double* out_inner,
-                double* out_gb, double* ident_out, bool have_mm, bool ident_gn, double ratio_max)
+                double* out_gb, double* ident_out, bool have_mm, bool ident_gn, double ratio_max, double g2, double err_max)
 {
   const int g = grid_for(n);
   // d_part: [0, 2g) pass-1 partials (k_negate_interp1), [2g, 4g) |step|^2 and max|step|, and the
@@ -610,7 +627,7 @@ int k_take_step(dlg_backend* b, const double* cauchy, const double* gn, const do
   DLG_LAUNCH_LAST(b, k_part_take_step, dim3(g), dim3(TPB), 0, b->stream, cauchy, gn, (const double*)b->d_part, g, gnpart, nbg,
                   n2c_dev, trustregion, p, step, p_new, n, hp ? hp : part2, out3, Jtx, gp,
                   fold ? (const double*)b->d_scal : (const double*)nullptr, b->h_scal, fold ? b->fold_scal_k7 : 0,
-                  hb, have_mm ? gnpart + 2*MAXB : (const double*)nullptr, have_mm ? nbg : 0, ident_gn ? 1 : 0, ratio_max, ident_out);
+                  hb, have_mm ? gnpart + 2*MAXB : (const double*)nullptr, have_mm ? nbg : 0, ident_gn ? 1 : 0, ratio_max, g2, err_max, ident_out);
   b->ident_launched = ident_out != nullptr;
   if(fold) b->scal_copied = true;
   if(!hp) hipLaunchKernelGGL(k_final, dim3(1), dim3(TPB), 0, b->stream, part2, g, 1, 1, out_n2_max, 2);
