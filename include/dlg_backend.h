@@ -324,6 +324,24 @@ int  dlg_solve_multi(dlg_backend_t* b, int slot, const double* rhs_host, double*
  * the reference (dogleg.c:1831-1921), built on the blocked solve */
 int  dlg_pseudoinverse_chunk(dlg_backend_t* b, int slot, int row0, int row1, double* out_host);
 
+/* ---- leverage blocks for the outlier API (dogleg.h: dogleg_getOutliernessFactors and friends; reference
+ * dogleg.c:2294-2660).  A feature f is featureSize (1 or 2) consecutive measurement rows from row f*featureSize;
+ * its leverage block is A_f = J_f (JtJ + lambda I)^-1 J_f^T with the factor held for `slot` and the slot's x and J on
+ * the device.  Only the forward solve is needed (A_f = V_f^T V_f, V_f = L^-1 P J_f^T); the sparse path visits, for
+ * every 16 measurement rows, only the supernodes their columns reach.  Bitwise reproducible.  A slot whose factor
+ * is not the one held is refused (DLG_ERR_STATE): factorise it first.  Not on a sharded / partitioned backend.
+ * dlg_feature_leverage: the packed upper blocks of features f0 .. f0 + nf - 1 ({a} / {a00, a01, a11} each). */
+int  dlg_feature_leverage(dlg_backend_t* b, int slot, int featureSize, int f0, int nf, double* A_host);
+/* the outlierness factors of features 0 .. nf - 1 with the given scale: featureSize 1, x_f^2 / (1 - a) * scale / 8;
+ * featureSize 2, x_f^T (B + B^2) x_f * scale / 8 with B = (A_f - I)^-1; DBL_MAX where |1 - a| or |det(A_f - I)| < 1e-8 */
+int  dlg_outlierness_factors(dlg_backend_t* b, int slot, int featureSize, int nf, double scale, double* factors_host);
+/* A = Jq (JtJ + lambda I)^-1 Jq^T (packed upper) for a feature that is not part of J: Jq featureSize x nstate,
+ * row-major, on the states istate .. istate + nstate - 1 */
+int  dlg_leverage_query(dlg_backend_t* b, int slot, const double* Jq, int istate, int nstate, int featureSize, double* A_host);
+/* sparse: of the plan of the last leverage call with this featureSize, the chunks of 16 rows, the supernode visits of
+ * all of them (the sum of the reaches) and the supernodes of the pattern */
+int  dlg_leverage_stats(dlg_backend_t* b, int featureSize, long* nchunks, long* visits, int* nsn);
+
 /* ---- downloads (returnContext, tests) -------------------------------------- */
 int  dlg_point_download(dlg_backend_t* b, int slot, int which, double* host, size_t n);
 /* dense factor in the reference's layout (packed as dpptrf('L') leaves it, or

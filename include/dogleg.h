@@ -307,6 +307,47 @@ void dogleg_testGradient_dense_products(unsigned int var, const double* p0,
                                         unsigned int Nstate, unsigned int Nmeas,
                                         dogleg_callback_dense_products_t* f, void* cookie);
 
+/* ---- outliers (reference dogleg.h:331-392; experimental there, and the prototypes are kept as they are).  Every entry
+ * point needs x and J of `point`, factorises JtJ + lambda I there (dogleg_computeJtJfactorization) if that is not held,
+ * and reads the leverage blocks A_f = J_f (JtJ + lambda I)^-1 J_f^T of the features from the device (dlg_backend.h:
+ * dlg_feature_leverage).  A feature is featureSize consecutive measurements starting at i*featureSize; featureSize <= 1
+ * means 1, sizes above 2 are refused.  Not available with DENSE_PRODUCTS (no Jacobian).
+ *
+ * Outlierness factors: one per feature, scaled by *scale, which is computed when *scale <= 0 (and written back):
+ * Nn = Nmeasurements - NoutlierFeatures*featureSize, scale = Nn / (4 (Nstate+1) |x|^2 / (Nn - Nstate - 1)).
+ * Size 1: x^2 / (1 - a) * scale/8; size 2: x^T (B + B^2) x * scale/8 with B = (A_f - I)^-1; DBL_MAX where the
+ * denominator (1 - a, det(A_f - I)) is below 1e-8 in magnitude. */
+bool dogleg_getOutliernessFactors(double* factors, double* scale, int featureSize, int Nfeatures,
+                                  int NoutlierFeatures, dogleg_operatingPoint_t* point,
+                                  dogleg_solverContext_t* ctx);
+
+/* one flag per feature */
+struct dogleg_outliers_t
+{
+  unsigned char marked : 1;
+};
+/* Marks new outliers: a feature not yet marked whose factor is >= 1 is marked when leaving it out costs less than 5 % of
+ * the confidence, 1 - getConfidence(i)/getConfidence(-1) < 0.05.  *Noutliers: the marked features before (it is the
+ * NoutlierFeatures of the factors) and after the call.  Returns whether any feature was newly marked; false also when
+ * the factors or getConfidence(-1) fail (*Noutliers unchanged) or a getConfidence(i) is negative (the count so far). */
+bool dogleg_markOutliers(struct dogleg_outliers_t* markedOutliers, double* scale, int* Noutliers,
+                         double (getConfidence)(int i_feature_exclude), int featureSize, int Nfeatures,
+                         dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx);
+
+/* debug report on stderr: a header, then per feature its factor and the relative drop of the confidence without it
+ * (getConfidence is called Nfeatures + 1 times) */
+void dogleg_reportOutliers(double (getConfidence)(int i_feature_exclude), double* scale, int featureSize,
+                           int Nfeatures, int Noutliers, dogleg_operatingPoint_t* point,
+                           dogleg_solverContext_t* ctx);
+
+/* the outlierness of a query feature that is not part of J (featureSize 2 only): Jq is 2 x NstateActive, row-major, on
+ * the states istateActive ..; A = Jq (JtJ + lambda I)^-1 Jq^T; returns scale (2 - tr (I + A)^-1), the scale recomputed
+ * with NoutlierFeatures, or -1.0 on failure */
+double dogleg_getOutliernessTrace_newFeature_sparse(const double* JqueryFeature, int istateActive,
+                                                    int NstateActive, int featureSize, int NoutlierFeatures,
+                                                    dogleg_operatingPoint_t* point,
+                                                    dogleg_solverContext_t* ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ BACKEND_SYMBOLS = [
     "dlg_step_tail_pending", "dlg_backend_ei_source", "dlg_backend_set_between", "dlg_backend_between_redone", "dlg_point_eval_early",
     "dlg_backend_share_rccl", "dlg_point_gather_device", "dlg_backend_reset", "dlg_backend_device",
     "dlg_sparse_pattern_matches", "dlg_sparse_drop_pattern", "dlg_sparse_region_probe", "dlg_run_steps", "dlg_backend_time_allreduce",
+    "dlg_feature_leverage", "dlg_outlierness_factors", "dlg_leverage_query", "dlg_leverage_stats",
 ]
 PROF_NAMES = ["K1_jtx", "K3K8_norm2Jv", "K4_kernel", "K4_total", "K5_factor", "K6_solve", "K7_step", "vec"]
 DOGLEG_SYMBOLS = [
@@ -54,6 +55,8 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_set_communicator", "dogleg_amd_set_allreduce", "dogleg_amd_clear_communicator",
     "dogleg_amd_rccl_unique_id", "dogleg_amd_rank", "dogleg_amd_release_cache",
     "dogleg_amd_id_file_publish", "dogleg_amd_id_file_wait", "dogleg_amd_last_solve_timing",
+    "dogleg_getOutliernessFactors", "dogleg_markOutliers", "dogleg_reportOutliers",
+    "dogleg_getOutliernessTrace_newFeature_sparse",
 ]
 
 _lib = None
@@ -118,6 +121,10 @@ def lib():
     L.dlg_solve_with_factor.argtypes = [V, C.c_int, D, D, C.c_int]
     L.dlg_solve_multi.argtypes = [V, C.c_int, D, D, C.c_int]
     L.dlg_pseudoinverse_chunk.argtypes = [V, C.c_int, C.c_int, C.c_int, D]
+    L.dlg_feature_leverage.argtypes = [V, C.c_int, C.c_int, C.c_int, C.c_int, D]
+    L.dlg_outlierness_factors.argtypes = [V, C.c_int, C.c_int, C.c_int, C.c_double, D]
+    L.dlg_leverage_query.argtypes = [V, C.c_int, D, C.c_int, C.c_int, C.c_int, D]
+    L.dlg_leverage_stats.argtypes = [V, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long), I]
     L.dlg_expected_improvement.argtypes = [V, C.c_int, C.c_int, D]
     L.dlg_point_download.argtypes = [V, C.c_int, C.c_int, D, C.c_size_t]
     L.dlg_factor_download_dense.argtypes = [V, D, C.c_size_t]
@@ -594,6 +601,33 @@ class Backend:
         out = np.zeros((row1 - row0, self.N))
         _ck(self.L.dlg_pseudoinverse_chunk(self.h, slot, row0, row1, dptr(out)), "pseudoinverse_chunk")
         return out
+
+    def feature_leverage(self, slot, feature_size, f0, nf):
+        """leverage blocks A_f = J_f inv(JtJ + lambda I) J_f^T of features f0 .. f0 + nf - 1, packed upper:
+        (nf,) for feature size 1, (nf, 3) = {a00, a01, a11} for size 2"""
+        nt = 3 if feature_size == 2 else 1
+        out = np.zeros(nf * nt)
+        _ck(self.L.dlg_feature_leverage(self.h, slot, feature_size, f0, nf, dptr(out)), "feature_leverage")
+        return out if nt == 1 else out.reshape(nf, 3)
+
+    def outlierness_factors(self, slot, feature_size, nf, scale):
+        out = np.zeros(nf)
+        _ck(self.L.dlg_outlierness_factors(self.h, slot, feature_size, nf, scale, dptr(out)), "outlierness_factors")
+        return out
+
+    def leverage_query(self, slot, Jq, istate):
+        """Jq (featureSize, nstate) on the states istate ..: Jq inv(JtJ + lambda I) Jq^T, packed upper"""
+        Jq = np.ascontiguousarray(np.atleast_2d(Jq), dtype=np.float64)
+        fs, ns = Jq.shape
+        out = np.zeros(fs * (fs + 1) // 2)
+        _ck(self.L.dlg_leverage_query(self.h, slot, dptr(Jq), istate, ns, fs, dptr(out)), "leverage_query")
+        return out
+
+    def leverage_stats(self, feature_size):
+        """(chunks, supernode visits of all chunks, supernodes) of the last sparse leverage plan"""
+        a, b, c = C.c_long(), C.c_long(), C.c_int()
+        _ck(self.L.dlg_leverage_stats(self.h, feature_size, C.byref(a), C.byref(b), C.byref(c)), "leverage_stats")
+        return a.value, b.value, c.value
 
     def make_step(self, frm, to, kind, trustregion, want_p=True):
         """p_new comes back in a page-locked buffer owned by this object (as the driver's operating

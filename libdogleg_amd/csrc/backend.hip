@@ -301,6 +301,7 @@ extern "C" void dlg_backend_destroy(dlg_backend_t* b)
   if(b->d_gnpart) (void)hipFree(b->d_gnpart);
   if(b->d_work) (void)hipFree(b->d_work);
   if(b->d_solve_scr) (void)hipFree(b->d_solve_scr);
+  if(b->d_lev) (void)hipFree(b->d_lev);
   if(b->d_red)  (void)hipFree(b->d_red);
   for(auto& pp : b->prof_pending) { (void)hipEventDestroy(pp.a); (void)hipEventDestroy(pp.b); }
   for(hipEvent_t e : b->prof_pool) (void)hipEventDestroy(e);
@@ -1944,6 +1945,146 @@ extern "C" int dlg_pseudoinverse_chunk(dlg_backend_t* b, int s, int row0, int ro
     { dlg_set_error("dlg_pseudoinverse_chunk: download failed"); rc = DLG_ERR_HIP; }
   }
   return rc;
+}
+
+// ---- leverage blocks and outlierness factors (the reference's outlier API, dogleg.c:2294-2660) ---------------------------
+// A_f = J_f (JtJ + lambda I)^-1 J_f^T of features of fs consecutive measurement rows, from the factor held for the slot and
+// the slot's Jacobian on the device.  Only the forward solve is needed, A_f = V_f^T V_f with V_f = L^-1 P J_f^T: sparse, the
+// forward solves of 16 rows at a time visit only the supernodes their columns reach (sparse_multi.hip), many chunks per
+// launch; dense, the forward half of the blocked solve on many chunks per launch sequence.  The Gram products are summed
+// on the device in a fixed order (two calls give the same bits); only nf values or blocks travel to the host.
+// A sparse pattern with a supernode wider than the blocked kernels take (or DOGLEG_AMD_LEVERAGE_SWEEP=1): the full solve
+// of every chunk (dlg_pseudoinverse_chunk's route) and its product with the chunk's rows of J.
+static int lev_scratch(dlg_backend* b, size_t doubles, double** out)
+{
+  if(doubles > b->lev_cap)
+  {
+    if(b->d_lev) { DLG_HIP(hipStreamSynchronize(b->stream)); (void)hipFree(b->d_lev); b->d_lev = nullptr; b->lev_cap = 0; }
+    if(hipMalloc(&b->d_lev, sizeof(double)*doubles) != hipSuccess) { (void)hipGetLastError(); dlg_set_error("out of device memory"); return DLG_ERR_NOMEM; }
+    b->lev_cap = doubles;
+  }
+  *out = b->d_lev;
+  return DLG_OK;
+}
+static int lev_check(dlg_backend* b, int s, int fs, const char* who)
+{
+  DLG_CHECK(check_slot(b, s));
+  DLG_CHECK(step_unprepare(b));
+  if(fs < 1 || fs > 2) { dlg_set_error("%s: feature size %d is not implemented (1 and 2 are)", who, fs); return DLG_ERR_ARG; }
+  if(b->type == DLG_DENSE_PRODUCTS) { dlg_set_error("%s: dense-products keeps no Jacobian", who); return DLG_ERR_STATE; }
+  if(!b->slot[s].have_inputs) { dlg_set_error("%s needs x and J of slot %d", who, s); return DLG_ERR_STATE; }
+  if(b->factor_slot != s) { dlg_set_error("%s: no factorization of slot %d is held", who, s); return DLG_ERR_STATE; }
+  if(b->sharded() || b->part_nranks > 1) { dlg_set_error("%s is not available on a sharded or partitioned backend", who); return DLG_ERR_STATE; }
+  return DLG_OK;
+}
+// solve the 16 interleaved right-hand sides in d_il in place (original order); d_cols: N x 16 scratch for the
+// one-column-at-a-time route of a pattern too wide for the blocked kernels
+static int solve_il(dlg_backend* b, double* d_il, double* d_cols, int ncols)
+{
+  if(multi_ok(b)) return solve_block_dev(b, d_il);
+  const size_t N = (size_t)b->N;
+  DLG_CHECK(multi_interleaved_to_cols(b, d_il, ncols, d_cols));
+  for(int c = 0; c < ncols; c++) DLG_CHECK(sparse_solve(b, d_cols + c*N, d_cols + c*N));
+  return multi_cols_to_interleaved(b, d_cols, ncols, d_il);
+}
+// the Gram products of every chunk through the full solve of the chunk (one slot per chunk)
+static int lev_sweep(dlg_backend* b, int s, int fs, int nf, double* d_gram)
+{
+  const int MRB = sparse_multi_rhs(), nrow = nf*fs;
+  const size_t N = (size_t)b->N;
+  double* d_cols = nullptr;
+  DLG_CHECK(solve_scratch(b, 2*N*MRB, &d_cols));
+  double* d_il = d_cols + N*MRB;
+  for(int ch = 0; ch*MRB < nrow; ch++)
+  {
+    const int nc = std::min(MRB, nrow - ch*MRB);
+    DLG_CHECK(sparse_jt_chunk_interleaved(b, s, ch*MRB, nc, d_il));
+    DLG_CHECK(solve_il(b, d_il, d_cols, nc));
+    DLG_CHECK(lev_gram_rows(b, s, ch*MRB, nc, fs, d_il, d_gram + (size_t)ch*LEV_NP));
+  }
+  return DLG_OK;
+}
+static int lev_run(dlg_backend* b, int s, int fs, int nf, int mode, double scale, double* out_host, const char* who)
+{
+  DLG_CHECK(lev_check(b, s, fs, who));
+  if(nf < 0 || (long)nf*fs > b->M) { dlg_set_error("%s: %d features of %d rows do not fit %d measurements", who, nf, fs, b->M); return DLG_ERR_ARG; }
+  if(nf == 0) return DLG_OK;
+  if(!out_host) { dlg_set_error("%s: bad argument", who); return DLG_ERR_ARG; }
+  const int MRB = sparse_multi_rhs(), nch = dlg_cdiv((long)nf*fs, MRB), nt = mode == 0 ? lev_nt(fs) : 1;
+  const size_t nout = (size_t)nf*nt, ngram = (size_t)nch*LEV_NP;
+  const bool sweep = b->type == DLG_SPARSE && (!sparse_multi_width_ok(b) || getenv("DOGLEG_AMD_LEVERAGE_SWEEP"));
+  double* d_buf = nullptr;
+  double* d_gram = nullptr; const int* d_slot_ptr = nullptr;
+  if(b->type == DLG_SPARSE && !sweep)
+  {
+    DLG_CHECK(lev_scratch(b, nout, &d_buf));
+    DLG_CHECK(sparse_leverage_reach(b, s, fs, nf, &d_gram, &d_slot_ptr, nullptr));
+  }
+  else if(b->type == DLG_SPARSE)
+  {
+    DLG_CHECK(lev_scratch(b, nout + ngram, &d_buf));
+    d_gram = d_buf + nout;
+    DLG_CHECK(lev_sweep(b, s, fs, nf, d_gram));
+  }
+  else
+  {
+    // the blocks of as many chunks at a time as 256 MB hold (at least one)
+    const size_t blk = (size_t)b->N*MRB, work = std::max<size_t>(blk, ((size_t)32 << 20) / blk * blk);
+    DLG_CHECK(lev_scratch(b, nout + ngram + std::min(work, blk*nch), &d_buf));
+    d_gram = d_buf + nout;
+    DLG_CHECK(dense_leverage_gram(b, s, fs, nf, d_gram + ngram, std::min(work, blk*nch), d_gram));
+  }
+  DLG_CHECK(lev_finish(b, s, nf, fs, d_slot_ptr, d_gram, scale, mode, d_buf));
+  if(hipMemcpyAsync(out_host, d_buf, sizeof(double)*nout, hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
+     hipStreamSynchronize(b->stream) != hipSuccess)
+  { dlg_set_error("%s: download failed", who); return DLG_ERR_HIP; }
+  return DLG_OK;
+}
+extern "C" int dlg_feature_leverage(dlg_backend_t* b, int s, int fs, int f0, int nf, double* A_host)
+{
+  if(f0 < 0 || nf < 0) { dlg_set_error("dlg_feature_leverage: bad feature range"); return DLG_ERR_ARG; }
+  const int nt = (fs == 2) ? 3 : 1;
+  std::vector<double> all((size_t)(f0 + nf)*nt);
+  DLG_CHECK(lev_run(b, s, fs, f0 + nf, 0, 0.0, all.data(), "dlg_feature_leverage"));
+  if(nf > 0) memcpy(A_host, all.data() + (size_t)f0*nt, sizeof(double)*(size_t)nf*nt);
+  return DLG_OK;
+}
+extern "C" int dlg_outlierness_factors(dlg_backend_t* b, int s, int fs, int nf, double scale, double* factors_host)
+{
+  return lev_run(b, s, fs, nf, 1, scale, factors_host, "dlg_outlierness_factors");
+}
+extern "C" int dlg_leverage_stats(dlg_backend_t* b, int fs, long* nchunks, long* visits, int* nsn)
+{
+  if(!b || b->type != DLG_SPARSE || !nchunks || !visits || !nsn) { dlg_set_error("dlg_leverage_stats: bad argument"); return DLG_ERR_ARG; }
+  return sparse_leverage_stats(b, fs, nchunks, visits, nsn);
+}
+// A = Jq (JtJ + lambda I)^-1 Jq^T for a query feature: Jq fs x nstate (row-major) on the states istate .. istate + nstate - 1
+extern "C" int dlg_leverage_query(dlg_backend_t* b, int s, const double* Jq, int istate, int nstate, int fs, double* A_host)
+{
+  DLG_CHECK(lev_check(b, s, fs, "dlg_leverage_query"));
+  if(!Jq || !A_host || istate < 0 || nstate < 1 || istate > b->N - nstate) { dlg_set_error("dlg_leverage_query: bad argument"); return DLG_ERR_ARG; }
+  const int MRB = sparse_multi_rhs();
+  const size_t N = (size_t)b->N;
+  double* d_cols = nullptr;
+  DLG_CHECK(solve_scratch(b, 2*N*MRB, &d_cols));
+  double* d_il = d_cols + N*MRB;
+  std::vector<double> blk((size_t)nstate*MRB, 0.0);
+  for(int j = 0; j < nstate; j++) for(int c = 0; c < fs; c++) blk[(size_t)j*MRB + c] = Jq[(size_t)c*nstate + j];
+  DLG_HIP(hipMemsetAsync(d_il, 0, sizeof(double)*N*MRB, b->stream));
+  DLG_HIP(hipMemcpyAsync(d_il + (size_t)istate*MRB, blk.data(), sizeof(double)*blk.size(), hipMemcpyHostToDevice, b->stream));
+  DLG_CHECK(solve_il(b, d_il, d_cols, fs));
+  DLG_HIP(hipMemcpyAsync(blk.data(), d_il + (size_t)istate*MRB, sizeof(double)*blk.size(), hipMemcpyDeviceToHost, b->stream));
+  DLG_HIP(hipStreamSynchronize(b->stream));
+  // upper triangle, row after row: A[i][k] = (solved column i) . (row k of Jq)
+  int o = 0;
+  for(int i = 0; i < fs; i++)
+    for(int k = i; k < fs; k++)
+    {
+      double acc = 0.0;
+      for(int j = 0; j < nstate; j++) acc += blk[(size_t)j*MRB + i]*Jq[(size_t)k*nstate + j];
+      A_host[o++] = acc;
+    }
+  return DLG_OK;
 }
 
 // ---------------------------------------------------------------- downloads --

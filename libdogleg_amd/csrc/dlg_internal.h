@@ -175,6 +175,7 @@ struct dlg_backend
                                        // flag is read after the solve's synchronisation
   double* d_work = nullptr;   // N-vector scratch
   double* d_solve_scr = nullptr; size_t solve_scr_cap = 0;   // scratch of the post-solve entry points (backend.hip: solve_scratch)
+  double* d_lev = nullptr; size_t lev_cap = 0;               // scratch of the leverage entry points (backend.hip: lev_scratch)
 
   // sparse
   SparseSym* sym = nullptr;
@@ -405,3 +406,24 @@ int multi_cols_to_interleaved(dlg_backend* b, const double* d_cols, int ncols, d
 int multi_interleaved_to_cols(dlg_backend* b, const double* d_il, int ncols, double* d_cols);
 int sparse_jt_chunk_interleaved(dlg_backend* b, int s, int row0, int ncols, double* d_il);
 int dense_jt_chunk_interleaved(dlg_backend* b, int s, int row0, int ncols, double* d_il);
+
+// leverage blocks A_f = J_f (JtJ + lambda I)^-1 J_f^T of features of fs = 1 or 2 consecutive measurement rows
+// (sparse_multi.hip / kernels_dense.hip): a chunk is MR = 16 rows (16 / fs features); every chunk leaves LEV_NP Gram
+// products per slot (slots of chunk ch: [slot_ptr[ch], slot_ptr[ch + 1]), slot_ptr == nullptr: slot ch), summed by
+// lev_finish in slot order.  Packed per feature: fs 1 {a}, fs 2 {a00, a01, a11}.
+constexpr int LEV_NP = 24;
+static __host__ __device__ inline int lev_np(int fs) { return fs == 1 ? 16 : 24; }
+static __host__ __device__ inline int lev_nt(int fs) { return fs == 1 ? 1 : 3; }
+// product p of a chunk: columns (a, c) of the chunk's 16 right-hand sides
+static __device__ inline void lev_prod(int fs, int p, int& a, int& c)
+{
+  if(fs == 1) { a = c = p; return; }
+  const int f = p / 3, e = p - 3*f;
+  a = 2*f + (e == 2); c = 2*f + (e >= 1);
+}
+int sparse_leverage_reach(dlg_backend* b, int s, int fs, int nf, double** d_gram, const int** d_slot_ptr, long* visits);
+int sparse_leverage_stats(const dlg_backend* b, int fs, long* nchunks, long* visits, int* nsn);
+void sparse_leverage_free(SparseSym* Y);
+int lev_gram_rows(dlg_backend* b, int s, int row0, int nrows, int fs, const double* d_il, double* d_gram);
+int lev_finish(dlg_backend* b, int s, int nf, int fs, const int* d_slot_ptr, const double* d_gram, double scale, int mode, double* d_out);
+int dense_leverage_gram(dlg_backend* b, int s, int fs, int nf, double* d_work, size_t work_doubles, double* d_gram);

@@ -1286,6 +1286,136 @@ bool dogleg_computeJtJfactorization(dogleg_operatingPoint_t* point, dogleg_solve
   return true;
 }
 
+// ---- outliers (dogleg.h; reference dogleg.c:2294-3149).  The leverage blocks come from the device (dlg_backend.h:
+// dlg_feature_leverage); what is left here is the host logic around them.
+} // extern "C"
+namespace {
+bool outlier_ready(dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx, const char* who)
+{
+  if(!point || !ctx) { MSG("%s(): no point or context", who); return false; }
+  if(!point->have_x) { MSG("%s() needs x, but it isn't available", who); return false; }
+  if(!point->have_J) { MSG("%s() needs J, but it isn't available", who); return false; }
+  if(ctx->solve_type == DOGLEG_DENSE_PRODUCTS) { MSG("%s() is not available with DENSE_PRODUCTS: there is no J", who); return false; }
+  return dogleg_computeJtJfactorization(point, ctx);
+}
+// a backend call that needs the factor of the point's slot: if the factor held is another slot's, factorise again and retry
+template <class F> bool with_point_factor(dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx, const char* what, F call)
+{
+  int rc = call();
+  if(rc == DLG_ERR_STATE)
+  {
+    point->have_factorization = false;
+    if(!dogleg_computeJtJfactorization(point, ctx)) return false;
+    rc = call();
+  }
+  return be_ok(rc, what);
+}
+// *scale <= 0: Nn / (4 (Nstate + 1) |x|^2 / (Nn - Nstate - 1)), Nn the measurements that are not outliers
+void outlier_scale(double* scale, const dogleg_solverContext_t* ctx, int NoutlierFeatures, int featureSize, double norm2_x)
+{
+  if(*scale > 0.0) return;
+  const int nn = ctx->Nmeasurements - NoutlierFeatures*featureSize;
+  *scale = (double)nn / (4.0*((double)(ctx->Nstate + 1)*norm2_x/(double)(nn - ctx->Nstate - 1)));
+}
+} // namespace
+extern "C" {
+
+bool dogleg_getOutliernessFactors(double* factors, double* scale, int featureSize, int Nfeatures,
+                                  int NoutlierFeatures, dogleg_operatingPoint_t* point,
+                                  dogleg_solverContext_t* ctx)
+{
+  if(featureSize <= 1) featureSize = 1;
+  if(featureSize > 2) { MSG("dogleg_getOutliernessFactors(): featureSize > 2 is not implemented (got %d)", featureSize); return false; }
+  if(!factors || !scale || Nfeatures < 0) { MSG("dogleg_getOutliernessFactors(): bad arguments"); return false; }
+  if(!outlier_ready(point, ctx, "dogleg_getOutliernessFactors")) return false;
+  if((long)Nfeatures*featureSize > (long)ctx->Nmeasurements)
+  { MSG("dogleg_getOutliernessFactors(): %d features of size %d exceed %d measurements", Nfeatures, featureSize, ctx->Nmeasurements); return false; }
+  outlier_scale(scale, ctx, NoutlierFeatures, featureSize, point->norm2_x);
+  Driver* d = D(ctx);
+  const double sc = *scale;
+  return with_point_factor(point, ctx, "outlierness factors",
+                           [&]{ return dlg_outlierness_factors(d->be, slot_of(d, point), featureSize, Nfeatures, sc, factors); });
+}
+
+bool dogleg_markOutliers(struct dogleg_outliers_t* markedOutliers, double* scale, int* Noutliers,
+                         double (getConfidence)(int i_feature_exclude), int featureSize, int Nfeatures,
+                         dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx)
+{
+  if(featureSize <= 1) featureSize = 1;
+  if(!markedOutliers || !Noutliers || !getConfidence || Nfeatures < 0) { MSG("dogleg_markOutliers(): bad arguments"); return false; }
+  std::vector<double> factors((size_t)Nfeatures);
+  if(!dogleg_getOutliernessFactors(factors.data(), scale, featureSize, Nfeatures, *Noutliers, point, ctx)) return false;
+  // candidates have a factor of at least 1; one is an outlier if leaving it out costs little confidence
+  const double confidence0 = getConfidence(-1);
+  if(confidence0 < 0.0) return false;
+  Driver* d = D(ctx);
+  VERBOSE(d, "Initial confidence: %g", confidence0);
+  bool markedAny = false;
+  *Noutliers = 0;
+  for(int i = 0; i < Nfeatures; i++)
+  {
+    if(markedOutliers[i].marked) { (*Noutliers)++; continue; }
+    if(factors[i] < 1.0) continue;
+    const double confidence = getConfidence(i);
+    if(confidence < 0.0) return false;
+    const double drop = 1.0 - confidence/confidence0;
+    if(drop < 0.05)
+    {
+      markedOutliers[i].marked = 1;
+      markedAny = true;
+      (*Noutliers)++;
+      VERBOSE(d, "Feature %d has outlierness factor %f. Culling produces a confidence: %g. relative loss: %g... YES an outlier; confidence drops little",
+              i, factors[i], confidence, drop);
+    }
+    else
+      VERBOSE(d, "Feature %d has outlierness factor %f. Culling produces a confidence: %g. relative loss: %g... NOT an outlier: confidence drops too much",
+              i, factors[i], confidence, drop);
+  }
+  return markedAny;
+}
+
+void dogleg_reportOutliers(double (getConfidence)(int i_feature_exclude), double* scale, int featureSize,
+                           int Nfeatures, int Noutliers, dogleg_operatingPoint_t* point,
+                           dogleg_solverContext_t* ctx)
+{
+  if(featureSize <= 1) featureSize = 1;
+  if(!getConfidence || Nfeatures < 0) { MSG("dogleg_reportOutliers(): bad arguments"); return; }
+  std::vector<double> factors((size_t)Nfeatures, 0.0);
+  (void)dogleg_getOutliernessFactors(factors.data(), scale, featureSize, Nfeatures, Noutliers, point, ctx);   // (a failure is reported, not fatal)
+  MSG("## Outlier statistics");
+  MSG("# i_feature outlier_factor confidence_drop_relative_if_removed");
+  const double confidence_full = getConfidence(-1);
+  for(int i = 0; i < Nfeatures; i++)
+  {
+    const double confidence = getConfidence(i);
+    MSG("%5d %9.3g %9.3g", i, factors[i], 1.0 - confidence/confidence_full);
+  }
+}
+
+double dogleg_getOutliernessTrace_newFeature_sparse(const double* JqueryFeature, int istateActive,
+                                                    int NstateActive, int featureSize, int NoutlierFeatures,
+                                                    dogleg_operatingPoint_t* point,
+                                                    dogleg_solverContext_t* ctx)
+{
+  const char* who = "dogleg_getOutliernessTrace_newFeature_sparse";
+  if(point && !point->have_x) { MSG("%s() needs x, but it isn't available", who); return -1.0; }
+  if(point && !point->have_J) { MSG("%s() needs J, but it isn't available", who); return -1.0; }
+  if(featureSize != 2) { MSG("%s(): only featureSize 2 is implemented (got %d)", who, featureSize); return -1.0; }
+  if(!JqueryFeature || NstateActive < 1) { MSG("%s(): bad arguments", who); return -1.0; }
+  if(!outlier_ready(point, ctx, who)) return -1.0;
+  Driver* d = D(ctx);
+  double A[3];
+  if(!with_point_factor(point, ctx, "leverage of a query feature",
+                        [&]{ return dlg_leverage_query(d->be, slot_of(d, point), JqueryFeature, istateActive, NstateActive, 2, A); }))
+    return -1.0;
+  // Mq = I + A; tr Mq^-1 = tr(Mq) / det(Mq)
+  const double m00 = 1.0 + A[0], m01 = A[1], m11 = 1.0 + A[2];
+  const double trace_inv = (m00 + m11)/(m00*m11 - m01*m01);
+  double scale = -1.0;
+  outlier_scale(&scale, ctx, NoutlierFeatures, featureSize, point->norm2_x);
+  return scale*(2.0 - trace_inv);
+}
+
 // ---- extension (not in the reference): multi-GPU.  See include/dogleg.h.
 int dogleg_amd_set_communicator(int rank, int nranks, int device, const void* rccl_unique_id128)
 {

@@ -21,6 +21,7 @@
 // state entries of a tile are contiguous -> coalesced 512-B wave loads.
 #include "dlg_internal.h"
 #include "panel_factor.h"
+#include <algorithm>
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -573,11 +574,13 @@ __global__ void __launch_bounds__(64) k_trsv_diag_bwd(const double* __restrict__
 // (v_mfma_f64_16x16x4_f64: A = a 16-row tile of L, B = the 64 x 16 block of solved unknowns in
 // LDS) -- the factor is read once per 16 right-hand sides.
 constexpr int DMR = 16;
-// X_blk = Linv_blk * Y_blk (forward) or Linv_blk^T * Y_blk (backward)
+// X_blk = Linv_blk * Y_blk (forward) or Linv_blk^T * Y_blk (backward); blockIdx.y: the block of right-hand sides
+// at y + blockIdx.y*ystride
 __global__ void __launch_bounds__(TPB) k_trsm_diag_m(const double* __restrict__ Linv, int kb, int nb,
-                                                     double* __restrict__ y, int transpose)
+                                                     double* __restrict__ y, int transpose, size_t ystride)
 {
   __shared__ double v[NB*DMR];
+  y += blockIdx.y*ystride;
   __shared__ double Ls[NB][NB + 1];
   const int tid = threadIdx.x, c = tid & (DMR - 1), tg = tid >> 4;
   for(int e = tid; e < NB*DMR; e += TPB) { const int k = e / DMR; v[e] = (k < nb) ? y[(size_t)(kb + k)*DMR + (e - k*DMR)] : 0.0; }
@@ -593,9 +596,10 @@ __global__ void __launch_bounds__(TPB) k_trsm_diag_m(const double* __restrict__ 
 }
 // forward: Y[i][:] -= L[i, kb:kb+nb] X[kb:kb+nb][:] for the rows i >= kb + nb; a wave per 16 rows
 __global__ void __launch_bounds__(TPB) k_trsm_update_fwd_m(const double* __restrict__ A, int lda, int kb, int nb,
-                                                           int n, double* __restrict__ y)
+                                                           int n, double* __restrict__ y, size_t ystride)
 {
   __shared__ double v[NB*DMR];
+  y += blockIdx.y*ystride;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, mm = lane & 15, kq = lane >> 4;
   for(int e = tid; e < NB*DMR; e += TPB) { const int k = e / DMR; v[e] = (k < nb) ? y[(size_t)(kb + k)*DMR + (e - k*DMR)] : 0.0; }
   __syncthreads();
@@ -641,6 +645,29 @@ __global__ void __launch_bounds__(TPB) k_jt_chunk_dense(const double* __restrict
   if(e >= (size_t)N*DMR) return;
   const int k = (int)(e / DMR), c = (int)(e % DMR);
   il[e] = (c < ncols) ? J[(size_t)(row0 + c)*N + k] : 0.0;
+}
+
+// leverage blocks (dense_leverage_gram): the interleaved blocks of nblk chunks of 16 rows of J, chunk q at il + q*N*DMR,
+// rows from row0 on, zero beyond nrow
+__global__ void __launch_bounds__(TPB) k_jt_chunks_dense(const double* __restrict__ J, int N, int row0, int nrow,
+                                                         double* __restrict__ il)
+{
+  const size_t e = (size_t)blockIdx.x*TPB + threadIdx.x;
+  if(e >= (size_t)N*DMR) return;
+  const int k = (int)(e / DMR), c = (int)(e % DMR), row = row0 + (int)blockIdx.y*DMR + c;
+  il[(size_t)blockIdx.y*N*DMR + e] = (row < nrow) ? J[(size_t)row*N + k] : 0.0;
+}
+// ... and the Gram products of each solved block V = L^-1 J_chunk^T: 8 row groups of 32 products, summed in a fixed order
+__global__ void __launch_bounds__(TPB) k_lev_gram_dense(const double* __restrict__ V, int n, int fs, double* __restrict__ gram)
+{
+  __shared__ double red[TPB];
+  const int tid = threadIdx.x, p = tid & 31, g = tid >> 5, np = lev_np(fs);
+  V += (size_t)blockIdx.x*n*DMR;
+  double acc = 0.0;
+  if(p < np) { int a, c; lev_prod(fs, p, a, c); for(int k = g; k < n; k += TPB/32) acc += V[(size_t)k*DMR + a]*V[(size_t)k*DMR + c]; }
+  red[tid] = acc;
+  __syncthreads();
+  if(tid < np) { double sum = 0.0; for(int q = 0; q < TPB/32; q++) sum += red[q*32 + tid]; gram[(size_t)blockIdx.x*LEV_NP + tid] = sum; }
 }
 
 // ------------------------------------------------------------ probes --------
@@ -1012,17 +1039,17 @@ int dense_solve_multi(dlg_backend* b, double* d_il)
   for(int kb = 0, blk = 0; kb < n; kb += NB, blk++)
   {
     const int nb = (n - kb < NB) ? n - kb : NB;
-    hipLaunchKernelGGL(k_trsm_diag_m, dim3(1), dim3(TPB), 0, st, b->Linv + (size_t)blk*NB*NB, kb, nb, d_il, 0);
+    hipLaunchKernelGGL(k_trsm_diag_m, dim3(1), dim3(TPB), 0, st, b->Linv + (size_t)blk*NB*NB, kb, nb, d_il, 0, (size_t)0);
     const int rem = n - kb - nb;
     if(rem > 0)
-      hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64))), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_il);
+      hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64))), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_il, (size_t)0);
   }
   const int nblk = dlg_cdiv(n, NB);
   for(int blk = nblk - 1; blk >= 0; blk--)
   {
     const int kb = blk*NB;
     const int nb = (n - kb < NB) ? n - kb : NB;
-    hipLaunchKernelGGL(k_trsm_diag_m, dim3(1), dim3(TPB), 0, st, b->Linv + (size_t)blk*NB*NB, kb, nb, d_il, 1);
+    hipLaunchKernelGGL(k_trsm_diag_m, dim3(1), dim3(TPB), 0, st, b->Linv + (size_t)blk*NB*NB, kb, nb, d_il, 1, (size_t)0);
     if(kb > 0)
       hipLaunchKernelGGL(k_trsm_update_bwd_m, dim3(dlg_cdiv(kb, 16*(TPB/64))), dim3(TPB), 0, st, b->G, n, kb, nb, d_il);
   }
@@ -1033,6 +1060,33 @@ int dense_jt_chunk_interleaved(dlg_backend* b, int s, int row0, int ncols, doubl
 {
   hipLaunchKernelGGL(k_jt_chunk_dense, dim3(dlg_cdiv((long)b->N*DMR, TPB)), dim3(TPB), 0, b->stream, b->slot[s].Jin(), b->N,
                      row0, ncols, d_il);
+  DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
+
+// Gram products of the first nf features of fs rows: the forward half of dense_solve_multi on J_chunk^T for as many chunks of
+// 16 rows at a time as d_work (work_doubles) holds, one launch sequence for all of them; one slot of LEV_NP per chunk
+int dense_leverage_gram(dlg_backend* b, int s, int fs, int nf, double* d_work, size_t work_doubles, double* d_gram)
+{
+  const int n = b->N, nrow = nf*fs, nch = dlg_cdiv(nrow, DMR);
+  const size_t blk = (size_t)n*DMR;
+  const int per = (int)std::min<size_t>(work_doubles / blk, 65535);
+  if(per < 1) { dlg_set_error("dense leverage: scratch too small"); return DLG_ERR_NOMEM; }
+  hipStream_t st = b->stream;
+  for(int q0 = 0; q0 < nch; q0 += per)
+  {
+    const int nq = std::min(per, nch - q0);
+    hipLaunchKernelGGL(k_jt_chunks_dense, dim3(dlg_cdiv((long)blk, TPB), nq), dim3(TPB), 0, st, b->slot[s].Jin(), n, q0*DMR, nrow, d_work);
+    for(int kb = 0, bi = 0; kb < n; kb += NB, bi++)
+    {
+      const int nb = (n - kb < NB) ? n - kb : NB;
+      hipLaunchKernelGGL(k_trsm_diag_m, dim3(1, nq), dim3(TPB), 0, st, b->Linv + (size_t)bi*NB*NB, kb, nb, d_work, 0, blk);
+      const int rem = n - kb - nb;
+      if(rem > 0)
+        hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64)), nq), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_work, blk);
+    }
+    hipLaunchKernelGGL(k_lev_gram_dense, dim3(nq), dim3(TPB), 0, st, d_work, n, fs, d_gram + (size_t)q0*LEV_NP);
+  }
   DLG_LAUNCH_CHECK();
   return DLG_OK;
 }

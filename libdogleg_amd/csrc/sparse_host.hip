@@ -22,6 +22,7 @@ void sparse_destroy(dlg_backend* b)
   if(Y->ev_spec) (void)hipEventDestroy(Y->ev_spec);
   if(Y->ev_spec_fork) (void)hipEventDestroy(Y->ev_spec_fork);
   for(void* p : Y->allocs) if(p) (void)hipFree(p);
+  sparse_leverage_free(Y);
   delete Y;
   b->sym = nullptr;
 }
