@@ -342,6 +342,31 @@ int  dlg_leverage_query(dlg_backend_t* b, int slot, const double* Jq, int istate
  * all of them (the sum of the reaches) and the supernodes of the pattern */
 int  dlg_leverage_stats(dlg_backend_t* b, int featureSize, long* nchunks, long* visits, int* nsn);
 
+/* ---- covariance blocks Sigma = (JtJ + lambda I)^-1, with the factor held for `slot` and the lambda it was made with.
+ * Unscaled: multiply by sigma^2 (for example |x|^2 / (Nmeas - Nstate)) for the parameter covariance.  Request q asks for
+ * Sigma[r0[q] : r0[q]+nr[q], c0[q] : c0[q]+nc[q]], written row-major; the blocks of all requests follow one another in
+ * request order.  The union of a request's two ranges holds at most 16 distinct variables (a diagonal block up to 16 wide,
+ * a cross block of disjoint ranges nr + nc <= 16); wider requests are refused (DLG_ERR_ARG): take those columns of the
+ * inverse from dlg_solve_multi with unit right-hand sides.  nreq == 0 does nothing.  Only the forward solve of the unit
+ * columns is needed; the sparse path visits, per chunk of 16 variables, only the supernodes on their paths to the root.
+ * Bitwise reproducible; sparse, a request's values do not depend on the other requests of the call or their order.  The
+ * plan of the last request list is kept and reused when the same arrays come again.  A slot whose factor is not the one
+ * held is refused (DLG_ERR_STATE): factorise it first.  Not on a sharded / partitioned backend.  All three solve types. */
+int  dlg_covariance_blocks(dlg_backend_t* b, int slot, int nreq, const int* r0, const int* nr, const int* c0, const int* nc,
+                           double* out_host);
+/* diag(Sigma), N values in the variables' order */
+int  dlg_marginal_variances(dlg_backend_t* b, int slot, double* var_host);
+/* of the last covariance plan run: its chunks of 16 variables, the supernode visits of all of them (sparse, blocked
+ * route; 0 otherwise) and the supernodes of the pattern */
+int  dlg_covariance_stats(dlg_backend_t* b, long* nchunks, long* visits, int* nsn);
+/* host seconds the last covariance plan run took to build when it was built (-1: none) */
+double dlg_covariance_plan_seconds(dlg_backend_t* b);
+/* host only: the symbolic phase on a pattern (as dlg_sparse_symbolic_probe) and the packing of a request list into
+ * chunks: chunk_of_req[q] (nreq values) and stats = {chunks, (chunk, supernode) pair visits, most distinct variables in
+ * a chunk} (nstats <= 3 of them).  Refuses what dlg_covariance_blocks refuses. */
+int  dlg_covariance_plan_probe(int N, int M, const int* colptr, const int* rowidx, int nreq, const int* r0, const int* nr,
+                               const int* c0, const int* nc, int* chunk_of_req, long* stats, int nstats);
+
 /* ---- downloads (returnContext, tests) -------------------------------------- */
 int  dlg_point_download(dlg_backend_t* b, int slot, int which, double* host, size_t n);
 /* dense factor in the reference's layout (packed as dpptrf('L') leaves it, or

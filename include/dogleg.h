@@ -348,6 +348,20 @@ double dogleg_getOutliernessTrace_newFeature_sparse(const double* JqueryFeature,
                                                     dogleg_operatingPoint_t* point,
                                                     dogleg_solverContext_t* ctx);
 
+/* ---- extension (not in the reference): parameter uncertainty from the factor held on the device.  Blocks of
+ * Sigma = (JtJ + lambda I)^-1 at `point`, lambda = ctx->lambda (the lambda of that factorisation), UNSCALED: multiply by
+ * sigma^2, for example |x|^2 / (Nmeasurements - Nstate), for the covariance of the parameters.  This replaces
+ * cholmod_solve on ctx->factorization with unit right-hand sides.  Request q is Sigma[r0[q] : r0[q]+nr[q],
+ * c0[q] : c0[q]+nc[q]], written row-major into out, the blocks of all requests one after another; its two ranges hold at
+ * most 16 distinct variables together (a diagonal block up to 16 wide, a cross block nr + nc <= 16), see
+ * dlg_backend.h: dlg_covariance_blocks.  Wider blocks: dlg_solve_multi with unit columns.
+ * Factorises at `point` if that factor is not held (dogleg_computeJtJfactorization).  All three solve types; one rank
+ * only.  0 on success, -1 on failure (with a message). */
+int dogleg_amd_covariance_blocks(double* out, int nreq, const int* r0, const int* nr, const int* c0, const int* nc,
+                                 dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx);
+/* diag(Sigma), Nstate values */
+int dogleg_amd_marginal_variances(double* var, dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx);
+
 #ifdef __cplusplus
 }
 #endif

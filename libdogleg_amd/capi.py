@@ -42,6 +42,8 @@ BACKEND_SYMBOLS = [
     "dlg_backend_share_rccl", "dlg_point_gather_device", "dlg_backend_reset", "dlg_backend_device",
     "dlg_sparse_pattern_matches", "dlg_sparse_drop_pattern", "dlg_sparse_region_probe", "dlg_run_steps", "dlg_backend_time_allreduce",
     "dlg_feature_leverage", "dlg_outlierness_factors", "dlg_leverage_query", "dlg_leverage_stats",
+    "dlg_covariance_blocks", "dlg_marginal_variances", "dlg_covariance_stats", "dlg_covariance_plan_seconds",
+    "dlg_covariance_plan_probe",
 ]
 PROF_NAMES = ["K1_jtx", "K3K8_norm2Jv", "K4_kernel", "K4_total", "K5_factor", "K6_solve", "K7_step", "vec"]
 DOGLEG_SYMBOLS = [
@@ -57,6 +59,7 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_id_file_publish", "dogleg_amd_id_file_wait", "dogleg_amd_last_solve_timing",
     "dogleg_getOutliernessFactors", "dogleg_markOutliers", "dogleg_reportOutliers",
     "dogleg_getOutliernessTrace_newFeature_sparse",
+    "dogleg_amd_covariance_blocks", "dogleg_amd_marginal_variances",
 ]
 
 _lib = None
@@ -125,6 +128,12 @@ def lib():
     L.dlg_outlierness_factors.argtypes = [V, C.c_int, C.c_int, C.c_int, C.c_double, D]
     L.dlg_leverage_query.argtypes = [V, C.c_int, D, C.c_int, C.c_int, C.c_int, D]
     L.dlg_leverage_stats.argtypes = [V, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long), I]
+    L.dlg_covariance_blocks.argtypes = [V, C.c_int, C.c_int, I, I, I, I, D]
+    L.dlg_marginal_variances.argtypes = [V, C.c_int, D]
+    L.dlg_covariance_stats.argtypes = [V, C.POINTER(C.c_long), C.POINTER(C.c_long), I]
+    L.dlg_covariance_plan_seconds.argtypes = [V]
+    L.dlg_covariance_plan_seconds.restype = C.c_double
+    L.dlg_covariance_plan_probe.argtypes = [C.c_int, C.c_int, I, I, C.c_int, I, I, I, I, I, C.POINTER(C.c_long), C.c_int]
     L.dlg_expected_improvement.argtypes = [V, C.c_int, C.c_int, D]
     L.dlg_point_download.argtypes = [V, C.c_int, C.c_int, D, C.c_size_t]
     L.dlg_factor_download_dense.argtypes = [V, D, C.c_size_t]
@@ -256,6 +265,17 @@ SYM_STAT_NAMES = ["var_blocks", "supernodes", "levels", "nnz_JtJ_lower", "nnz_L"
                   "factor_flops", "max_panel", "asm_tasks", "update_items", "relpos", "out_blocks",
                   "contribs", "update_subtasks", "solve_scratch", "jtx_tasks", "asm_mfma_tasks",
                   "asm_kgroups", "asm_shapes"]
+
+
+def covariance_plan_probe(N, M, Jp, Ji, r0, nr, c0, nc):
+    """host only: (chunk of each request, {chunks, pair visits, most distinct variables in a chunk}) of a request list"""
+    L = lib()
+    r0, nr, c0, nc = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.int32) for a in (r0, nr, c0, nc))
+    ch = np.zeros(max(len(r0), 1), dtype=np.int32)
+    st = (C.c_long * 3)()
+    _ck(L.dlg_covariance_plan_probe(N, M, iptr(Jp), iptr(Ji), len(r0), iptr(r0), iptr(nr), iptr(c0), iptr(nc),
+                                    iptr(ch), st, 3), "covariance_plan_probe")
+    return ch[:len(r0)], dict(chunks=st[0], visits=st[1], maxvar=st[2])
 
 
 def symbolic_probe(N, M, Jp, Ji, row0=0, row1=None, want_perm=False):
@@ -628,6 +648,36 @@ class Backend:
         a, b, c = C.c_long(), C.c_long(), C.c_int()
         _ck(self.L.dlg_leverage_stats(self.h, feature_size, C.byref(a), C.byref(b), C.byref(c)), "leverage_stats")
         return a.value, b.value, c.value
+
+    def covariance_blocks(self, slot, r0, nr, c0, nc):
+        """blocks Sigma[r0:r0+nr, c0:c0+nc] of inv(JtJ + lambda I) (the held factor, unscaled), one array (nr[q], nc[q])
+        per request"""
+        r0, nr, c0, nc = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.int32) for a in (r0, nr, c0, nc))
+        n = len(r0)
+        out = np.zeros(max(int(np.sum(nr.astype(np.int64) * nc)), 1))
+        _ck(self.L.dlg_covariance_blocks(self.h, slot, n, iptr(r0), iptr(nr), iptr(c0), iptr(nc), dptr(out)),
+            "covariance_blocks")
+        blocks, o = [], 0
+        for q in range(n):
+            k = int(nr[q]) * int(nc[q])
+            blocks.append(out[o:o + k].reshape(int(nr[q]), int(nc[q])))
+            o += k
+        return blocks
+
+    def marginal_variances(self, slot):
+        """diag(inv(JtJ + lambda I)) with the held factor, unscaled"""
+        out = np.zeros(self.N)
+        _ck(self.L.dlg_marginal_variances(self.h, slot, dptr(out)), "marginal_variances")
+        return out
+
+    def covariance_stats(self):
+        """(chunks, supernode visits of all chunks, supernodes) of the last covariance plan run"""
+        a, b, c = C.c_long(), C.c_long(), C.c_int()
+        _ck(self.L.dlg_covariance_stats(self.h, C.byref(a), C.byref(b), C.byref(c)), "covariance_stats")
+        return a.value, b.value, c.value
+
+    def covariance_plan_seconds(self):
+        return self.L.dlg_covariance_plan_seconds(self.h)
 
     def make_step(self, frm, to, kind, trustregion, want_p=True):
         """p_new comes back in a page-locked buffer owned by this object (as the driver's operating

@@ -302,6 +302,7 @@ extern "C" void dlg_backend_destroy(dlg_backend_t* b)
   if(b->d_work) (void)hipFree(b->d_work);
   if(b->d_solve_scr) (void)hipFree(b->d_solve_scr);
   if(b->d_lev) (void)hipFree(b->d_lev);
+  if(b->cov) { for(int i = 0; i < 2; i++) cov_plan_release(b->cov[i]); delete[] b->cov; }
   if(b->d_red)  (void)hipFree(b->d_red);
   for(auto& pp : b->prof_pending) { (void)hipEventDestroy(pp.a); (void)hipEventDestroy(pp.b); }
   for(hipEvent_t e : b->prof_pool) (void)hipEventDestroy(e);
@@ -2085,6 +2086,95 @@ extern "C" int dlg_leverage_query(dlg_backend_t* b, int s, const double* Jq, int
       A_host[o++] = acc;
     }
   return DLG_OK;
+}
+
+// ---- covariance blocks Sigma = (JtJ + lambda I)^-1 with the factor held for the slot ----------------------------------
+// Sigma[u, v] = (L^-1 P e_u)^T (L^-1 P e_v): only the forward solve of unit columns is needed.  Requests are packed into
+// chunks of 16 distinct variables (sparse_multi.hip: cov_pack_requests); sparse, each chunk's forward solve visits only the
+// supernodes on the paths from its columns to the root, many chunks per launch, and every (chunk, supernode) pair leaves
+// the Gram products its chunk needs; dense, the forward half of the blocked solve from the tile of the chunks' smallest
+// variable on.  k_cov_finish sums each value's slots in a fixed order and writes the blocks straight into one device
+// buffer: only the requested values cross PCIe.  The plan of the last request list (and the marginal-variance plan) is kept.
+// A sparse pattern with a supernode wider than the blocked kernels take, or DOGLEG_AMD_LEVERAGE_SWEEP=1: the full solve of
+// every chunk's unit columns (solve_il) and its requested rows.
+static int cov_run(dlg_backend* b, int s, int which, int nreq, const int* r0, const int* nr, const int* c0, const int* nc,
+                   double* out_host, const char* who)
+{
+  DLG_CHECK(check_slot(b, s));
+  if(nreq < 0) { dlg_set_error("%s: bad argument", who); return DLG_ERR_ARG; }
+  if(which == 0 && nreq == 0) return DLG_OK;
+  if(!out_host || (which == 0 && (!r0 || !nr || !c0 || !nc))) { dlg_set_error("%s: bad argument", who); return DLG_ERR_ARG; }
+  if(b->sharded() || b->part_nranks > 1) { dlg_set_error("%s is not available on a sharded or partitioned backend", who); return DLG_ERR_STATE; }
+  DLG_CHECK(step_unprepare(b));
+  if(b->factor_slot != s) { dlg_set_error("%s: no factorization of slot %d is held", who, s); return DLG_ERR_STATE; }
+  if(b->type == DLG_SPARSE && !b->sym) { dlg_set_error("%s: no sparse pattern", who); return DLG_ERR_STATE; }
+  const bool sparse = b->type == DLG_SPARSE;
+  const int route = !sparse ? 2 : (!sparse_multi_width_ok(b) || getenv("DOGLEG_AMD_LEVERAGE_SWEEP")) ? 1 : 0;
+  if(!b->cov) b->cov = new CovPlan[2];
+  CovPlan& P = b->cov[which];
+  const uint64_t pk = sparse ? sparse_pattern_key(b) : 0;
+  std::vector<int> key = {route, b->N, (int)(pk & 0x7fffffff), (int)((pk >> 31) & 0x7fffffff), (int)(pk >> 62), nreq};
+  if(which == 0)
+    for(const int* a : {r0, nr, c0, nc}) key.insert(key.end(), a, a + nreq);
+  if(P.key != key)
+  {
+    DLG_HIP(hipStreamSynchronize(b->stream));
+    cov_plan_release(P);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = cov_plan_build(b, P, route, which, nreq, r0, nr, c0, nc, who);
+    if(rc != DLG_OK) { cov_plan_release(P); return rc; }
+    P.t_plan = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    P.key = key;
+  }
+  const int MRB = sparse_multi_rhs(), nch = P.K.nch;
+  const size_t N = (size_t)b->N;
+  if(route == 0) DLG_CHECK(sparse_cov_reach_run(b, P));
+  else if(route == 1)
+  {
+    double* d_cols = nullptr;
+    DLG_CHECK(solve_scratch(b, 2*N*MRB, &d_cols));
+    double* d_il = d_cols + N*MRB;
+    for(int ch = 0; ch < nch; ch++)
+    {
+      int ncol = 0;
+      while(ncol < MRB && P.K.var[(size_t)ch*MRB + ncol] >= 0) ncol++;
+      DLG_CHECK(cov_unit_il(b, P, ch, d_il));
+      DLG_CHECK(solve_il(b, d_il, d_cols, ncol));
+      DLG_CHECK(cov_pick(b, P, ch, d_il));
+    }
+  }
+  else
+  {
+    // the blocks of as many chunks at a time as 256 MB hold (at least one)
+    const size_t blk = N*MRB, work = std::max<size_t>(blk, ((size_t)32 << 20) / blk * blk);
+    double* d_work = nullptr;
+    DLG_CHECK(lev_scratch(b, std::min(work, blk*nch), &d_work));
+    DLG_CHECK(dense_cov_gram(b, P, d_work, std::min(work, blk*nch)));
+  }
+  DLG_CHECK(cov_finish(b, P));
+  b->cov_last = which;
+  if(P.ne > 0 && (hipMemcpyAsync(out_host, P.out, sizeof(double)*(size_t)P.ne, hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
+                  hipStreamSynchronize(b->stream) != hipSuccess))
+  { dlg_set_error("%s: download failed", who); return DLG_ERR_HIP; }
+  return DLG_OK;
+}
+extern "C" int dlg_covariance_blocks(dlg_backend_t* b, int s, int nreq, const int* r0, const int* nr, const int* c0,
+                                     const int* nc, double* out_host)
+{
+  return cov_run(b, s, 0, nreq, r0, nr, c0, nc, out_host, "dlg_covariance_blocks");
+}
+extern "C" int dlg_marginal_variances(dlg_backend_t* b, int s, double* var_host)
+{
+  return cov_run(b, s, 1, 0, nullptr, nullptr, nullptr, nullptr, var_host, "dlg_marginal_variances");
+}
+extern "C" int dlg_covariance_stats(dlg_backend_t* b, long* nchunks, long* visits, int* nsn)
+{
+  if(!b || !nchunks || !visits || !nsn) { dlg_set_error("dlg_covariance_stats: bad argument"); return DLG_ERR_ARG; }
+  return sparse_cov_stats(b, nchunks, visits, nsn);
+}
+extern "C" double dlg_covariance_plan_seconds(dlg_backend_t* b)
+{
+  return (b && b->cov && b->cov_last >= 0) ? b->cov[b->cov_last].t_plan : -1.0;
 }
 
 // ---------------------------------------------------------------- downloads --

@@ -176,6 +176,7 @@ struct dlg_backend
   double* d_work = nullptr;   // N-vector scratch
   double* d_solve_scr = nullptr; size_t solve_scr_cap = 0;   // scratch of the post-solve entry points (backend.hip: solve_scratch)
   double* d_lev = nullptr; size_t lev_cap = 0;               // scratch of the leverage entry points (backend.hip: lev_scratch)
+  struct CovPlan* cov = nullptr; int cov_last = -1;          // [2] plans of the covariance entry points (requests, marginal variances), the last one run
 
   // sparse
   SparseSym* sym = nullptr;
@@ -427,3 +428,60 @@ void sparse_leverage_free(SparseSym* Y);
 int lev_gram_rows(dlg_backend* b, int s, int row0, int nrows, int fs, const double* d_il, double* d_gram);
 int lev_finish(dlg_backend* b, int s, int nf, int fs, const int* d_slot_ptr, const double* d_gram, double scale, int mode, double* d_out);
 int dense_leverage_gram(dlg_backend* b, int s, int fs, int nf, double* d_work, size_t work_doubles, double* d_gram);
+
+// ---- covariance blocks Sigma = (JtJ + lambda I)^-1 (backend.hip: dlg_covariance_blocks / dlg_marginal_variances).
+// A request is the sub-block Sigma[r0 : r0+nr, c0 : c0+nc] whose two ranges hold at most COV_MAXV distinct variables.
+// Requests are packed whole into chunks of at most MR = 16 distinct variables (one unit right-hand side each); a chunk
+// needs the Gram products (a, c), a <= c, of the columns its requests pair up, at most COV_NP.
+constexpr int COV_MAXV = 16;
+constexpr int COV_NP = COV_MAXV*(COV_MAXV + 1)/2;
+struct CovPack
+{
+  int nch = 0, maxvar = 0;
+  std::vector<int> var;        // [nch * 16] variables of a chunk, original order (-1: none)
+  std::vector<int> pptr, prod; // products of chunk ch: prod[pptr[ch] .. pptr[ch + 1]), each a*16 + c
+  std::vector<int> req_ch;     // chunk of each request
+  std::vector<int> e_ch, e_p;  // per output value: its chunk and the index of its product there
+  std::vector<int> kb0;        // dense: per chunk the first tile (of 64 variables) its solve needs
+};
+// iperm: the permutation of the factor (sparse; null: dense, requests ordered by variable)
+int cov_pack_requests(int N, const int* iperm, int nreq, const int* r0, const int* nr, const int* c0,
+                      const int* nc, CovPack& K, const char* who);
+void cov_pack_marginal(int N, const int* perm, CovPack& K);       // 16 consecutive (permuted) columns per chunk
+// a reach plan (sparse_multi.hip): per chunk the supernodes on the paths from its columns to the root as (chunk,
+// supernode) pairs sorted by (level, supernode), chunks cut into batches whose update blocks fit the scratch
+struct ReachPlan
+{
+  int nf = -1, nch = 0, npair = 0, nbatch = 0;
+  long visits = 0;                  // pairs = supernode visits of all chunks
+  int64_t scr_rows = 0;             // update-block rows of the largest batch
+  int *pair_sn = nullptr, *pair_ch = nullptr, *cp_ptr = nullptr, *wl = nullptr;
+  int64_t* pair_off = nullptr;      // first row of the pair's update block in its batch's scratch
+  double *gram = nullptr, *scr = nullptr;
+  std::vector<int> wl_ptr;          // [nbatch * nlevels + 1] into wl: the pairs of a batch by level
+};
+void reach_plan_release(ReachPlan& P);
+// a packed request list on the device, kept by the backend for the next call with the same arrays
+struct CovPlan
+{
+  std::vector<int> key;             // route, pattern, N, then the request arrays it was built for
+  CovPack K;
+  long ne = 0;                      // output values
+  double t_plan = 0.0;              // host seconds of the last build
+  int *var = nullptr, *kb0 = nullptr, *pcol = nullptr, *pptr = nullptr, *prod = nullptr, *e_ch = nullptr, *e_p = nullptr, *slot_ptr = nullptr;
+  int64_t* goff = nullptr;          // first product of a slot in gram
+  double *gram = nullptr, *out = nullptr;
+  ReachPlan R;                      // sparse, blocked route: slots are the (chunk, supernode) pairs
+};
+void cov_plan_release(CovPlan& P);
+int cov_plan_build(dlg_backend* b, CovPlan& P, int route, int which, int nreq, const int* r0, const int* nr, const int* c0,
+                   const int* nc, const char* who);
+uint64_t sparse_pattern_key(const dlg_backend* b);
+int sparse_cov_reach_plan(dlg_backend* b, CovPlan& P);            // R, goff, slot_ptr, pcol and gram of the reach route
+int sparse_cov_reach_run(dlg_backend* b, CovPlan& P);
+int sparse_cov_stats(const dlg_backend* b, long* nchunks, long* visits, int* nsn);
+int cov_unit_il(dlg_backend* b, const CovPlan& P, int ch, double* d_il);
+int cov_pick(dlg_backend* b, const CovPlan& P, int ch, const double* d_il);
+int cov_finish(dlg_backend* b, const CovPlan& P);
+int dense_cov_setup(dlg_backend* b, CovPlan& P);      // P.kb0
+int dense_cov_gram(dlg_backend* b, const CovPlan& P, double* d_work, size_t work_doubles);

@@ -1416,6 +1416,41 @@ double dogleg_getOutliernessTrace_newFeature_sparse(const double* JqueryFeature,
   return scale*(2.0 - trace_inv);
 }
 
+// ---- extension (not in the reference): covariance blocks from the factor held on the device (dlg_backend.h:
+// dlg_covariance_blocks).  What the reference's users get from cholmod_solve on ctx->factorization with unit right-hand sides.
+} // extern "C"
+namespace {
+bool cov_ready(dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx, const char* who)
+{
+  if(!point || !ctx) { MSG("%s(): no point or context", who); return false; }
+  const Driver* d = D(ctx);
+  if(d->sharded && d->nranks > 1) { MSG("%s() works on one rank only (this context has %d)", who, d->nranks); return false; }
+  return dogleg_computeJtJfactorization(point, ctx);
+}
+} // namespace
+extern "C" {
+
+int dogleg_amd_covariance_blocks(double* out, int nreq, const int* r0, const int* nr, const int* c0, const int* nc,
+                                 dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx)
+{
+  const char* who = "dogleg_amd_covariance_blocks";
+  if(nreq < 0 || (nreq > 0 && (!out || !r0 || !nr || !c0 || !nc))) { MSG("%s(): bad arguments", who); return -1; }
+  if(!cov_ready(point, ctx, who)) return -1;
+  Driver* d = D(ctx);
+  return with_point_factor(point, ctx, "covariance blocks",
+                           [&]{ return dlg_covariance_blocks(d->be, slot_of(d, point), nreq, r0, nr, c0, nc, out); }) ? 0 : -1;
+}
+
+int dogleg_amd_marginal_variances(double* var, dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx)
+{
+  const char* who = "dogleg_amd_marginal_variances";
+  if(!var) { MSG("%s(): bad arguments", who); return -1; }
+  if(!cov_ready(point, ctx, who)) return -1;
+  Driver* d = D(ctx);
+  return with_point_factor(point, ctx, "marginal variances",
+                           [&]{ return dlg_marginal_variances(d->be, slot_of(d, point), var); }) ? 0 : -1;
+}
+
 // ---- extension (not in the reference): multi-GPU.  See include/dogleg.h.
 int dogleg_amd_set_communicator(int rank, int nranks, int device, const void* rccl_unique_id128)
 {

@@ -575,10 +575,13 @@ __global__ void __launch_bounds__(64) k_trsv_diag_bwd(const double* __restrict__
 // LDS) -- the factor is read once per 16 right-hand sides.
 constexpr int DMR = 16;
 // X_blk = Linv_blk * Y_blk (forward) or Linv_blk^T * Y_blk (backward); blockIdx.y: the block of right-hand sides
-// at y + blockIdx.y*ystride
+// at y + blockIdx.y*ystride.  ystart (forward, may be null): the first tile of each block that is not zero -- a block
+// whose tiles up to kb are all zero stays as it is (the solve and the updates would leave exact zeros there)
 __global__ void __launch_bounds__(TPB) k_trsm_diag_m(const double* __restrict__ Linv, int kb, int nb,
-                                                     double* __restrict__ y, int transpose, size_t ystride)
+                                                     double* __restrict__ y, int transpose, size_t ystride,
+                                                     const int* __restrict__ ystart)
 {
+  if(ystart && kb < ystart[blockIdx.y]) return;
   __shared__ double v[NB*DMR];
   y += blockIdx.y*ystride;
   __shared__ double Ls[NB][NB + 1];
@@ -596,8 +599,10 @@ __global__ void __launch_bounds__(TPB) k_trsm_diag_m(const double* __restrict__ 
 }
 // forward: Y[i][:] -= L[i, kb:kb+nb] X[kb:kb+nb][:] for the rows i >= kb + nb; a wave per 16 rows
 __global__ void __launch_bounds__(TPB) k_trsm_update_fwd_m(const double* __restrict__ A, int lda, int kb, int nb,
-                                                           int n, double* __restrict__ y, size_t ystride)
+                                                           int n, double* __restrict__ y, size_t ystride,
+                                                           const int* __restrict__ ystart)
 {
+  if(ystart && kb < ystart[blockIdx.y]) return;
   __shared__ double v[NB*DMR];
   y += blockIdx.y*ystride;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, mm = lane & 15, kq = lane >> 4;
@@ -668,6 +673,35 @@ __global__ void __launch_bounds__(TPB) k_lev_gram_dense(const double* __restrict
   red[tid] = acc;
   __syncthreads();
   if(tid < np) { double sum = 0.0; for(int q = 0; q < TPB/32; q++) sum += red[q*32 + tid]; gram[(size_t)blockIdx.x*LEV_NP + tid] = sum; }
+}
+
+// covariance blocks (dense_cov_gram): the unit right-hand sides of nblk chunks from chunk q0 on, chunk q at il + q*N*DMR
+// (variables var[16 ch + c], -1: none) ...
+__global__ void __launch_bounds__(TPB) k_cov_units_dense(const int* __restrict__ var, int N, int q0, double* __restrict__ il)
+{
+  const size_t e = (size_t)blockIdx.x*TPB + threadIdx.x;
+  if(e >= (size_t)N*DMR) return;
+  const int k = (int)(e / DMR), c = (int)(e % DMR);
+  il[(size_t)blockIdx.y*N*DMR + e] = (var[(size_t)(q0 + blockIdx.y)*DMR + c] == k) ? 1.0 : 0.0;
+}
+// ... and the products of each solved block V = L^-1 [e_var]: rows kb0 .. n - 1 (above the chunk's first tile V is
+// zero), 4 row groups summed in a fixed order
+__global__ void __launch_bounds__(TPB) k_cov_gram_dense(const double* __restrict__ V, int n, int q0, const int* __restrict__ kb0_of,
+                                                        const int* __restrict__ pptr, const int* __restrict__ prod,
+                                                        const int64_t* __restrict__ goff, double* __restrict__ gram)
+{
+  __shared__ double red[4][COV_NP];
+  const int ch = q0 + blockIdx.x, tid = threadIdx.x, g = tid >> 6, p0 = pptr[ch], np = pptr[ch+1] - p0, kb0 = kb0_of[ch];
+  V += (size_t)blockIdx.x*n*DMR;
+  for(int t = tid & 63; t < np; t += 64)
+  {
+    const int a = prod[p0 + t] / DMR, c = prod[p0 + t] % DMR;
+    double acc = 0.0;
+    for(int k = kb0 + g; k < n; k += 4) acc += V[(size_t)k*DMR + a]*V[(size_t)k*DMR + c];
+    red[g][t] = acc;
+  }
+  __syncthreads();
+  if(tid < np) gram[goff[ch] + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
 // ------------------------------------------------------------ probes --------
@@ -1039,17 +1073,17 @@ int dense_solve_multi(dlg_backend* b, double* d_il)
   for(int kb = 0, blk = 0; kb < n; kb += NB, blk++)
   {
     const int nb = (n - kb < NB) ? n - kb : NB;
-    hipLaunchKernelGGL(k_trsm_diag_m, dim3(1), dim3(TPB), 0, st, b->Linv + (size_t)blk*NB*NB, kb, nb, d_il, 0, (size_t)0);
+    hipLaunchKernelGGL(k_trsm_diag_m, dim3(1), dim3(TPB), 0, st, b->Linv + (size_t)blk*NB*NB, kb, nb, d_il, 0, (size_t)0, nullptr);
     const int rem = n - kb - nb;
     if(rem > 0)
-      hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64))), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_il, (size_t)0);
+      hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64))), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_il, (size_t)0, nullptr);
   }
   const int nblk = dlg_cdiv(n, NB);
   for(int blk = nblk - 1; blk >= 0; blk--)
   {
     const int kb = blk*NB;
     const int nb = (n - kb < NB) ? n - kb : NB;
-    hipLaunchKernelGGL(k_trsm_diag_m, dim3(1), dim3(TPB), 0, st, b->Linv + (size_t)blk*NB*NB, kb, nb, d_il, 1, (size_t)0);
+    hipLaunchKernelGGL(k_trsm_diag_m, dim3(1), dim3(TPB), 0, st, b->Linv + (size_t)blk*NB*NB, kb, nb, d_il, 1, (size_t)0, nullptr);
     if(kb > 0)
       hipLaunchKernelGGL(k_trsm_update_bwd_m, dim3(dlg_cdiv(kb, 16*(TPB/64))), dim3(TPB), 0, st, b->G, n, kb, nb, d_il);
   }
@@ -1080,12 +1114,58 @@ int dense_leverage_gram(dlg_backend* b, int s, int fs, int nf, double* d_work, s
     for(int kb = 0, bi = 0; kb < n; kb += NB, bi++)
     {
       const int nb = (n - kb < NB) ? n - kb : NB;
-      hipLaunchKernelGGL(k_trsm_diag_m, dim3(1, nq), dim3(TPB), 0, st, b->Linv + (size_t)bi*NB*NB, kb, nb, d_work, 0, blk);
+      hipLaunchKernelGGL(k_trsm_diag_m, dim3(1, nq), dim3(TPB), 0, st, b->Linv + (size_t)bi*NB*NB, kb, nb, d_work, 0, blk, nullptr);
       const int rem = n - kb - nb;
       if(rem > 0)
-        hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64)), nq), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_work, blk);
+        hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64)), nq), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_work, blk, nullptr);
     }
     hipLaunchKernelGGL(k_lev_gram_dense, dim3(nq), dim3(TPB), 0, st, d_work, n, fs, d_gram + (size_t)q0*LEV_NP);
+  }
+  DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
+
+// covariance blocks: the forward half of dense_solve_multi on the unit columns of as many chunks at a time as d_work
+// holds, one launch sequence for all of them from the first tile any of them needs; each chunk's workgroups return at
+// once on the tiles above its own first tile P.kb0[ch] (the tile of its smallest variable: above it V is zero; the
+// chunks are sorted by variable, so a batch's chunks start near one another); one slot per chunk at P.goff[ch]
+// the first tile each chunk's forward solve needs: that of its smallest variable
+int dense_cov_setup(dlg_backend* b, CovPlan& P)
+{
+  CovPack& K = P.K;
+  K.kb0.assign(K.nch, 0);
+  for(int ch = 0; ch < K.nch; ch++)
+  {
+    int vmin = b->N;
+    for(int c = 0; c < DMR; c++) if(K.var[(size_t)ch*DMR + c] >= 0) vmin = std::min(vmin, K.var[(size_t)ch*DMR + c]);
+    K.kb0[ch] = vmin / NB*NB;
+  }
+  DLG_HIP(hipMalloc(&P.kb0, sizeof(int)*(size_t)std::max(K.nch, 1)));
+  if(K.nch > 0) DLG_HIP(hipMemcpy(P.kb0, K.kb0.data(), sizeof(int)*(size_t)K.nch, hipMemcpyHostToDevice));
+  return DLG_OK;
+}
+int dense_cov_gram(dlg_backend* b, const CovPlan& P, double* d_work, size_t work_doubles)
+{
+  const int n = b->N, nch = P.K.nch;
+  const size_t blk = (size_t)n*DMR;
+  const int per = (int)std::min<size_t>(work_doubles / blk, 65535);
+  if(per < 1) { dlg_set_error("dense covariance: scratch too small"); return DLG_ERR_NOMEM; }
+  hipStream_t st = b->stream;
+  for(int q0 = 0; q0 < nch; q0 += per)
+  {
+    const int nq = std::min(per, nch - q0);
+    int kb0 = n;
+    for(int q = q0; q < q0 + nq; q++) kb0 = std::min(kb0, P.K.kb0[q]);
+    hipLaunchKernelGGL(k_cov_units_dense, dim3(dlg_cdiv((long)blk, TPB), nq), dim3(TPB), 0, st, P.var, n, q0, d_work);
+    for(int kb = kb0; kb < n; kb += NB)
+    {
+      const int nb = (n - kb < NB) ? n - kb : NB;
+      hipLaunchKernelGGL(k_trsm_diag_m, dim3(1, nq), dim3(TPB), 0, st, b->Linv + (size_t)(kb / NB)*NB*NB, kb, nb, d_work, 0, blk, P.kb0 + q0);
+      const int rem = n - kb - nb;
+      if(rem > 0)
+        hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64)), nq), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_work, blk, P.kb0 + q0);
+    }
+    hipLaunchKernelGGL(k_cov_gram_dense, dim3(nq), dim3(TPB), 0, st, d_work, n, q0, P.kb0, P.pptr, P.prod, P.goff, P.gram);
   }
   DLG_LAUNCH_CHECK();
   return DLG_OK;

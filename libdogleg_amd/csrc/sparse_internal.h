@@ -137,16 +137,8 @@ struct SparseSym
   double *ms_scr = nullptr, *ms_y = nullptr; int ms_lds_f = 0, ms_lds_b = 0;     // multi-right-hand-side solves (sparse_multi.hip)
   // leverage blocks (sparse_multi.hip, sparse_leverage_reach): per chunk of 16 measurement rows, the supernodes on the paths
   // from its columns to the root (its reach) as (chunk, supernode) pairs, one plan per feature size (index fs - 1)
-  struct LevPlan
-  {
-    int nf = -1, nch = 0, npair = 0, nbatch = 0;
-    long visits = 0;                  // pairs = supernode visits of all chunks
-    int64_t scr_rows = 0;             // update-block rows of the largest batch
-    int *pair_sn = nullptr, *pair_ch = nullptr, *cp_ptr = nullptr, *wl = nullptr;
-    int64_t* pair_off = nullptr;      // first row of the pair's update block in its batch's scratch
-    double *gram = nullptr, *scr = nullptr;
-    std::vector<int> wl_ptr;          // [nbatch * nlevels + 1] into wl: the pairs of a batch by level
-  } lev[2];
+  typedef ReachPlan LevPlan;
+  LevPlan lev[2];
   int* lev_iperm = nullptr; std::vector<int> lev_jp, lev_ji; int lev_lds = 0;
   // speculative assembly beside K1 (sparse_assemble_speculative): second panel buffer, its state
   double* Lx_spec = nullptr; hipEvent_t ev_spec = nullptr, ev_spec_fork = nullptr;

@@ -15,6 +15,7 @@
 #include "sparse_internal.h"
 #include <algorithm>
 #include <cfloat>
+#include <cstdint>
 
 namespace {
 constexpr int MR = 16;                 // right-hand sides per pass
@@ -227,6 +228,80 @@ __device__ __forceinline__ int lev_lower_bound(const int* __restrict__ v, int n,
   return lo;
 }
 
+// the shared steps of the reach-restricted forward kernels (k_lev_fwd_level, k_cov_fwd_level), one (chunk, supernode) pair
+// per workgroup.  The updates of the chunk's pairs in front of pair p (pairs p0 .. p - 1): rows of their update blocks
+// inside [c0, c0 + w), subtracted from Ys in pair order.
+__device__ __forceinline__ void reach_gather(int p0, int p, int c0, int w, const int* __restrict__ pair_sn,
+                                             const int64_t* __restrict__ pair_off, const int* __restrict__ sn_c0,
+                                             const int* __restrict__ sn_rowptr, const int* __restrict__ sn_rows,
+                                             const double* __restrict__ scr, int* src_i0, int* src_i1, double* Ys, int tid)
+{
+  for(int b0 = p0; b0 < p; b0 += LEV_SRC)
+  {
+    const int nb = min(LEV_SRC, p - b0);
+    __syncthreads();
+    if(tid < nb)
+    {
+      const int d = pair_sn[b0 + tid], wd = sn_c0[d+1] - sn_c0[d];
+      const int rd = sn_rowptr[d+1] - sn_rowptr[d] - wd - 1;
+      const int* rows = sn_rows + sn_rowptr[d] + wd;
+      src_i0[tid] = lev_lower_bound(rows, rd, c0);
+      src_i1[tid] = lev_lower_bound(rows, rd, c0 + w);
+    }
+    __syncthreads();
+    for(int t = 0; t < nb; t++)
+    {
+      const int i0 = src_i0[t], i1 = src_i1[t];
+      if(i0 == i1) continue;                      // (the same for every thread)
+      const int d = pair_sn[b0 + t];
+      const int* rows = sn_rows + sn_rowptr[d] + (sn_c0[d+1] - sn_c0[d]);
+      const double* U = scr + (size_t)pair_off[b0 + t]*MR;
+      for(int e = tid; e < (i1 - i0)*MR; e += TPB)
+      {
+        const int i = i0 + e / MR, cc = e & (MR - 1);
+        Ys[(rows[i] - c0)*MR + cc] -= U[(size_t)i*MR + cc];
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+}
+// y_t = L_tt^-1 Ys, column by column (thread = right-hand side c, row group g), into Yd
+__device__ __forceinline__ void reach_sweep(const double* Lt, const double* dinv, int w, double* Ys, double* Yd, int c, int g)
+{
+  for(int j = 0; j < w; j++)
+  {
+    const double yj = Ys[j*MR + c]*dinv[j];
+    if(g == (j & 15)) Yd[j*MR + c] = yj;
+    for(int i = j + 1 + g; i < w; i += TPB/MR) Ys[i*MR + c] -= Lt[tri(i, j)]*yj;
+    __syncthreads();
+  }
+}
+// U = L_below y_t (r x MR) on the matrix cores: a wave takes row tiles of 16
+__device__ __forceinline__ void reach_below(const double* __restrict__ L, int nrows, int w, int r, const double* Yd,
+                                            double* __restrict__ U, int tid)
+{
+  const int lane = tid & 63, wv = tid >> 6, mm = lane & 15, kq = lane >> 4;
+  for(int t = wv; 16*t < r; t += TPB/64)
+  {
+    const int row = 16*t + mm;
+    const double* Lr = L + w + min(row, r - 1);
+    ms_v4d acc = {0.0, 0.0, 0.0, 0.0};
+    for(int k4 = 0; k4 < w; k4 += 8)
+    {
+      const int ka = k4 + kq, kb = k4 + 4 + kq;
+      const double a0 = (ka < w && row < r) ? Lr[(size_t)ka*nrows] : 0.0;
+      const double a1 = (kb < w && row < r) ? Lr[(size_t)kb*nrows] : 0.0;
+      const double b0 = (ka < w) ? Yd[ka*MR + mm] : 0.0;
+      const double b1 = (kb < w) ? Yd[kb*MR + mm] : 0.0;
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc, 0, 0, 0);
+    }
+#pragma unroll
+    for(int q = 0; q < 4; q++) { const int i = 16*t + kq + 4*q; if(i < r) U[(size_t)i*MR + mm] = acc[q]; }
+  }
+}
+
 __global__ void __launch_bounds__(TPB) k_lev_fwd_level(const int* __restrict__ wl,
                                                        const int* __restrict__ pair_sn,
                                                        const int* __restrict__ pair_ch,
@@ -268,65 +343,69 @@ __global__ void __launch_bounds__(TPB) k_lev_fwd_level(const int* __restrict__ w
     if(row < nrow_feat)
       for(int q = Jp[row]; q < Jp[row+1]; q++) { const int k = iperm[Ji[q]] - c0; if(k >= 0 && k < w) Ys[k*MR + tid] += Jv[q]; }
   }
-  // the updates of the chunk's pairs in front of this one: rows of their update blocks inside [c0, c0 + w)
-  for(int b0 = cp_ptr[ch]; b0 < p; b0 += LEV_SRC)
-  {
-    const int nb = min(LEV_SRC, p - b0);
-    __syncthreads();
-    if(tid < nb)
-    {
-      const int d = pair_sn[b0 + tid], wd = sn_c0[d+1] - sn_c0[d];
-      const int rd = sn_rowptr[d+1] - sn_rowptr[d] - wd - 1;
-      const int* rows = sn_rows + sn_rowptr[d] + wd;
-      src_i0[tid] = lev_lower_bound(rows, rd, c0);
-      src_i1[tid] = lev_lower_bound(rows, rd, c0 + w);
-    }
-    __syncthreads();
-    for(int t = 0; t < nb; t++)
-    {
-      const int i0 = src_i0[t], i1 = src_i1[t];
-      if(i0 == i1) continue;                      // (the same for every thread)
-      const int d = pair_sn[b0 + t];
-      const int* rows = sn_rows + sn_rowptr[d] + (sn_c0[d+1] - sn_c0[d]);
-      const double* U = scr + (size_t)pair_off[b0 + t]*MR;
-      for(int e = tid; e < (i1 - i0)*MR; e += TPB)
-      {
-        const int i = i0 + e / MR, cc = e & (MR - 1);
-        Ys[(rows[i] - c0)*MR + cc] -= U[(size_t)i*MR + cc];
-      }
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  for(int j = 0; j < w; j++)
-  {
-    const double yj = Ys[j*MR + c]*dinv[j];
-    if(g == (j & 15)) Yd[j*MR + c] = yj;
-    for(int i = j + 1 + g; i < w; i += TPB/MR) Ys[i*MR + c] -= Lt[tri(i, j)]*yj;
-    __syncthreads();
-  }
+  reach_gather(cp_ptr[ch], p, c0, w, pair_sn, pair_off, sn_c0, sn_rowptr, sn_rows, scr, src_i0, src_i1, Ys, tid);
+  reach_sweep(Lt, dinv, w, Ys, Yd, c, g);
   lev_gram_block(Yd, w, fs, red, gram + (size_t)p*LEV_NP, tid);
-  // U = L_below y_t on the matrix cores, into this pair's update block
-  const int lane = tid & 63, wv = tid >> 6, mm = lane & 15, kq = lane >> 4;
-  double* U = scr + (size_t)pair_off[p]*MR;
-  for(int t = wv; 16*t < r; t += TPB/64)
+  reach_below(L, nrows, w, r, Yd, scr + (size_t)pair_off[p]*MR, tid);   // into this pair's update block
+}
+
+// ---- covariance blocks (sparse_covariance_reach): the same forward solves with unit right-hand sides.  Column c of a chunk
+// is e at the permuted index pcol[c] (-1: unused), so it is non-zero only on the path from that column's supernode to the
+// root.  The pair stores the Gram products Yd^T Yd its chunk needs (prod: a*16 + c, a <= c) in its own slot.
+__global__ void __launch_bounds__(TPB) k_cov_fwd_level(const int* __restrict__ wl,
+                                                       const int* __restrict__ pair_sn,
+                                                       const int* __restrict__ pair_ch,
+                                                       const int64_t* __restrict__ pair_off,
+                                                       const int* __restrict__ cp_ptr,
+                                                       const int* __restrict__ sn_c0,
+                                                       const int* __restrict__ sn_rowptr,
+                                                       const int* __restrict__ sn_rows,
+                                                       const int64_t* __restrict__ sn_lx,
+                                                       const double* __restrict__ Lx,
+                                                       const int* __restrict__ pcol,
+                                                       const int* __restrict__ pptr,
+                                                       const int* __restrict__ prod,
+                                                       const int64_t* __restrict__ goff,
+                                                       double* __restrict__ scr,
+                                                       double* __restrict__ gram)
+{
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  __shared__ int src_i0[LEV_SRC], src_i1[LEV_SRC];
+  __shared__ double red[MR*MR];
+  const int p = wl[blockIdx.x], s = pair_sn[p], ch = pair_ch[p];
+  const int c0 = sn_c0[s], w = sn_c0[s+1] - c0;
+  const int nrows = sn_rowptr[s+1] - sn_rowptr[s];
+  const int r = nrows - w - 1;
+  const double* L = Lx + sn_lx[s];
+  const int tid = threadIdx.x, c = tid & (MR - 1), g = tid >> 4;
+  double* Lt = lds;
+  double* dinv = Lt + ((w*(w + 1)/2 + 1) & ~1);
+  double* Ys = dinv + ((w + 1) & ~1);
+  double* Yd = Ys + w*MR;
+  ms_stage_top(L, nrows, w, Lt, dinv, tid);
+  for(int e = tid; e < w*MR; e += TPB) Ys[e] = 0.0;
+  __syncthreads();
+  if(tid < MR) { const int k = pcol[(size_t)ch*MR + tid] - c0; if(k >= 0 && k < w) Ys[k*MR + tid] = 1.0; }
+  reach_gather(cp_ptr[ch], p, c0, w, pair_sn, pair_off, sn_c0, sn_rowptr, sn_rows, scr, src_i0, src_i1, Ys, tid);
+  reach_sweep(Lt, dinv, w, Ys, Yd, c, g);
+  // Gram Yd^T Yd (16 x 16) on the matrix cores, one wave, K = w padded to a multiple of 4: A[i][k] = Yd[k][i] and
+  // B[k][j] = Yd[k][j] are the same lane value; D[i][j] is register q of lane 16*kq + j with i = kq + 4 q (the f64 map)
+  if(tid < 64)
   {
-    const int row = 16*t + mm;
-    const double* Lr = L + w + min(row, r - 1);
+    const int mm = tid & 15, kq = tid >> 4;
     ms_v4d acc = {0.0, 0.0, 0.0, 0.0};
-    for(int k4 = 0; k4 < w; k4 += 8)
+    for(int k4 = 0; k4 < w; k4 += 4)
     {
-      const int ka = k4 + kq, kb = k4 + 4 + kq;
-      const double a0 = (ka < w && row < r) ? Lr[(size_t)ka*nrows] : 0.0;
-      const double a1 = (kb < w && row < r) ? Lr[(size_t)kb*nrows] : 0.0;
-      const double b0 = (ka < w) ? Yd[ka*MR + mm] : 0.0;
-      const double b1 = (kb < w) ? Yd[kb*MR + mm] : 0.0;
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc, 0, 0, 0);
+      const double a = (k4 + kq < w) ? Yd[(k4 + kq)*MR + mm] : 0.0;
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, acc, 0, 0, 0);
     }
 #pragma unroll
-    for(int q = 0; q < 4; q++) { const int i = 16*t + kq + 4*q; if(i < r) U[(size_t)i*MR + mm] = acc[q]; }
+    for(int q = 0; q < 4; q++) red[(kq + 4*q)*MR + mm] = acc[q];
   }
+  __syncthreads();
+  const int q0 = pptr[ch], np = pptr[ch+1] - q0;
+  if(tid < np) gram[goff[p] + tid] = red[prod[q0 + tid]];
+  reach_below(L, nrows, w, r, Yd, scr + (size_t)pair_off[p]*MR, tid);
 }
 
 // the Gram products of a chunk from its solved block U = (JtJ + lambda I)^-1 Jt[:, rows] (interleaved, original order):
@@ -373,6 +452,38 @@ __global__ void __launch_bounds__(TPB) k_lev_finish(int nf, int fs, const int* _
   const double xBx = (x0*x0*j00 + 2.0*x0*x1*j01 + x1*x1*j11)/det;
   const double v0 = x0*j00 + x1*j01, v1 = x0*j01 + x1*j11;
   out[f] = (xBx + (v0*v0 + v1*v1)/(det*det))*k;
+}
+
+// covariance: per output element e, the product e_p[e] of chunk e_ch[e], its slots summed in order (slot q at goff[q];
+// the slots of chunk ch: [slot_ptr[ch], slot_ptr[ch + 1]))
+__global__ void __launch_bounds__(TPB) k_cov_finish(long ne, const int* __restrict__ e_ch, const int* __restrict__ e_p,
+                                                    const int* __restrict__ slot_ptr, const int64_t* __restrict__ goff,
+                                                    const double* __restrict__ gram, double* __restrict__ out)
+{
+  const long e = (long)blockIdx.x*TPB + threadIdx.x;
+  if(e >= ne) return;
+  const int ch = e_ch[e], t = e_p[e];
+  double acc = 0.0;
+  for(int q = slot_ptr[ch]; q < slot_ptr[ch+1]; q++) acc += gram[goff[q] + t];
+  out[e] = acc;
+}
+// the full-sweep route: unit right-hand sides of chunk ch (variables var[c], original order, -1: none), interleaved
+__global__ void __launch_bounds__(TPB) k_cov_unit_il(const int* __restrict__ var, int ch, int N, double* __restrict__ il)
+{
+  const size_t e = (size_t)blockIdx.x*TPB + threadIdx.x;
+  if(e >= (size_t)N*MR) return;
+  const int k = (int)(e / MR), c = (int)(e % MR);
+  il[e] = (var[(size_t)ch*MR + c] == k) ? 1.0 : 0.0;
+}
+// ... and its products from the solved block X = Sigma[:, var]: product (a, c) is X[var[a]][c]
+__global__ void __launch_bounds__(TPB) k_cov_pick(const int* __restrict__ var, const int* __restrict__ pptr,
+                                                  const int* __restrict__ prod, const int64_t* __restrict__ goff, int ch,
+                                                  const double* __restrict__ X, double* __restrict__ gram)
+{
+  const int t = threadIdx.x, q0 = pptr[ch];
+  if(t >= pptr[ch+1] - q0) return;
+  const int a = prod[q0 + t] / MR, c = prod[q0 + t] % MR;
+  gram[goff[ch] + t] = X[(size_t)var[(size_t)ch*MR + a]*MR + c];
 }
 
 size_t ms_lds_fwd(int w) { return sizeof(double)*(size_t)(((w*(w + 1)/2 + 1) & ~1) + ((w + 1) & ~1) + 2*w*MR); }
@@ -443,40 +554,23 @@ int sparse_jt_chunk_interleaved(dlg_backend* b, int s, int row0, int ncols, doub
 }
 
 // ---- leverage blocks: the reach of every chunk, launched level by level over many chunks -------------------------------
-namespace {
-constexpr int64_t LEV_BATCH_ROWS = (int64_t)1 << 21;     // update-block rows of the chunks of one batch (256 MB of scratch)
-
-void lev_plan_release(SparseSym::LevPlan& P)
+void reach_plan_release(ReachPlan& P)
 {
   for(void* q : {(void*)P.pair_sn, (void*)P.pair_ch, (void*)P.cp_ptr, (void*)P.wl, (void*)P.pair_off, (void*)P.gram, (void*)P.scr})
     if(q) (void)hipFree(q);
-  P = SparseSym::LevPlan();
+  P = ReachPlan();
 }
+namespace {
+constexpr int64_t LEV_BATCH_ROWS = (int64_t)1 << 21;     // update-block rows of the chunks of one batch (256 MB of scratch)
 
-// the (chunk, supernode) pairs of the chunks of nf features of fs rows: every chunk's reach sorted by (level, supernode),
-// chunks cut into batches of at most LEV_BATCH_ROWS update-block rows, a batch's pairs listed by level
-int lev_plan_build(dlg_backend* b, int fs, int nf)
+struct ReachHost { std::vector<int> pair_sn, pair_ch, cp_ptr, wl, wl_ptr; std::vector<int64_t> pair_off; int nbatch = 0; int64_t scr_rows = 0; };
+
+// the (chunk, supernode) pairs of nch chunks whose columns start at the supernodes starts(ch, list) lists: every chunk's
+// reach (the union of the paths from those to the root) sorted by (level, supernode), chunks cut into batches of at most
+// LEV_BATCH_ROWS update-block rows, a batch's pairs listed by level.  Host only.
+template <class F> void reach_build(const SymHost& H, int nch, F starts, ReachHost& R)
 {
-  SparseSym* Y = b->sym;
-  const SymHost& H = Y->H;
-  SparseSym::LevPlan& P = Y->lev[fs - 1];
-  if(P.nf == nf) return DLG_OK;
-  DLG_HIP(hipStreamSynchronize(b->stream));
-  lev_plan_release(P);
-  if(!Y->lev_iperm)
-  {
-    DLG_CHECK(upload(Y->lev_iperm, H.iperm)); Y->allocs.push_back(Y->lev_iperm);
-    const int mloc = dlg_mloc(b);
-    Y->lev_jp.resize((size_t)mloc + 1);
-    DLG_HIP(hipMemcpy(Y->lev_jp.data(), Y->Jp, sizeof(int)*((size_t)mloc + 1), hipMemcpyDeviceToHost));
-    Y->lev_ji.resize((size_t)Y->lev_jp[mloc]);
-    if(!Y->lev_ji.empty()) DLG_HIP(hipMemcpy(Y->lev_ji.data(), Y->Ji, sizeof(int)*Y->lev_ji.size(), hipMemcpyDeviceToHost));
-    int wmax = 1;
-    for(int s = 0; s < H.nsn; s++) wmax = std::max(wmax, H.sn_c0[s+1] - H.sn_c0[s]);
-    Y->lev_lds = (int)ms_lds_fwd(wmax);
-    DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lev_fwd_level), hipFuncAttributeMaxDynamicSharedMemorySize, Y->lev_lds));
-  }
-  const int nsn = H.nsn, nrow = nf*fs, nch = dlg_cdiv(nrow, MR);
+  const int nsn = H.nsn;
   std::vector<int> parent(nsn), rbelow(nsn);
   for(int s = 0; s < nsn; s++)
   {
@@ -484,22 +578,24 @@ int lev_plan_build(dlg_backend* b, int fs, int nf)
     rbelow[s] = H.sn_rowptr[s+1] - H.sn_rowptr[s] - w - 1;
     parent[s] = rbelow[s] > 0 ? H.col_sn[H.sn_rows[H.sn_rowptr[s] + w]] : -1;   // the supernode of the first row below
   }
-  std::vector<int> stamp(nsn, -1), pair_sn, pair_ch, cp_ptr(1, 0), reach;
+  std::vector<int> stamp(nsn, -1), reach, st;
+  std::vector<int>& pair_sn = R.pair_sn; std::vector<int>& pair_ch = R.pair_ch; std::vector<int>& cp_ptr = R.cp_ptr;
+  cp_ptr.assign(1, 0);
   for(int ch = 0; ch < nch; ch++)
   {
-    reach.clear();
-    for(int row = ch*MR; row < std::min(nrow, ch*MR + MR); row++)
-      for(int q = Y->lev_jp[row]; q < Y->lev_jp[row+1]; q++)
-        for(int s = H.col_sn[H.iperm[Y->lev_ji[q]]]; s >= 0 && stamp[s] != ch; s = parent[s]) { stamp[s] = ch; reach.push_back(s); }
+    reach.clear(); st.clear();
+    starts(ch, st);
+    for(int s0 : st)
+      for(int s = s0; s >= 0 && stamp[s] != ch; s = parent[s]) { stamp[s] = ch; reach.push_back(s); }
     std::sort(reach.begin(), reach.end(), [&](int a, int c) { return H.sn_level[a] != H.sn_level[c] ? H.sn_level[a] < H.sn_level[c] : a < c; });
     for(int s : reach) { pair_sn.push_back(s); pair_ch.push_back(ch); }
     cp_ptr.push_back((int)pair_sn.size());
   }
   const int npair = (int)pair_sn.size(), nl = H.nlevels;
-  std::vector<int64_t> pair_off(npair);
-  std::vector<int> wl; wl.reserve(npair);
+  R.pair_off.assign(npair, 0);
+  std::vector<int>& wl = R.wl; wl.reserve(npair);
   std::vector<int> cnt(nl);
-  P.wl_ptr.assign(1, 0);
+  R.wl_ptr.assign(1, 0);
   for(int ch0 = 0; ch0 < nch;)
   {
     // a batch: whole chunks while their update blocks fit (at least one chunk)
@@ -509,30 +605,309 @@ int lev_plan_build(dlg_backend* b, int fs, int nf)
       int64_t rc = 0;
       for(int q = cp_ptr[ch1]; q < cp_ptr[ch1+1]; q++) rc += rbelow[pair_sn[q]];
       if(ch1 > ch0 && rows + rc > LEV_BATCH_ROWS) break;
-      for(int q = cp_ptr[ch1]; q < cp_ptr[ch1+1]; q++) { pair_off[q] = rows; rows += rbelow[pair_sn[q]]; }
+      for(int q = cp_ptr[ch1]; q < cp_ptr[ch1+1]; q++) { R.pair_off[q] = rows; rows += rbelow[pair_sn[q]]; }
       ch1++;
     }
-    P.scr_rows = std::max(P.scr_rows, rows);
+    R.scr_rows = std::max(R.scr_rows, rows);
     std::fill(cnt.begin(), cnt.end(), 0);
     for(int q = cp_ptr[ch0]; q < cp_ptr[ch1]; q++) cnt[H.sn_level[pair_sn[q]]]++;
     const size_t base = wl.size();
     std::vector<size_t> at(nl);
-    for(int l = 0, acc = 0; l < nl; l++) { at[l] = base + acc; acc += cnt[l]; P.wl_ptr.push_back((int)(base + acc)); }
+    for(int l = 0, acc = 0; l < nl; l++) { at[l] = base + acc; acc += cnt[l]; R.wl_ptr.push_back((int)(base + acc)); }
     wl.resize(base + (cp_ptr[ch1] - cp_ptr[ch0]));
     for(int q = cp_ptr[ch0]; q < cp_ptr[ch1]; q++) wl[at[H.sn_level[pair_sn[q]]]++] = q;
-    P.nbatch++;
+    R.nbatch++;
     ch0 = ch1;
   }
-  DLG_CHECK(upload(P.pair_sn, pair_sn)); DLG_CHECK(upload(P.pair_ch, pair_ch)); DLG_CHECK(upload(P.cp_ptr, cp_ptr));
-  DLG_CHECK(upload(P.wl, wl)); DLG_CHECK(upload(P.pair_off, pair_off));
-  DLG_HIP(hipMalloc(&P.gram, sizeof(double)*LEV_NP*(size_t)std::max(npair, 1)));
+}
+// the device half of a reach plan (its gram is the caller's)
+int reach_upload(const ReachHost& R, int nch, ReachPlan& P)
+{
+  DLG_CHECK(upload(P.pair_sn, R.pair_sn)); DLG_CHECK(upload(P.pair_ch, R.pair_ch)); DLG_CHECK(upload(P.cp_ptr, R.cp_ptr));
+  DLG_CHECK(upload(P.wl, R.wl)); DLG_CHECK(upload(P.pair_off, R.pair_off));
+  P.wl_ptr = R.wl_ptr; P.nbatch = R.nbatch; P.scr_rows = R.scr_rows;
   DLG_HIP(hipMalloc(&P.scr, sizeof(double)*MR*(size_t)std::max<int64_t>(P.scr_rows, 1)));
-  P.nf = nf; P.nch = nch; P.npair = npair; P.visits = npair;
+  P.nch = nch; P.npair = (int)R.pair_sn.size(); P.visits = P.npair;
   return DLG_OK;
+}
+// what both reach routes need once per pattern: iperm on the device, the LDS of the widest supernode
+int reach_setup(dlg_backend* b)
+{
+  SparseSym* Y = b->sym;
+  const SymHost& H = Y->H;
+  if(Y->lev_iperm) return DLG_OK;
+  DLG_CHECK(upload(Y->lev_iperm, H.iperm)); Y->allocs.push_back(Y->lev_iperm);
+  const int mloc = dlg_mloc(b);
+  Y->lev_jp.resize((size_t)mloc + 1);
+  DLG_HIP(hipMemcpy(Y->lev_jp.data(), Y->Jp, sizeof(int)*((size_t)mloc + 1), hipMemcpyDeviceToHost));
+  Y->lev_ji.resize((size_t)Y->lev_jp[mloc]);
+  if(!Y->lev_ji.empty()) DLG_HIP(hipMemcpy(Y->lev_ji.data(), Y->Ji, sizeof(int)*Y->lev_ji.size(), hipMemcpyDeviceToHost));
+  int wmax = 1;
+  for(int s = 0; s < H.nsn; s++) wmax = std::max(wmax, H.sn_c0[s+1] - H.sn_c0[s]);
+  Y->lev_lds = (int)ms_lds_fwd(wmax);
+  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lev_fwd_level), hipFuncAttributeMaxDynamicSharedMemorySize, Y->lev_lds));
+  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_fwd_level), hipFuncAttributeMaxDynamicSharedMemorySize, Y->lev_lds));
+  return DLG_OK;
+}
+
+// the (chunk, supernode) pairs of the chunks of nf features of fs rows
+int lev_plan_build(dlg_backend* b, int fs, int nf)
+{
+  SparseSym* Y = b->sym;
+  const SymHost& H = Y->H;
+  SparseSym::LevPlan& P = Y->lev[fs - 1];
+  if(P.nf == nf) return DLG_OK;
+  DLG_HIP(hipStreamSynchronize(b->stream));
+  reach_plan_release(P);
+  DLG_CHECK(reach_setup(b));
+  const int nrow = nf*fs, nch = dlg_cdiv(nrow, MR);
+  ReachHost R;
+  reach_build(H, nch, [&](int ch, std::vector<int>& st) {
+    for(int row = ch*MR; row < std::min(nrow, ch*MR + MR); row++)
+      for(int q = Y->lev_jp[row]; q < Y->lev_jp[row+1]; q++) st.push_back(H.col_sn[H.iperm[Y->lev_ji[q]]]);
+  }, R);
+  DLG_CHECK(reach_upload(R, nch, P));
+  DLG_HIP(hipMalloc(&P.gram, sizeof(double)*LEV_NP*(size_t)std::max(P.npair, 1)));
+  P.nf = nf;
+  return DLG_OK;
+}
+
+// ---- covariance blocks: packing requests into chunks (host) ----------------------------------------------------------
+// the distinct variables of a request, ascending: one or two ranges
+void cov_req_vars(int r0, int nr, int c0, int nc, std::vector<int>& v)
+{
+  v.clear();
+  for(int i = 0; i < nr; i++) v.push_back(r0 + i);
+  for(int j = 0; j < nc; j++) v.push_back(c0 + j);
+  std::sort(v.begin(), v.end());
+  v.erase(std::unique(v.begin(), v.end()), v.end());
 }
 } // namespace
 
-void sparse_leverage_free(SparseSym* Y) { for(auto& P : Y->lev) lev_plan_release(P); }
+// Requests sorted by the elimination position (permuted column: a postorder of the tree) of their shallowest column, then
+// of their deepest (dense: the largest variable, then the smallest), so that requests sharing their shallowest variables
+// are neighbours -- in bundle adjustment the points are eliminated first, and a camera's blocks with its points follow
+// one another; then packed next-fit into chunks of at most 16 distinct variables, a request whole into one chunk; a
+// variable already in the chunk is not repeated.
+int cov_pack_requests(int N, const int* iperm, int nreq, const int* r0, const int* nr, const int* c0,
+                      const int* nc, CovPack& K, const char* who)
+{
+  K = CovPack();
+  std::vector<int64_t> key_hi(nreq), key_lo(nreq);
+  std::vector<int> v;
+  for(int q = 0; q < nreq; q++)
+  {
+    if(nr[q] < 1 || nc[q] < 1 || r0[q] < 0 || c0[q] < 0 || r0[q] > N - nr[q] || c0[q] > N - nc[q])
+    { dlg_set_error("%s: request %d (rows %d + %d, columns %d + %d) is empty or outside the %d variables", who, q, r0[q], nr[q], c0[q], nc[q], N); return DLG_ERR_ARG; }
+    if(nr[q] > COV_MAXV || nc[q] > COV_MAXV) v.assign(COV_MAXV + 1, 0);
+    else cov_req_vars(r0[q], nr[q], c0[q], nc[q], v);
+    if((int)v.size() > COV_MAXV)
+    { dlg_set_error("%s: request %d spans more than %d distinct variables; take wider blocks of the inverse from dlg_solve_multi with unit columns", who, q, COV_MAXV); return DLG_ERR_ARG; }
+    int64_t hi = -1, lo = INT64_MAX;
+    for(int x : v) { const int64_t k = iperm ? (int64_t)iperm[x] : (int64_t)x; hi = std::max(hi, k); lo = std::min(lo, k); }
+    key_hi[q] = hi; key_lo[q] = lo;
+  }
+  std::vector<int> ord(nreq);
+  for(int q = 0; q < nreq; q++) ord[q] = q;
+  std::sort(ord.begin(), ord.end(), [&](int a, int c) { return key_hi[a] != key_hi[c] ? key_hi[a] < key_hi[c] : key_lo[a] != key_lo[c] ? key_lo[a] < key_lo[c] : a < c; });
+  K.req_ch.assign(nreq, -1);
+  std::vector<int> cur;                      // variables of the open chunk
+  std::vector<int> ch_first(1, 0);           // requests of chunk ch: ord[ch_first[ch] .. ch_first[ch + 1])
+  for(int i = 0; i < nreq; i++)
+  {
+    const int q = ord[i];
+    cov_req_vars(r0[q], nr[q], c0[q], nc[q], v);
+    int add = 0;
+    for(int x : v) add += std::find(cur.begin(), cur.end(), x) == cur.end();
+    if((int)cur.size() + add > COV_MAXV)
+    {
+      K.maxvar = std::max(K.maxvar, (int)cur.size());
+      for(int c = 0; c < MR; c++) K.var.push_back(c < (int)cur.size() ? cur[c] : -1);
+      cur.clear(); ch_first.push_back(i);
+    }
+    for(int x : v) if(std::find(cur.begin(), cur.end(), x) == cur.end()) cur.push_back(x);
+    K.req_ch[q] = (int)ch_first.size() - 1;
+  }
+  if(nreq > 0)
+  {
+    K.maxvar = std::max(K.maxvar, (int)cur.size());
+    for(int c = 0; c < MR; c++) K.var.push_back(c < (int)cur.size() ? cur[c] : -1);
+    ch_first.push_back(nreq);
+  }
+  K.nch = (int)K.var.size() / MR;
+  // products: per chunk in the order its requests first need them; per output value (request order) its product
+  std::vector<int> pidx(MR*MR, -1);
+  std::vector<int64_t> e0(nreq + 1, 0);
+  for(int q = 0; q < nreq; q++) e0[q+1] = e0[q] + (int64_t)nr[q]*nc[q];
+  K.e_ch.resize(e0[nreq]); K.e_p.resize(e0[nreq]);
+  K.pptr.assign(1, 0);
+  for(int ch = 0; ch < K.nch; ch++)
+  {
+    std::fill(pidx.begin(), pidx.end(), -1);
+    const int* vv = K.var.data() + (size_t)ch*MR;
+    auto loc = [&](int x) { int c = 0; while(vv[c] != x) c++; return c; };
+    for(int i = ch_first[ch]; i < ch_first[ch+1]; i++)
+    {
+      const int q = ord[i];
+      int lr[COV_MAXV], lc[COV_MAXV];
+      for(int a = 0; a < nr[q]; a++) lr[a] = loc(r0[q] + a);
+      for(int c = 0; c < nc[q]; c++) lc[c] = loc(c0[q] + c);
+      for(int a = 0; a < nr[q]; a++)
+        for(int c = 0; c < nc[q]; c++)
+        {
+          const int x = std::min(lr[a], lc[c]), y = std::max(lr[a], lc[c]);
+          int& t = pidx[x*MR + y];
+          if(t < 0) { t = (int)K.prod.size() - K.pptr[ch]; K.prod.push_back(x*MR + y); }
+          const int64_t e = e0[q] + (int64_t)a*nc[q] + c;
+          K.e_ch[e] = ch; K.e_p[e] = t;
+        }
+    }
+    K.pptr.push_back((int)K.prod.size());
+  }
+  return DLG_OK;
+}
+void cov_pack_marginal(int N, const int* perm, CovPack& K)
+{
+  K = CovPack();
+  K.nch = dlg_cdiv(N, MR);
+  K.var.assign((size_t)K.nch*MR, -1);
+  K.pptr.assign(1, 0);
+  K.e_ch.resize(N); K.e_p.resize(N);
+  for(int ch = 0; ch < K.nch; ch++)
+  {
+    const int n = std::min(MR, N - ch*MR);
+    for(int c = 0; c < n; c++)
+    {
+      const int k = ch*MR + c, x = perm ? perm[k] : k;
+      K.var[(size_t)ch*MR + c] = x;
+      K.prod.push_back(c*MR + c);
+      K.e_ch[x] = ch; K.e_p[x] = c;
+    }
+    K.pptr.push_back((int)K.prod.size());
+    K.maxvar = std::max(K.maxvar, n);
+  }
+}
+void cov_plan_release(CovPlan& P)
+{
+  for(void* q : {(void*)P.var, (void*)P.kb0, (void*)P.pcol, (void*)P.pptr, (void*)P.prod, (void*)P.e_ch, (void*)P.e_p, (void*)P.slot_ptr,
+                 (void*)P.goff, (void*)P.gram, (void*)P.out})
+    if(q) (void)hipFree(q);
+  reach_plan_release(P.R);
+  P = CovPlan();
+}
+
+// the reach route of a packed plan: every chunk's reach from its columns' supernodes, a slot of the chunk's products per pair
+int sparse_cov_reach_plan(dlg_backend* b, CovPlan& P)
+{
+  SparseSym* Y = b->sym;
+  const SymHost& H = Y->H;
+  DLG_CHECK(reach_setup(b));
+  const CovPack& K = P.K;
+  ReachHost R;
+  reach_build(H, K.nch, [&](int ch, std::vector<int>& st) {
+    for(int c = 0; c < MR; c++) { const int x = K.var[(size_t)ch*MR + c]; if(x >= 0) st.push_back(H.col_sn[H.iperm[x]]); }
+  }, R);
+  DLG_CHECK(reach_upload(R, K.nch, P.R));
+  std::vector<int64_t> goff(R.pair_sn.size() + 1, 0);
+  for(size_t q = 0; q < R.pair_sn.size(); q++) { const int ch = R.pair_ch[q]; goff[q+1] = goff[q] + (K.pptr[ch+1] - K.pptr[ch]); }
+  std::vector<int> pcol(K.var.size());
+  for(size_t i = 0; i < K.var.size(); i++) pcol[i] = K.var[i] >= 0 ? H.iperm[K.var[i]] : -1;
+  DLG_CHECK(upload(P.goff, goff)); DLG_CHECK(upload(P.pcol, pcol));
+  DLG_HIP(hipMalloc(&P.gram, sizeof(double)*(size_t)std::max<int64_t>(goff.back(), 1)));
+  P.slot_ptr = nullptr;                      // (R.cp_ptr)
+  return DLG_OK;
+}
+int sparse_cov_reach_run(dlg_backend* b, CovPlan& P)
+{
+  SparseSym* Y = b->sym;
+  DLG_CHECK(reach_setup(b));                 // (the LDS attribute and size of this pattern's widest supernode)
+  const int nl = Y->H.nlevels;
+  const ReachPlan& R = P.R;
+  for(int bt = 0; bt < R.nbatch; bt++)
+    for(int l = 0; l < nl; l++)
+    {
+      const int w0 = R.wl_ptr[(size_t)bt*nl + l], n = R.wl_ptr[(size_t)bt*nl + l + 1] - w0;
+      if(n > 0)
+        hipLaunchKernelGGL(k_cov_fwd_level, dim3(n), dim3(TPB), Y->lev_lds, b->stream, R.wl + w0, R.pair_sn, R.pair_ch, R.pair_off,
+                           R.cp_ptr, Y->sn_c0, Y->sn_rowptr, Y->sn_rows, Y->sn_lx, Y->Lx, P.pcol, P.pptr, P.prod, P.goff, R.scr, P.gram);
+    }
+  DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
+// build plan P for route 0 (sparse, reach), 1 (sparse, full sweep) or 2 (dense): which 0, the requests; 1, the marginal
+// variances
+int cov_plan_build(dlg_backend* b, CovPlan& P, int route, int which, int nreq, const int* r0, const int* nr, const int* c0,
+                   const int* nc, const char* who)
+{
+  const SymHost* H = route < 2 ? &b->sym->H : nullptr;
+  if(which == 0) DLG_CHECK(cov_pack_requests(b->N, H ? H->iperm.data() : nullptr, nreq, r0, nr, c0, nc, P.K, who));
+  else cov_pack_marginal(b->N, H ? H->perm.data() : nullptr, P.K);
+  const CovPack& K = P.K;
+  P.ne = (long)K.e_ch.size();
+  DLG_CHECK(upload(P.var, K.var)); DLG_CHECK(upload(P.pptr, K.pptr)); DLG_CHECK(upload(P.prod, K.prod));
+  DLG_CHECK(upload(P.e_ch, K.e_ch)); DLG_CHECK(upload(P.e_p, K.e_p));
+  DLG_HIP(hipMalloc(&P.out, sizeof(double)*(size_t)std::max<long>(P.ne, 1)));
+  if(route == 0) return sparse_cov_reach_plan(b, P);
+  if(route == 2) DLG_CHECK(dense_cov_setup(b, P));
+  // one slot per chunk
+  std::vector<int> slot_ptr(K.nch + 1);
+  std::vector<int64_t> goff(K.nch + 1);
+  for(int ch = 0; ch <= K.nch; ch++) { slot_ptr[ch] = ch; goff[ch] = K.pptr[ch]; }
+  DLG_CHECK(upload(P.slot_ptr, slot_ptr)); DLG_CHECK(upload(P.goff, goff));
+  DLG_HIP(hipMalloc(&P.gram, sizeof(double)*(size_t)std::max(K.pptr.back(), 1)));
+  return DLG_OK;
+}
+uint64_t sparse_pattern_key(const dlg_backend* b) { return b->sym ? b->sym->pat_key : 0; }
+int sparse_cov_stats(const dlg_backend* b, long* nchunks, long* visits, int* nsn)
+{
+  if(!b->cov || b->cov_last < 0) { dlg_set_error("no covariance plan has been run"); return DLG_ERR_STATE; }
+  const CovPlan& P = b->cov[b->cov_last];
+  *nchunks = P.K.nch; *visits = P.R.npair > 0 ? P.R.visits : 0; *nsn = b->sym ? b->sym->H.nsn : 0;
+  return DLG_OK;
+}
+int cov_unit_il(dlg_backend* b, const CovPlan& P, int ch, double* d_il)
+{
+  hipLaunchKernelGGL(k_cov_unit_il, dim3(dlg_cdiv((long)b->N*MR, TPB)), dim3(TPB), 0, b->stream, P.var, ch, b->N, d_il);
+  DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
+int cov_pick(dlg_backend* b, const CovPlan& P, int ch, const double* d_il)
+{
+  hipLaunchKernelGGL(k_cov_pick, dim3(1), dim3(TPB), 0, b->stream, P.var, P.pptr, P.prod, P.goff, ch, d_il, P.gram);
+  DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
+int cov_finish(dlg_backend* b, const CovPlan& P)
+{
+  if(P.ne <= 0) return DLG_OK;
+  hipLaunchKernelGGL(k_cov_finish, dim3(dlg_cdiv(P.ne, TPB)), dim3(TPB), 0, b->stream, P.ne, P.e_ch, P.e_p,
+                     P.R.cp_ptr ? P.R.cp_ptr : P.slot_ptr, P.goff, P.gram, P.out);
+  DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
+
+// host only: the symbolic phase on a pattern and the packing and reach of a request list (the CPU tests check the
+// packing without a GPU).  stats: {chunks, pair visits, most distinct variables in a chunk}
+extern "C" int dlg_covariance_plan_probe(int N, int M, const int* colptr, const int* rowidx, int nreq, const int* r0,
+                                         const int* nr, const int* c0, const int* nc, int* chunk_of_req, long* stats, int nstats)
+{
+  if(nreq < 0 || (nreq > 0 && (!r0 || !nr || !c0 || !nc))) { dlg_set_error("dlg_covariance_plan_probe: bad argument"); return DLG_ERR_ARG; }
+  SymHost H;
+  char err[512];
+  if(sym_analyze(H, N, M, colptr, rowidx, 0, M, err, sizeof(err))) { dlg_set_error("symbolic analysis: %s", err); return DLG_ERR_ARG; }
+  CovPack K;
+  DLG_CHECK(cov_pack_requests(N, H.iperm.data(), nreq, r0, nr, c0, nc, K, "dlg_covariance_plan_probe"));
+  ReachHost R;
+  reach_build(H, K.nch, [&](int ch, std::vector<int>& st) {
+    for(int c = 0; c < MR; c++) { const int x = K.var[(size_t)ch*MR + c]; if(x >= 0) st.push_back(H.col_sn[H.iperm[x]]); }
+  }, R);
+  if(chunk_of_req) for(int q = 0; q < nreq; q++) chunk_of_req[q] = K.req_ch[q];
+  const long v[] = { (long)K.nch, (long)R.pair_sn.size(), (long)K.maxvar };
+  for(int i = 0; i < nstats && i < 3; i++) stats[i] = v[i];
+  return DLG_OK;
+}
+
+void sparse_leverage_free(SparseSym* Y) { for(auto& P : Y->lev) reach_plan_release(P); }
 
 // Gram products of the first nf features of fs rows through the reach-restricted forward solves; *d_gram / *d_slot_ptr:
 // what lev_finish sums
