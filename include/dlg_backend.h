@@ -367,6 +367,26 @@ double dlg_covariance_plan_seconds(dlg_backend_t* b);
 int  dlg_covariance_plan_probe(int N, int M, const int* colptr, const int* rowidx, int nreq, const int* r0, const int* nr,
                                const int* c0, const int* nc, int* chunk_of_req, long* stats, int nstats);
 
+/* ---- the selected inverse: Sigma = (JtJ + lambda I)^-1 at n entries (row[e], col[e]) of the structure of the factor,
+ * with the factor held for `slot` and the lambda it was made with, unscaled, written to out_host in entry order.  Either
+ * order of an entry is taken; every entry of the structure of JtJ is in the structure of the factor (so is every pair of
+ * variables that share a measurement row); an entry off it is refused (DLG_ERR_ARG, pointing to dlg_covariance_blocks).
+ * Sparse: Sigma is formed on the whole structure of L in one sweep from the root of the supernodal tree down (the
+ * Takahashi equations), whatever n is; dense: the structure is the whole matrix, Sigma = L^-T L^-1.  Bitwise
+ * reproducible; a value does not depend on the other entries of the call.  The lookup of the last entry arrays is kept
+ * and reused when the same arrays come again.  n == 0 does nothing.  Refused as dlg_covariance_blocks: a bad argument, a
+ * sharded or partitioned backend, no factor held for the slot, no pattern.  All three solve types. */
+int  dlg_covariance_entries(dlg_backend_t* b, int slot, long n, const int* row, const int* col, double* out_host);
+/* of the last dlg_covariance_entries call: host seconds it spent building plans (the sweep's plan, the entry lookup; 0 if
+ * both were kept), the values held for Sigma (sparse: the panels of L; dense: N * N) and the doubles of the sweep's front
+ * scratch (sparse; 0 dense) */
+int  dlg_covariance_entries_stats(dlg_backend_t* b, double* plan_seconds, long* sx_values, long* front_values);
+/* host only: the symbolic phase on a pattern (as dlg_sparse_symbolic_probe) and, per entry, whether it lies in the structure
+ * of the factor (in_struct[e] = 0 / 1); stats = {entries of that structure (lower triangle with the diagonal), doubles of the
+ * sweep's front scratch, columns of the widest supernode} (nstats <= 3 of them) */
+int  dlg_covariance_entries_probe(int N, int M, const int* colptr, const int* rowidx, long n, const int* row, const int* col,
+                                  int* in_struct, long* stats, int nstats);
+
 /* ---- downloads (returnContext, tests) -------------------------------------- */
 int  dlg_point_download(dlg_backend_t* b, int slot, int which, double* host, size_t n);
 /* dense factor in the reference's layout (packed as dpptrf('L') leaves it, or

@@ -361,6 +361,14 @@ int dogleg_amd_covariance_blocks(double* out, int nreq, const int* r0, const int
                                  dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx);
 /* diag(Sigma), Nstate values */
 int dogleg_amd_marginal_variances(double* var, dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx);
+/* Sigma at n single entries (row[e], col[e]), either order, written to out in entry order: entries of the structure of
+ * the factor, which holds every entry (i, j) whose variables share a measurement row (every block of JtJ: in bundle
+ * adjustment the camera, point and global blocks and every observed camera x point block) and the fill of the
+ * factorisation.  An entry off it is refused.  All of them come from one sweep over the factor (the selected inverse),
+ * see dlg_backend.h: dlg_covariance_entries.  Factorises at `point` if that factor is not held; all three solve types;
+ * one rank only.  0 on success, -1 on failure (with a message). */
+int dogleg_amd_covariance_entries(double* out, long n, const int* row, const int* col,
+                                  dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx);
 
 #ifdef __cplusplus
 }

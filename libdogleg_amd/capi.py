@@ -43,7 +43,7 @@ BACKEND_SYMBOLS = [
     "dlg_sparse_pattern_matches", "dlg_sparse_drop_pattern", "dlg_sparse_region_probe", "dlg_run_steps", "dlg_backend_time_allreduce",
     "dlg_feature_leverage", "dlg_outlierness_factors", "dlg_leverage_query", "dlg_leverage_stats",
     "dlg_covariance_blocks", "dlg_marginal_variances", "dlg_covariance_stats", "dlg_covariance_plan_seconds",
-    "dlg_covariance_plan_probe",
+    "dlg_covariance_plan_probe", "dlg_covariance_entries", "dlg_covariance_entries_stats", "dlg_covariance_entries_probe",
 ]
 PROF_NAMES = ["K1_jtx", "K3K8_norm2Jv", "K4_kernel", "K4_total", "K5_factor", "K6_solve", "K7_step", "vec"]
 DOGLEG_SYMBOLS = [
@@ -59,7 +59,7 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_id_file_publish", "dogleg_amd_id_file_wait", "dogleg_amd_last_solve_timing",
     "dogleg_getOutliernessFactors", "dogleg_markOutliers", "dogleg_reportOutliers",
     "dogleg_getOutliernessTrace_newFeature_sparse",
-    "dogleg_amd_covariance_blocks", "dogleg_amd_marginal_variances",
+    "dogleg_amd_covariance_blocks", "dogleg_amd_marginal_variances", "dogleg_amd_covariance_entries",
 ]
 
 _lib = None
@@ -134,6 +134,9 @@ def lib():
     L.dlg_covariance_plan_seconds.argtypes = [V]
     L.dlg_covariance_plan_seconds.restype = C.c_double
     L.dlg_covariance_plan_probe.argtypes = [C.c_int, C.c_int, I, I, C.c_int, I, I, I, I, I, C.POINTER(C.c_long), C.c_int]
+    L.dlg_covariance_entries.argtypes = [V, C.c_int, C.c_long, I, I, D]
+    L.dlg_covariance_entries_stats.argtypes = [V, D, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    L.dlg_covariance_entries_probe.argtypes = [C.c_int, C.c_int, I, I, C.c_long, I, I, I, C.POINTER(C.c_long), C.c_int]
     L.dlg_expected_improvement.argtypes = [V, C.c_int, C.c_int, D]
     L.dlg_point_download.argtypes = [V, C.c_int, C.c_int, D, C.c_size_t]
     L.dlg_factor_download_dense.argtypes = [V, D, C.c_size_t]
@@ -276,6 +279,20 @@ def covariance_plan_probe(N, M, Jp, Ji, r0, nr, c0, nc):
     _ck(L.dlg_covariance_plan_probe(N, M, iptr(Jp), iptr(Ji), len(r0), iptr(r0), iptr(nr), iptr(c0), iptr(nc),
                                     iptr(ch), st, 3), "covariance_plan_probe")
     return ch[:len(r0)], dict(chunks=st[0], visits=st[1], maxvar=st[2])
+
+
+def covariance_entries_probe(N, M, Jp, Ji, row, col):
+    """host only: (whether each entry (row[e], col[e]) is in the structure of the factor, {nnz: entries of that structure
+    (lower triangle with the diagonal), front_doubles: the selected inverse's front scratch})"""
+    L = lib()
+    Jp = np.ascontiguousarray(Jp, dtype=np.int32)
+    Ji = np.ascontiguousarray(Ji, dtype=np.int32)
+    row, col = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.int32) for a in (row, col))
+    ins = np.zeros(max(len(row), 1), dtype=np.int32)
+    st = (C.c_long * 3)()
+    _ck(L.dlg_covariance_entries_probe(N, M, iptr(Jp), iptr(Ji), len(row), iptr(row), iptr(col), iptr(ins), st, 3),
+        "covariance_entries_probe")
+    return ins[:len(row)].astype(bool), dict(nnz=st[0], front_doubles=st[1], wmax=st[2])
 
 
 def symbolic_probe(N, M, Jp, Ji, row0=0, row1=None, want_perm=False):
@@ -678,6 +695,21 @@ class Backend:
 
     def covariance_plan_seconds(self):
         return self.L.dlg_covariance_plan_seconds(self.h)
+
+    def covariance_entries(self, slot, row, col):
+        """Sigma[row[e], col[e]] of inv(JtJ + lambda I) (the held factor, unscaled) at entries of the structure of the
+        factor, one value per entry"""
+        row, col = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.int32) for a in (row, col))
+        assert len(row) == len(col)
+        out = np.zeros(max(len(row), 1))
+        _ck(self.L.dlg_covariance_entries(self.h, slot, len(row), iptr(row), iptr(col), dptr(out)), "covariance_entries")
+        return out[:len(row)]
+
+    def covariance_entries_stats(self):
+        """(plan seconds of the last call, values held for Sigma, doubles of the front scratch)"""
+        t, a, f = C.c_double(), C.c_long(), C.c_long()
+        _ck(self.L.dlg_covariance_entries_stats(self.h, C.byref(t), C.byref(a), C.byref(f)), "covariance_entries_stats")
+        return t.value, a.value, f.value
 
     def make_step(self, frm, to, kind, trustregion, want_p=True):
         """p_new comes back in a page-locked buffer owned by this object (as the driver's operating

@@ -303,6 +303,7 @@ extern "C" void dlg_backend_destroy(dlg_backend_t* b)
   if(b->d_solve_scr) (void)hipFree(b->d_solve_scr);
   if(b->d_lev) (void)hipFree(b->d_lev);
   if(b->cov) { for(int i = 0; i < 2; i++) cov_plan_release(b->cov[i]); delete[] b->cov; }
+  selinv_release(b);
   if(b->d_red)  (void)hipFree(b->d_red);
   for(auto& pp : b->prof_pending) { (void)hipEventDestroy(pp.a); (void)hipEventDestroy(pp.b); }
   for(hipEvent_t e : b->prof_pool) (void)hipEventDestroy(e);
@@ -351,6 +352,7 @@ extern "C" int dlg_backend_reset(dlg_backend_t* b)
   b->ei_count = 0; b->p_side_pending = false;      // (the test hook counts the values of ONE solve; the copy stream was waited for above)
   DLG_HIP(hipMemsetAsync(b->d_scal, 0, sizeof(double)*dlg_backend::NSCAL, b->stream));
   if(b->type == DLG_SPARSE) sparse_reset(b);
+  selinv_release(b);
   DLG_HIP(hipStreamSynchronize(b->stream));
   return DLG_OK;
 }
@@ -2175,6 +2177,22 @@ extern "C" int dlg_covariance_stats(dlg_backend_t* b, long* nchunks, long* visit
 extern "C" double dlg_covariance_plan_seconds(dlg_backend_t* b)
 {
   return (b && b->cov && b->cov_last >= 0) ? b->cov[b->cov_last].t_plan : -1.0;
+}
+
+// ---- the selected inverse: Sigma at entries of the structure of the factor (sparse_selinv.hip).  The refusals are those
+// of cov_run, and an entry off the structure.
+extern "C" int dlg_covariance_entries(dlg_backend_t* b, int s, long n, const int* row, const int* col, double* out_host)
+{
+  const char* who = "dlg_covariance_entries";
+  DLG_CHECK(check_slot(b, s));
+  if(n < 0) { dlg_set_error("%s: bad argument", who); return DLG_ERR_ARG; }
+  if(n == 0) return DLG_OK;
+  if(!row || !col || !out_host) { dlg_set_error("%s: bad argument", who); return DLG_ERR_ARG; }
+  if(b->sharded() || b->part_nranks > 1) { dlg_set_error("%s is not available on a sharded or partitioned backend", who); return DLG_ERR_STATE; }
+  DLG_CHECK(step_unprepare(b));
+  if(b->factor_slot != s) { dlg_set_error("%s: no factorization of slot %d is held", who, s); return DLG_ERR_STATE; }
+  if(b->type == DLG_SPARSE && !b->sym) { dlg_set_error("%s: no sparse pattern", who); return DLG_ERR_STATE; }
+  return selinv_entries(b, n, row, col, out_host, who);
 }
 
 // ---------------------------------------------------------------- downloads --

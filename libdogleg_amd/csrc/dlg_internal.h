@@ -177,6 +177,7 @@ struct dlg_backend
   double* d_solve_scr = nullptr; size_t solve_scr_cap = 0;   // scratch of the post-solve entry points (backend.hip: solve_scratch)
   double* d_lev = nullptr; size_t lev_cap = 0;               // scratch of the leverage entry points (backend.hip: lev_scratch)
   struct CovPlan* cov = nullptr; int cov_last = -1;          // [2] plans of the covariance entry points (requests, marginal variances), the last one run
+  struct SelInv* selinv = nullptr;                           // the selected inverse and its entry lookup (dlg_covariance_entries)
 
   // sparse
   SparseSym* sym = nullptr;
@@ -485,3 +486,32 @@ int cov_pick(dlg_backend* b, const CovPlan& P, int ch, const double* d_il);
 int cov_finish(dlg_backend* b, const CovPlan& P);
 int dense_cov_setup(dlg_backend* b, CovPlan& P);      // P.kb0
 int dense_cov_gram(dlg_backend* b, const CovPlan& P, double* d_work, size_t work_doubles);
+
+// ---- the selected inverse: Sigma on the structure of the factor (sparse_selinv.hip: dlg_covariance_entries).  Sparse,
+// Sigma is formed on every panel entry of L in one sweep from the root down (Sx, laid out as Lx); dense, the whole of
+// Sigma = L^-T L^-1.  Built on first use, released with the pattern, by dlg_backend_reset and with the backend.
+struct SelTask { int s, ti, tj, pad; };
+struct SelInv
+{
+  // sparse sweep plan (of the pattern)
+  bool sparse_ready = false;
+  int ndepth = 0, nprep = 0;
+  std::vector<int> tb_ptr, tc_ptr;  // [ndepth + 1] into task: the Sigma_BJ tiles and the Sigma_JJ tiles of a depth
+  SelTask *prep = nullptr, *task = nullptr;
+  int *par = nullptr, *prel = nullptr; int64_t* foff = nullptr;
+  int64_t fsize[2] = {0, 0}, sx_n = 0; int prep_lds = 0;
+  double *Sx = nullptr, *Yb = nullptr, *F[2] = {nullptr, nullptr};
+  // dense: L^-1 row-major, Sigma (lower, column-major), the forward solve's chunks of 16 unit columns
+  int dn = 0, dnch = 0, dper = 0;
+  int *dvar = nullptr, *dystart = nullptr;
+  double *Linv_rm = nullptr, *Sig = nullptr, *dwork = nullptr;
+  // entry lookup of the last request arrays: positions in Sx / Sig
+  std::vector<int> qkey;
+  long nq = 0;
+  int64_t* qpos = nullptr; double* qout = nullptr;
+  double t_plan = -1.0;             // host seconds the last call spent on plans (sweep and lookup), 0: all cached
+};
+void selinv_release(dlg_backend* b);
+void selinv_release_sparse(dlg_backend* b);   // what was built against the pattern
+int selinv_entries(dlg_backend* b, long n, const int* row, const int* col, double* out_host, const char* who);
+int dense_selinv_run(dlg_backend* b, SelInv& X);   // X.Sig = (L L^T)^-1, lower (kernels_dense.hip)

@@ -1451,6 +1451,17 @@ int dogleg_amd_marginal_variances(double* var, dogleg_operatingPoint_t* point, d
                            [&]{ return dlg_marginal_variances(d->be, slot_of(d, point), var); }) ? 0 : -1;
 }
 
+int dogleg_amd_covariance_entries(double* out, long n, const int* row, const int* col,
+                                  dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx)
+{
+  const char* who = "dogleg_amd_covariance_entries";
+  if(n < 0 || (n > 0 && (!out || !row || !col))) { MSG("%s(): bad arguments", who); return -1; }
+  if(!cov_ready(point, ctx, who)) return -1;
+  Driver* d = D(ctx);
+  return with_point_factor(point, ctx, "covariance entries",
+                           [&]{ return dlg_covariance_entries(d->be, slot_of(d, point), n, row, col, out); }) ? 0 : -1;
+}
+
 // ---- extension (not in the reference): multi-GPU.  See include/dogleg.h.
 int dogleg_amd_set_communicator(int rank, int nranks, int device, const void* rccl_unique_id128)
 {

@@ -704,6 +704,16 @@ __global__ void __launch_bounds__(TPB) k_cov_gram_dense(const double* __restrict
   if(tid < np) gram[goff[ch] + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
+// the selected inverse, dense (dense_selinv_run): the solved unit blocks V = L^-1 [e_16q .. e_16q+15] of nq chunks from q0
+// on, re-laid out into L^-1 row-major (row k at R + k*N)
+__global__ void __launch_bounds__(TPB) k_linv_rowmajor(const double* __restrict__ V, int N, int q0, double* __restrict__ R)
+{
+  const size_t e = (size_t)blockIdx.x*TPB + threadIdx.x;
+  if(e >= (size_t)N*DMR) return;
+  const int k = (int)(e / DMR), c = (int)(e % DMR), col = (q0 + (int)blockIdx.y)*DMR + c;
+  if(col < N) R[(size_t)k*N + col] = V[(size_t)blockIdx.y*N*DMR + e];
+}
+
 // ------------------------------------------------------------ probes --------
 __global__ void __launch_bounds__(TPB, 8) k_probe_mfma(double* out, int iters)
 {
@@ -1167,6 +1177,51 @@ int dense_cov_gram(dlg_backend* b, const CovPlan& P, double* d_work, size_t work
     }
     hipLaunchKernelGGL(k_cov_gram_dense, dim3(nq), dim3(TPB), 0, st, d_work, n, q0, P.kb0, P.pptr, P.prod, P.goff, P.gram);
   }
+  DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
+
+// the selected inverse, dense: the structure is the whole matrix.  L^-1 from the forward half of the blocked solve on
+// identity chunks of 16 columns (each skipping the tiles above its first column), re-laid out row-major, then
+// Sigma = (L^-1)^T L^-1 on the matrix cores (k_syrk_lower: lower triangle, column-major, ld N)
+int dense_selinv_run(dlg_backend* b, SelInv& X)
+{
+  const int n = b->N;
+  const size_t blk = (size_t)n*DMR;
+  hipStream_t st = b->stream;
+  if(X.dn != n)
+  {
+    X.dn = n; X.dnch = dlg_cdiv(n, DMR);
+    X.dper = (int)std::min<size_t>(std::max<size_t>(1, ((size_t)32 << 20) / blk), (size_t)std::min(X.dnch, 65535));
+    std::vector<int> var((size_t)X.dnch*DMR), ystart(X.dnch);
+    for(size_t i = 0; i < var.size(); i++) var[i] = (int)i < n ? (int)i : -1;
+    for(int q = 0; q < X.dnch; q++) ystart[q] = q*DMR / NB*NB;
+    DLG_HIP(hipMalloc(&X.dvar, sizeof(int)*var.size()));
+    DLG_HIP(hipMemcpy(X.dvar, var.data(), sizeof(int)*var.size(), hipMemcpyHostToDevice));
+    DLG_HIP(hipMalloc(&X.dystart, sizeof(int)*ystart.size()));
+    DLG_HIP(hipMemcpy(X.dystart, ystart.data(), sizeof(int)*ystart.size(), hipMemcpyHostToDevice));
+    DLG_HIP(hipMalloc(&X.Linv_rm, sizeof(double)*(size_t)n*n));
+    DLG_HIP(hipMalloc(&X.Sig, sizeof(double)*(size_t)n*n));
+    DLG_HIP(hipMalloc(&X.dwork, sizeof(double)*blk*X.dper));
+  }
+  for(int q0 = 0; q0 < X.dnch; q0 += X.dper)
+  {
+    const int nq = std::min(X.dper, X.dnch - q0);
+    const int kb0 = q0*DMR / NB*NB;
+    hipLaunchKernelGGL(k_cov_units_dense, dim3(dlg_cdiv((long)blk, TPB), nq), dim3(TPB), 0, st, X.dvar, n, q0, X.dwork);
+    for(int kb = kb0; kb < n; kb += NB)
+    {
+      const int nb = (n - kb < NB) ? n - kb : NB;
+      hipLaunchKernelGGL(k_trsm_diag_m, dim3(1, nq), dim3(TPB), 0, st, b->Linv + (size_t)(kb / NB)*NB*NB, kb, nb, X.dwork, 0, blk, X.dystart + q0);
+      const int rem = n - kb - nb;
+      if(rem > 0)
+        hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64)), nq), dim3(TPB), 0, st, b->G, n, kb, nb, n, X.dwork, blk, X.dystart + q0);
+    }
+    hipLaunchKernelGGL(k_linv_rowmajor, dim3(dlg_cdiv((long)blk, TPB), nq), dim3(TPB), 0, st, X.dwork, n, q0, X.Linv_rm);
+  }
+  DLG_HIP(hipMemsetAsync(X.Sig, 0, sizeof(double)*(size_t)n*n, st));
+  if(n >= 1024) DLG_CHECK(launch_syrk<64>(st, X.Sig, n, X.Linv_rm, n, n, n, 1.0, 0.0, false, nullptr, 0));
+  else          DLG_CHECK(launch_syrk<32>(st, X.Sig, n, X.Linv_rm, n, n, n, 1.0, 0.0, false, nullptr, 0));
   DLG_LAUNCH_CHECK();
   return DLG_OK;
 }
