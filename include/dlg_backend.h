@@ -387,6 +387,31 @@ int  dlg_covariance_entries_stats(dlg_backend_t* b, double* plan_seconds, long* 
 int  dlg_covariance_entries_probe(int N, int M, const int* colptr, const int* rowidx, long n, const int* row, const int* col,
                                   int* in_struct, long* stats, int nstats);
 
+/* ---- query covariance: the uncertainty of derived quantities q(p), Var(q) = Jq Sigma Jq^T with Jq = dq/dp, with the factor
+ * held for `slot` and the lambda it was made with, unscaled.  A query is a block of 1 to 16 rows, each a sparse vector over
+ * the N variables in the caller's variable order; the rows of a batch come as one CSR: rowptr[nrows + 1], var[], val[], and
+ * query k is rows qrow[k] .. qrow[k+1] - 1.  Within a row indices may come in any order; duplicates are summed; an empty
+ * row gives zeros.  Query k of fs rows writes its fs x fs symmetric block in full, row-major; the blocks of all queries
+ * follow one another in query order.  nobs < 0, the plain form Jq Sigma Jq^T; 0 <= nobs <= Nmeas, the observation
+ * (sandwich) form Jq Sigma J[0:nobs]^T J[0:nobs] Sigma Jq^T with the slot's J (sparse and dense only: dense-products has
+ * no J, DLG_ERR_STATE).  Queries are packed whole, in order, into chunks of 16 rows; the plain form needs only the
+ * forward solve, and the sparse path visits, per chunk, only the supernodes its rows' variables reach.  The observation
+ * form solves each chunk in full and forms (J[0:nobs] U)^T (J[0:nobs] U) in one pass over J per 4 chunks.  Bitwise
+ * reproducible; sparse, a query's block does not depend on the other queries of the call or their order.  The plan of the
+ * last batch is kept under the pattern and qrow / rowptr / var; val is uploaded at every call.  Refused: a query with 0
+ * or more than 16 rows (take those from dlg_solve_multi on the columns of Jq^T), an index outside [0, N), nobs > Nmeas
+ * (DLG_ERR_ARG); no factor held for the slot, a sharded or partitioned backend (DLG_ERR_STATE).  nq == 0 does nothing. */
+int  dlg_query_covariance(dlg_backend_t* b, int slot, int nq, const int* qrow, const int* rowptr, const int* var,
+                          const double* val, int nobs, double* out_host);
+/* of the last query plan run: chunks, (chunk, supernode) visits (sparse reach route; 0 otherwise), supernodes of the pattern */
+int  dlg_query_covariance_stats(dlg_backend_t* b, long* nchunks, long* visits, int* nsn);
+/* host seconds the last dlg_query_covariance call spent building its plan (0: kept; -1: none) */
+double dlg_query_covariance_plan_seconds(dlg_backend_t* b);
+/* host only, no GPU: the symbolic phase on a pattern plus the plan of a query batch.  chunk_of_query[nq]; stats = {chunks,
+ * visits, most rows in a chunk} (nstats <= 3 of them).  Refuses what dlg_query_covariance refuses of the arrays. */
+int  dlg_query_covariance_plan_probe(int N, int M, const int* colptr, const int* rowidx, int nq, const int* qrow,
+                                     const int* rowptr, const int* var, int* chunk_of_query, long* stats, int nstats);
+
 /* ---- downloads (returnContext, tests) -------------------------------------- */
 int  dlg_point_download(dlg_backend_t* b, int slot, int which, double* host, size_t n);
 /* dense factor in the reference's layout (packed as dpptrf('L') leaves it, or

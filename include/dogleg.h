@@ -369,6 +369,16 @@ int dogleg_amd_marginal_variances(double* var, dogleg_operatingPoint_t* point, d
  * one rank only.  0 on success, -1 on failure (with a message). */
 int dogleg_amd_covariance_entries(double* out, long n, const int* row, const int* col,
                                   dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx);
+/* the covariance of derived quantities: for query k (rows qrow[k] .. qrow[k+1] - 1 of the CSR rowptr / var / val, 1 to 16
+ * rows over the Nstate variables), the fs x fs block Jq Sigma Jq^T, written in full, row-major, the queries' blocks one
+ * after another.  Nobservations < 0: that plain form; 0 <= Nobservations <= Nmeasurements: the observation (sandwich)
+ * form Jq Sigma J_obs^T J_obs Sigma Jq^T, J_obs the first Nobservations measurement rows (for measurement vectors that
+ * carry regularisation or prior terms behind the observations; not with DENSE_PRODUCTS).  See dlg_backend.h:
+ * dlg_query_covariance.  Wider queries: dlg_solve_multi on the columns of Jq^T.  Factorises at `point` if that factor is
+ * not held; one rank only.  0 on success, -1 on failure (with a message). */
+int dogleg_amd_query_covariance(double* out, int nq, const int* qrow, const int* rowptr, const int* var,
+                                const double* val, int Nobservations,
+                                dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx);
 
 #ifdef __cplusplus
 }

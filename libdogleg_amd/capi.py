@@ -44,6 +44,7 @@ BACKEND_SYMBOLS = [
     "dlg_feature_leverage", "dlg_outlierness_factors", "dlg_leverage_query", "dlg_leverage_stats",
     "dlg_covariance_blocks", "dlg_marginal_variances", "dlg_covariance_stats", "dlg_covariance_plan_seconds",
     "dlg_covariance_plan_probe", "dlg_covariance_entries", "dlg_covariance_entries_stats", "dlg_covariance_entries_probe",
+    "dlg_query_covariance", "dlg_query_covariance_stats", "dlg_query_covariance_plan_seconds", "dlg_query_covariance_plan_probe",
 ]
 PROF_NAMES = ["K1_jtx", "K3K8_norm2Jv", "K4_kernel", "K4_total", "K5_factor", "K6_solve", "K7_step", "vec"]
 DOGLEG_SYMBOLS = [
@@ -60,6 +61,7 @@ DOGLEG_SYMBOLS = [
     "dogleg_getOutliernessFactors", "dogleg_markOutliers", "dogleg_reportOutliers",
     "dogleg_getOutliernessTrace_newFeature_sparse",
     "dogleg_amd_covariance_blocks", "dogleg_amd_marginal_variances", "dogleg_amd_covariance_entries",
+    "dogleg_amd_query_covariance",
 ]
 
 _lib = None
@@ -137,6 +139,13 @@ def lib():
     L.dlg_covariance_entries.argtypes = [V, C.c_int, C.c_long, I, I, D]
     L.dlg_covariance_entries_stats.argtypes = [V, D, C.POINTER(C.c_long), C.POINTER(C.c_long)]
     L.dlg_covariance_entries_probe.argtypes = [C.c_int, C.c_int, I, I, C.c_long, I, I, I, C.POINTER(C.c_long), C.c_int]
+    if hasattr(L, "dlg_query_covariance"):          # (a DLG_TEST_LIB built before query covariance has none of these)
+        L.dlg_query_covariance.argtypes = [V, C.c_int, C.c_int, I, I, I, D, C.c_int, D]
+        L.dlg_query_covariance_stats.argtypes = [V, C.POINTER(C.c_long), C.POINTER(C.c_long), I]
+        L.dlg_query_covariance_plan_seconds.argtypes = [V]
+        L.dlg_query_covariance_plan_seconds.restype = C.c_double
+        L.dlg_query_covariance_plan_probe.argtypes = [C.c_int, C.c_int, I, I, C.c_int, I, I, I, I, C.POINTER(C.c_long),
+                                                      C.c_int]
     L.dlg_expected_improvement.argtypes = [V, C.c_int, C.c_int, D]
     L.dlg_point_download.argtypes = [V, C.c_int, C.c_int, D, C.c_size_t]
     L.dlg_factor_download_dense.argtypes = [V, D, C.c_size_t]
@@ -279,6 +288,20 @@ def covariance_plan_probe(N, M, Jp, Ji, r0, nr, c0, nc):
     _ck(L.dlg_covariance_plan_probe(N, M, iptr(Jp), iptr(Ji), len(r0), iptr(r0), iptr(nr), iptr(c0), iptr(nc),
                                     iptr(ch), st, 3), "covariance_plan_probe")
     return ch[:len(r0)], dict(chunks=st[0], visits=st[1], maxvar=st[2])
+
+
+def query_covariance_plan_probe(N, M, Jp, Ji, qrow, rowptr, var):
+    """host only: (chunk of each query, {chunks, pair visits, most rows in a chunk}) of a query batch"""
+    L = lib()
+    Jp = np.ascontiguousarray(Jp, dtype=np.int32)
+    Ji = np.ascontiguousarray(Ji, dtype=np.int32)
+    qrow, rowptr, var = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.int32) for a in (qrow, rowptr, var))
+    nq = len(qrow) - 1
+    ch = np.zeros(max(nq, 1), dtype=np.int32)
+    st = (C.c_long * 3)()
+    _ck(L.dlg_query_covariance_plan_probe(N, M, iptr(Jp), iptr(Ji), nq, iptr(qrow), iptr(rowptr), iptr(var), iptr(ch),
+                                          st, 3), "query_covariance_plan_probe")
+    return ch[:nq], dict(chunks=st[0], visits=st[1], maxrows=st[2])
 
 
 def covariance_entries_probe(N, M, Jp, Ji, row, col):
@@ -704,6 +727,32 @@ class Backend:
         out = np.zeros(max(len(row), 1))
         _ck(self.L.dlg_covariance_entries(self.h, slot, len(row), iptr(row), iptr(col), dptr(out)), "covariance_entries")
         return out[:len(row)]
+
+    def query_covariance(self, slot, qrow, rowptr, var, val, nobs=-1):
+        """Jq Sigma Jq^T (nobs < 0) or Jq Sigma J[0:nobs]^T J[0:nobs] Sigma Jq^T per query of the CSR batch (query k: rows
+        qrow[k] .. qrow[k+1] - 1), with the held factor, unscaled: one (fs, fs) array per query"""
+        qrow, rowptr, var = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.int32) for a in (qrow, rowptr, var))
+        val = np.ascontiguousarray(np.atleast_1d(val), dtype=np.float64)
+        nq = len(qrow) - 1
+        fs = np.diff(qrow.astype(np.int64))
+        out = np.zeros(max(int(np.sum(fs * fs)), 1))
+        _ck(self.L.dlg_query_covariance(self.h, slot, nq, iptr(qrow), iptr(rowptr), iptr(var), dptr(val), nobs, dptr(out)),
+            "query_covariance")
+        blocks, o = [], 0
+        for k in range(nq):
+            n = int(fs[k])
+            blocks.append(out[o:o + n * n].reshape(n, n))
+            o += n * n
+        return blocks
+
+    def query_covariance_stats(self):
+        """(chunks, supernode visits of all chunks, supernodes) of the last query covariance plan run"""
+        a, b, c = C.c_long(), C.c_long(), C.c_int()
+        _ck(self.L.dlg_query_covariance_stats(self.h, C.byref(a), C.byref(b), C.byref(c)), "query_covariance_stats")
+        return a.value, b.value, c.value
+
+    def query_covariance_plan_seconds(self):
+        return self.L.dlg_query_covariance_plan_seconds(self.h)
 
     def covariance_entries_stats(self):
         """(plan seconds of the last call, values held for Sigma, doubles of the front scratch)"""

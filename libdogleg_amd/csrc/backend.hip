@@ -302,7 +302,7 @@ extern "C" void dlg_backend_destroy(dlg_backend_t* b)
   if(b->d_work) (void)hipFree(b->d_work);
   if(b->d_solve_scr) (void)hipFree(b->d_solve_scr);
   if(b->d_lev) (void)hipFree(b->d_lev);
-  if(b->cov) { for(int i = 0; i < 2; i++) cov_plan_release(b->cov[i]); delete[] b->cov; }
+  if(b->cov) { for(int i = 0; i < COV_NPLAN; i++) cov_plan_release(b->cov[i]); delete[] b->cov; }
   selinv_release(b);
   if(b->d_red)  (void)hipFree(b->d_red);
   for(auto& pp : b->prof_pending) { (void)hipEventDestroy(pp.a); (void)hipEventDestroy(pp.b); }
@@ -2061,35 +2061,6 @@ extern "C" int dlg_leverage_stats(dlg_backend_t* b, int fs, long* nchunks, long*
   if(!b || b->type != DLG_SPARSE || !nchunks || !visits || !nsn) { dlg_set_error("dlg_leverage_stats: bad argument"); return DLG_ERR_ARG; }
   return sparse_leverage_stats(b, fs, nchunks, visits, nsn);
 }
-// A = Jq (JtJ + lambda I)^-1 Jq^T for a query feature: Jq fs x nstate (row-major) on the states istate .. istate + nstate - 1
-extern "C" int dlg_leverage_query(dlg_backend_t* b, int s, const double* Jq, int istate, int nstate, int fs, double* A_host)
-{
-  DLG_CHECK(lev_check(b, s, fs, "dlg_leverage_query"));
-  if(!Jq || !A_host || istate < 0 || nstate < 1 || istate > b->N - nstate) { dlg_set_error("dlg_leverage_query: bad argument"); return DLG_ERR_ARG; }
-  const int MRB = sparse_multi_rhs();
-  const size_t N = (size_t)b->N;
-  double* d_cols = nullptr;
-  DLG_CHECK(solve_scratch(b, 2*N*MRB, &d_cols));
-  double* d_il = d_cols + N*MRB;
-  std::vector<double> blk((size_t)nstate*MRB, 0.0);
-  for(int j = 0; j < nstate; j++) for(int c = 0; c < fs; c++) blk[(size_t)j*MRB + c] = Jq[(size_t)c*nstate + j];
-  DLG_HIP(hipMemsetAsync(d_il, 0, sizeof(double)*N*MRB, b->stream));
-  DLG_HIP(hipMemcpyAsync(d_il + (size_t)istate*MRB, blk.data(), sizeof(double)*blk.size(), hipMemcpyHostToDevice, b->stream));
-  DLG_CHECK(solve_il(b, d_il, d_cols, fs));
-  DLG_HIP(hipMemcpyAsync(blk.data(), d_il + (size_t)istate*MRB, sizeof(double)*blk.size(), hipMemcpyDeviceToHost, b->stream));
-  DLG_HIP(hipStreamSynchronize(b->stream));
-  // upper triangle, row after row: A[i][k] = (solved column i) . (row k of Jq)
-  int o = 0;
-  for(int i = 0; i < fs; i++)
-    for(int k = i; k < fs; k++)
-    {
-      double acc = 0.0;
-      for(int j = 0; j < nstate; j++) acc += blk[(size_t)j*MRB + i]*Jq[(size_t)k*nstate + j];
-      A_host[o++] = acc;
-    }
-  return DLG_OK;
-}
-
 // ---- covariance blocks Sigma = (JtJ + lambda I)^-1 with the factor held for the slot ----------------------------------
 // Sigma[u, v] = (L^-1 P e_u)^T (L^-1 P e_v): only the forward solve of unit columns is needed.  Requests are packed into
 // chunks of 16 distinct variables (sparse_multi.hip: cov_pack_requests); sparse, each chunk's forward solve visits only the
@@ -2112,7 +2083,7 @@ static int cov_run(dlg_backend* b, int s, int which, int nreq, const int* r0, co
   if(b->type == DLG_SPARSE && !b->sym) { dlg_set_error("%s: no sparse pattern", who); return DLG_ERR_STATE; }
   const bool sparse = b->type == DLG_SPARSE;
   const int route = !sparse ? 2 : (!sparse_multi_width_ok(b) || getenv("DOGLEG_AMD_LEVERAGE_SWEEP")) ? 1 : 0;
-  if(!b->cov) b->cov = new CovPlan[2];
+  if(!b->cov) b->cov = new CovPlan[COV_NPLAN];
   CovPlan& P = b->cov[which];
   const uint64_t pk = sparse ? sparse_pattern_key(b) : 0;
   std::vector<int> key = {route, b->N, (int)(pk & 0x7fffffff), (int)((pk >> 31) & 0x7fffffff), (int)(pk >> 62), nreq};
@@ -2177,6 +2148,133 @@ extern "C" int dlg_covariance_stats(dlg_backend_t* b, long* nchunks, long* visit
 extern "C" double dlg_covariance_plan_seconds(dlg_backend_t* b)
 {
   return (b && b->cov && b->cov_last >= 0) ? b->cov[b->cov_last].t_plan : -1.0;
+}
+
+// ---- query covariance Jq Sigma Jq^T (plain form) and Jq Sigma J_obs^T J_obs Sigma Jq^T (observation form) ----------------
+// Var(q) = V^T V with V = L^-1 P Jq^T: the plain form needs only the forward solve of Jq's rows.  Queries (1 to 16 rows of a
+// CSR) are packed whole into chunks of 16 rows (sparse_multi.hip: query_pack); sparse, each chunk's forward solve visits
+// only the supernodes its rows' variables reach (k_cov_fwd_level with the rows as right-hand sides), and every (chunk,
+// supernode) pair leaves the products of the chunk's queries; dense, the forward half of the blocked solve.  A sparse
+// pattern with a supernode wider than the blocked kernels take, or DOGLEG_AMD_LEVERAGE_SWEEP=1: the full solve of each
+// chunk (solve_il) and the products of its rows with the solved columns.  The observation form: U = Sigma Jq^T by full
+// solves, then the products of (J[0:nobs] U)^T (J[0:nobs] U), QOBS_NC chunks per pass over J (query_cov.hip).  The plan is
+// kept under the pattern and the index arrays; the values are uploaded at every call.  which: b->cov[2] (the public call)
+// or b->cov[3] (dlg_leverage_query).
+static int qcov_run(dlg_backend* b, int s, int which, int nq, const int* qrow, const int* rowptr, const int* var,
+                    const double* val, int nobs, double* out_host, const char* who)
+{
+  DLG_CHECK(check_slot(b, s));
+  if(nq < 0) { dlg_set_error("%s: bad argument", who); return DLG_ERR_ARG; }
+  if(nq == 0) return DLG_OK;
+  if(!qrow || !rowptr || !var || !val || !out_host) { dlg_set_error("%s: bad argument", who); return DLG_ERR_ARG; }
+  if(b->sharded() || b->part_nranks > 1) { dlg_set_error("%s is not available on a sharded or partitioned backend", who); return DLG_ERR_STATE; }
+  DLG_CHECK(step_unprepare(b));
+  if(nobs > b->M) { dlg_set_error("%s: nobs = %d exceeds the %d measurements", who, nobs, b->M); return DLG_ERR_ARG; }
+  if(nobs >= 0 && b->type == DLG_DENSE_PRODUCTS) { dlg_set_error("%s: the observation form needs J; dense-products keeps none", who); return DLG_ERR_STATE; }
+  if(nobs >= 0 && !b->slot[s].have_inputs) { dlg_set_error("%s: the observation form needs J of slot %d", who, s); return DLG_ERR_STATE; }
+  if(b->factor_slot != s) { dlg_set_error("%s: no factorization of slot %d is held", who, s); return DLG_ERR_STATE; }
+  if(b->type == DLG_SPARSE && !b->sym) { dlg_set_error("%s: no sparse pattern", who); return DLG_ERR_STATE; }
+  // (the key needs well-formed rows: what is not, query_pack refuses with its message)
+  bool wellformed = qrow[0] >= 0;
+  for(int k = 0; k < nq && wellformed; k++) wellformed = qrow[k+1] - qrow[k] >= 1 && qrow[k+1] - qrow[k] <= QCOV_MAXROWS;
+  if(wellformed) wellformed = rowptr[qrow[nq]] >= rowptr[qrow[0]];
+  if(!wellformed) { CovPack K; const int rc = query_pack(b->N, nq, qrow, rowptr, var, K, who); if(rc != DLG_OK) return rc; }
+  const bool sparse = b->type == DLG_SPARSE;
+  const int route = nobs >= 0 ? 1 : !sparse ? 2 : (!sparse_multi_width_ok(b) || getenv("DOGLEG_AMD_LEVERAGE_SWEEP")) ? 1 : 0;
+  if(!b->cov) b->cov = new CovPlan[COV_NPLAN];
+  CovPlan& P = b->cov[which];
+  const uint64_t pk = sparse ? sparse_pattern_key(b) : 0;
+  const int e0 = rowptr[qrow[0]], e1 = rowptr[qrow[nq]];
+  std::vector<int> key = {route, b->N, (int)(pk & 0x7fffffff), (int)((pk >> 31) & 0x7fffffff), (int)(pk >> 62), nq};
+  key.insert(key.end(), qrow, qrow + nq + 1);
+  key.insert(key.end(), rowptr + qrow[0], rowptr + qrow[nq] + 1);
+  key.insert(key.end(), var + e0, var + e1);
+  P.t_plan = 0.0;
+  if(P.key != key)
+  {
+    DLG_HIP(hipStreamSynchronize(b->stream));
+    cov_plan_release(P);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = query_plan_build(b, P, route, nq, qrow, rowptr, var, who);
+    if(rc != DLG_OK) { cov_plan_release(P); return rc; }
+    P.t_plan = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    P.key = key;
+  }
+  if(P.qnnz > 0) DLG_HIP(hipMemcpyAsync(P.qval, val + e0, sizeof(double)*(size_t)P.qnnz, hipMemcpyHostToDevice, b->stream));
+  const int MRB = sparse_multi_rhs(), nch = P.K.nch;
+  const size_t N = (size_t)b->N;
+  if(route == 0) DLG_CHECK(sparse_query_reach_run(b, P));
+  else if(route == 2)
+  {
+    const size_t blk = N*MRB, work = std::max<size_t>(blk, ((size_t)32 << 20) / blk * blk);
+    double* d_work = nullptr;
+    DLG_CHECK(lev_scratch(b, std::min(work, blk*nch), &d_work));
+    DLG_CHECK(dense_cov_gram(b, P, d_work, std::min(work, blk*nch)));
+  }
+  else if(nobs < 0)
+  {
+    double* d_cols = nullptr;
+    DLG_CHECK(solve_scratch(b, 2*N*MRB, &d_cols));
+    double* d_il = d_cols + N*MRB;
+    for(int ch = 0; ch < nch; ch++)
+    {
+      DLG_CHECK(query_rhs_il(b, P, ch, 1, d_il));
+      DLG_CHECK(solve_il(b, d_il, d_cols, P.K.crow[ch+1] - P.K.crow[ch]));
+      DLG_CHECK(query_gram_rows(b, P, ch, d_il));
+    }
+  }
+  else
+  {
+    double *d_cols = nullptr, *d_U = nullptr;
+    DLG_CHECK(solve_scratch(b, N*MRB, &d_cols));
+    DLG_CHECK(lev_scratch(b, N*MRB*QOBS_NC + (size_t)QOBS_WG*QOBS_NC*MRB*MRB, &d_U));
+    double* d_part = d_U + N*MRB*QOBS_NC;
+    for(int ch0 = 0; ch0 < nch; ch0 += QOBS_NC)
+    {
+      const int nc = std::min(QOBS_NC, nch - ch0);
+      DLG_CHECK(query_rhs_il(b, P, ch0, nc, d_U));
+      for(int q = 0; q < nc; q++) DLG_CHECK(solve_il(b, d_U + (size_t)q*N*MRB, d_cols, P.K.crow[ch0+q+1] - P.K.crow[ch0+q]));
+      DLG_CHECK(query_obs_gram(b, s, P, ch0, nc, nobs, d_U, d_part));
+    }
+  }
+  DLG_CHECK(cov_finish(b, P));
+  if(P.ne > 0 && (hipMemcpyAsync(out_host, P.out, sizeof(double)*(size_t)P.ne, hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
+                  hipStreamSynchronize(b->stream) != hipSuccess))
+  { dlg_set_error("%s: download failed", who); return DLG_ERR_HIP; }
+  return DLG_OK;
+}
+extern "C" int dlg_query_covariance(dlg_backend_t* b, int s, int nq, const int* qrow, const int* rowptr, const int* var,
+                                    const double* val, int nobs, double* out_host)
+{
+  return qcov_run(b, s, 2, nq, qrow, rowptr, var, val, nobs, out_host, "dlg_query_covariance");
+}
+extern "C" int dlg_query_covariance_stats(dlg_backend_t* b, long* nchunks, long* visits, int* nsn)
+{
+  if(!b || !nchunks || !visits || !nsn) { dlg_set_error("dlg_query_covariance_stats: bad argument"); return DLG_ERR_ARG; }
+  if(!b->cov || b->cov[2].key.empty()) { dlg_set_error("no query covariance plan has been run"); return DLG_ERR_STATE; }
+  return cov_plan_stats(b, b->cov[2], nchunks, visits, nsn);
+}
+extern "C" double dlg_query_covariance_plan_seconds(dlg_backend_t* b)
+{
+  return (b && b->cov && !b->cov[2].key.empty()) ? b->cov[2].t_plan : -1.0;
+}
+// A = Jq (JtJ + lambda I)^-1 Jq^T for a query feature: Jq fs x nstate (row-major) on the states istate .. istate + nstate - 1,
+// one query of fs rows (qcov_run on its own plan)
+extern "C" int dlg_leverage_query(dlg_backend_t* b, int s, const double* Jq, int istate, int nstate, int fs, double* A_host)
+{
+  const char* who = "dlg_leverage_query";
+  DLG_CHECK(lev_check(b, s, fs, who));
+  if(!Jq || !A_host || istate < 0 || nstate < 1 || istate > b->N - nstate) { dlg_set_error("%s: bad argument", who); return DLG_ERR_ARG; }
+  const int qrow[2] = {0, fs};
+  std::vector<int> rowptr(fs + 1), var((size_t)fs*nstate);
+  for(int c = 0; c <= fs; c++) rowptr[c] = c*nstate;
+  for(int c = 0; c < fs; c++) for(int j = 0; j < nstate; j++) var[(size_t)c*nstate + j] = istate + j;
+  double blk[4];
+  DLG_CHECK(qcov_run(b, s, 3, 1, qrow, rowptr.data(), var.data(), Jq, -1, blk, who));
+  // upper triangle, row after row
+  int o = 0;
+  for(int i = 0; i < fs; i++) for(int k = i; k < fs; k++) A_host[o++] = blk[i*fs + k];
+  return DLG_OK;
 }
 
 // ---- the selected inverse: Sigma at entries of the structure of the factor (sparse_selinv.hip).  The refusals are those

@@ -444,6 +444,9 @@ struct CovPack
   std::vector<int> req_ch;     // chunk of each request
   std::vector<int> e_ch, e_p;  // per output value: its chunk and the index of its product there
   std::vector<int> kb0;        // dense: per chunk the first tile (of 64 variables) its solve needs
+  // query covariance: the chunk's columns are rows crow[ch] .. crow[ch + 1] - 1 of the query CSR (rebased to row 0 and
+  // entry 0: qrp [rows + 1], qvar in the caller's variable order)
+  std::vector<int> crow, qrp, qvar;
 };
 // iperm: the permutation of the factor (sparse; null: dense, requests ordered by variable)
 int cov_pack_requests(int N, const int* iperm, int nreq, const int* r0, const int* nr, const int* c0,
@@ -473,7 +476,12 @@ struct CovPlan
   int64_t* goff = nullptr;          // first product of a slot in gram
   double *gram = nullptr, *out = nullptr;
   ReachPlan R;                      // sparse, blocked route: slots are the (chunk, supernode) pairs
+  // query plans: K.crow / K.qrp on the device, the variables (permuted on the sparse reach route), the values of the call
+  int *crow = nullptr, *qrp = nullptr, *qvar = nullptr;
+  double* qval = nullptr; long qnnz = 0;
 };
+// b->cov: the plans of dlg_covariance_blocks, dlg_marginal_variances, dlg_query_covariance and dlg_leverage_query
+constexpr int COV_NPLAN = 4;
 void cov_plan_release(CovPlan& P);
 int cov_plan_build(dlg_backend* b, CovPlan& P, int route, int which, int nreq, const int* r0, const int* nr, const int* c0,
                    const int* nc, const char* who);
@@ -481,11 +489,28 @@ uint64_t sparse_pattern_key(const dlg_backend* b);
 int sparse_cov_reach_plan(dlg_backend* b, CovPlan& P);            // R, goff, slot_ptr, pcol and gram of the reach route
 int sparse_cov_reach_run(dlg_backend* b, CovPlan& P);
 int sparse_cov_stats(const dlg_backend* b, long* nchunks, long* visits, int* nsn);
+int cov_plan_stats(const dlg_backend* b, const CovPlan& P, long* nchunks, long* visits, int* nsn);
 int cov_unit_il(dlg_backend* b, const CovPlan& P, int ch, double* d_il);
 int cov_pick(dlg_backend* b, const CovPlan& P, int ch, const double* d_il);
 int cov_finish(dlg_backend* b, const CovPlan& P);
 int dense_cov_setup(dlg_backend* b, CovPlan& P);      // P.kb0
 int dense_cov_gram(dlg_backend* b, const CovPlan& P, double* d_work, size_t work_doubles);
+
+// ---- query covariance Jq Sigma Jq^T (backend.hip: dlg_query_covariance).  A query is 1 .. 16 rows of a CSR over the
+// variables; queries are packed whole, in order, into chunks of at most 16 rows (one right-hand side a row); a query of fs
+// rows needs the fs (fs + 1) / 2 Gram products of its own rows.  The plan is a CovPlan (K.crow non-empty); route 0: the
+// reach of the chunks' variables (sparse), 1: full solves (sparse sweep, and the observation form), 2: dense forward.
+constexpr int QCOV_MAXROWS = 16;
+int query_pack(int N, int nq, const int* qrow, const int* rowptr, const int* var, CovPack& K, const char* who);
+int query_plan_build(dlg_backend* b, CovPlan& P, int route, int nq, const int* qrow, const int* rowptr, const int* var,
+                     const char* who);
+int sparse_query_reach_run(dlg_backend* b, CovPlan& P);
+int query_rhs_il(dlg_backend* b, const CovPlan& P, int ch0, int nch, double* d_il);   // Jq^T of chunks ch0 .. (interleaved, original order), chunk q at d_il + q N 16
+int query_gram_rows(dlg_backend* b, const CovPlan& P, int ch, const double* d_il);    // products of chunk ch from U = Sigma Jq^T
+// the observation form: products of (J[0:nobs] U)^T (J[0:nobs] U) of chunks ch0 .. ch0 + nch - 1 (nch <= QOBS_NC), U of
+// chunk ch0 + q at d_U + q N 16; d_part: QOBS_WG * QOBS_NC * 256 doubles of scratch
+constexpr int QOBS_NC = 4, QOBS_WG = 1024;
+int query_obs_gram(dlg_backend* b, int s, const CovPlan& P, int ch0, int nch, int nobs, const double* d_U, double* d_part);
 
 // ---- the selected inverse: Sigma on the structure of the factor (sparse_selinv.hip: dlg_covariance_entries).  Sparse,
 // Sigma is formed on every panel entry of L in one sweep from the root down (Sx, laid out as Lx); dense, the whole of

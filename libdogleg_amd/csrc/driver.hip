@@ -1462,6 +1462,18 @@ int dogleg_amd_covariance_entries(double* out, long n, const int* row, const int
                            [&]{ return dlg_covariance_entries(d->be, slot_of(d, point), n, row, col, out); }) ? 0 : -1;
 }
 
+int dogleg_amd_query_covariance(double* out, int nq, const int* qrow, const int* rowptr, const int* var,
+                                const double* val, int Nobservations,
+                                dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx)
+{
+  const char* who = "dogleg_amd_query_covariance";
+  if(nq < 0 || (nq > 0 && (!out || !qrow || !rowptr || !var || !val))) { MSG("%s(): bad arguments", who); return -1; }
+  if(!cov_ready(point, ctx, who)) return -1;
+  Driver* d = D(ctx);
+  return with_point_factor(point, ctx, "query covariance",
+                           [&]{ return dlg_query_covariance(d->be, slot_of(d, point), nq, qrow, rowptr, var, val, Nobservations, out); }) ? 0 : -1;
+}
+
 // ---- extension (not in the reference): multi-GPU.  See include/dogleg.h.
 int dogleg_amd_set_communicator(int rank, int nranks, int device, const void* rccl_unique_id128)
 {

@@ -1147,8 +1147,11 @@ int dense_cov_setup(dlg_backend* b, CovPlan& P)
   for(int ch = 0; ch < K.nch; ch++)
   {
     int vmin = b->N;
-    for(int c = 0; c < DMR; c++) if(K.var[(size_t)ch*DMR + c] >= 0) vmin = std::min(vmin, K.var[(size_t)ch*DMR + c]);
-    K.kb0[ch] = vmin / NB*NB;
+    if(!K.crow.empty())        // a query plan: the smallest variable of the chunk's rows
+      for(int q = K.qrp[K.crow[ch]]; q < K.qrp[K.crow[ch+1]]; q++) vmin = std::min(vmin, K.qvar[q]);
+    else
+      for(int c = 0; c < DMR; c++) if(K.var[(size_t)ch*DMR + c] >= 0) vmin = std::min(vmin, K.var[(size_t)ch*DMR + c]);
+    K.kb0[ch] = std::min(vmin, b->N - 1) / NB*NB;
   }
   DLG_HIP(hipMalloc(&P.kb0, sizeof(int)*(size_t)std::max(K.nch, 1)));
   if(K.nch > 0) DLG_HIP(hipMemcpy(P.kb0, K.kb0.data(), sizeof(int)*(size_t)K.nch, hipMemcpyHostToDevice));
@@ -1166,7 +1169,8 @@ int dense_cov_gram(dlg_backend* b, const CovPlan& P, double* d_work, size_t work
     const int nq = std::min(per, nch - q0);
     int kb0 = n;
     for(int q = q0; q < q0 + nq; q++) kb0 = std::min(kb0, P.K.kb0[q]);
-    hipLaunchKernelGGL(k_cov_units_dense, dim3(dlg_cdiv((long)blk, TPB), nq), dim3(TPB), 0, st, P.var, n, q0, d_work);
+    if(P.crow) DLG_CHECK(query_rhs_il(b, P, q0, nq, d_work));      // (a query plan: the rows of Jq)
+    else hipLaunchKernelGGL(k_cov_units_dense, dim3(dlg_cdiv((long)blk, TPB), nq), dim3(TPB), 0, st, P.var, n, q0, d_work);
     for(int kb = kb0; kb < n; kb += NB)
     {
       const int nb = (n - kb < NB) ? n - kb : NB;

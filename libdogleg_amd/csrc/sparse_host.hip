@@ -24,7 +24,7 @@ void sparse_destroy(dlg_backend* b)
   for(void* p : Y->allocs) if(p) (void)hipFree(p);
   sparse_leverage_free(Y);
   // the covariance plans were built against this pattern's symbolic phase (reach, permutation): they go with it
-  if(b->cov) { if(b->stream) (void)hipStreamSynchronize(b->stream); for(int i = 0; i < 2; i++) cov_plan_release(b->cov[i]); }
+  if(b->cov) { if(b->stream) (void)hipStreamSynchronize(b->stream); for(int i = 0; i < COV_NPLAN; i++) cov_plan_release(b->cov[i]); }
   b->cov_last = -1;
   selinv_release(b);     // (its sweep plan and lookup were built against this pattern too)
   delete Y;

@@ -352,6 +352,29 @@ __global__ void __launch_bounds__(TPB) k_lev_fwd_level(const int* __restrict__ w
 // ---- covariance blocks (sparse_covariance_reach): the same forward solves with unit right-hand sides.  Column c of a chunk
 // is e at the permuted index pcol[c] (-1: unused), so it is non-zero only on the path from that column's supernode to the
 // root.  The pair stores the Gram products Yd^T Yd its chunk needs (prod: a*16 + c, a <= c) in its own slot.
+// Query covariance (sparse_query_reach_run) runs the same kernel with right-hand sides from a caller's CSR (RhsCsr).
+struct RhsUnit
+{
+  const int* __restrict__ pcol;
+  __device__ __forceinline__ void load(int ch, int c0, int w, double* Ys, int tid) const
+  { if(tid < MR) { const int k = pcol[(size_t)ch*MR + tid] - c0; if(k >= 0 && k < w) Ys[k*MR + tid] = 1.0; } }
+};
+// column c of chunk ch is row crow[ch] + c of the CSR (rp, pv: permuted indices, val), if below crow[ch + 1]; one thread per
+// row, in the row's order (duplicates summed, as k_lev_fwd_level loads J)
+struct RhsCsr
+{
+  const int* __restrict__ crow; const int* __restrict__ rp; const int* __restrict__ pv; const double* __restrict__ val;
+  __device__ __forceinline__ void load(int ch, int c0, int w, double* Ys, int tid) const
+  {
+    if(tid < MR)
+    {
+      const int row = crow[ch] + tid;
+      if(row < crow[ch+1])
+        for(int q = rp[row]; q < rp[row+1]; q++) { const int k = pv[q] - c0; if(k >= 0 && k < w) Ys[k*MR + tid] += val[q]; }
+    }
+  }
+};
+template <class Rhs>
 __global__ void __launch_bounds__(TPB) k_cov_fwd_level(const int* __restrict__ wl,
                                                        const int* __restrict__ pair_sn,
                                                        const int* __restrict__ pair_ch,
@@ -362,7 +385,7 @@ __global__ void __launch_bounds__(TPB) k_cov_fwd_level(const int* __restrict__ w
                                                        const int* __restrict__ sn_rows,
                                                        const int64_t* __restrict__ sn_lx,
                                                        const double* __restrict__ Lx,
-                                                       const int* __restrict__ pcol,
+                                                       Rhs rhs,
                                                        const int* __restrict__ pptr,
                                                        const int* __restrict__ prod,
                                                        const int64_t* __restrict__ goff,
@@ -385,7 +408,7 @@ __global__ void __launch_bounds__(TPB) k_cov_fwd_level(const int* __restrict__ w
   ms_stage_top(L, nrows, w, Lt, dinv, tid);
   for(int e = tid; e < w*MR; e += TPB) Ys[e] = 0.0;
   __syncthreads();
-  if(tid < MR) { const int k = pcol[(size_t)ch*MR + tid] - c0; if(k >= 0 && k < w) Ys[k*MR + tid] = 1.0; }
+  rhs.load(ch, c0, w, Ys, tid);
   reach_gather(cp_ptr[ch], p, c0, w, pair_sn, pair_off, sn_c0, sn_rowptr, sn_rows, scr, src_i0, src_i1, Ys, tid);
   reach_sweep(Lt, dinv, w, Ys, Yd, c, g);
   // Gram Yd^T Yd (16 x 16) on the matrix cores, one wave, K = w padded to a multiple of 4: A[i][k] = Yd[k][i] and
@@ -646,7 +669,8 @@ int reach_setup(dlg_backend* b)
   for(int s = 0; s < H.nsn; s++) wmax = std::max(wmax, H.sn_c0[s+1] - H.sn_c0[s]);
   Y->lev_lds = (int)ms_lds_fwd(wmax);
   DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lev_fwd_level), hipFuncAttributeMaxDynamicSharedMemorySize, Y->lev_lds));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_fwd_level), hipFuncAttributeMaxDynamicSharedMemorySize, Y->lev_lds));
+  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_fwd_level<RhsUnit>), hipFuncAttributeMaxDynamicSharedMemorySize, Y->lev_lds));
+  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_fwd_level<RhsCsr>), hipFuncAttributeMaxDynamicSharedMemorySize, Y->lev_lds));
   return DLG_OK;
 }
 
@@ -790,7 +814,7 @@ void cov_pack_marginal(int N, const int* perm, CovPack& K)
 void cov_plan_release(CovPlan& P)
 {
   for(void* q : {(void*)P.var, (void*)P.kb0, (void*)P.pcol, (void*)P.pptr, (void*)P.prod, (void*)P.e_ch, (void*)P.e_p, (void*)P.slot_ptr,
-                 (void*)P.goff, (void*)P.gram, (void*)P.out})
+                 (void*)P.goff, (void*)P.gram, (void*)P.out, (void*)P.crow, (void*)P.qrp, (void*)P.qvar, (void*)P.qval})
     if(q) (void)hipFree(q);
   reach_plan_release(P.R);
   P = CovPlan();
@@ -828,8 +852,8 @@ int sparse_cov_reach_run(dlg_backend* b, CovPlan& P)
     {
       const int w0 = R.wl_ptr[(size_t)bt*nl + l], n = R.wl_ptr[(size_t)bt*nl + l + 1] - w0;
       if(n > 0)
-        hipLaunchKernelGGL(k_cov_fwd_level, dim3(n), dim3(TPB), Y->lev_lds, b->stream, R.wl + w0, R.pair_sn, R.pair_ch, R.pair_off,
-                           R.cp_ptr, Y->sn_c0, Y->sn_rowptr, Y->sn_rows, Y->sn_lx, Y->Lx, P.pcol, P.pptr, P.prod, P.goff, R.scr, P.gram);
+        hipLaunchKernelGGL(k_cov_fwd_level<RhsUnit>, dim3(n), dim3(TPB), Y->lev_lds, b->stream, R.wl + w0, R.pair_sn, R.pair_ch, R.pair_off,
+                           R.cp_ptr, Y->sn_c0, Y->sn_rowptr, Y->sn_rows, Y->sn_lx, Y->Lx, RhsUnit{P.pcol}, P.pptr, P.prod, P.goff, R.scr, P.gram);
     }
   DLG_LAUNCH_CHECK();
   return DLG_OK;
@@ -862,6 +886,11 @@ int sparse_cov_stats(const dlg_backend* b, long* nchunks, long* visits, int* nsn
 {
   if(!b->cov || b->cov_last < 0) { dlg_set_error("no covariance plan has been run"); return DLG_ERR_STATE; }
   const CovPlan& P = b->cov[b->cov_last];
+  *nchunks = P.K.nch; *visits = P.R.npair > 0 ? P.R.visits : 0; *nsn = b->sym ? b->sym->H.nsn : 0;
+  return DLG_OK;
+}
+int cov_plan_stats(const dlg_backend* b, const CovPlan& P, long* nchunks, long* visits, int* nsn)
+{
   *nchunks = P.K.nch; *visits = P.R.npair > 0 ? P.R.visits : 0; *nsn = b->sym ? b->sym->H.nsn : 0;
   return DLG_OK;
 }
@@ -902,6 +931,145 @@ extern "C" int dlg_covariance_plan_probe(int N, int M, const int* colptr, const 
     for(int c = 0; c < MR; c++) { const int x = K.var[(size_t)ch*MR + c]; if(x >= 0) st.push_back(H.col_sn[H.iperm[x]]); }
   }, R);
   if(chunk_of_req) for(int q = 0; q < nreq; q++) chunk_of_req[q] = K.req_ch[q];
+  const long v[] = { (long)K.nch, (long)R.pair_sn.size(), (long)K.maxvar };
+  for(int i = 0; i < nstats && i < 3; i++) stats[i] = v[i];
+  return DLG_OK;
+}
+
+// ---- query covariance: packing a query batch into chunks (host) -------------------------------------------------------
+// Queries whole, greedily in query order, into chunks of at most 16 rows; a query of fs rows keeps the fs (fs + 1) / 2
+// products of its own rows; per output value (the queries' full fs x fs blocks, row-major, in query order) its product.
+int query_pack(int N, int nq, const int* qrow, const int* rowptr, const int* var, CovPack& K, const char* who)
+{
+  K = CovPack();
+  if(nq < 0 || (nq > 0 && (!qrow || !rowptr || !var))) { dlg_set_error("%s: bad argument", who); return DLG_ERR_ARG; }
+  if(nq == 0) return DLG_OK;
+  if(qrow[0] < 0) { dlg_set_error("%s: qrow[0] = %d is negative", who, qrow[0]); return DLG_ERR_ARG; }
+  for(int k = 0; k < nq; k++)
+  {
+    const int fs = qrow[k+1] - qrow[k];
+    if(fs < 1 || fs > QCOV_MAXROWS)
+    { dlg_set_error("%s: query %d has %d rows (1 to %d are taken); take wider queries from dlg_solve_multi on the columns of Jq^T", who, k, fs, QCOV_MAXROWS); return DLG_ERR_ARG; }
+  }
+  const int r0 = qrow[0], nrow = qrow[nq] - r0, e0 = rowptr[r0];
+  K.qrp.resize((size_t)nrow + 1);
+  for(int i = 0; i <= nrow; i++)
+  {
+    K.qrp[i] = rowptr[r0 + i] - e0;
+    if(K.qrp[i] < (i ? K.qrp[i-1] : 0)) { dlg_set_error("%s: rowptr decreases at row %d", who, r0 + i); return DLG_ERR_ARG; }
+  }
+  K.qvar.assign(var + e0, var + e0 + K.qrp[nrow]);
+  for(size_t q = 0; q < K.qvar.size(); q++)
+    if(K.qvar[q] < 0 || K.qvar[q] >= N) { dlg_set_error("%s: index %d at entry %ld is outside the %d variables", who, K.qvar[q], (long)(e0 + q), N); return DLG_ERR_ARG; }
+  K.req_ch.assign(nq, -1);
+  K.crow.assign(1, 0);
+  for(int k = 0; k < nq; k++)
+  {
+    const int a0 = qrow[k] - r0, a1 = qrow[k+1] - r0;
+    if(a1 - K.crow.back() > MR) K.crow.push_back(a0);
+    K.req_ch[k] = (int)K.crow.size() - 1;
+  }
+  K.crow.push_back(nrow);
+  K.nch = (int)K.crow.size() - 1;
+  for(int ch = 0; ch < K.nch; ch++) K.maxvar = std::max(K.maxvar, K.crow[ch+1] - K.crow[ch]);
+  int64_t ne = 0;
+  for(int k = 0; k < nq; k++) ne += (int64_t)(qrow[k+1] - qrow[k])*(qrow[k+1] - qrow[k]);
+  K.e_ch.resize(ne); K.e_p.resize(ne);
+  K.pptr.assign(1, 0);
+  int64_t e = 0;
+  for(int k = 0, ch = 0; k < nq; k++)
+  {
+    for(; ch < K.req_ch[k]; ch++) K.pptr.push_back((int)K.prod.size());
+    const int fs = qrow[k+1] - qrow[k], a0 = qrow[k] - r0 - K.crow[ch], p0 = (int)K.prod.size() - K.pptr[ch];
+    for(int i = 0; i < fs; i++) for(int j = i; j < fs; j++) K.prod.push_back((a0 + i)*MR + a0 + j);
+    // product (i, j), i <= j, of the query at p0 + i fs - i (i - 1) / 2 + (j - i)
+    for(int i = 0; i < fs; i++)
+      for(int j = 0; j < fs; j++, e++)
+      {
+        const int x = std::min(i, j), y = std::max(i, j);
+        K.e_ch[e] = ch; K.e_p[e] = p0 + x*fs - x*(x - 1)/2 + (y - x);
+      }
+  }
+  while((int)K.pptr.size() <= K.nch) K.pptr.push_back((int)K.prod.size());
+  return DLG_OK;
+}
+namespace {
+// the supernodes the columns of chunk ch start at: those of its rows' variables
+void query_starts(const SymHost& H, const CovPack& K, int ch, std::vector<int>& st)
+{
+  for(int q = K.qrp[K.crow[ch]]; q < K.qrp[K.crow[ch+1]]; q++) st.push_back(H.col_sn[H.iperm[K.qvar[q]]]);
+}
+} // namespace
+// the device half of a query plan: the CSR, per route the slots (route 0: the reach of each chunk, a slot of the chunk's
+// products per pair; otherwise a slot per chunk), the values' buffer
+int query_plan_build(dlg_backend* b, CovPlan& P, int route, int nq, const int* qrow, const int* rowptr, const int* var,
+                     const char* who)
+{
+  DLG_CHECK(query_pack(b->N, nq, qrow, rowptr, var, P.K, who));
+  const CovPack& K = P.K;
+  P.ne = (long)K.e_ch.size();
+  P.qnnz = (long)K.qvar.size();
+  DLG_CHECK(upload(P.pptr, K.pptr)); DLG_CHECK(upload(P.prod, K.prod));
+  DLG_CHECK(upload(P.e_ch, K.e_ch)); DLG_CHECK(upload(P.e_p, K.e_p));
+  DLG_CHECK(upload(P.crow, K.crow)); DLG_CHECK(upload(P.qrp, K.qrp));
+  DLG_HIP(hipMalloc(&P.out, sizeof(double)*(size_t)std::max<long>(P.ne, 1)));
+  DLG_HIP(hipMalloc(&P.qval, sizeof(double)*(size_t)std::max<long>(P.qnnz, 1)));
+  if(route == 0)
+  {
+    SparseSym* Y = b->sym;
+    const SymHost& H = Y->H;
+    DLG_CHECK(reach_setup(b));
+    ReachHost R;
+    reach_build(H, K.nch, [&](int ch, std::vector<int>& st) { query_starts(H, K, ch, st); }, R);
+    DLG_CHECK(reach_upload(R, K.nch, P.R));
+    std::vector<int64_t> goff(R.pair_sn.size() + 1, 0);
+    for(size_t q = 0; q < R.pair_sn.size(); q++) { const int ch = R.pair_ch[q]; goff[q+1] = goff[q] + (K.pptr[ch+1] - K.pptr[ch]); }
+    std::vector<int> pv(K.qvar.size());
+    for(size_t q = 0; q < pv.size(); q++) pv[q] = H.iperm[K.qvar[q]];
+    DLG_CHECK(upload(P.goff, goff)); DLG_CHECK(upload(P.qvar, pv));
+    DLG_HIP(hipMalloc(&P.gram, sizeof(double)*(size_t)std::max<int64_t>(goff.back(), 1)));
+    return DLG_OK;
+  }
+  DLG_CHECK(upload(P.qvar, K.qvar));
+  if(route == 2) DLG_CHECK(dense_cov_setup(b, P));
+  std::vector<int> slot_ptr(K.nch + 1);
+  std::vector<int64_t> goff(K.nch + 1);
+  for(int ch = 0; ch <= K.nch; ch++) { slot_ptr[ch] = ch; goff[ch] = K.pptr[ch]; }
+  DLG_CHECK(upload(P.slot_ptr, slot_ptr)); DLG_CHECK(upload(P.goff, goff));
+  DLG_HIP(hipMalloc(&P.gram, sizeof(double)*(size_t)std::max(K.pptr.back(), 1)));
+  return DLG_OK;
+}
+int sparse_query_reach_run(dlg_backend* b, CovPlan& P)
+{
+  SparseSym* Y = b->sym;
+  DLG_CHECK(reach_setup(b));
+  const int nl = Y->H.nlevels;
+  const ReachPlan& R = P.R;
+  const RhsCsr rhs{P.crow, P.qrp, P.qvar, P.qval};
+  for(int bt = 0; bt < R.nbatch; bt++)
+    for(int l = 0; l < nl; l++)
+    {
+      const int w0 = R.wl_ptr[(size_t)bt*nl + l], n = R.wl_ptr[(size_t)bt*nl + l + 1] - w0;
+      if(n > 0)
+        hipLaunchKernelGGL(k_cov_fwd_level<RhsCsr>, dim3(n), dim3(TPB), Y->lev_lds, b->stream, R.wl + w0, R.pair_sn, R.pair_ch, R.pair_off,
+                           R.cp_ptr, Y->sn_c0, Y->sn_rowptr, Y->sn_rows, Y->sn_lx, Y->Lx, rhs, P.pptr, P.prod, P.goff, R.scr, P.gram);
+    }
+  DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
+// host only: the symbolic phase on a pattern and the packing and reach of a query batch.  stats: {chunks, pair visits, most
+// rows in a chunk}
+extern "C" int dlg_query_covariance_plan_probe(int N, int M, const int* colptr, const int* rowidx, int nq, const int* qrow,
+                                               const int* rowptr, const int* var, int* chunk_of_query, long* stats, int nstats)
+{
+  SymHost H;
+  char err[512];
+  if(sym_analyze(H, N, M, colptr, rowidx, 0, M, err, sizeof(err))) { dlg_set_error("symbolic analysis: %s", err); return DLG_ERR_ARG; }
+  CovPack K;
+  DLG_CHECK(query_pack(N, nq, qrow, rowptr, var, K, "dlg_query_covariance_plan_probe"));
+  ReachHost R;
+  reach_build(H, K.nch, [&](int ch, std::vector<int>& st) { query_starts(H, K, ch, st); }, R);
+  if(chunk_of_query) for(int k = 0; k < nq; k++) chunk_of_query[k] = K.req_ch[k];
   const long v[] = { (long)K.nch, (long)R.pair_sn.size(), (long)K.maxvar };
   for(int i = 0; i < nstats && i < 3; i++) stats[i] = v[i];
   return DLG_OK;
