@@ -380,6 +380,57 @@ int dogleg_amd_query_covariance(double* out, int nq, const int* qrow, const int*
                                 const double* val, int Nobservations,
                                 dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx);
 
+/* ---- extension (not in the reference): many small dense problems at once, the whole dog-leg loop on the device.
+ * B independent problems of one shape (Nstate, Nmeas) advance together in rounds; every problem has its own trust
+ * region, lambda and stopping test, and problem b does exactly what dogleg_optimize_dense2 does on that problem alone
+ * with the same parameters: the same trial points, accept / reject decisions, trust-region updates, lambda schedule
+ * (0 -> 1e-10 -> x10, only when a factorisation the reference would attempt fails) and the same ways to stop.  A round
+ * is one call of the batch callback for the live problems' trial points and a constant number of launches of the
+ * library, whatever B is; the host reads one counter of live problems per round.
+ *
+ * The batch callback evaluates the LIVE problems.  All pointers are device memory.
+ *   p_dev    in : [B][Nstate]
+ *   x_dev    out: [B][Nmeas]
+ *   J_dev    out: [B][Nmeas][Nstate], row-major per problem (the dense callback's layout)
+ *   live_dev in : [B] bytes; 0: problem b needs no evaluation in this call, whatever is written for it is ignored
+ *                 (a callback may evaluate it anyway)
+ *   hip_stream  : enqueue here, do not synchronise (as dogleg_callback_device_t)
+ *
+ * Limits (refused with a message and -1): B, Nstate or Nmeas 0, a NULL p / f / results, Nstate above
+ * DOGLEG_AMD_BATCH_MAX_NSTATE (larger problems: a loop over dogleg_optimize_dense2), a set communicator (one rank only),
+ * device memory: B * Nmeas * (Nstate + 1) doubles for x and J of the trial points, plus B * (Nstate * (Nstate + 11) / 2 + 8)
+ * doubles of state (a call that does not fit fails with a message that names the size).  The debug / debug_vnlog bits of the parameters are ignored.  There is no returnContext: for the
+ * factor, the outliers or the covariance of one problem, run it through dogleg_optimize_dense2 from the returned p[b]. */
+typedef void (dogleg_callback_device_batch_t)(const double* p_dev, double* x_dev, double* J_dev,
+                                              const unsigned char* live_dev, unsigned int B,
+                                              void* hip_stream, void* cookie);
+#define DOGLEG_AMD_BATCH_MAX_NSTATE     32
+#define DOGLEG_AMD_BATCH_JTX            1   /* |Jt x|_inf <= Jt_x_threshold at the start or at an accepted point   */
+#define DOGLEG_AMD_BATCH_SMALL_STEP     2   /* max |step| <= update_threshold: that step is not applied             */
+#define DOGLEG_AMD_BATCH_TRUSTREGION    3   /* trustregion < trustregion_threshold after a rejected trial           */
+#define DOGLEG_AMD_BATCH_MAX_ITERATIONS 4   /* max_iterations accepted steps                                        */
+#define DOGLEG_AMD_BATCH_FAILED         5   /* non-finite x or J, lambda overflow, an undefined (NaN) gain ratio    */
+typedef struct
+{
+  double norm2_x;        /* at the returned p[b]; negative: this problem failed                     */
+  double trustregion;    /* when it stopped                                                         */
+  double lambda;         /* its sticky damping when it stopped                                      */
+  int    iterations;     /* accepted steps                                                          */
+  int    evaluations;    /* times the callback's result for this problem was used                   */
+  int    status;         /* DOGLEG_AMD_BATCH_{JTX, SMALL_STEP, TRUSTREGION, MAX_ITERATIONS, FAILED} */
+} dogleg_amd_batch_result_t;
+/* p: [B][Nstate] on the host, in = initial estimates, out = optima.  0, or -1 on bad arguments / no device /
+ * allocation failure (message on stderr, p untouched).  A problem that fails is reported in its result (its p[b]
+ * stays as it was on input) and does not stop the others.  parameters == NULL: the process-global set. */
+int dogleg_amd_optimize_dense_batch(double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                    dogleg_callback_device_batch_t* f, void* cookie,
+                                    const dogleg_parameters2_t* parameters,
+                                    dogleg_amd_batch_result_t* results);
+/* measurement: the calling thread's last batch call: out[0] = rounds, and, if DOGLEG_AMD_BATCH_TIMING=1 was set for
+ * it (three events a round on the stream), out[1] = ms in the callback's kernels, out[2] = ms in the library's.
+ * Returns the number of entries written (at most n, at most 3). */
+int dogleg_amd_batch_last_stats(double* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

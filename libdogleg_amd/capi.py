@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer,
+from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult,
                           CB_SPARSE, CB_DENSE, CB_PRODUCTS, dptr, iptr)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,6 +62,7 @@ DOGLEG_SYMBOLS = [
     "dogleg_getOutliernessTrace_newFeature_sparse",
     "dogleg_amd_covariance_blocks", "dogleg_amd_marginal_variances", "dogleg_amd_covariance_entries",
     "dogleg_amd_query_covariance",
+    "dogleg_amd_optimize_dense_batch", "dogleg_amd_batch_last_stats",
 ]
 
 _lib = None
@@ -209,6 +210,9 @@ def lib():
     L.dlg_sparse_pattern_matches.argtypes = [V, I, I]
     L.dlg_sparse_drop_pattern.argtypes = [V]
     L.dogleg_amd_release_cache.restype = None
+    if hasattr(L, "dogleg_amd_optimize_dense_batch"):          # (a DLG_TEST_LIB built before the batch solver has neither)
+        L.dogleg_amd_optimize_dense_batch.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, V, V, PP, C.POINTER(BatchResult)]
+        L.dogleg_amd_batch_last_stats.argtypes = [D, C.c_int]
     L.dogleg_amd_last_solve_timing.argtypes = [D, I]
     L.dlg_point_gather_device.argtypes = [V, C.c_int, V, V, I]
     L.dogleg_setMaxIterations.argtypes = [C.c_int]
@@ -271,6 +275,28 @@ def optimize_device(p0, N, M, nnz, Jp, Ji, cb, cookie, params=None, capacity=256
     finally:
         L.dlg_set_trace(None)
     return r, p, tr
+
+
+def optimize_dense_batch(p0s, N, M, cb, cookie, params=None):
+    """dogleg_amd_optimize_dense_batch: p0s (B, N) start points, cb the address of a dogleg_callback_device_batch_t.
+    Returns (rc, p (B, N), results): results a numpy record array with the fields of dogleg_amd_batch_result_t
+    (norm2_x, trustregion, lambda_, iterations, evaluations, status)."""
+    L = lib()
+    p = np.array(p0s, dtype=np.float64, copy=True).reshape(-1, N)
+    B = p.shape[0]
+    res = (BatchResult * max(B, 1))()
+    rc = L.dogleg_amd_optimize_dense_batch(dptr(p), B, N, M, cb, cookie, C.byref(params) if params is not None else None, res)
+    dt = np.dtype(dict(names=[n for n, _ in BatchResult._fields_], formats=[np.dtype(t) for _, t in BatchResult._fields_],
+                       offsets=[getattr(BatchResult, n).offset for n, _ in BatchResult._fields_],
+                       itemsize=C.sizeof(BatchResult)))
+    return rc, p, np.frombuffer(res, dtype=dt)[:B].copy()
+
+
+def batch_last_stats():
+    """{rounds, ms_callback, ms_library} of the calling thread's last batch call (the times: DOGLEG_AMD_BATCH_TIMING=1)"""
+    out = (C.c_double * 3)()
+    lib().dogleg_amd_batch_last_stats(out, 3)
+    return dict(rounds=int(out[0]), ms_callback=out[1], ms_library=out[2])
 
 
 SYM_STAT_NAMES = ["var_blocks", "supernodes", "levels", "nnz_JtJ_lower", "nnz_L", "panel_doubles",

@@ -1,0 +1,11 @@
+// dense_batch.h -- the batch solver of dense_batch.hip as the driver sees it (not installed).
+#pragma once
+#include "../../include/dogleg.h"
+
+// arguments checked by the caller (driver.hip: dogleg_amd_optimize_dense_batch); 0 / -1 with a message on stderr
+int  dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int M,
+                         dogleg_callback_device_batch_t* f, void* cookie,
+                         const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results);
+// the device buffers, the stream and the page-locked counter kept between calls (dogleg_amd_release_cache)
+void dlg_dense_batch_release();
+int  dlg_dense_batch_last_stats(double* out, int n);

@@ -23,6 +23,7 @@
 #include "../../include/dogleg.h"
 #include "../../include/dlg_backend.h"
 #include "../../include/dlg_trace.h"
+#include "dense_batch.h"
 
 #define MSG(...) do { fprintf(stderr, "libdogleg_amd: " __VA_ARGS__); fputc('\n', stderr); } while(0)
 #define VERBOSE(c, ...) do { if((c)->pub.parameters->debug && !(c)->pub.parameters->debug_vnlog) MSG(__VA_ARGS__); } while(0)
@@ -1490,6 +1491,29 @@ int dogleg_amd_set_allreduce(int rank, int nranks, int device, dogleg_amd_allred
   return 0;
 }
 void dogleg_amd_clear_communicator(void) { t_comm = Comm(); }
+
+// ---- extension (not in the reference): a batch of small dense problems, the dog-leg loop on the device (dense_batch.hip)
+int dogleg_amd_optimize_dense_batch(double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                    dogleg_callback_device_batch_t* f, void* cookie,
+                                    const dogleg_parameters2_t* parameters, dogleg_amd_batch_result_t* results)
+{
+  const char* who = "dogleg_amd_optimize_dense_batch";
+  if(!p || !f || !results) { MSG("%s: p, the callback and results must be given", who); return -1; }
+  if(B == 0 || Nstate == 0 || Nmeas == 0) { MSG("%s: B = %u, Nstate = %u, Nmeas = %u: none may be 0", who, B, Nstate, Nmeas); return -1; }
+  if(Nstate > DOGLEG_AMD_BATCH_MAX_NSTATE)
+  {
+    MSG("%s: Nstate = %u, the batch kernels take at most %d variables (larger problems: a loop over dogleg_optimize_dense2)", who,
+        Nstate, DOGLEG_AMD_BATCH_MAX_NSTATE);
+    return -1;
+  }
+  if(B > 0x7fffffffu/4 || Nmeas > 0x7fffffffu/(Nstate + 1))
+  { MSG("%s: B = %u problems of %u x %u: beyond the index range of the batch kernels", who, B, Nmeas, Nstate); return -1; }
+  const char* ws = getenv("DOGLEG_AMD_WORLD_SIZE");
+  if(t_comm.set || (ws && atoi(ws) > 1))
+  { MSG("%s: one rank only (a communicator is set: dogleg_amd_clear_communicator)", who); return -1; }
+  return dlg_dense_batch_run(p, B, Nstate, Nmeas, f, cookie, parameters ? parameters : &g_params, results);
+}
+int dogleg_amd_batch_last_stats(double* out, int n) { return out ? dlg_dense_batch_last_stats(out, n) : 0; }
 // what the library keeps between solves (the idle backend with its device memory, page-locked host buffers)
 void dogleg_amd_release_cache(void)
 {
@@ -1502,6 +1526,7 @@ void dogleg_amd_release_cache(void)
   }
   if(be) dlg_backend_destroy(be);
   for(const PinnedBuf& b : pool) (void)hipHostFree(b.p);
+  dlg_dense_batch_release();
 }
 // where the calling thread's last solve spent its wall time (DOGLEG_AMD_TIMING=1 must have been set for it): milliseconds and
 // calls of {pattern, model callback, inputs to the backend, dlg_point_eval, dlg_take_step / dlg_step, trace records,

@@ -111,6 +111,21 @@ class TraceBuffer:
         return [self._trials[i].asdict() for i in range(self.ntrials)]
 
 
+BATCH_JTX, BATCH_SMALL_STEP, BATCH_TRUSTREGION, BATCH_MAX_ITERATIONS, BATCH_FAILED = 1, 2, 3, 4, 5
+BATCH_MAX_NSTATE = 32
+
+
+class BatchResult(C.Structure):
+    """dogleg_amd_batch_result_t (include/dogleg.h)."""
+    _fields_ = [
+        ("norm2_x", C.c_double), ("trustregion", C.c_double), ("lambda_", C.c_double),
+        ("iterations", C.c_int), ("evaluations", C.c_int), ("status", C.c_int),
+    ]
+
+
+# dogleg_callback_device_batch_t
+CB_DEVICE_BATCH = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p)
+
 CB_SPARSE = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double),
                         C.POINTER(CholmodSparse), C.c_void_p)
 CB_DENSE = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double),
