@@ -399,8 +399,9 @@ int dogleg_amd_query_covariance(double* out, int nq, const int* qrow, const int*
  * Limits (refused with a message and -1): B, Nstate or Nmeas 0, a NULL p / f / results, Nstate above
  * DOGLEG_AMD_BATCH_MAX_NSTATE (larger problems: a loop over dogleg_optimize_dense2), a set communicator (one rank only),
  * device memory: B * Nmeas * (Nstate + 1) doubles for x and J of the trial points, plus B * (Nstate * (Nstate + 11) / 2 + 8)
- * doubles of state (a call that does not fit fails with a message that names the size).  The debug / debug_vnlog bits of the parameters are ignored.  There is no returnContext: for the
- * factor, the outliers or the covariance of one problem, run it through dogleg_optimize_dense2 from the returned p[b]. */
+ * doubles of state (a call that does not fit fails with a message that names the size).  The debug / debug_vnlog bits of the parameters are ignored.  There is no returnContext: the
+ * covariance and the outlierness factors of every problem come from dogleg_amd_dense_batch_uncertainty below; for the factor
+ * itself, or for marking outliers, run the problem through dogleg_optimize_dense2 from the returned p[b]. */
 typedef void (dogleg_callback_device_batch_t)(const double* p_dev, double* x_dev, double* J_dev,
                                               const unsigned char* live_dev, unsigned int B,
                                               void* hip_stream, void* cookie);
@@ -430,6 +431,47 @@ int dogleg_amd_optimize_dense_batch(double* p, unsigned int B, unsigned int Nsta
  * it (three events a round on the stream), out[1] = ms in the callback's kernels, out[2] = ms in the library's.
  * Returns the number of entries written (at most n, at most 3). */
 int dogleg_amd_batch_last_stats(double* out, int n);
+
+/* Per-problem uncertainty of a batch: at the points p[b] (normally what the batch solve returned), Sigma_b = (JtJ + lambda I)^-1
+ * with J of problem b at p[b], its diagonal, and the outlierness factors of the problem's features, for all B problems in
+ * one call: the batch callback is invoked exactly ONCE, at p, with every live byte 1, and one launch of the library
+ * follows it, whatever B is.
+ *   lambda      [B] in/out, or NULL (start at 0, not reported): problem b is factorised at lambda[b] -- pass results[b].lambda
+ *               of the solve --; where a pivot is <= 0 the solve's schedule applies (0 -> 1e-10 -> x10) until the
+ *               factorisation succeeds or lambda is no longer finite.  The lambda that was used is written back.  A negative
+ *               or NaN lambda[b] fails that problem alone (FAILED; it is written back as it came).
+ *   covariance  [B][Nstate][Nstate] full, row-major, UNSCALED as dogleg_amd_covariance_blocks (multiply by sigma^2), or NULL
+ *   variances   [B][Nstate], the diagonals (the same bits as the diagonal of covariance), or NULL
+ *   factors     [B][Nmeas / featureSize], or NULL: the contract written above dogleg_getOutliernessFactors with the leverage
+ *               block A_f = J_f Sigma_b J_f^T; features are consecutive measurements from 0 (a trailing odd measurement is
+ *               not covered at size 2); DBL_MAX where |1 - a| or |det(A_f - I)| is below 1e-8
+ *   scale       [B] in/out, required with factors: a scale[b] <= 0 is computed with NoutlierFeatures = 0,
+ *               Nmeas / (4 (Nstate+1) |x|^2 / (Nmeas - Nstate - 1)), and written back
+ *   featureSize <= 1 means 1, sizes above 2 are refused
+ *   status      [B], required: DOGLEG_AMD_BATCH_UNC_OK or _FAILED.  A FAILED problem gets NaN in every requested output (and
+ *               in a scale that was to be computed from a non-finite x); it does not disturb the others and the call still
+ *               returns 0.
+ * Problem b's output bits do not depend on B, on its position or on its neighbours.
+ * Refused with a message and -1 before any device work, outputs untouched: a NULL p / f / status, B, Nstate or Nmeas 0,
+ * Nstate above DOGLEG_AMD_BATCH_MAX_NSTATE, featureSize above 2, factors without scale, a scale[b] <= 0 while
+ * Nmeas <= Nstate + 1, all three outputs NULL, a set communicator, device memory that does not fit (the message names the
+ * size): B * Nmeas * (Nstate + 1) doubles for x and J plus the inputs and the requested outputs.
+ * Memory the library keeps after the call (dogleg_amd_release_cache gives it back): the device buffers, and one page-locked
+ * host buffer as large as the inputs and the requested outputs together, 8 B (2 Nstate + 3 + Nstate^2 + Nmeas / featureSize)
+ * bytes with everything asked for -- about 370 MB for B = 131 072 problems of 96 x 16.
+ * Not covered on a batch: NoutlierFeatures / marking outliers, and covariance blocks across several problems. */
+#define DOGLEG_AMD_BATCH_UNC_OK      0
+#define DOGLEG_AMD_BATCH_UNC_FAILED  1   /* non-finite x or J at p[b], or lambda overflowed before a factorisation succeeded */
+                                         /* (also: a negative or NaN lambda[b] on input) */
+int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                       dogleg_callback_device_batch_t* f, void* cookie,
+                                       double* lambda, double* covariance, double* variances, double* factors,
+                                       double* scale, int featureSize, int* status);
+/* measurement: the calling thread's last uncertainty call: out[0] = kernel launches of the library, out[1] = stream
+ * synchronisations, out[2] = copies and fills on the stream (none of the three depends on B), and, if
+ * DOGLEG_AMD_BATCH_TIMING=1 was set for it, out[3] = ms in the callback's kernels, out[4] = ms in the library's.
+ * Returns the number of entries written (at most n, at most 5). */
+int dogleg_amd_batch_uncertainty_last_stats(double* out, int n);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,7 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_covariance_blocks", "dogleg_amd_marginal_variances", "dogleg_amd_covariance_entries",
     "dogleg_amd_query_covariance",
     "dogleg_amd_optimize_dense_batch", "dogleg_amd_batch_last_stats",
+    "dogleg_amd_dense_batch_uncertainty", "dogleg_amd_batch_uncertainty_last_stats",
 ]
 
 _lib = None
@@ -213,6 +214,9 @@ def lib():
     if hasattr(L, "dogleg_amd_optimize_dense_batch"):          # (a DLG_TEST_LIB built before the batch solver has neither)
         L.dogleg_amd_optimize_dense_batch.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, V, V, PP, C.POINTER(BatchResult)]
         L.dogleg_amd_batch_last_stats.argtypes = [D, C.c_int]
+    if hasattr(L, "dogleg_amd_dense_batch_uncertainty"):
+        L.dogleg_amd_dense_batch_uncertainty.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, V, V, D, D, D, D, D, C.c_int, I]
+        L.dogleg_amd_batch_uncertainty_last_stats.argtypes = [D, C.c_int]
     L.dogleg_amd_last_solve_timing.argtypes = [D, I]
     L.dlg_point_gather_device.argtypes = [V, C.c_int, V, V, I]
     L.dogleg_setMaxIterations.argtypes = [C.c_int]
@@ -297,6 +301,36 @@ def batch_last_stats():
     out = (C.c_double * 3)()
     lib().dogleg_amd_batch_last_stats(out, 3)
     return dict(rounds=int(out[0]), ms_callback=out[1], ms_library=out[2])
+
+
+def dense_batch_uncertainty(p, N, M, cb, cookie, lam=None, want=("cov", "var", "factors"), fs=1, scale=None):
+    """dogleg_amd_dense_batch_uncertainty at the points p (B, N).  lam: (B,) or None (NULL: start at 0); want: which of
+    "cov", "var", "factors" to ask for; scale: (B,) or a number for all, None: computed (<= 0).  Returns dict(rc, status,
+    lam (None if lam was None), and cov (B, N, N) / var (B, N) / factors (B, M // max(fs, 1)) + scale (B,) as asked)."""
+    L = lib()
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, N)
+    B = p.shape[0]
+    out = dict(lam=None if lam is None else np.array(lam, dtype=np.float64, copy=True).reshape(B))
+    out["status"] = np.full(B, -1, dtype=np.int32)
+    if "cov" in want:
+        out["cov"] = np.zeros((B, N, N))
+    if "var" in want:
+        out["var"] = np.zeros((B, N))
+    if "factors" in want:
+        out["factors"] = np.zeros((B, M // max(fs, 1)))
+        out["scale"] = np.full(B, -1.0) if scale is None else np.array(np.broadcast_to(scale, (B,)), dtype=np.float64)
+    opt = lambda k: dptr(out[k]) if out.get(k) is not None else None
+    out["rc"] = L.dogleg_amd_dense_batch_uncertainty(dptr(p), B, N, M, cb, cookie, opt("lam"), opt("cov"), opt("var"),
+                                                     opt("factors"), opt("scale"), fs, iptr(out["status"]))
+    return out
+
+
+def batch_uncertainty_last_stats():
+    """{launches, syncs, copies, ms_callback, ms_library} of the calling thread's last dense_batch_uncertainty (the times:
+    DOGLEG_AMD_BATCH_TIMING=1)"""
+    out = (C.c_double * 5)()
+    lib().dogleg_amd_batch_uncertainty_last_stats(out, 5)
+    return dict(launches=int(out[0]), syncs=int(out[1]), copies=int(out[2]), ms_callback=out[3], ms_library=out[4])
 
 
 SYM_STAT_NAMES = ["var_blocks", "supernodes", "levels", "nnz_JtJ_lower", "nnz_L", "panel_doubles",

@@ -6,6 +6,11 @@
 int  dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int M,
                          dogleg_callback_device_batch_t* f, void* cookie,
                          const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results);
-// the device buffers, the stream and the page-locked counter kept between calls (dogleg_amd_release_cache)
+// dogleg_amd_dense_batch_uncertainty behind the driver's checks (fs is 1 or 2 here); 0 / -1 with a message on stderr
+int  dlg_dense_batch_uncertainty_run(const double* p, unsigned int B, unsigned int N, unsigned int M,
+                                     dogleg_callback_device_batch_t* f, void* cookie, double* lambda, double* covariance,
+                                     double* variances, double* factors, double* scale, int fs, int* status);
+int  dlg_dense_batch_uncertainty_last_stats(double* out, int n);
+// the device buffers, the stream, the page-locked counter and staging kept between calls (dogleg_amd_release_cache)
 void dlg_dense_batch_release();
 int  dlg_dense_batch_last_stats(double* out, int n);

@@ -14,11 +14,15 @@
 // the point it started from (p, Jt x, the Cauchy and Gauss-Newton steps, JtJ: N (N + 11) / 2 doubles) lies in device
 // memory per problem; the J of a point is never read a second time and only one x / J buffer per problem exists.
 // Plain FMAs, no MFMA: DESIGN.md section 3, "Batches of small dense problems".
+//
+// dogleg_amd_dense_batch_uncertainty (k_batch_uncertainty, below the round kernel): covariance, variances and outlierness
+// factors of every problem at given points, one callback and one launch, on the same sweep, Cholesky and cache.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
+#include <cfloat>
 #include <mutex>
 #include <vector>
 #include "dense_batch.h"
@@ -132,31 +136,31 @@ __device__ inline double solve_packed(const double* L, double b, int N, int lane
   return b;
 }
 
-// one round of problem b; returns whether the problem is still live
+// entry lane + 64 k of the packed triangle is (ei[k], ej[k]), ei >= ej; (0, 0) beyond NP
 template <int NMAX>
-__device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
+__device__ __forceinline__ void packed_entries(int N, int NP, int lane, int* ei, int* ej)
 {
-  using C = BatchCfg<NMAX>;
-  const int N = A.N, M = A.M, NP = A.NP;
-  double* SA = S;                      // JtJ of the point the step is taken from
-  double* SL = S + C::NP;              // its factor; during the sweep the row tile
-  double* SV = SL + C::SCR;            // an N-vector
-  double* tile = SL; double* xt = SL + BATCH_TILE;
-  const size_t bN = (size_t)b*N;
-
-  // ---- the sweep over the trial point's x and J: norm2(x), Jt x, JtJ (eval_point, dogleg.c:1004-1083, and the rows'
-  // outer products dogleg.c:712-714) ----
-  int ei[C::NE], ej[C::NE];
 #pragma unroll
-  for(int k = 0; k < C::NE; k++)
+  for(int k = 0; k < BatchCfg<NMAX>::NE; k++)
   {
     const int e = lane + 64*k;
     int c = 0;
     if(e < NP) { while(e >= col_off(c + 1, N)) c++; }
     ej[k] = c; ei[k] = e < NP ? c + e - col_off(c, N) : 0;
   }
-  const double* Jb = A.J + (size_t)b*M*N;
-  const double* xb = A.x + (size_t)b*M;
+}
+
+// the sweep over one point's x and J (xb: M, Jb: M x N row-major): returns norm2(x), leaves the packed lower triangle of
+// JtJ in SA and (Jt x)[lane] in gacc (eval_point, dogleg.c:1004-1083, and the rows' outer products dogleg.c:712-714).
+// tile: BATCH_TILE + 64 doubles of LDS.  Shared by the round and the uncertainty kernel: one order of operations.
+template <int NMAX>
+__device__ __forceinline__ double sweep_point(const double* Jb, const double* xb, int N, int M, int NP, int lane,
+                                              double* SA, double* tile, double& gacc_out)
+{
+  using C = BatchCfg<NMAX>;
+  double* xt = tile + BATCH_TILE;
+  int ei[C::NE], ej[C::NE];
+  packed_entries<NMAX>(N, NP, lane, ei, ej);
   const int T = min(64, BATCH_TILE/N);
   double acc[C::NE], gacc = 0.0, n2 = 0.0;
 #pragma unroll
@@ -199,6 +203,24 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
 #pragma unroll
   for(int k = 0; k < C::NE; k++) if(lane + 64*k < NP) SA[lane + 64*k] = acc[k];
   wsync();
+  gacc_out = gacc;
+  return n2x;
+}
+
+// one round of problem b; returns whether the problem is still live
+template <int NMAX>
+__device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
+{
+  using C = BatchCfg<NMAX>;
+  const int N = A.N, M = A.M, NP = A.NP;
+  double* SA = S;                      // JtJ of the point the step is taken from
+  double* SL = S + C::NP;              // its factor; during the sweep the row tile
+  double* SV = SL + C::SCR;            // an N-vector
+  const size_t bN = (size_t)b*N;
+
+  // ---- the sweep over the trial point's x and J: norm2(x), Jt x, JtJ ----
+  double gacc;
+  const double n2x = sweep_point<NMAX>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc);
   // a non-finite x or J shows in norm2(x) or on the diagonal of JtJ
   const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
   const bool finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
@@ -354,6 +376,203 @@ __global__ void __launch_bounds__(64*BATCH_WPB) k_batch_round(BatchDev A)
   }
 }
 
+// ---- dogleg_amd_dense_batch_uncertainty: Sigma_b = (JtJ + lambda I)^-1, its diagonal and the outlierness factors of every
+// problem at the points p[b], ONE launch behind one call of the batch callback.  Per wave: the sweep of the round kernel
+// (|x|^2, JtJ), the lambda loop on chol_packed, the factor inverted in place, Sigma = L^-T L^-1 into the LDS that held JtJ
+// (it is not needed once the factorisation stands: Sigma costs no LDS of its own), then a second sweep over J in which
+// one lane takes one feature.  No sum crosses lanes after the first sweep.
+struct UncDev
+{
+  int B, N, M, NP, fs, NF;
+  const double* x; const double* J;
+  double *lam, *scale, *cov, *var, *fac;     // cov, var, fac (and scale with fac): nullptr where not asked for
+  int* status;
+};
+
+// x' (B + B^2) x scale / 8 with B = (A_f - I)^-1, dogleg.h above dogleg_getOutliernessFactors (the arithmetic of
+// k_lev_finish, sparse_multi.hip)
+__device__ inline double factor1(double a, double x0, double k)
+{
+  const double den = 1.0 - a;
+  return fabs(den) < 1e-8 ? DBL_MAX : x0*x0/den*k;
+}
+__device__ inline double factor2(double a00, double a01, double a11, double x0, double x1, double k)
+{
+  const double m00 = a00 - 1.0, m01 = a01, m11 = a11 - 1.0;
+  const double det = m00*m11 - m01*m01;
+  if(fabs(det) < 1e-8) return DBL_MAX;
+  const double j00 = m11, j01 = -m01, j11 = m00;           // adjugate of A_f - I
+  const double xBx = (x0*x0*j00 + 2.0*x0*x1*j01 + x1*x1*j11)/det;
+  const double v0 = x0*j00 + x1*j01, v1 = x0*j01 + x1*j11;
+  return (xBx + (v0*v0 + v1*v1)/(det*det))*k;
+}
+
+template <int NMAX>
+__device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
+{
+  using C = BatchCfg<NMAX>;
+  const int N = A.N, M = A.M, NP = A.NP;
+  double* SA = S;                      // JtJ, then Sigma
+  double* SL = S + C::NP;              // the row tile of the sweeps; between them the factor and its inverse
+  const double* Jb = A.J + (size_t)b*M*N;
+  const double* xb = A.x + (size_t)b*M;
+
+  double gacc;
+  const double n2x = sweep_point<NMAX>(Jb, xb, N, M, NP, lane, SA, SL, gacc);
+  const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
+  bool ok = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
+
+  // ---- the factorisation at lambda[b]; a pivot <= 0 moves lambda as the solve does (dogleg.c:634-820) ----
+  double lam = A.lam[b];
+  if(!(lam >= 0.0)) ok = false;        // a negative or NaN lambda[b]: FAILED, written back as it came
+  while(ok)
+  {
+    wsync();
+    for(int e = lane; e < NP; e += 64) SL[e] = SA[e];
+    wsync();
+    if(lam > 0.0 && lane < N) SL[col_off(lane, N)] += lam;
+    wsync();
+    if(chol_packed(SL, N, lane)) break;
+    lam = lam == 0.0 ? LAMBDA_INITIAL : lam*10.0;
+    if(!isfinite(lam)) ok = false;
+  }
+  double scale = 0.0;
+  if(A.fac)
+  {
+    scale = A.scale[b];
+    if(!(scale > 0.0))
+    {
+      // NoutlierFeatures = 0 (driver.hip: outlier_scale); NaN for a problem that failed on a non-finite x
+      scale = (double)M/(4.0*((double)(N + 1)*n2x/(double)(M - N - 1)));
+      if(lane == 0) A.scale[b] = scale;
+    }
+  }
+  if(lane == 0) { A.lam[b] = lam; A.status[b] = ok ? DOGLEG_AMD_BATCH_UNC_OK : DOGLEG_AMD_BATCH_UNC_FAILED; }
+  if(!ok)
+  {
+    const double nan = __builtin_nan("");
+    if(A.var && lane < N) A.var[(size_t)b*N + lane] = nan;
+    if(A.cov) for(int e = lane; e < N*N; e += 64) A.cov[(size_t)b*N*N + e] = nan;
+    if(A.fac) for(int f = lane; f < A.NF; f += 64) A.fac[(size_t)b*A.NF + f] = nan;
+    return;
+  }
+
+  // ---- X = L^-1 in place, from the last column to the first (DTRTI2 'L'): column j of X is -X[j+1:, j+1:] L[j+1:, j] / L[j][j],
+  // lane l takes row j + 1 + l ----
+  for(int j = N - 1; j >= 0; j--)
+  {
+    const int jj = col_off(j, N), i = j + 1 + lane;
+    const double d = 1.0/SL[jj];
+    double s = 0.0;
+    if(i < N)
+    {
+      for(int k = j + 1; k <= i; k++) s += SL[col_off(k, N) + i - k]*SL[jj + k - j];
+      s *= -d;
+    }
+    wsync();
+    if(lane == 0) SL[jj] = d;
+    if(i < N) SL[jj + 1 + lane] = s;
+    wsync();
+  }
+  // ---- Sigma = X' X, one lane per entry: Sigma[i][j] = sum over r >= i of X[r][i] X[r][j] (i >= j) ----
+  {
+    int ei[C::NE], ej[C::NE];
+    packed_entries<NMAX>(N, NP, lane, ei, ej);
+#pragma unroll
+    for(int k = 0; k < C::NE; k++)
+      if(lane + 64*k < NP)
+      {
+        const double* ci = SL + col_off(ei[k], N); const double* cj = SL + col_off(ej[k], N) + ei[k] - ej[k];
+        double s = 0.0;
+        for(int r = 0; r < N - ei[k]; r++) s += ci[r]*cj[r];
+        SA[lane + 64*k] = s;
+      }
+  }
+  wsync();
+  if(A.var && lane < N) A.var[(size_t)b*N + lane] = SA[col_off(lane, N)];
+  if(A.cov)
+    for(int e = lane; e < N*N; e += 64)
+    {
+      const int i = e/N;
+      A.cov[(size_t)b*N*N + e] = sym_at(SA, i, e - i*N, N);
+    }
+  if(!A.fac) return;
+
+  // ---- the second sweep over J: tiles of T rows, row stride N | 1 in LDS (lanes read different rows: an odd stride keeps
+  // them on different banks), lane t takes feature t of the tile: a = J_f Sigma J_f' against Sigma in LDS ----
+  const int fs = A.fs, NF = A.NF, NS = N | 1, Mc = NF*fs;
+  int T = min(min(64, BATCH_TILE/N), (BATCH_TILE + 64)/NS);
+  if(fs == 2) T &= ~1;
+  constexpr int NL = BATCH_TILE/64;
+  int po[NL];
+#pragma unroll
+  for(int u = 0; u < NL; u++) { const int e = lane + 64*u, r = e/N; po[u] = r*NS + e - r*N; }
+  const double kf = scale/8.0;
+  double* tile = SL;
+  double v[NL];
+  {
+    const int cnt = min(T, Mc)*N;
+#pragma unroll
+    for(int u = 0; u < NL; u++) v[u] = lane + 64*u < cnt ? Jb[lane + 64*u] : 0.0;
+  }
+  for(int r0 = 0; r0 < Mc; r0 += T)
+  {
+    const int tc = min(T, Mc - r0);
+    wsync();
+#pragma unroll
+    for(int u = 0; u < NL; u++) if(lane + 64*u < T*N) tile[po[u]] = v[u];
+    wsync();
+    if(r0 + T < Mc)
+    {
+      const int r1 = r0 + T, cnt = min(T, Mc - r1)*N;
+      const double* Jn = Jb + (size_t)r1*N;
+#pragma unroll
+      for(int u = 0; u < NL; u++) v[u] = lane + 64*u < cnt ? Jn[lane + 64*u] : 0.0;
+    }
+    if(lane*fs < tc)
+    {
+      const size_t f = (size_t)(r0/fs + lane);
+      if(fs == 1)
+      {
+        const double* r = tile + lane*NS;
+        double a = 0.0;
+        int idx = 0;
+        for(int j = 0; j < N; j++)
+        {
+          const double rj = r[j], d = SA[idx++];
+          double t0 = 0.0;
+          for(int i = j + 1; i < N; i++) t0 += SA[idx++]*r[i];
+          a += rj*(d*rj + 2.0*t0);
+        }
+        A.fac[(size_t)b*NF + f] = factor1(a, xb[r0 + lane], kf);
+      }
+      else
+      {
+        const double* ra = tile + 2*lane*NS; const double* rb = ra + NS;
+        double a00 = 0.0, a01 = 0.0, a11 = 0.0;
+        int idx = 0;
+        for(int j = 0; j < N; j++)
+        {
+          const double aj = ra[j], bj = rb[j], d = SA[idx++];
+          double t0 = 0.0, t1 = 0.0;
+          for(int i = j + 1; i < N; i++) { const double s = SA[idx++]; t0 += s*ra[i]; t1 += s*rb[i]; }
+          a00 += aj*(d*aj + 2.0*t0); a01 += aj*(d*bj + t1) + bj*t0; a11 += bj*(d*bj + 2.0*t1);
+        }
+        A.fac[(size_t)b*NF + f] = factor2(a00, a01, a11, xb[r0 + 2*lane], xb[r0 + 2*lane + 1], kf);
+      }
+    }
+  }
+}
+
+template <int NMAX>
+__global__ void __launch_bounds__(64*BATCH_WPB) k_batch_uncertainty(UncDev A)
+{
+  __shared__ double lds[BATCH_WPB*(BatchCfg<NMAX>::NP + BatchCfg<NMAX>::SCR)];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x*BATCH_WPB + w;
+  if(b < A.B) unc_problem<NMAX>(A, b, lane, lds + w*(BatchCfg<NMAX>::NP + BatchCfg<NMAX>::SCR));
+}
+
 __global__ void __launch_bounds__(256) k_batch_init(BatchDev A)
 {
   const int b = blockIdx.x*256 + threadIdx.x;
@@ -374,10 +593,12 @@ struct BatchCache
   int* h_counter = nullptr;
   void* d_eval = nullptr; size_t eval_bytes = 0;      // x, J of the trial points
   void* d_state = nullptr; size_t state_bytes = 0;    // everything else
+  void* h_stage = nullptr; size_t stage_bytes = 0;    // page-locked: what the uncertainty call uploads and reads back
 };
 std::mutex g_mu;
 BatchCache g_cache;
 thread_local double t_stats[3] = {0.0, 0.0, 0.0};
+thread_local double t_unc_stats[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 
 void release_locked()
 {
@@ -389,6 +610,7 @@ void release_locked()
     if(K.d_eval) (void)hipFree(K.d_eval);
     if(K.d_state) (void)hipFree(K.d_state);
     if(K.h_counter) (void)hipHostFree(K.h_counter);
+    if(K.h_stage) (void)hipHostFree(K.h_stage);
     for(hipEvent_t& e : K.ev) if(e) (void)hipEventDestroy(e);
     if(K.stream) (void)hipStreamDestroy(K.stream);
     if(sw) (void)hipSetDevice(cur);
@@ -399,14 +621,13 @@ void release_locked()
 #define BHIP(call) \
   do { hipError_t e__ = (call); \
        if(e__ != hipSuccess) { dlg_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e__)); \
-                               BMSG("dogleg_amd_optimize_dense_batch: %s -> %s", #call, hipGetErrorString(e__)); (void)hipGetLastError(); return -1; } } while(0)
+                               BMSG("%s: %s -> %s", who, #call, hipGetErrorString(e__)); (void)hipGetLastError(); return -1; } } while(0)
 
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f, void* cookie,
-               const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)
+// the device, the stream and the page-locked counter of the cache
+int cache_open(const char* who)
 {
-  const char* who = "dogleg_amd_optimize_dense_batch";
   int ndev = 0;
   if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
   {
@@ -424,6 +645,35 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg
     K.device = dev;
     BHIP(hipHostMalloc((void**)&K.h_counter, sizeof(int)));
   }
+  return 0;
+}
+// the two device buffers of the cache, grown to eval_bytes and state_bytes
+bool cache_ensure(const char* who, unsigned int B, unsigned int N, unsigned int M, size_t eval_bytes, size_t state_bytes)
+{
+  BatchCache& K = g_cache;
+  auto ensure = [&](void** ptr, size_t* have, size_t want) -> bool {
+    if(*have >= want) return true;
+    if(*ptr) { (void)hipFree(*ptr); *ptr = nullptr; *have = 0; }
+    if(hipMalloc(ptr, want) != hipSuccess)
+    {
+      (void)hipGetLastError(); *ptr = nullptr;
+      dlg_set_error("%s: cannot allocate %zu bytes of device memory", who, want);
+      BMSG("%s: B = %u problems of %u x %u need %zu + %zu bytes of device memory: the allocation of %zu failed", who, B, M, N,
+           eval_bytes, state_bytes, want);
+      return false;
+    }
+    *have = want;
+    return true;
+  };
+  return ensure(&K.d_eval, &K.eval_bytes, eval_bytes) && ensure(&K.d_state, &K.state_bytes, state_bytes);
+}
+
+int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f, void* cookie,
+               const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)
+{
+  const char* who = "dogleg_amd_optimize_dense_batch";
+  if(cache_open(who)) return -1;
+  BatchCache& K = g_cache;
   const int NP = (int)(N*(N + 1)/2);
   // sizes in doubles first: B * M * (N + 1) can pass 2^64 bytes
   const double eval_d = (double)B*(double)M*((double)N + 1.0);
@@ -439,21 +689,7 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg
   const size_t sc_bytes = align256(sizeof(double)*(size_t)B*SC_COUNT), st_bytes = align256(sizeof(int)*(size_t)B*ST_COUNT);
   const size_t live_bytes = align256(B);
   const size_t eval_bytes = x_bytes + J_bytes, state_bytes = 5*vec_bytes + G_bytes + sc_bytes + st_bytes + live_bytes + 256;
-  auto ensure = [&](void** ptr, size_t* have, size_t want) -> bool {
-    if(*have >= want) return true;
-    if(*ptr) { (void)hipFree(*ptr); *ptr = nullptr; *have = 0; }
-    if(hipMalloc(ptr, want) != hipSuccess)
-    {
-      (void)hipGetLastError(); *ptr = nullptr;
-      dlg_set_error("%s: cannot allocate %zu bytes of device memory", who, want);
-      BMSG("%s: B = %u problems of %u x %u need %zu + %zu bytes of device memory: the allocation of %zu failed", who, B, M, N,
-           eval_bytes, state_bytes, want);
-      return false;
-    }
-    *have = want;
-    return true;
-  };
-  if(!ensure(&K.d_eval, &K.eval_bytes, eval_bytes) || !ensure(&K.d_state, &K.state_bytes, state_bytes)) return -1;
+  if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes)) return -1;
 
   BatchDev A;
   A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = NP;
@@ -530,6 +766,94 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg
   return 0;
 }
 
+int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f, void* cookie,
+               double* lambda, double* covariance, double* variances, double* factors, double* scale, int fs, int* status)
+{
+  const char* who = "dogleg_amd_dense_batch_uncertainty";
+  double* const ts = t_unc_stats;              // kernel launches, synchronisations, copies + fills: counted where they happen
+  for(int k = 0; k < 5; k++) ts[k] = 0.0;
+  const unsigned int NF = M/(unsigned int)fs;
+  const double eval_d = (double)B*(double)M*((double)N + 1.0);
+  const double state_d = (double)B*((double)N + 3.0 + (variances ? N : 0.0) + (covariance ? (double)N*N : 0.0) + (factors ? NF : 0.0));
+  if((eval_d + state_d)*8.0 > 1.0e15)
+  {
+    dlg_set_error("%s: %.3g bytes of device memory", who, (eval_d + state_d)*8.0);
+    BMSG("%s: B = %u problems of %u x %u need %.3g bytes of device memory", who, B, M, N, (eval_d + state_d)*8.0);
+    return -1;
+  }
+  // (the arithmetic above needs no device: a call that cannot fit is refused before any device work)
+  if(cache_open(who)) return -1;
+  BatchCache& K = g_cache;
+  // device (and staging) layout: p | lambda | scale | status | variances | covariance | factors, then the live bytes;
+  // up: p .. scale, down: lambda .. factors, one copy each
+  const size_t x_bytes = align256(sizeof(double)*(size_t)B*M), J_bytes = align256(sizeof(double)*(size_t)B*M*N);
+  const size_t p_bytes = align256(sizeof(double)*(size_t)B*N), b_bytes = align256(sizeof(double)*(size_t)B);
+  const size_t st_bytes = align256(sizeof(int)*(size_t)B);
+  const size_t var_bytes = variances ? p_bytes : 0, cov_bytes = covariance ? align256(sizeof(double)*(size_t)B*N*N) : 0;
+  const size_t fac_bytes = factors ? align256(sizeof(double)*(size_t)B*NF) : 0;
+  const size_t o_lam = p_bytes, o_scale = o_lam + b_bytes, o_st = o_scale + b_bytes, o_var = o_st + st_bytes;
+  const size_t o_cov = o_var + var_bytes, o_fac = o_cov + cov_bytes, io_bytes = o_fac + fac_bytes;
+  const size_t eval_bytes = x_bytes + J_bytes, state_bytes = io_bytes + align256(B);
+  if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes)) return -1;
+  if(K.stage_bytes < io_bytes)
+  {
+    if(K.h_stage) { (void)hipHostFree(K.h_stage); K.h_stage = nullptr; K.stage_bytes = 0; }
+    if(hipHostMalloc(&K.h_stage, io_bytes) != hipSuccess)
+    {
+      (void)hipGetLastError(); K.h_stage = nullptr;
+      dlg_set_error("%s: cannot allocate %zu bytes of page-locked memory", who, io_bytes);
+      BMSG("%s: B = %u problems of %u x %u need %zu bytes of page-locked host memory: the allocation failed", who, B, M, N, io_bytes);
+      return -1;
+    }
+    K.stage_bytes = io_bytes;
+  }
+  char* d = (char*)K.d_state; char* h = (char*)K.h_stage;
+  UncDev A;
+  A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = (int)(N*(N + 1)/2); A.fs = fs; A.NF = (int)NF;
+  A.x = (double*)K.d_eval; A.J = (double*)((char*)K.d_eval + x_bytes);
+  double* d_p = (double*)d;
+  A.lam = (double*)(d + o_lam); A.scale = factors ? (double*)(d + o_scale) : nullptr; A.status = (int*)(d + o_st);
+  A.var = variances ? (double*)(d + o_var) : nullptr; A.cov = covariance ? (double*)(d + o_cov) : nullptr;
+  A.fac = factors ? (double*)(d + o_fac) : nullptr;
+  unsigned char* d_live = (unsigned char*)(d + io_bytes);
+
+  memcpy(h, p, sizeof(double)*(size_t)B*N);
+  if(lambda) memcpy(h + o_lam, lambda, sizeof(double)*B); else memset(h + o_lam, 0, sizeof(double)*B);
+  if(factors) memcpy(h + o_scale, scale, sizeof(double)*B);
+
+  const bool timing = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
+  if(timing) for(hipEvent_t& e : K.ev) if(!e) BHIP(hipEventCreate(&e));
+  hipStream_t st = K.stream;
+  BHIP(hipMemcpyAsync(d, h, o_st, hipMemcpyHostToDevice, st)); ts[2] += 1.0;
+  BHIP(hipMemsetAsync(d_live, 1, B, st)); ts[2] += 1.0;
+  if(timing) BHIP(hipEventRecord(K.ev[0], st));
+  f(d_p, const_cast<double*>(A.x), const_cast<double*>(A.J), d_live, B, (void*)st, cookie);
+  if(timing) BHIP(hipEventRecord(K.ev[1], st));
+  const dim3 grid((B + BATCH_WPB - 1)/BATCH_WPB), block(64*BATCH_WPB);
+  if(N <= 8)       hipLaunchKernelGGL(k_batch_uncertainty<8>, grid, block, 0, st, A);
+  else if(N <= 16) hipLaunchKernelGGL(k_batch_uncertainty<16>, grid, block, 0, st, A);
+  else if(N <= 24) hipLaunchKernelGGL(k_batch_uncertainty<24>, grid, block, 0, st, A);
+  else             hipLaunchKernelGGL(k_batch_uncertainty<32>, grid, block, 0, st, A);
+  BHIP(hipGetLastError()); ts[0] += 1.0;
+  if(timing) BHIP(hipEventRecord(K.ev[2], st));
+  BHIP(hipMemcpyAsync(h + o_lam, d + o_lam, io_bytes - o_lam, hipMemcpyDeviceToHost, st)); ts[2] += 1.0;
+  BHIP(hipStreamSynchronize(st)); ts[1] += 1.0;
+  double ms_cb = 0.0, ms_lib = 0.0;
+  if(timing)
+  {
+    float a = 0.f, c = 0.f;
+    BHIP(hipEventElapsedTime(&a, K.ev[0], K.ev[1])); BHIP(hipEventElapsedTime(&c, K.ev[1], K.ev[2]));
+    ms_cb = a; ms_lib = c;
+  }
+  if(lambda) memcpy(lambda, h + o_lam, sizeof(double)*B);
+  if(factors) { memcpy(scale, h + o_scale, sizeof(double)*B); memcpy(factors, h + o_fac, sizeof(double)*(size_t)B*NF); }
+  memcpy(status, h + o_st, sizeof(int)*B);
+  if(variances) memcpy(variances, h + o_var, sizeof(double)*(size_t)B*N);
+  if(covariance) memcpy(covariance, h + o_cov, sizeof(double)*(size_t)B*N*N);
+  ts[3] = ms_cb; ts[4] = ms_lib;
+  return 0;
+}
+
 } // namespace
 
 int dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f,
@@ -539,6 +863,21 @@ int dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int 
   const int rc = run_locked(p, B, N, M, f, cookie, prm, results);
   if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
   return rc;
+}
+int dlg_dense_batch_uncertainty_run(const double* p, unsigned int B, unsigned int N, unsigned int M,
+                                     dogleg_callback_device_batch_t* f, void* cookie, double* lambda, double* covariance,
+                                     double* variances, double* factors, double* scale, int fs, int* status)
+{
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int rc = unc_locked(p, B, N, M, f, cookie, lambda, covariance, variances, factors, scale, fs, status);
+  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
+  return rc;
+}
+int dlg_dense_batch_uncertainty_last_stats(double* out, int n)
+{
+  int k = 0;
+  for(; k < n && k < 5; k++) out[k] = t_unc_stats[k];
+  return k;
 }
 void dlg_dense_batch_release()
 {

@@ -1514,6 +1514,40 @@ int dogleg_amd_optimize_dense_batch(double* p, unsigned int B, unsigned int Nsta
   return dlg_dense_batch_run(p, B, Nstate, Nmeas, f, cookie, parameters ? parameters : &g_params, results);
 }
 int dogleg_amd_batch_last_stats(double* out, int n) { return out ? dlg_dense_batch_last_stats(out, n) : 0; }
+int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                       dogleg_callback_device_batch_t* f, void* cookie,
+                                       double* lambda, double* covariance, double* variances, double* factors,
+                                       double* scale, int featureSize, int* status)
+{
+  const char* who = "dogleg_amd_dense_batch_uncertainty";
+  if(!p || !f || !status) { MSG("%s: p, the callback and status must be given", who); return -1; }
+  if(B == 0 || Nstate == 0 || Nmeas == 0) { MSG("%s: B = %u, Nstate = %u, Nmeas = %u: none may be 0", who, B, Nstate, Nmeas); return -1; }
+  if(Nstate > DOGLEG_AMD_BATCH_MAX_NSTATE)
+  {
+    MSG("%s: Nstate = %u, the batch kernels take at most %d variables (larger problems: a loop over dogleg_optimize_dense2)", who,
+        Nstate, DOGLEG_AMD_BATCH_MAX_NSTATE);
+    return -1;
+  }
+  if(B > 0x7fffffffu/4 || Nmeas > 0x7fffffffu/(Nstate + 1))
+  { MSG("%s: B = %u problems of %u x %u: beyond the index range of the batch kernels", who, B, Nmeas, Nstate); return -1; }
+  if(featureSize > 2) { MSG("%s: featureSize = %d: only 1 and 2 are supported", who, featureSize); return -1; }
+  const int fs = featureSize <= 1 ? 1 : 2;
+  if(!covariance && !variances && !factors) { MSG("%s: none of covariance, variances, factors is asked for", who); return -1; }
+  if(factors && !scale) { MSG("%s: factors need scale", who); return -1; }
+  if(factors && Nmeas/(unsigned int)fs == 0) { MSG("%s: Nmeas = %u holds no feature of size %d", who, Nmeas, fs); return -1; }
+  if(factors && Nmeas <= Nstate + 1)
+    for(unsigned int b = 0; b < B; b++)
+      if(!(scale[b] > 0.0))
+      {
+        MSG("%s: scale[%u] <= 0 is to be computed, which needs Nmeas > Nstate + 1 (%u, %u)", who, b, Nmeas, Nstate);
+        return -1;
+      }
+  const char* ws = getenv("DOGLEG_AMD_WORLD_SIZE");
+  if(t_comm.set || (ws && atoi(ws) > 1))
+  { MSG("%s: one rank only (a communicator is set: dogleg_amd_clear_communicator)", who); return -1; }
+  return dlg_dense_batch_uncertainty_run(p, B, Nstate, Nmeas, f, cookie, lambda, covariance, variances, factors, scale, fs, status);
+}
+int dogleg_amd_batch_uncertainty_last_stats(double* out, int n) { return out ? dlg_dense_batch_uncertainty_last_stats(out, n) : 0; }
 // what the library keeps between solves (the idle backend with its device memory, page-locked host buffers)
 void dogleg_amd_release_cache(void)
 {
