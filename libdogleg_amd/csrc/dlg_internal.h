@@ -54,6 +54,8 @@ struct DlgSlot
   const double* Jin() const { return J_bound ? J_bound : J; }
 };
 
+struct DevScratch { double* p = nullptr; size_t cap = 0; };      // a device buffer that only grows (cap in doubles)
+
 struct dlg_backend
 {
   int type = 0, N = 0, M = 0, nnz = 0, flags = 0, device = 0;
@@ -174,9 +176,10 @@ struct dlg_backend
   bool    defer_factor_sync = false;   // dlg_gauss_newton: the *_factorize calls enqueue only; the pivot
                                        // flag is read after the solve's synchronisation
   double* d_work = nullptr;   // N-vector scratch
-  double* d_solve_scr = nullptr; size_t solve_scr_cap = 0;   // scratch of the post-solve entry points (backend.hip: solve_scratch)
-  double* d_lev = nullptr; size_t lev_cap = 0;               // scratch of the leverage entry points (backend.hip: lev_scratch)
-  struct CovPlan* cov = nullptr; int cov_last = -1;          // [2] plans of the covariance entry points (requests, marginal variances), the last one run
+  // scratch of the users of the held factor (factor_users.hip: grow): right-hand sides of the solves, and Gram products
+  // and forward-solve blocks of the leverage / covariance calls (two: the observation form of the query covariance uses both at once)
+  DevScratch solve_scr, lev_scr;
+  struct CovPlan* cov = nullptr; int cov_last = -1;          // [COV_NPLAN] plans of the covariance entry points, the last of [0] (requests) and [1] (marginal variances) run
   struct SelInv* selinv = nullptr;                           // the selected inverse and its entry lookup (dlg_covariance_entries)
 
   // sparse
@@ -398,6 +401,14 @@ void sparse_release_held(dlg_backend* b);
 int sparse_restore_factor(dlg_backend* b, bool* restored, bool rearm = true);
 double sparse_current_lambda(const dlg_backend* b);                                 // of the last factorisation enqueued
 const double* sparse_pivot_minmax(const dlg_backend* b, int* n);                    // [supernode][min, max] of diag(L) left by the last backward solve
+// ---- the users of the held factor (factor_users.hip).  What such an entry point needs beyond a factor held for its slot:
+// the slot's Jacobian on the device (refuses a dense-products backend and a slot without inputs), a backend that is not
+// sharded, one that is not partitioned, a pattern on a sparse backend.  backend.hip: the one place that refuses.
+enum { DLG_NEEDS_J = 1, DLG_NEEDS_UNSHARDED = 2, DLG_NEEDS_UNPARTITIONED = 4, DLG_NEEDS_PATTERN = 8 };
+int dlg_factor_user_begin(dlg_backend* b, int s, const char* who, unsigned needs);
+// how the forward solves of the chunks go (factor_users.hip: factor_route); the value is part of a plan's key
+enum FactorRoute { ROUTE_REACH = 0, ROUTE_SWEEP = 1, ROUTE_DENSE = 2 };
+
 // blocked multi-right-hand-side solves (sparse_multi.hip / kernels_dense.hip): MR = 16 right-hand sides
 // interleaved [N][MR] (element (variable k, rhs c) at k*MR + c), solved in place, original order
 int sparse_multi_width_ok(const dlg_backend* b);
@@ -430,7 +441,7 @@ int lev_gram_rows(dlg_backend* b, int s, int row0, int nrows, int fs, const doub
 int lev_finish(dlg_backend* b, int s, int nf, int fs, const int* d_slot_ptr, const double* d_gram, double scale, int mode, double* d_out);
 int dense_leverage_gram(dlg_backend* b, int s, int fs, int nf, double* d_work, size_t work_doubles, double* d_gram);
 
-// ---- covariance blocks Sigma = (JtJ + lambda I)^-1 (backend.hip: dlg_covariance_blocks / dlg_marginal_variances).
+// ---- covariance blocks Sigma = (JtJ + lambda I)^-1 (factor_users.hip: dlg_covariance_blocks / dlg_marginal_variances).
 // A request is the sub-block Sigma[r0 : r0+nr, c0 : c0+nc] whose two ranges hold at most COV_MAXV distinct variables.
 // Requests are packed whole into chunks of at most MR = 16 distinct variables (one unit right-hand side each); a chunk
 // needs the Gram products (a, c), a <= c, of the columns its requests pair up, at most COV_NP.
@@ -483,12 +494,11 @@ struct CovPlan
 // b->cov: the plans of dlg_covariance_blocks, dlg_marginal_variances, dlg_query_covariance and dlg_leverage_query
 constexpr int COV_NPLAN = 4;
 void cov_plan_release(CovPlan& P);
-int cov_plan_build(dlg_backend* b, CovPlan& P, int route, int which, int nreq, const int* r0, const int* nr, const int* c0,
+int cov_plan_build(dlg_backend* b, CovPlan& P, FactorRoute route, int which, int nreq, const int* r0, const int* nr, const int* c0,
                    const int* nc, const char* who);
 uint64_t sparse_pattern_key(const dlg_backend* b);
 int sparse_cov_reach_plan(dlg_backend* b, CovPlan& P);            // R, goff, slot_ptr, pcol and gram of the reach route
 int sparse_cov_reach_run(dlg_backend* b, CovPlan& P);
-int sparse_cov_stats(const dlg_backend* b, long* nchunks, long* visits, int* nsn);
 int cov_plan_stats(const dlg_backend* b, const CovPlan& P, long* nchunks, long* visits, int* nsn);
 int cov_unit_il(dlg_backend* b, const CovPlan& P, int ch, double* d_il);
 int cov_pick(dlg_backend* b, const CovPlan& P, int ch, const double* d_il);
@@ -496,13 +506,13 @@ int cov_finish(dlg_backend* b, const CovPlan& P);
 int dense_cov_setup(dlg_backend* b, CovPlan& P);      // P.kb0
 int dense_cov_gram(dlg_backend* b, const CovPlan& P, double* d_work, size_t work_doubles);
 
-// ---- query covariance Jq Sigma Jq^T (backend.hip: dlg_query_covariance).  A query is 1 .. 16 rows of a CSR over the
+// ---- query covariance Jq Sigma Jq^T (factor_users.hip: dlg_query_covariance).  A query is 1 .. 16 rows of a CSR over the
 // variables; queries are packed whole, in order, into chunks of at most 16 rows (one right-hand side a row); a query of fs
 // rows needs the fs (fs + 1) / 2 Gram products of its own rows.  The plan is a CovPlan (K.crow non-empty); route 0: the
 // reach of the chunks' variables (sparse), 1: full solves (sparse sweep, and the observation form), 2: dense forward.
 constexpr int QCOV_MAXROWS = 16;
 int query_pack(int N, int nq, const int* qrow, const int* rowptr, const int* var, CovPack& K, const char* who);
-int query_plan_build(dlg_backend* b, CovPlan& P, int route, int nq, const int* qrow, const int* rowptr, const int* var,
+int query_plan_build(dlg_backend* b, CovPlan& P, FactorRoute route, int nq, const int* qrow, const int* rowptr, const int* var,
                      const char* who);
 int sparse_query_reach_run(dlg_backend* b, CovPlan& P);
 int query_rhs_il(dlg_backend* b, const CovPlan& P, int ch0, int nch, double* d_il);   // Jq^T of chunks ch0 .. (interleaved, original order), chunk q at d_il + q N 16

@@ -1075,19 +1075,28 @@ int dense_solve(dlg_backend* b, const double* rhs, double* out)
   return DLG_OK;
 }
 
+// L Y = B in place, tile after tile from the tile at kb0 on, for nq blocks of 16 interleaved right-hand sides [n][16] that
+// lie stride doubles apart; ystart (or null): per block the tile its right-hand sides begin at -- its workgroups return
+// at once on the tiles above
+static void dense_fwd_tiles(dlg_backend* b, hipStream_t st, double* d_work, size_t stride, int nq, int kb0, const int* ystart)
+{
+  const int n = b->N;
+  for(int kb = kb0; kb < n; kb += NB)
+  {
+    const int nb = (n - kb < NB) ? n - kb : NB;
+    hipLaunchKernelGGL(k_trsm_diag_m, dim3(1, nq), dim3(TPB), 0, st, b->Linv + (size_t)(kb / NB)*NB*NB, kb, nb, d_work, 0, stride, ystart);
+    const int rem = n - kb - nb;
+    if(rem > 0)
+      hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64)), nq), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_work, stride, ystart);
+  }
+}
+
 // (L L^T) X = B for 16 interleaved right-hand sides [n][16], in place
 int dense_solve_multi(dlg_backend* b, double* d_il)
 {
   const int n = b->N;
   hipStream_t st = b->stream;
-  for(int kb = 0, blk = 0; kb < n; kb += NB, blk++)
-  {
-    const int nb = (n - kb < NB) ? n - kb : NB;
-    hipLaunchKernelGGL(k_trsm_diag_m, dim3(1), dim3(TPB), 0, st, b->Linv + (size_t)blk*NB*NB, kb, nb, d_il, 0, (size_t)0, nullptr);
-    const int rem = n - kb - nb;
-    if(rem > 0)
-      hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64))), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_il, (size_t)0, nullptr);
-  }
+  dense_fwd_tiles(b, st, d_il, 0, 1, 0, nullptr);
   const int nblk = dlg_cdiv(n, NB);
   for(int blk = nblk - 1; blk >= 0; blk--)
   {
@@ -1121,14 +1130,7 @@ int dense_leverage_gram(dlg_backend* b, int s, int fs, int nf, double* d_work, s
   {
     const int nq = std::min(per, nch - q0);
     hipLaunchKernelGGL(k_jt_chunks_dense, dim3(dlg_cdiv((long)blk, TPB), nq), dim3(TPB), 0, st, b->slot[s].Jin(), n, q0*DMR, nrow, d_work);
-    for(int kb = 0, bi = 0; kb < n; kb += NB, bi++)
-    {
-      const int nb = (n - kb < NB) ? n - kb : NB;
-      hipLaunchKernelGGL(k_trsm_diag_m, dim3(1, nq), dim3(TPB), 0, st, b->Linv + (size_t)bi*NB*NB, kb, nb, d_work, 0, blk, nullptr);
-      const int rem = n - kb - nb;
-      if(rem > 0)
-        hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64)), nq), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_work, blk, nullptr);
-    }
+    dense_fwd_tiles(b, st, d_work, blk, nq, 0, nullptr);
     hipLaunchKernelGGL(k_lev_gram_dense, dim3(nq), dim3(TPB), 0, st, d_work, n, fs, d_gram + (size_t)q0*LEV_NP);
   }
   DLG_LAUNCH_CHECK();
@@ -1171,14 +1173,7 @@ int dense_cov_gram(dlg_backend* b, const CovPlan& P, double* d_work, size_t work
     for(int q = q0; q < q0 + nq; q++) kb0 = std::min(kb0, P.K.kb0[q]);
     if(P.crow) DLG_CHECK(query_rhs_il(b, P, q0, nq, d_work));      // (a query plan: the rows of Jq)
     else hipLaunchKernelGGL(k_cov_units_dense, dim3(dlg_cdiv((long)blk, TPB), nq), dim3(TPB), 0, st, P.var, n, q0, d_work);
-    for(int kb = kb0; kb < n; kb += NB)
-    {
-      const int nb = (n - kb < NB) ? n - kb : NB;
-      hipLaunchKernelGGL(k_trsm_diag_m, dim3(1, nq), dim3(TPB), 0, st, b->Linv + (size_t)(kb / NB)*NB*NB, kb, nb, d_work, 0, blk, P.kb0 + q0);
-      const int rem = n - kb - nb;
-      if(rem > 0)
-        hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64)), nq), dim3(TPB), 0, st, b->G, n, kb, nb, n, d_work, blk, P.kb0 + q0);
-    }
+    dense_fwd_tiles(b, st, d_work, blk, nq, kb0, P.kb0 + q0);
     hipLaunchKernelGGL(k_cov_gram_dense, dim3(nq), dim3(TPB), 0, st, d_work, n, q0, P.kb0, P.pptr, P.prod, P.goff, P.gram);
   }
   DLG_LAUNCH_CHECK();
@@ -1213,14 +1208,7 @@ int dense_selinv_run(dlg_backend* b, SelInv& X)
     const int nq = std::min(X.dper, X.dnch - q0);
     const int kb0 = q0*DMR / NB*NB;
     hipLaunchKernelGGL(k_cov_units_dense, dim3(dlg_cdiv((long)blk, TPB), nq), dim3(TPB), 0, st, X.dvar, n, q0, X.dwork);
-    for(int kb = kb0; kb < n; kb += NB)
-    {
-      const int nb = (n - kb < NB) ? n - kb : NB;
-      hipLaunchKernelGGL(k_trsm_diag_m, dim3(1, nq), dim3(TPB), 0, st, b->Linv + (size_t)(kb / NB)*NB*NB, kb, nb, X.dwork, 0, blk, X.dystart + q0);
-      const int rem = n - kb - nb;
-      if(rem > 0)
-        hipLaunchKernelGGL(k_trsm_update_fwd_m, dim3(dlg_cdiv(rem, 16*(TPB/64)), nq), dim3(TPB), 0, st, b->G, n, kb, nb, n, X.dwork, blk, X.dystart + q0);
-    }
+    dense_fwd_tiles(b, st, X.dwork, blk, nq, kb0, X.dystart + q0);
     hipLaunchKernelGGL(k_linv_rowmajor, dim3(dlg_cdiv((long)blk, TPB), nq), dim3(TPB), 0, st, X.dwork, n, q0, X.Linv_rm);
   }
   DLG_HIP(hipMemsetAsync(X.Sig, 0, sizeof(double)*(size_t)n*n, st));

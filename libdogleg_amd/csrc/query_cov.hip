@@ -1,4 +1,4 @@
-// query_cov.hip -- query covariance Jq Sigma Jq^T (backend.hip: dlg_query_covariance), the kernels outside the reach route.
+// query_cov.hip -- query covariance Jq Sigma Jq^T (factor_users.hip: dlg_query_covariance), the kernels outside the reach route.
 // The reach route (the forward solve of the chunks' rows on the supernodes they reach) is k_cov_fwd_level<RhsCsr> in
 // sparse_multi.hip; here:
 //   k_query_rhs_il     the rows of a chunk as interleaved right-hand sides Jq^T (the full-solve routes, dense forward)

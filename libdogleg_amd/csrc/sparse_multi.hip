@@ -673,6 +673,66 @@ int reach_setup(dlg_backend* b)
   DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_fwd_level<RhsCsr>), hipFuncAttributeMaxDynamicSharedMemorySize, Y->lev_lds));
   return DLG_OK;
 }
+// the levels of a reach plan that hold pairs, batch after batch: launch(the level's pairs in R.wl, how many)
+template <class F> void reach_for_each_level(const ReachPlan& R, int nl, F launch)
+{
+  for(int bt = 0; bt < R.nbatch; bt++)
+    for(int l = 0; l < nl; l++)
+    {
+      const int w0 = R.wl_ptr[(size_t)bt*nl + l], n = R.wl_ptr[(size_t)bt*nl + l + 1] - w0;
+      if(n > 0) launch(R.wl + w0, n);
+    }
+}
+// the supernodes the columns of chunk ch start at: those of its variables (covariance blocks) ...
+void cov_starts(const SymHost& H, const CovPack& K, int ch, std::vector<int>& st)
+{
+  for(int c = 0; c < MR; c++) { const int x = K.var[(size_t)ch*MR + c]; if(x >= 0) st.push_back(H.col_sn[H.iperm[x]]); }
+}
+// ... those of its rows' variables (query covariance)
+void query_starts(const SymHost& H, const CovPack& K, int ch, std::vector<int>& st)
+{
+  for(int q = K.qrp[K.crow[ch]]; q < K.qrp[K.crow[ch+1]]; q++) st.push_back(H.col_sn[H.iperm[K.qvar[q]]]);
+}
+// the slots of a packed plan's Gram products.  Reach route: the reach of every chunk from starts(H, K, ch, list), a slot
+// of the chunk's products per (chunk, supernode) pair (cov_finish walks R.cp_ptr)
+template <class F> int reach_slots(dlg_backend* b, CovPlan& P, F starts)
+{
+  const SymHost& H = b->sym->H;
+  const CovPack& K = P.K;
+  DLG_CHECK(reach_setup(b));
+  ReachHost R;
+  reach_build(H, K.nch, [&](int ch, std::vector<int>& st) { starts(H, K, ch, st); }, R);
+  DLG_CHECK(reach_upload(R, K.nch, P.R));
+  std::vector<int64_t> goff(R.pair_sn.size() + 1, 0);
+  for(size_t q = 0; q < R.pair_sn.size(); q++) { const int ch = R.pair_ch[q]; goff[q+1] = goff[q] + (K.pptr[ch+1] - K.pptr[ch]); }
+  DLG_CHECK(upload(P.goff, goff));
+  DLG_HIP(hipMalloc(&P.gram, sizeof(double)*(size_t)std::max<int64_t>(goff.back(), 1)));
+  return DLG_OK;
+}
+// ... every other route: one slot per chunk
+int chunk_slots(CovPlan& P)
+{
+  const CovPack& K = P.K;
+  std::vector<int> slot_ptr(K.nch + 1);
+  std::vector<int64_t> goff(K.nch + 1);
+  for(int ch = 0; ch <= K.nch; ch++) { slot_ptr[ch] = ch; goff[ch] = K.pptr[ch]; }
+  DLG_CHECK(upload(P.slot_ptr, slot_ptr)); DLG_CHECK(upload(P.goff, goff));
+  DLG_HIP(hipMalloc(&P.gram, sizeof(double)*(size_t)std::max(K.pptr.back(), 1)));
+  return DLG_OK;
+}
+// the forward solves of a packed plan's chunks on the supernodes they reach, level by level
+template <class Rhs> int reach_run(dlg_backend* b, CovPlan& P, const Rhs& rhs)
+{
+  SparseSym* Y = b->sym;
+  DLG_CHECK(reach_setup(b));                 // (the LDS attribute and size of this pattern's widest supernode)
+  const ReachPlan& R = P.R;
+  reach_for_each_level(R, Y->H.nlevels, [&](const int* wl, int n) {
+    hipLaunchKernelGGL(k_cov_fwd_level<Rhs>, dim3(n), dim3(TPB), Y->lev_lds, b->stream, wl, R.pair_sn, R.pair_ch, R.pair_off,
+                       R.cp_ptr, Y->sn_c0, Y->sn_rowptr, Y->sn_rows, Y->sn_lx, Y->Lx, rhs, P.pptr, P.prod, P.goff, R.scr, P.gram);
+  });
+  DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
 
 // the (chunk, supernode) pairs of the chunks of nf features of fs rows
 int lev_plan_build(dlg_backend* b, int fs, int nf)
@@ -820,50 +880,22 @@ void cov_plan_release(CovPlan& P)
   P = CovPlan();
 }
 
-// the reach route of a packed plan: every chunk's reach from its columns' supernodes, a slot of the chunk's products per pair
+// the reach route of a packed plan: the slots, and the chunks' columns in the factor's order
 int sparse_cov_reach_plan(dlg_backend* b, CovPlan& P)
 {
-  SparseSym* Y = b->sym;
-  const SymHost& H = Y->H;
-  DLG_CHECK(reach_setup(b));
+  const SymHost& H = b->sym->H;
   const CovPack& K = P.K;
-  ReachHost R;
-  reach_build(H, K.nch, [&](int ch, std::vector<int>& st) {
-    for(int c = 0; c < MR; c++) { const int x = K.var[(size_t)ch*MR + c]; if(x >= 0) st.push_back(H.col_sn[H.iperm[x]]); }
-  }, R);
-  DLG_CHECK(reach_upload(R, K.nch, P.R));
-  std::vector<int64_t> goff(R.pair_sn.size() + 1, 0);
-  for(size_t q = 0; q < R.pair_sn.size(); q++) { const int ch = R.pair_ch[q]; goff[q+1] = goff[q] + (K.pptr[ch+1] - K.pptr[ch]); }
+  DLG_CHECK(reach_slots(b, P, cov_starts));
   std::vector<int> pcol(K.var.size());
   for(size_t i = 0; i < K.var.size(); i++) pcol[i] = K.var[i] >= 0 ? H.iperm[K.var[i]] : -1;
-  DLG_CHECK(upload(P.goff, goff)); DLG_CHECK(upload(P.pcol, pcol));
-  DLG_HIP(hipMalloc(&P.gram, sizeof(double)*(size_t)std::max<int64_t>(goff.back(), 1)));
-  P.slot_ptr = nullptr;                      // (R.cp_ptr)
-  return DLG_OK;
+  return upload(P.pcol, pcol);
 }
-int sparse_cov_reach_run(dlg_backend* b, CovPlan& P)
-{
-  SparseSym* Y = b->sym;
-  DLG_CHECK(reach_setup(b));                 // (the LDS attribute and size of this pattern's widest supernode)
-  const int nl = Y->H.nlevels;
-  const ReachPlan& R = P.R;
-  for(int bt = 0; bt < R.nbatch; bt++)
-    for(int l = 0; l < nl; l++)
-    {
-      const int w0 = R.wl_ptr[(size_t)bt*nl + l], n = R.wl_ptr[(size_t)bt*nl + l + 1] - w0;
-      if(n > 0)
-        hipLaunchKernelGGL(k_cov_fwd_level<RhsUnit>, dim3(n), dim3(TPB), Y->lev_lds, b->stream, R.wl + w0, R.pair_sn, R.pair_ch, R.pair_off,
-                           R.cp_ptr, Y->sn_c0, Y->sn_rowptr, Y->sn_rows, Y->sn_lx, Y->Lx, RhsUnit{P.pcol}, P.pptr, P.prod, P.goff, R.scr, P.gram);
-    }
-  DLG_LAUNCH_CHECK();
-  return DLG_OK;
-}
-// build plan P for route 0 (sparse, reach), 1 (sparse, full sweep) or 2 (dense): which 0, the requests; 1, the marginal
-// variances
-int cov_plan_build(dlg_backend* b, CovPlan& P, int route, int which, int nreq, const int* r0, const int* nr, const int* c0,
+int sparse_cov_reach_run(dlg_backend* b, CovPlan& P) { return reach_run(b, P, RhsUnit{P.pcol}); }
+// build plan P for a route: which 0, the requests; 1, the marginal variances
+int cov_plan_build(dlg_backend* b, CovPlan& P, FactorRoute route, int which, int nreq, const int* r0, const int* nr, const int* c0,
                    const int* nc, const char* who)
 {
-  const SymHost* H = route < 2 ? &b->sym->H : nullptr;
+  const SymHost* H = route != ROUTE_DENSE ? &b->sym->H : nullptr;
   if(which == 0) DLG_CHECK(cov_pack_requests(b->N, H ? H->iperm.data() : nullptr, nreq, r0, nr, c0, nc, P.K, who));
   else cov_pack_marginal(b->N, H ? H->perm.data() : nullptr, P.K);
   const CovPack& K = P.K;
@@ -871,24 +903,12 @@ int cov_plan_build(dlg_backend* b, CovPlan& P, int route, int which, int nreq, c
   DLG_CHECK(upload(P.var, K.var)); DLG_CHECK(upload(P.pptr, K.pptr)); DLG_CHECK(upload(P.prod, K.prod));
   DLG_CHECK(upload(P.e_ch, K.e_ch)); DLG_CHECK(upload(P.e_p, K.e_p));
   DLG_HIP(hipMalloc(&P.out, sizeof(double)*(size_t)std::max<long>(P.ne, 1)));
-  if(route == 0) return sparse_cov_reach_plan(b, P);
-  if(route == 2) DLG_CHECK(dense_cov_setup(b, P));
-  // one slot per chunk
-  std::vector<int> slot_ptr(K.nch + 1);
-  std::vector<int64_t> goff(K.nch + 1);
-  for(int ch = 0; ch <= K.nch; ch++) { slot_ptr[ch] = ch; goff[ch] = K.pptr[ch]; }
-  DLG_CHECK(upload(P.slot_ptr, slot_ptr)); DLG_CHECK(upload(P.goff, goff));
-  DLG_HIP(hipMalloc(&P.gram, sizeof(double)*(size_t)std::max(K.pptr.back(), 1)));
-  return DLG_OK;
+  if(route == ROUTE_REACH) return sparse_cov_reach_plan(b, P);
+  if(route == ROUTE_DENSE) DLG_CHECK(dense_cov_setup(b, P));
+  return chunk_slots(P);
 }
 uint64_t sparse_pattern_key(const dlg_backend* b) { return b->sym ? b->sym->pat_key : 0; }
-int sparse_cov_stats(const dlg_backend* b, long* nchunks, long* visits, int* nsn)
-{
-  if(!b->cov || b->cov_last < 0) { dlg_set_error("no covariance plan has been run"); return DLG_ERR_STATE; }
-  const CovPlan& P = b->cov[b->cov_last];
-  *nchunks = P.K.nch; *visits = P.R.npair > 0 ? P.R.visits : 0; *nsn = b->sym ? b->sym->H.nsn : 0;
-  return DLG_OK;
-}
+// of a plan that has been run: chunks, supernode visits of all chunks (reach route), supernodes of the pattern
 int cov_plan_stats(const dlg_backend* b, const CovPlan& P, long* nchunks, long* visits, int* nsn)
 {
   *nchunks = P.K.nch; *visits = P.R.npair > 0 ? P.R.visits : 0; *nsn = b->sym ? b->sym->H.nsn : 0;
@@ -927,9 +947,7 @@ extern "C" int dlg_covariance_plan_probe(int N, int M, const int* colptr, const 
   CovPack K;
   DLG_CHECK(cov_pack_requests(N, H.iperm.data(), nreq, r0, nr, c0, nc, K, "dlg_covariance_plan_probe"));
   ReachHost R;
-  reach_build(H, K.nch, [&](int ch, std::vector<int>& st) {
-    for(int c = 0; c < MR; c++) { const int x = K.var[(size_t)ch*MR + c]; if(x >= 0) st.push_back(H.col_sn[H.iperm[x]]); }
-  }, R);
+  reach_build(H, K.nch, [&](int ch, std::vector<int>& st) { cov_starts(H, K, ch, st); }, R);
   if(chunk_of_req) for(int q = 0; q < nreq; q++) chunk_of_req[q] = K.req_ch[q];
   const long v[] = { (long)K.nch, (long)R.pair_sn.size(), (long)K.maxvar };
   for(int i = 0; i < nstats && i < 3; i++) stats[i] = v[i];
@@ -993,16 +1011,9 @@ int query_pack(int N, int nq, const int* qrow, const int* rowptr, const int* var
   while((int)K.pptr.size() <= K.nch) K.pptr.push_back((int)K.prod.size());
   return DLG_OK;
 }
-namespace {
-// the supernodes the columns of chunk ch start at: those of its rows' variables
-void query_starts(const SymHost& H, const CovPack& K, int ch, std::vector<int>& st)
-{
-  for(int q = K.qrp[K.crow[ch]]; q < K.qrp[K.crow[ch+1]]; q++) st.push_back(H.col_sn[H.iperm[K.qvar[q]]]);
-}
-} // namespace
 // the device half of a query plan: the CSR, per route the slots (route 0: the reach of each chunk, a slot of the chunk's
 // products per pair; otherwise a slot per chunk), the values' buffer
-int query_plan_build(dlg_backend* b, CovPlan& P, int route, int nq, const int* qrow, const int* rowptr, const int* var,
+int query_plan_build(dlg_backend* b, CovPlan& P, FactorRoute route, int nq, const int* qrow, const int* rowptr, const int* var,
                      const char* who)
 {
   DLG_CHECK(query_pack(b->N, nq, qrow, rowptr, var, P.K, who));
@@ -1014,49 +1025,19 @@ int query_plan_build(dlg_backend* b, CovPlan& P, int route, int nq, const int* q
   DLG_CHECK(upload(P.crow, K.crow)); DLG_CHECK(upload(P.qrp, K.qrp));
   DLG_HIP(hipMalloc(&P.out, sizeof(double)*(size_t)std::max<long>(P.ne, 1)));
   DLG_HIP(hipMalloc(&P.qval, sizeof(double)*(size_t)std::max<long>(P.qnnz, 1)));
-  if(route == 0)
+  if(route == ROUTE_REACH)
   {
-    SparseSym* Y = b->sym;
-    const SymHost& H = Y->H;
-    DLG_CHECK(reach_setup(b));
-    ReachHost R;
-    reach_build(H, K.nch, [&](int ch, std::vector<int>& st) { query_starts(H, K, ch, st); }, R);
-    DLG_CHECK(reach_upload(R, K.nch, P.R));
-    std::vector<int64_t> goff(R.pair_sn.size() + 1, 0);
-    for(size_t q = 0; q < R.pair_sn.size(); q++) { const int ch = R.pair_ch[q]; goff[q+1] = goff[q] + (K.pptr[ch+1] - K.pptr[ch]); }
+    const SymHost& H = b->sym->H;
+    DLG_CHECK(reach_slots(b, P, query_starts));
     std::vector<int> pv(K.qvar.size());
     for(size_t q = 0; q < pv.size(); q++) pv[q] = H.iperm[K.qvar[q]];
-    DLG_CHECK(upload(P.goff, goff)); DLG_CHECK(upload(P.qvar, pv));
-    DLG_HIP(hipMalloc(&P.gram, sizeof(double)*(size_t)std::max<int64_t>(goff.back(), 1)));
-    return DLG_OK;
+    return upload(P.qvar, pv);
   }
   DLG_CHECK(upload(P.qvar, K.qvar));
-  if(route == 2) DLG_CHECK(dense_cov_setup(b, P));
-  std::vector<int> slot_ptr(K.nch + 1);
-  std::vector<int64_t> goff(K.nch + 1);
-  for(int ch = 0; ch <= K.nch; ch++) { slot_ptr[ch] = ch; goff[ch] = K.pptr[ch]; }
-  DLG_CHECK(upload(P.slot_ptr, slot_ptr)); DLG_CHECK(upload(P.goff, goff));
-  DLG_HIP(hipMalloc(&P.gram, sizeof(double)*(size_t)std::max(K.pptr.back(), 1)));
-  return DLG_OK;
+  if(route == ROUTE_DENSE) DLG_CHECK(dense_cov_setup(b, P));
+  return chunk_slots(P);
 }
-int sparse_query_reach_run(dlg_backend* b, CovPlan& P)
-{
-  SparseSym* Y = b->sym;
-  DLG_CHECK(reach_setup(b));
-  const int nl = Y->H.nlevels;
-  const ReachPlan& R = P.R;
-  const RhsCsr rhs{P.crow, P.qrp, P.qvar, P.qval};
-  for(int bt = 0; bt < R.nbatch; bt++)
-    for(int l = 0; l < nl; l++)
-    {
-      const int w0 = R.wl_ptr[(size_t)bt*nl + l], n = R.wl_ptr[(size_t)bt*nl + l + 1] - w0;
-      if(n > 0)
-        hipLaunchKernelGGL(k_cov_fwd_level<RhsCsr>, dim3(n), dim3(TPB), Y->lev_lds, b->stream, R.wl + w0, R.pair_sn, R.pair_ch, R.pair_off,
-                           R.cp_ptr, Y->sn_c0, Y->sn_rowptr, Y->sn_rows, Y->sn_lx, Y->Lx, rhs, P.pptr, P.prod, P.goff, R.scr, P.gram);
-    }
-  DLG_LAUNCH_CHECK();
-  return DLG_OK;
-}
+int sparse_query_reach_run(dlg_backend* b, CovPlan& P) { return reach_run(b, P, RhsCsr{P.crow, P.qrp, P.qvar, P.qval}); }
 // host only: the symbolic phase on a pattern and the packing and reach of a query batch.  stats: {chunks, pair visits, most
 // rows in a chunk}
 extern "C" int dlg_query_covariance_plan_probe(int N, int M, const int* colptr, const int* rowidx, int nq, const int* qrow,
@@ -1085,16 +1066,11 @@ int sparse_leverage_reach(dlg_backend* b, int s, int fs, int nf, double** d_gram
   if(!Y) { dlg_set_error("dlg_sparse_set_pattern must be called first"); return DLG_ERR_STATE; }
   DLG_CHECK(lev_plan_build(b, fs, nf));
   SparseSym::LevPlan& P = Y->lev[fs - 1];
-  const int nl = Y->H.nlevels;
-  for(int bt = 0; bt < P.nbatch; bt++)
-    for(int l = 0; l < nl; l++)
-    {
-      const int w0 = P.wl_ptr[(size_t)bt*nl + l], n = P.wl_ptr[(size_t)bt*nl + l + 1] - w0;
-      if(n > 0)
-        hipLaunchKernelGGL(k_lev_fwd_level, dim3(n), dim3(TPB), Y->lev_lds, b->stream, P.wl + w0, P.pair_sn, P.pair_ch, P.pair_off,
-                           P.cp_ptr, Y->sn_c0, Y->sn_rowptr, Y->sn_rows, Y->sn_lx, Y->lev_iperm, Y->Jp, Y->Ji, b->slot[s].Jin(),
-                           Y->Lx, nf*fs, fs, P.scr, P.gram);
-    }
+  reach_for_each_level(P, Y->H.nlevels, [&](const int* wl, int n) {
+    hipLaunchKernelGGL(k_lev_fwd_level, dim3(n), dim3(TPB), Y->lev_lds, b->stream, wl, P.pair_sn, P.pair_ch, P.pair_off,
+                       P.cp_ptr, Y->sn_c0, Y->sn_rowptr, Y->sn_rows, Y->sn_lx, Y->lev_iperm, Y->Jp, Y->Ji, b->slot[s].Jin(),
+                       Y->Lx, nf*fs, fs, P.scr, P.gram);
+  });
   DLG_LAUNCH_CHECK();
   *d_gram = P.gram; *d_slot_ptr = P.cp_ptr;
   if(visits) *visits = P.visits;
