@@ -157,7 +157,8 @@ int  dlg_sparse_stats(dlg_backend_t* b, long* nnz_JtJ_lower, long* nnz_L,
  * units would get it, checked for everything the kernel takes on trust (destinations inside LDS, replicas'
  * slices covering an update matrix exactly once, children before parents).  stats[] = {first level of the
  * region, supernodes, workgroups, LDS bytes, workgroups that keep a slice of their update matrix, supernodes
- * whose update matrix is summed in HBM} */
+ * whose update matrix is summed in HBM, 64-bit FNV-1a hash over every field of the schedule, the same over the
+ * per-level launch parameters of the factorisation}, as many as nstats asks for */
 int  dlg_sparse_region_probe(int N, int M, const int* colptr, const int* rowidx, int ncu, long* stats, int nstats);
 
 /* launch schedule of the factorisation: the number of levels of the supernodal

@@ -409,18 +409,20 @@ def partition_probe(N, M, Jp, Ji, rank, nranks):
     return {k: st[i] for i, k in enumerate(PART_STAT_NAMES)}, own.astype(bool)
 
 
-REGION_STAT_NAMES = ["level0", "supernodes", "workgroups", "lds_bytes", "sliced_workgroups", "hbm_update_matrices"]
+REGION_STAT_NAMES = ["level0", "supernodes", "workgroups", "lds_bytes", "sliced_workgroups", "hbm_update_matrices",
+                     "schedule_hash", "level_params_hash"]
 
 
 def region_probe(N, M, Jp, Ji, ncu=256):
     """Host-only: the one-launch region of the factorisation of a pattern on a chip with `ncu` CUs, checked
-    (raises DlgError on a violated invariant).  Returns a dict of REGION_STAT_NAMES."""
+    (raises DlgError on a violated invariant).  Returns a dict of REGION_STAT_NAMES; the two hashes (64-bit FNV-1a
+    over the fields of the schedule / of the per-level launch parameters) as unsigned integers."""
     L = lib()
     Jp = np.ascontiguousarray(Jp, dtype=np.int32)
     Ji = np.ascontiguousarray(Ji, dtype=np.int32)
     st = (C.c_long * len(REGION_STAT_NAMES))()
     _ck(L.dlg_sparse_region_probe(N, M, iptr(Jp), iptr(Ji), ncu, st, len(REGION_STAT_NAMES)), "region probe")
-    return {k: st[i] for i, k in enumerate(REGION_STAT_NAMES)}
+    return {k: (st[i] & (2**64 - 1) if k.endswith("_hash") else st[i]) for i, k in enumerate(REGION_STAT_NAMES)}
 
 
 def rccl_unique_id():

@@ -1121,467 +1121,100 @@ __global__ void __launch_bounds__(TPB) k_update_fin(int f0, const int* __restric
 
 } // namespace
 
-static int env_int_host(const char* n, int d) { const char* v = getenv(n); return v ? atoi(v) : d; }
-// per-level launch parameters of the factor and update kernels
-// plan_only: everything but the HIP calls (uploads, allocations, function attributes) -- the schedule of the
-// one-launch region is left in Y->pr_*_h for dlg_sparse_region_probe (host-only checks, no GPU)
-int sparse_factor_setup(dlg_backend* b, bool plan_only)
+// the one dispatch over the instantiations of k_factor_level (leaf: the lean one, 256 threads only; the compiler
+// lays the kernels out in the order they are first named: <256> in front of <256, true>)
+static void launch_factor_level(int nt, bool leaf, int grid, int lds, hipStream_t st, const SparseSym* Y, const FwItem* items,
+                                const MfChild* rec, const uint16_t* dst, int fmode, int* fl, int ep, DlgHandoff ho, int64_t pacc)
+{
+#define DLG_FL_LAUNCH(...) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<__VA_ARGS__>), dim3(grid), dim3(nt), lds, st, \
+                                              items, rec, Y->sn_bd_col, dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, fl, ep, ho, pacc)
+  if(nt == 128) DLG_FL_LAUNCH(128);
+  else if(nt == 256 && !leaf) DLG_FL_LAUNCH(256);
+  else if(nt == 256) DLG_FL_LAUNCH(256, true);
+  else { nt = 512; DLG_FL_LAUNCH(512); }
+#undef DLG_FL_LAUNCH
+}
+constexpr int FMODE_B16 = 16;      // panel_factor_b16 where the panel has at most 512 rows: every launch asks for it
+
+// the levels of region R, the first of which is l, in one launch (its epoch is the caller's: ++R.epoch)
+static void launch_region(dlg_backend* b, const PrRegion& R, int l)
+{
+  SparseSym* Y = b->sym;
+  const int fmode = 2 + 4*R.stage + FMODE_B16 + 256*(l & 31);
+  const int64_t pacc = Y->pr_acc ? (int64_t)(Y->pr_acc - Y->uscr) : 0;
+  launch_factor_level(Y->fac.nt[l], false, R.nwg, R.lds, b->stream, Y, R.item, R.rec, R.dst, fmode, R.flag, R.epoch,
+                      dlg_handoff(b, 1 << 21), pacc);
+}
+
+// a region's schedule on the device (R.level0 >= H.nlevels: there is none)
+static int region_upload(dlg_backend* b, PrRegion& R, const RegionPlan& P)
+{
+  SparseSym* Y = b->sym;
+  R.level0 = P.level0; R.level1 = P.level1; R.lds = P.lds; R.stage = P.stage; R.nwg = P.nwg;
+  if(P.level0 >= Y->H.nlevels) return DLG_OK;
+  if(!R.item) { DLG_CHECK(upload(R.item, P.item)); Y->allocs.push_back(R.item); }
+  if(!R.rec)  { DLG_CHECK(upload(R.rec, P.rec));   Y->allocs.push_back(R.rec); }
+  if(!R.dst)  { DLG_CHECK(upload(R.dst, P.dst));   Y->allocs.push_back(R.dst); }
+  return DLG_OK;
+}
+// ... and its flags: one per workgroup of the region + the fork gate
+static int region_flags(dlg_backend* b, PrRegion& R)
+{
+  SparseSym* Y = b->sym;
+  if(R.level0 >= Y->H.nlevels || R.flag) return DLG_OK;
+  DLG_HIP(hipMalloc(&R.flag, sizeof(int)*((size_t)R.nwg + 1)));
+  Y->allocs.push_back(R.flag);
+  DLG_HIP(hipMemsetAsync(R.flag, 0, sizeof(int)*((size_t)R.nwg + 1), b->stream));
+  R.epoch = 0;
+  return DLG_OK;
+}
+
+// launch parameters of K5: the plan (sparse_region.cpp) and what it needs on the device
+int sparse_factor_setup(dlg_backend* b)
 {
   SparseSym* Y = b->sym;
   const SymHost& H = Y->H;
-  Y->fac_b16 = true;
-  Y->fac_lds.assign(H.nlevels, 0); Y->fac_nt.assign(H.nlevels, 512); Y->upd_coop.assign(H.nlevels, 0);
-  Y->upd_lds.assign(H.nlevels, 0); Y->upd_nw.assign(H.nlevels, 0);
-  Y->syrk_lds.assign(H.nlevels, 0); Y->syrk_nt.assign(H.nlevels, 256); Y->syrk_kc.assign(H.nlevels, 4);
-  Y->syrk_fused.assign(H.nlevels, 0); Y->fin_ny.assign(H.nlevels, 1); Y->fac_stage.assign(H.nlevels, 0);
-  // levels whose work items are all unsliced block-diagonal panels (merged leaves) outside the
-  // multifrontal region, with members of at most 4 columns and at most 64 columns in all: the lean
-  // instantiation (k_factor_level<256, true>)
-  Y->fac_leaf.assign(H.nlevels, 0);
-  for(int l = 0; l < H.nlevels && !getenv("DOGLEG_AMD_NO_LEAF_KERNEL"); l++)
-  {
-    bool all = H.fw_lvl_ptr[l+1] > H.fw_lvl_ptr[l] && l < H.mf_level0;
-    long maxr = 0;
-    for(int i = H.fw_lvl_ptr[l]; i < H.fw_lvl_ptr[l+1] && all; i++)
-    {
-      const FwItem& it = H.fw_item[i];
-      if(!(it.nbd > 0 && it.top < 0 && it.bdw > 0 && it.bdw <= 4 && it.w <= 64)) all = false;
-      maxr = std::max(maxr, (long)it.w + (it.r1 - it.r0));
-    }
-    // (the instantiation exists for 256 threads: the block size the level gets below)
-    const int nt = (maxr <= 128) ? 128 : (maxr <= 256 ? 256 : 512);
-    Y->fac_leaf[l] = (all && nt == 256) ? 1 : 0;
-  }
-  for(int l = 0; l < H.nlevels; l++)
-  {
-    long maxp = 0, maxw = 0, maxr = 0;
-    for(int i = H.lvl_ptr[l]; i < H.lvl_ptr[l+1]; i++)
-    {
-      const int s = H.lvl_sn[i];
-      const long wv = H.sn_c0[s+1] - H.sn_c0[s];
-      if(wv > maxw) maxw = wv;
-    }
-    for(int i = H.fw_lvl_ptr[l]; i < H.fw_lvl_ptr[l+1]; i++)
-    {
-      const int s = H.fw_sn[i];
-      const long wv = H.sn_c0[s+1] - H.sn_c0[s];
-      const long nloc = wv + (H.fw_r1[i] - H.fw_r0[i]);
-      // even leading dimension in LDS; unsliced block-diagonal tops (merged leaves) use the compact
-      // layout that never stages the top block (k_factor_level: cmp)
-      const bool cmp = H.sn_bd_ptr[s+1] > H.sn_bd_ptr[s] && H.sn_top[s] < 0;
-      const long mbl = nloc - wv;
-      const long p = cmp ? ((mbl + 1) & ~1L)*wv + (Y->fac_leaf[l] ? 4 : 8)*wv + 1 : ((nloc + 1) & ~1L)*wv;
-      if(p > maxp) maxp = p;
-      if(nloc > maxr) maxr = nloc;
-    }
-    Y->fac_nt[l] = (maxr <= 128) ? 128 : (maxr <= 256 ? 256 : 512);
-    if(l >= H.mf_level0) Y->fac_nt[l] = env_int_host("DOGLEG_AMD_MF_NT", 512);
-    Y->upd_coop[l] = (maxw > 8) ? 1 : 0;           // heavy sources: matrix-core / cooperative update kernels
-    if(maxp*8 > FAC_LDS_BUDGET) { dlg_set_error("internal error: a factor slice does not fit LDS (%ld doubles)", maxp); return DLG_ERR_ARG; }
-    Y->fac_lds[l] = (int)(maxp*8);
-    long maxslab = 0;
-    for(int it = H.ui_lvl_ptr[l]; it < H.ui_lvl_ptr[l+1]; it++)
-    {
-      const int t = H.ui_t[it];
-      const long sl = (long)(H.sn_rowptr[t+1] - H.sn_rowptr[t])*H.ui_nc[it];
-      if(sl > maxslab) maxslab = sl;
-    }
-    long finslab = 0;
-    for(int f = H.uf_lvl_ptr[l]; f < H.uf_lvl_ptr[l+1]; f++)
-    {
-      const int it = H.uf_item[f], t = H.ui_t[it];
-      finslab = std::max(finslab, (long)(H.sn_rowptr[t+1] - H.sn_rowptr[t])*H.ui_nc[it]);
-    }
-    Y->fin_ny[l] = (int)std::min(64L, std::max(1L, (finslab + 31)/32));
-    int nw = 0;
-    if(maxslab > 0) { nw = (int)(LDS_BUDGET/(maxslab*8)); if(nw > 4) nw = 4; }
-    Y->upd_nw[l] = nw;
-    Y->upd_lds[l] = (int)(maxslab*8*nw);
-    // heavy sources: 2 = matrix-core update kernel (needs the target slabs in LDS), 1 = cooperative
-    // kernel accumulating in HBM (also selectable with DOGLEG_AMD_NO_UPDATE_MFMA for testing)
-    if(Y->upd_coop[l] && nw > 0 && !getenv("DOGLEG_AMD_NO_UPDATE_MFMA")) Y->upd_coop[l] = 2;
-    if(H.upd_syrk[l])
-    {
-      long ldbmax = 0, k4max = 0, tmax = 0;
-      for(int i = H.lvl_ptr[l]; i < H.lvl_ptr[l+1]; i++)
-      {
-        const int d = H.lvl_sn[i];
-        const long wd = H.sn_c0[d+1] - H.sn_c0[d], mb = H.sn_rowptr[d+1] - H.sn_rowptr[d] - wd;
-        ldbmax = std::max(ldbmax, ((mb + 31)/32)*32 + 16); k4max = std::max(k4max, (wd + 3)/4*4);
-        tmax = std::max(tmax, (mb + 15)/16);
-      }
-      long kc = (65536/(ldbmax*8)) & ~3L;            // source columns staged per round (<= 64 KB of LDS)
-      if(kc > k4max) kc = k4max;
-      Y->syrk_kc[l] = (int)kc;
-      Y->syrk_lds[l] = (int)(kc*ldbmax*8);
-      Y->syrk_nt[l] = (tmax*(tmax + 1)/2 <= 32) ? 256 : 1024;
-      // no supernode of the level is cut into slices: the factor kernel forms the U_d itself
-      bool unsliced = true;
-      for(int i = H.lvl_ptr[l]; i < H.lvl_ptr[l+1]; i++) if(H.sn_top[H.lvl_sn[i]] >= 0) unsliced = false;
-      Y->syrk_fused[l] = (unsliced && nw > 0 && !getenv("DOGLEG_AMD_NO_SYRK_FUSE")) ? 1 : 0;
-    }
-    if(l >= H.mf_level0 || Y->syrk_fused[l])
-    {
-      // room for the update matrix behind the panel where both fit (same rule as the kernel and,
-      // for supernodes with children, as the symbolic phase).  Childless supernodes only stage it
-      // if that does not cost the level a resident workgroup per CU.
-      long with_children = Y->fac_lds[l], leaves = Y->fac_lds[l];
-      for(int i = H.lvl_ptr[l]; i < H.lvl_ptr[l+1]; i++)
-      {
-        const int s = H.lvl_sn[i];
-        const long wv = H.sn_c0[s+1] - H.sn_c0[s], nr = H.sn_rowptr[s+1] - H.sn_rowptr[s], mb = nr - wv;
-        const bool cmp = H.sn_bd_ptr[s+1] > H.sn_bd_ptr[s] && H.sn_top[s] < 0;
-        const long pan = cmp ? ((mb + 1) & ~1L)*wv + (Y->fac_leaf[l] ? 4 : 8)*wv : ((nr + 1) & ~1L)*wv;
-        const int jsp = cmp ? (int)mb : sym_w_split(wv, nr);      // the kernel's rule (sym_w_split: part of W may sit in the top block's upper triangle)
-        const long need = (pan + (jsp >= 0 ? sym_w_linear(mb, jsp) : mb*(mb + 1)/2) + 1)*8;
-        const long need0 = (pan + 1)*8;          // at least the scratch slot behind the panel
-        const long want = (need <= FAC_LDS_BUDGET && jsp >= 0) ? need : need0;
-        const bool has_children = l >= H.mf_level0 && H.mf_cptr[s+1] > H.mf_cptr[s];
-        if(has_children) with_children = std::max(with_children, want); else leaves = std::max(leaves, want);
-      }
-      const long base = std::max((long)Y->fac_lds[l], with_children);
-      const long per_cu0 = 163840/(base + 3584), per_cu1 = 163840/(std::max(base, leaves) + 3584);
-      Y->fac_stage[l] = (per_cu1 == per_cu0) ? 1 : 0;
-      Y->fac_lds[l] = (int)(Y->fac_stage[l] ? std::max(base, leaves) : base);
-    }
-    if(getenv("DOGLEG_AMD_SYM_DEBUG"))
-      fprintf(stderr, "factor level %d: %d supernodes, dynamic LDS %d bytes, update matrices staged %d, leaf instantiation %d, gather: %d waves, %d bytes\n",
-              l, H.lvl_ptr[l+1] - H.lvl_ptr[l], Y->fac_lds[l], (int)Y->fac_stage[l], (int)Y->fac_leaf[l], Y->upd_nw[l], Y->upd_lds[l]);
-  }
-  if(!Y->uw_flat && !H.uw_item.empty() && !plan_only)
+  const RegionKnobs K = region_knobs_env(b->ncu);
+  char err[256];
+  if(fac_level_params(H, Y->fac, err, sizeof(err))) { dlg_set_error("%s", err); return DLG_ERR_ARG; }
+  if(!Y->uw_flat && !H.uw_item.empty())
   {
     std::vector<GatherUnit> fl(H.uw_item.size());
     for(size_t u = 0; u < fl.size(); u++)
     {
       const int item = H.uw_item[u], t = H.ui_t[item];
       const int nr = H.sn_rowptr[t+1] - H.sn_rowptr[t];
-      fl[u].lt = H.sn_lx[t] + (int64_t)H.ui_col[item]*nr; fl[u].part = H.uw_part[u];
-      fl[u].s0 = H.uw_s0[u]; fl[u].s1 = H.uw_s1[u]; fl[u].nrows_t = nr; fl[u].nc = H.ui_nc[item];
+      fl[u] = GatherUnit{ H.sn_lx[t] + (int64_t)H.ui_col[item]*nr, H.uw_part[u], H.uw_s0[u], H.uw_s1[u], nr, H.ui_nc[item] };
     }
     DLG_CHECK(upload(Y->uw_flat, fl)); Y->allocs.push_back(Y->uw_flat);
   }
-  // Persistent top region: the last levels of the multifrontal region hold a few supernodes each and
-  // every one of them waits for the one before -- each kernel boundary costs the launch gap, a cold
-  // panel load and the store of the panel before the next level may start.  They go out as ONE
-  // launch, workgroups in level order (a workgroup only ever waits for lower-numbered ones, so
-  // in-order dispatch cannot deadlock): a workgroup stages its panel at once, waits for its
-  // children's flags, and raises its own flag as soon as its update matrix is out -- before its
-  // panel goes back to HBM.  Conditions: unsliced supernodes, update matrices staged in LDS (their
-  // hand-off is the write-through store of that LDS copy), one block size, no update units.
-  // A subtree partition has TWO such regions (round 4): the levels of the rank's own subtrees up to the cut
-  // (PrRegion lo: measured per level launch they cost a rank 35 - 40 us a level, profiles/r04_scaling_projection.md)
-  // and, behind the sum over the ranks, the replicated levels above it (PrRegion top, as on one rank).
-  Y->pr_level0 = H.nlevels; Y->pr2_level0 = H.nlevels; Y->pr2_level1 = -1;
-  const bool dbg = getenv("DOGLEG_AMD_TIMING") != nullptr;
-  bool acc_any = false;
-  // levels [lo, hi] (as far down from hi as the conditions hold) -> region R; returns its first level (> hi: none)
-  auto build_region = [&](int lo_min, int hi, int& r_level0, int& r_lds, int& r_stage, int& r_nwg,
-                          std::vector<FwItem>& items, std::vector<MfChild>& rec, std::vector<uint16_t>& dst) -> int
+  // A subtree partition has TWO regions: the rank's own levels up to the cut (lo: a cut that leaves at least two multifrontal
+  // levels below it) and, behind the sum over the ranks, the replicated levels above it (top, as on one rank).
+  const bool part = H.part_nranks > 1;
+  const RegionPlan top = region_plan(H, Y->fac, part ? H.cut_level + 1 : 1, H.nlevels - 1, K);
+  DLG_CHECK(region_upload(b, Y->top, top));
+  bool acc_any = top.acc_any;
+  Y->lo.level0 = H.nlevels;
+  if(part && H.cut_level >= 2 && K.lower)
   {
-    r_level0 = H.nlevels; r_nwg = 0;
-    if(getenv("DOGLEG_AMD_NO_PERSIST") || H.nlevels < 2 || hi < lo_min) return DLG_OK;
-    // (a workgroup of the region fills a CU; the cap counts SUPERNODES: twice the CUs -- with replicas the launch holds more
-    // workgroups than the chip has CUs anyway, they are dispatched in order and only wait for lower-numbered ones)
-    const int ncu = b->ncu;
-    // (supernodes; since the replicas of round 3 a region holds more workgroups than the chip has CUs anyway.  Round 5: five
-    // times the CUs -- config #5's levels 1 - 3 (269 + 251 + 128 supernodes) were one launch each in front of a region of
-    // 406: K5 2.33 -> 2.07 ms with all of them in it, 227 -> 234 steps/s.  The backward solve keeps twice the CUs: its
-    // region runs from the root DOWN, the populous levels last, and those are faster as launches of their own.)
-    const int cap = env_int_host("DOGLEG_AMD_PERSIST_MAX", 5*ncu);
-    int total = 0, l0 = hi + 1, lds = 0, stage = 1;
-    const int nt = Y->fac_nt[hi];
-    for(int l = hi; l >= std::max(1, lo_min); l--)
-    {
-      const int n = H.fw_lvl_ptr[l+1] - H.fw_lvl_ptr[l];
-      if(l < H.mf_level0) break;
-      if(n == 0 || total + n > cap || Y->fac_nt[l] != nt || Y->fac_lds[l] <= 0) break;
-      if(H.uw_lvl_ptr[l+1] > H.uw_lvl_ptr[l] || H.uf_lvl_ptr[l+1] > H.uf_lvl_ptr[l]) break;
-      bool ok = true;
-      for(int i = H.fw_lvl_ptr[l]; i < H.fw_lvl_ptr[l+1] && ok; i++)
-      {
-        const FwItem& it = H.fw_item[i];
-        if(it.top >= 0 || it.r0 != 0 || it.nbd > 0) ok = false;
-      }
-      if(!ok) break;
-      stage = stage && Y->fac_stage[l]; total += n; l0 = l; lds = std::max(lds, Y->fac_lds[l]);
-    }
-    if(hi + 1 - l0 < 2) return DLG_OK;
-    r_level0 = l0; r_lds = lds; r_stage = stage;
-    // Replicas: the upper levels hold fewer supernodes than the chip has CUs, and behind the panel sweep of a
-    // supernode sits its update matrix W = (children) - B B', a third of the level's critical path on ONE CU.
-    // A supernode of such a level is given to several workgroups: each stages the panel, adds the children
-    // and runs the sweep -- the same instructions on the same data, so the same bits, and nothing to hand
-    // over between them --, then forms and publishes only its share of W's tile columns; the parent waits
-    // for all of them.  A level gets replicas while it and its neighbour level still fit the chip together
-    // (a workgroup that finds no CU starts late and pays its panel load on the critical path).
-    {
-      const int rmax = std::max(1, std::min(8, env_int_host("DOGLEG_AMD_FRONT_REPLICAS", 8)));
-      const int fill = ncu/2, fill0 = ncu/2;
-      const bool slice_ok = !getenv("DOGLEG_AMD_NO_FRONT_SLICES");
-      std::vector<int> first(H.fw_item.size(), -1), count(H.fw_item.size(), 0);
-      // the region's own children records and destination lists: those of the symbolic phase (whole update
-      // matrix behind the panel), and behind them the lists of the replicas that keep a slice of it
-      rec = H.mf_rec; dst = H.mf_dst;
-      auto lin = [](long j, long mb) { return j*mb - j*(j - 1)/2; };       // packed index of (j, j)
-      long lds_need = lds;
-      // Workgroups are dispatched in index order and a level holds more of them than CUs are free when its turn comes
-      // (config #4: 230 + 134 + 128 + ... on 256 CUs): the ones that find a CU late should be the ones with slack.  A
-      // level's supernodes are listed by the estimated time their subtree is done, the latest first (a static estimate:
-      // columns swept in blocks of 16, rows, a constant for the children's sum and the hand-off) -- a parent whose
-      // children are the level's slowest is on its CU, panel staged, when they arrive.  Levels stay in order (a
-      // workgroup only waits for lower-numbered ones); no arithmetic depends on the order.
-      std::vector<double> est(H.fw_item.size(), 0.0);
-      std::vector<int> item_of_sn(H.nsn, -1);
-      for(int l = r_level0; l <= hi; l++)
-        for(int i = H.fw_lvl_ptr[l]; i < H.fw_lvl_ptr[l+1]; i++) item_of_sn[H.fw_sn[i]] = i;
-      for(int l = r_level0; l <= hi; l++)
-      {
-        const int n = H.fw_lvl_ptr[l+1] - H.fw_lvl_ptr[l];
-        std::vector<int> order(n);
-        for(int k = 0; k < n; k++) order[k] = H.fw_lvl_ptr[l] + k;
-        for(int i : order)
-        {
-          const FwItem& fi = H.fw_item[i];
-          double e0 = 0.0;
-          for(int k = 0; k < fi.nch; k++) { const int ci = item_of_sn[H.mf_child[fi.ch0 + k]]; if(ci >= 0) e0 = std::max(e0, est[ci]); }
-          est[i] = e0 + 3.0*((fi.w + 15)/16) + 0.02*fi.nrows + 9.0;
-        }
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b2) { return est[a] > est[b2]; });
-        // (the first level of the region is its most populous one, and the Cauchy step's pass over J runs beside
-        // it: replicas there cost more in CUs than they save -- only what does not fit LDS whole is sliced)
-        const int rl = std::max(1, std::min(rmax, (l == r_level0 ? fill0 : fill)/std::max(n, 1)));
-        // (the first level's supernodes whose panel is at least 70 % of the
-        // level's largest get a second workgroup for their update matrix, while CUs are left)
-        const int l1_pct = (l == r_level0 && rl == 1) ? 70 : 0;
-        long l1_max = 0; int l1_left = std::max(0, ncu - n);
-        if(l1_pct > 0) for(int i = H.fw_lvl_ptr[l]; i < H.fw_lvl_ptr[l+1]; i++) l1_max = std::max(l1_max, (long)H.fw_item[i].nrows*H.fw_item[i].w);
-        for(int i : order)
-        {
-          FwItem it = H.fw_item[i];
-          const int mb = it.nrows - it.w, T = (mb + 15) >> 4;
-          int rl_i = rl;
-          if(l1_pct > 0 && l1_left > 0 && (long)it.nrows*it.w*100 >= l1_max*l1_pct) { rl_i = 2; l1_left--; }
-          const long ldp = (it.nrows + 1) & ~1L, pan = ldp*it.w, room = FAC_LDS_BUDGET/8 - pan - 2;
-          const bool has_w = mb > 0 && it.u_off >= 0;
-          // an update matrix that does not fit LDS whole (it.jsp < 0) fits in slices: two replicas at least
-          int want = has_w ? std::min(rl_i, T) : 1;
-          if(has_w && it.jsp < 0 && slice_ok) want = std::max(want, std::min(2, T));
-          std::vector<int> cut;
-          int nrep = 1;
-          for(; want <= std::min(8, std::max(T, 1)); want++)
-          {
-            // contiguous tile columns, tile counts T - t, the largest share as small as possible
-            for(int cap2 = (T*(T + 1)/2 + want - 1)/std::max(want, 1); ; cap2++)
-            {
-              cut.assign(1, 0);
-              int load = 0;
-              for(int t = 0; t < T; t++)
-              {
-                if(load > 0 && load + (T - t) > cap2) { cut.push_back(t); load = 0; }
-                load += T - t;
-              }
-              cut.push_back(T);
-              if((int)cut.size() - 1 <= want) break;
-            }
-            nrep = std::max(1, (int)cut.size() - 1);
-            if(nrep == 1 || !slice_ok) break;
-            bool fits = true;
-            for(int r = 0; r < nrep; r++)
-            {
-              const long jA = std::min<long>(16L*cut[r], mb), jB = std::min<long>(16L*cut[r+1], mb);
-              if(lin(jB, mb) - lin(jA, mb) + 1 > room) fits = false;
-            }
-            if(fits) break;
-            nrep = 1;                                   // (more, narrower slices)
-          }
-          bool hbm_rep = false;
-          if(nrep == 1 || !slice_ok)
-          {
-            // one workgroup (or replicas that each stage the whole update matrix: DOGLEG_AMD_NO_FRONT_SLICES)
-            if(it.jsp < 0)
-            {
-              nrep = 1;
-              if(has_w && it.nch > 0) acc_any = true;
-              // Round 6: an update matrix that is summed in HBM (a panel that fills LDS by itself: config #5's fronts of
-              // 250 - 300 rows x 60 - 66 columns) gets replicas too -- each sweeps the panel and OWNS a stretch of tile
-              // columns of the update matrix in HBM: it sums the children's entries of that stretch only (its own destination
-              // lists drop the others), forms B B' of those tiles and publishes them.  One workgroup formed all 120 tiles of
-              // such a front, 30 - 46 us of every level on config #5's critical path (profiles/r05_top_of_tree_levels_config5.txt).
-              const int want_h = (has_w && slice_ok) ? std::min(std::min(rl_i, T), 8) : 1;      // (at least 2 / 3 / 4 of them also on the populous levels: 336 / 330 / 326 steps/s against 338)
-              if(want_h > 1)
-              {
-                for(int cap2 = (T*(T + 1)/2 + want_h - 1)/want_h; ; cap2++)
-                {
-                  cut.assign(1, 0);
-                  int load = 0;
-                  for(int t = 0; t < T; t++)
-                  {
-                    if(load > 0 && load + (T - t) > cap2) { cut.push_back(t); load = 0; }
-                    load += T - t;
-                  }
-                  cut.push_back(T);
-                  if((int)cut.size() - 1 <= want_h) break;
-                }
-                nrep = std::max(1, (int)cut.size() - 1);
-                hbm_rep = nrep > 1;
-              }
-            }
-            else if(nrep > 1) { /* whole-W replicas: the kernel's column-range copy-out */ }
-          }
-          first[i] = (int)items.size(); count[i] = nrep;
-          for(int r = 0; r < nrep; r++)
-          {
-            it = H.fw_item[i];
-            it.rep = r; it.tj0 = (nrep == 1) ? 0 : cut[r]; it.tj1 = (nrep == 1 || r == nrep - 1) ? (1 << 20) : cut[r+1];
-            it.rsv2 = nrep;      // (the LAST replica stores the panel, once the others have read it: k_factor_level)
-            it.pad = l;          // (the level: for the profile build's dump)
-            if(hbm_rep)
-            {
-              // (not `sliced`: nothing of the update matrix is in LDS; [eA, eB) is the stretch of the packed triangle this
-              // replica zeroes, sums and forms -- k_factor_level)
-              const long jA = std::min<long>(16L*it.tj0, mb), jB = (r == nrep - 1) ? mb : std::min<long>(16L*it.tj1, mb);
-              const long eA = lin(jA, mb), eB = lin(jB, mb);
-              it.sliced = 0; it.eA = (int)eA; it.eB = (int)eB;
-              lds_need = std::max(lds_need, (pan + 2)*8);
-              const int ch0_new = (int)rec.size();
-              for(int k = 0; k < it.nch; k++)
-              {
-                MfChild rc = H.mf_rec[it.ch0 + k];
-                const int c = H.mf_child[it.ch0 + k];
-                const int mc = (H.sn_rowptr[c+1] - H.sn_rowptr[c]) - (H.sn_c0[c+1] - H.sn_c0[c]);
-                const int* map = &H.relpos[H.sn_prel[c]];
-                const int nc = mc*(mc + 1)/2;
-                rc.dst_off = (int64_t)dst.size();
-                rc.rsv = (rc.rsv >= 0 && first[rc.rsv] >= 0) ? (first[rc.rsv] | (count[rc.rsv] << 20)) : -1;
-                dst.reserve(dst.size() + rc.npad);
-                for(int j = 0; j < mc; j++)
-                  for(int q = j; q < mc; q++)
-                  {
-                    const long fi = map[q], fj = map[j], jw = fj - it.w;
-                    const long d = (fj < it.w) ? fi + fj*ldp
-                                 : (jw >= jA && jw < jB) ? (0x8000 | (lin(jw, mb) + (fi - fj))) : pan;      // pan: the scratch slot
-                    dst.push_back((uint16_t)d);
-                  }
-                for(int e = nc; e < rc.npad; e++) dst.push_back((uint16_t)pan);
-                rec.push_back(rc);
-              }
-              it.ch0 = ch0_new;
-            }
-            else if(nrep > 1 && slice_ok)
-            {
-              const long jA = std::min<long>(16L*it.tj0, mb), jB = (r == nrep - 1) ? mb : std::min<long>(16L*it.tj1, mb);
-              const long eA = lin(jA, mb), eB = lin(jB, mb), slp = eA & 1;
-              it.sliced = 1; it.eA = (int)eA; it.eB = (int)eB;
-              lds_need = std::max(lds_need, (pan + slp + (eB - eA) + 2)*8);
-              const long wt = pan + slp, trash = wt + (eB - eA);
-              const int ch0_new = (int)rec.size();
-              for(int k = 0; k < it.nch; k++)
-              {
-                MfChild rc = H.mf_rec[it.ch0 + k];
-                const int c = H.mf_child[it.ch0 + k];
-                const int mc = (H.sn_rowptr[c+1] - H.sn_rowptr[c]) - (H.sn_c0[c+1] - H.sn_c0[c]);
-                const int* map = &H.relpos[H.sn_prel[c]];
-                const int nc = mc*(mc + 1)/2;
-                rc.dst_off = (int64_t)dst.size();
-                rc.rsv = (rc.rsv >= 0 && first[rc.rsv] >= 0) ? (first[rc.rsv] | (count[rc.rsv] << 20)) : -1;
-                dst.reserve(dst.size() + rc.npad);
-                for(int j = 0; j < mc; j++)
-                  for(int q = j; q < mc; q++)
-                  {
-                    const long fi = map[q], fj = map[j], jw = fj - it.w;
-                    const long d = (fj < it.w) ? fi + fj*ldp
-                                 : (jw >= jA && jw < jB) ? wt + (lin(jw, mb) - eA) + (fi - fj) : trash;
-                    dst.push_back((uint16_t)d);
-                  }
-                for(int e = nc; e < rc.npad; e++) dst.push_back((uint16_t)trash);
-                rec.push_back(rc);
-              }
-              it.ch0 = ch0_new;
-            }
-            items.push_back(it);
-          }
-        }
-      }
-      // (the records of the symbolic phase: the children's workgroups in this launch)
-      for(size_t k = 0; k < H.mf_rec.size(); k++)
-        rec[k].rsv = (rec[k].rsv >= 0 && first[rec[k].rsv] >= 0) ? (first[rec[k].rsv] | (count[rec[k].rsv] << 20)) : -1;
-      r_nwg = (int)items.size();
-      r_lds = (int)std::max<long>(r_lds, lds_need);
-    }
-    if(dbg)
-      fprintf(stderr, "libdogleg_amd: one-launch region of the factorisation: levels %d..%d of %d (%d supernodes, %d workgroups, %d bytes of LDS, multifrontal from level %d)\n",
-              r_level0, hi, H.nlevels, total, r_nwg, r_lds, H.mf_level0);
-    return DLG_OK;
-  };
-  {
-    const bool part = H.part_nranks > 1;
-    std::vector<FwItem> items; std::vector<MfChild> rec; std::vector<uint16_t> dst;
-    DLG_CHECK(build_region(part ? H.cut_level + 1 : 1, H.nlevels - 1, Y->pr_level0, Y->pr_lds, Y->pr_stage, Y->pr_nwg, items, rec, dst));
-    if(Y->pr_level0 < H.nlevels)
-    {
-      if(plan_only) { Y->pr_item_h.swap(items); Y->pr_rec_h.swap(rec); Y->pr_dst_h.swap(dst); }
-      else
-      {
-        if(!Y->pr_item) { DLG_CHECK(upload(Y->pr_item, items)); Y->allocs.push_back(Y->pr_item); }
-        if(!Y->pr_rec)  { DLG_CHECK(upload(Y->pr_rec, rec));   Y->allocs.push_back(Y->pr_rec); }
-        if(!Y->pr_dst)  { DLG_CHECK(upload(Y->pr_dst, dst));   Y->allocs.push_back(Y->pr_dst); }
-      }
-    }
-    // the rank's own levels up to the cut (a partition whose cut leaves at least two multifrontal levels below it)
-    if(part && H.cut_level >= 2 && !plan_only && !getenv("DOGLEG_AMD_NO_LOWER_REGION"))
-    {
-      std::vector<FwItem> items2; std::vector<MfChild> rec2; std::vector<uint16_t> dst2;
-      DLG_CHECK(build_region(1, H.cut_level, Y->pr2_level0, Y->pr2_lds, Y->pr2_stage, Y->pr2_nwg, items2, rec2, dst2));
-      if(Y->pr2_level0 <= H.cut_level)
-      {
-        Y->pr2_level1 = H.cut_level;
-        if(!Y->pr2_item) { DLG_CHECK(upload(Y->pr2_item, items2)); Y->allocs.push_back(Y->pr2_item); }
-        if(!Y->pr2_rec)  { DLG_CHECK(upload(Y->pr2_rec, rec2));   Y->allocs.push_back(Y->pr2_rec); }
-        if(!Y->pr2_dst)  { DLG_CHECK(upload(Y->pr2_dst, dst2));   Y->allocs.push_back(Y->pr2_dst); }
-      }
-      else Y->pr2_level0 = H.nlevels;
-    }
-    // update matrices of a region that do not fit LDS are summed (atomics) in a shadow of the scratch,
-    // so that the slot the parent reads only ever sees write-through stores
-    if(acc_any && !Y->pr_acc && !plan_only)
-    {
-      DLG_HIP(hipMalloc(&Y->pr_acc, sizeof(double)*(size_t)std::max<int64_t>(1, H.uscr_size)));
-      Y->allocs.push_back(Y->pr_acc);
-    }
+    const RegionPlan lo = region_plan(H, Y->fac, 1, H.cut_level, K);
+    DLG_CHECK(region_upload(b, Y->lo, lo));
+    acc_any = acc_any || lo.acc_any;
   }
-  if(plan_only) return DLG_OK;
-  if(Y->pr_level0 < H.nlevels && !Y->fac_flag)
+  // update matrices of a region that do not fit LDS are summed (atomics) in a shadow of the scratch,
+  // so that the slot the parent reads only ever sees write-through stores
+  if(acc_any && !Y->pr_acc)
   {
-    DLG_HIP(hipMalloc(&Y->fac_flag, sizeof(int)*((size_t)Y->pr_nwg + 1)));         // one per workgroup of the region + the fork gate
-    Y->allocs.push_back(Y->fac_flag);
-    DLG_HIP(hipMemsetAsync(Y->fac_flag, 0, sizeof(int)*((size_t)Y->pr_nwg + 1), b->stream));
-    Y->fac_epoch = 0;
+    DLG_HIP(hipMalloc(&Y->pr_acc, sizeof(double)*(size_t)std::max<int64_t>(1, H.uscr_size)));
+    Y->allocs.push_back(Y->pr_acc);
   }
-  if(Y->pr2_level0 < H.nlevels && !Y->fac2_flag)
-  {
-    DLG_HIP(hipMalloc(&Y->fac2_flag, sizeof(int)*((size_t)Y->pr2_nwg + 1)));
-    Y->allocs.push_back(Y->fac2_flag);
-    DLG_HIP(hipMemsetAsync(Y->fac2_flag, 0, sizeof(int)*((size_t)Y->pr2_nwg + 1), b->stream));
-    Y->fac2_epoch = 0;
-  }
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_factor_level<128>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, FAC_LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_factor_level<256>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, FAC_LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_factor_level<256, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, FAC_LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_factor_level<512>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, FAC_LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_level),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_syrk<256>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_syrk<1024>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_gather<TPB>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_mfma),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
+  DLG_CHECK(region_flags(b, Y->top));
+  DLG_CHECK(region_flags(b, Y->lo));
+  // the kernels that ask for more dynamic LDS than the default: the first four the factor budget, the rest the common one
+  const void* const big_lds[] = { (const void*)&k_factor_level<128>, (const void*)&k_factor_level<256>, (const void*)&k_factor_level<256, true>,
+                                  (const void*)&k_factor_level<512>, (const void*)&k_update_level, (const void*)&k_update_syrk<256>,
+                                  (const void*)&k_update_syrk<1024>, (const void*)&k_update_gather<TPB>, (const void*)&k_update_mfma };
+  for(int i = 0; i < 9; i++) DLG_HIP(hipFuncSetAttribute(big_lds[i], hipFuncAttributeMaxDynamicSharedMemorySize, i < 4 ? FAC_LDS_BUDGET : LDS_BUDGET));
   return DLG_OK;
 }
 
@@ -1639,14 +1272,14 @@ int sparse_factor_levels(dlg_backend* b, int part)
   // A factorisation enqueued ahead of the caller's decision (backend.hip, step_prepare) comes in two parts where its
   // first launch is a level of its own: part 1 = that launch (the leaf level), part 2 = everything behind it.  Same
   // launches in the same order on the same stream as part 0.
-  const bool split = Y->pr_level0 > 0 && H.nlevels >= 2 && H.part_nranks <= 1 && H.fw_lvl_ptr[1] > H.fw_lvl_ptr[0];
+  const bool split = Y->top.level0 > 0 && H.nlevels >= 2 && H.part_nranks <= 1 && H.fw_lvl_ptr[1] > H.fw_lvl_ptr[0];
   if(part == 2 && !split) return DLG_OK;
   if(part != 2)
   {
   if(H.part_nranks > 1 && H.cut_level < 0) DLG_CHECK(sparse_partition_reduce(b));     // nothing below the cut
   // (fin on the side, sparse_assemble.hip: the partial-sum stages of the ancestors' panels may still be on the second
   // stream -- level 0 does not touch those panels; whatever follows it does)
-  if(Y->pr_level0 == 0 || H.nlevels < 2) DLG_CHECK(sparse_fin_side_gate(b));
+  if(Y->top.level0 == 0 || H.nlevels < 2) DLG_CHECK(sparse_fin_side_gate(b));
   }
   for(int l = 0; l < H.nlevels; l++)
   {
@@ -1655,118 +1288,84 @@ int sparse_factor_levels(dlg_backend* b, int part)
     const int n = H.fw_lvl_ptr[l+1] - H.fw_lvl_ptr[l];
     // from the first level that cannot fill the chip on, the factorisation is latency-bound:
     // independent work (the Cauchy step's pass over J) may run beside it
-    const bool gate_here = (l == Y->pr_level0 && Y->fac_flag) || (l == Y->pr2_level0 && Y->fac2_flag);      // (no event on this stream: the launch opens a gate)
+    const bool gate_here = (l == Y->top.level0 && Y->top.flag) || (l == Y->lo.level0 && Y->lo.flag);      // (no event on this stream: the launch opens a gate)
     if(l > 0 && n < 256 && !gate_here) dlg_fork_point(b);
-    if(l == Y->pr2_level0 && Y->fac2_flag)
+    if(l == Y->lo.level0 && Y->lo.flag)
     {
       // a subtree partition: the rank's own levels up to the cut in one launch (sparse_factor_setup, region "lo")
-      const int np = Y->pr2_nwg;
-      const int fmode = 2 + 4*Y->pr2_stage + (Y->fac_b16 ? 16 : 0) + 256*(l & 31);
-      int* fl = Y->fac2_flag; const int ep = ++Y->fac2_epoch;
-      if(l > 0 && n < 256) dlg_fork_gate(b, fl + np, ep);
-      const int64_t pacc = Y->pr_acc ? (int64_t)(Y->pr_acc - Y->uscr) : 0;
-      const DlgHandoff ho = dlg_handoff(b, 1 << 21);
+      PrRegion& R = Y->lo;
+      ++R.epoch;
+      if(l > 0 && n < 256) dlg_fork_gate(b, R.flag + R.nwg, R.epoch);
       {
         DlgRegionTurn turn(b);            // (held for the launch only: the sum over the ranks behind it blocks in the caller's hook)
-        if(Y->fac_nt[l] == 128)
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<128>), dim3(np), dim3(128), Y->pr2_lds, st,
-                             Y->pr2_item, Y->pr2_rec, Y->sn_bd_col, Y->pr2_dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, fl, ep, ho, pacc);
-        else if(Y->fac_nt[l] == 256)
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<256>), dim3(np), dim3(256), Y->pr2_lds, st,
-                             Y->pr2_item, Y->pr2_rec, Y->sn_bd_col, Y->pr2_dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, fl, ep, ho, pacc);
-        else
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<512>), dim3(np), dim3(512), Y->pr2_lds, st,
-                             Y->pr2_item, Y->pr2_rec, Y->sn_bd_col, Y->pr2_dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, fl, ep, ho, pacc);
+        launch_region(b, R, l);
       }
-      l = Y->pr2_level1;                                 // (= the cut: everything below it is done)
+      l = R.level1;                                 // (= the cut: everything below it is done)
       if(H.part_nranks > 1 && l == H.cut_level) { DLG_LAUNCH_CHECK(); DLG_CHECK(sparse_partition_reduce(b)); }
       continue;
     }
-    if(l == Y->pr_level0)
+    if(l == Y->top.level0)
     {
       // the persistent top region: every remaining level in one launch (sparse_factor_setup)
-      const int np = Y->pr_nwg;           // the region's own work items (replicas) and children records
-      const int fmode = 2 + 4*Y->pr_stage + (Y->fac_b16 ? 16 : 0) + 256*(l & 31);
-      int* fl = Y->fac_flag; const int ep = ++Y->fac_epoch;
+      PrRegion& R = Y->top;
+      ++R.epoch;
       // (the gate goes up with the region's LAST workgroup -- the top of the tree, on the chip once the populous levels below
       // it have drained --, however many supernodes the region's first level has: with `n < 256` asked for here too, config #5
       // -- 285 supernodes on level 1 -- never forked, and its Cauchy pass ran beside the backward solve instead)
-      if(gate_here && l > 0) dlg_fork_gate(b, fl + np, ep);
-      const int64_t pacc = Y->pr_acc ? (int64_t)(Y->pr_acc - Y->uscr) : 0;
-      const DlgHandoff ho = dlg_handoff(b, 1 << 21);
+      if(gate_here && l > 0) dlg_fork_gate(b, R.flag + R.nwg, R.epoch);
       DlgRegionTurn turn(b);
-      if(Y->fac_nt[l] == 128)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<128>), dim3(np), dim3(128), Y->pr_lds, st,
-                           Y->pr_item, Y->pr_rec, Y->sn_bd_col, Y->pr_dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, fl, ep, ho, pacc);
-      else if(Y->fac_nt[l] == 256)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<256>), dim3(np), dim3(256), Y->pr_lds, st,
-                           Y->pr_item, Y->pr_rec, Y->sn_bd_col, Y->pr_dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, fl, ep, ho, pacc);
-      else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<512>), dim3(np), dim3(512), Y->pr_lds, st,
-                           Y->pr_item, Y->pr_rec, Y->sn_bd_col, Y->pr_dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, fl, ep, ho, pacc);
+      launch_region(b, R, l);
       break;
     }
     if(n > 0 && !launched_before)
     {
-      const int o = H.fw_lvl_ptr[l];
-      const int sweep_bits = (Y->fac_b16 ? 16 : 0);
-      const int fmode = ((l >= H.mf_level0) ? 2 : Y->syrk_fused[l]) + 4*Y->fac_stage[l] + sweep_bits + 256*(l & 31);
-      if(Y->fac_nt[l] == 128)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<128>), dim3(n), dim3(128), Y->fac_lds[l], st,
-                           Y->fw_item + o, Y->mf_rec, Y->sn_bd_col, Y->mf_dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, (int*)nullptr, 0, DlgHandoff{nullptr, 0, 0}, (int64_t)0);
-      else if(Y->fac_nt[l] == 256 && Y->fac_leaf[l])
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<256, true>), dim3(n), dim3(256), Y->fac_lds[l], st,
-                           Y->fw_item + o, Y->mf_rec, Y->sn_bd_col, Y->mf_dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, (int*)nullptr, 0, DlgHandoff{nullptr, 0, 0}, (int64_t)0);
-      else if(Y->fac_nt[l] == 256)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<256>), dim3(n), dim3(256), Y->fac_lds[l], st,
-                           Y->fw_item + o, Y->mf_rec, Y->sn_bd_col, Y->mf_dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, (int*)nullptr, 0, DlgHandoff{nullptr, 0, 0}, (int64_t)0);
-      else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<512>), dim3(n), dim3(512), Y->fac_lds[l], st,
-                           Y->fw_item + o, Y->mf_rec, Y->sn_bd_col, Y->mf_dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, (int*)nullptr, 0, DlgHandoff{nullptr, 0, 0}, (int64_t)0);
+      const int fmode = ((l >= H.mf_level0) ? 2 : Y->fac.syrk_fused[l]) + 4*Y->fac.stage[l] + FMODE_B16 + 256*(l & 31);
+      launch_factor_level(Y->fac.nt[l], Y->fac.leaf[l], n, Y->fac.lds[l], st, Y, Y->fw_item + H.fw_lvl_ptr[l], Y->mf_rec, Y->mf_dst,
+                          fmode, (int*)nullptr, 0, DlgHandoff{nullptr, 0, 0}, (int64_t)0);
     }
     if(part == 1 && split && l == 0) { Y->fac_pending = true; DLG_LAUNCH_CHECK(); return DLG_OK; }
     // (behind the leaf level's factor kernel, in front of its updates: the gather kernel looks at the word itself,
     // in front of anything else a one-wave kernel waits for it)
     const int nu = H.uw_lvl_ptr[l+1] - H.uw_lvl_ptr[l];
-    const bool gather_next = nu > 0 && H.upd_syrk[l] && Y->upd_nw[l] > 0;
+    const bool gather_next = nu > 0 && H.upd_syrk[l] && Y->fac.upd_nw[l] > 0;
     const int fin_ep = (l == 0 && gather_next) ? Y->fin_side_owed : 0;
     if(fin_ep) Y->fin_side_owed = 0;
     if(l == 0) DLG_CHECK(sparse_fin_side_gate(b));
     if(gather_next)
     {
       const int ns = H.xl_ptr[l+1] - H.xl_ptr[l];
-      if(Y->syrk_fused[l] || ns == 0) { /* phase 1 was done by the factor kernel */ }
-      else if(Y->syrk_nt[l] == 256)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_syrk<256>), dim3(ns), dim3(256), Y->syrk_lds[l], st,
+      if(Y->fac.syrk_fused[l] || ns == 0) { /* phase 1 was done by the factor kernel */ }
+      else if(Y->fac.syrk_nt[l] == 256)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_syrk<256>), dim3(ns), dim3(256), Y->fac.syrk_lds[l], st,
                            Y->xl_sn + H.xl_ptr[l], Y->sn_c0, Y->sn_rowptr, Y->sn_lx, Y->u_off, Y->Lx, Y->uscr,
-                           Y->syrk_kc[l]);
+                           Y->fac.syrk_kc[l]);
       else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_syrk<1024>), dim3(ns), dim3(1024), Y->syrk_lds[l], st,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_syrk<1024>), dim3(ns), dim3(1024), Y->fac.syrk_lds[l], st,
                            Y->xl_sn + H.xl_ptr[l], Y->sn_c0, Y->sn_rowptr, Y->sn_lx, Y->u_off, Y->Lx, Y->uscr,
-                           Y->syrk_kc[l]);
+                           Y->fac.syrk_kc[l]);
       // (one wave per unit, all units resident at once, was measured: 78 us against 48 with up to four
       // waves sharing a unit's sub-tasks)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_gather<TPB>), dim3(nu), dim3(TPB), Y->upd_lds[l], st, H.uw_lvl_ptr[l],
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_gather<TPB>), dim3(nu), dim3(TPB), Y->fac.upd_lds[l], st, H.uw_lvl_ptr[l],
                          Y->uw_flat, Y->usub, Y->usub_u, Y->relpos, Y->Lx, Y->upart, Y->uscr,
-                         Y->upd_nw[l], Y->d_info,
+                         Y->fac.upd_nw[l], Y->d_info,
                          fin_ep ? (const int*)(Y->fin_flag + 1) : (const int*)nullptr, fin_ep,
                          reinterpret_cast<int*>(b->d_scal + (dlg_backend::NSCAL - 2)));
     }
-    else if(nu > 0 && Y->upd_coop[l] == 2)
-      hipLaunchKernelGGL(k_update_mfma, dim3(nu), dim3(TPB), Y->upd_lds[l], st, H.uw_lvl_ptr[l],
+    else if(nu > 0 && Y->fac.upd_coop[l] == 2)
+      hipLaunchKernelGGL(k_update_mfma, dim3(nu), dim3(TPB), Y->fac.upd_lds[l], st, H.uw_lvl_ptr[l],
                          Y->uw_item, Y->uw_s0, Y->uw_s1, Y->uw_part, Y->ui_t, Y->ui_col, Y->ui_nc,
-                         Y->usub, Y->relpos, Y->sn_rowptr, Y->sn_lx, Y->Lx, Y->upart, Y->upd_nw[l], (const int*)Y->d_info);
-    else if(nu > 0 && Y->upd_coop[l])
+                         Y->usub, Y->relpos, Y->sn_rowptr, Y->sn_lx, Y->Lx, Y->upart, Y->fac.upd_nw[l], (const int*)Y->d_info);
+    else if(nu > 0 && Y->fac.upd_coop[l])
       hipLaunchKernelGGL(k_update_coop, dim3(nu), dim3(TPB), 0, st, H.uw_lvl_ptr[l],
                          Y->uw_item, Y->uw_s0, Y->uw_s1, Y->uw_part, Y->ui_t, Y->ui_col, Y->ui_nc,
                          Y->usub, Y->relpos, Y->sn_rowptr, Y->sn_lx, Y->Lx, Y->upart, (const int*)Y->d_info);
     else if(nu > 0)
-      hipLaunchKernelGGL(k_update_level, dim3(nu), dim3(TPB), Y->upd_lds[l], st, H.uw_lvl_ptr[l],
+      hipLaunchKernelGGL(k_update_level, dim3(nu), dim3(TPB), Y->fac.upd_lds[l], st, H.uw_lvl_ptr[l],
                          Y->uw_item, Y->uw_s0, Y->uw_s1, Y->uw_part, Y->ui_t, Y->ui_col, Y->ui_nc,
-                         Y->usub, Y->relpos, Y->sn_rowptr, Y->sn_lx, Y->Lx, Y->upart, Y->upd_nw[l], (const int*)Y->d_info);
+                         Y->usub, Y->relpos, Y->sn_rowptr, Y->sn_lx, Y->Lx, Y->upart, Y->fac.upd_nw[l], (const int*)Y->d_info);
     const int nfz = H.uf_lvl_ptr[l+1] - H.uf_lvl_ptr[l];
     if(nfz > 0)
-      hipLaunchKernelGGL(k_update_fin, dim3(nfz, Y->fin_ny[l]), dim3(TPB), 0, st, H.uf_lvl_ptr[l], Y->uf_item, Y->uf_n,
+      hipLaunchKernelGGL(k_update_fin, dim3(nfz, Y->fac.fin_ny[l]), dim3(TPB), 0, st, H.uf_lvl_ptr[l], Y->uf_item, Y->uf_n,
                          Y->uf_off, Y->ui_t, Y->ui_col, Y->ui_nc, Y->sn_rowptr, Y->sn_lx, Y->Lx,
                          Y->upart, (const int*)Y->d_info);
     // subtree partition: everything below the cut is done -- the sum over the ranks, then the replicated top
@@ -1779,86 +1378,21 @@ int sparse_factor_levels(dlg_backend* b, int part)
   return DLG_OK;
 }
 
-// Host only (no GPU): the schedule of the one-launch region of the factorisation for a pattern as a chip with
-// `ncu` compute units would get it -- and a check of everything the kernel takes on trust: every destination
-// inside the workgroup's LDS, the slices of a supernode's replicas covering its update matrix exactly once,
-// children listed before their parents.  stats = {first level, supernodes, workgroups, LDS bytes, sliced
-// workgroups, supernodes whose update matrix stays in HBM}.  Returns DLG_ERR_STATE with a message on a violation.
+// Host only (no GPU): the plan of the one-launch region for a pattern as a chip with `ncu` compute units would get it,
+// checked (region_check); stats as include/dlg_backend.h lists them.  DLG_ERR_STATE with a message on a violation.
 extern "C" int dlg_sparse_region_probe(int N, int M, const int* colptr, const int* rowidx, int ncu, long* stats, int nstats)
 {
-  dlg_backend b;
-  b.type = DLG_SPARSE; b.N = N; b.M = M; b.nnz = colptr[M]; b.ncu = ncu; b.row0 = 0; b.row1 = M; b.mloc = M;
-  SparseSym Y;
-  b.sym = &Y;
+  SymHost H;
   char err[512];
-  if(sym_analyze(Y.H, N, M, colptr, rowidx, 0, M, err, sizeof(err))) { b.sym = nullptr; dlg_set_error("symbolic analysis: %s", err); return DLG_ERR_ARG; }
-  const int rc = sparse_factor_setup(&b, true);
-  b.sym = nullptr;
-  if(rc != DLG_OK) return rc;
-  const SymHost& H = Y.H;
-  long nsliced = 0, nhbm = 0;
-  auto fail = [&](const char* what, size_t g) { dlg_set_error("one-launch region: %s (workgroup %zu)", what, g); return DLG_ERR_STATE; };
-  std::vector<long> covered;
-  for(size_t g = 0; g < Y.pr_item_h.size(); g++)
-  {
-    const FwItem& it = Y.pr_item_h[g];
-    const long mb = it.nrows - it.w, ldp = (it.nrows + 1) & ~1L, pan = ldp*it.w, ntri = mb*(mb + 1)/2;
-    const long T = (mb + 15) >> 4;
-    if(it.rep == 0) covered.assign((size_t)std::max<long>(T, 1), 0);
-    for(long t = std::min<long>(it.tj0, T); t < std::min<long>(it.tj1, T); t++) covered[(size_t)t]++;
-    long lds_end;
-    if(it.sliced)
-    {
-      nsliced++;
-      const long jA = std::min<long>(16L*it.tj0, mb), jB = it.tj1 >= T ? mb : std::min<long>(16L*it.tj1, mb);
-      if(it.eA != jA*mb - jA*(jA - 1)/2 || it.eB != jB*mb - jB*(jB - 1)/2) return fail("slice bounds do not match its tile columns", g);
-      lds_end = pan + (it.eA & 1) + (it.eB - it.eA) + 1;             // + the scratch slot
-    }
-    else
-    {
-      if(it.jsp < 0 && mb > 0 && it.u_off >= 0)
-      {
-        if(it.rep == 0) nhbm++;
-        // (replicas of an update matrix that is summed in HBM own the packed entries [eA, eB): their tile columns)
-        if(it.rsv2 > 1)
-        {
-          const long jA = std::min<long>(16L*it.tj0, mb), jB = it.tj1 >= T ? mb : std::min<long>(16L*it.tj1, mb);
-          if(it.eA != jA*mb - jA*(jA - 1)/2 || it.eB != jB*mb - jB*(jB - 1)/2) return fail("an HBM replica's stretch does not match its tile columns", g);
-        }
-        else if(it.tj0 != 0 || it.tj1 < T) return fail("a single workgroup that does not form the whole update matrix", g);
-      }
-      // (the kernel stages the whole update matrix behind the panel when the supernode has children, or -- childless --
-      // when the launch stages those too)
-      const bool staged = it.jsp >= 0 && mb > 0 && it.u_off >= 0 && (it.nch > 0 || Y.pr_stage);
-      lds_end = pan + (staged ? sym_w_linear(mb, it.jsp) : 0) + 1;
-    }
-    if(lds_end*8 > Y.pr_lds) return fail("its LDS need exceeds the launch's", g);
-    if(Y.pr_lds > FAC_LDS_BUDGET) return fail("the launch's LDS exceeds the budget", g);
-    for(int k = 0; k < it.nch; k++)
-    {
-      if((size_t)(it.ch0 + k) >= Y.pr_rec_h.size()) return fail("children record out of range", g);
-      const MfChild& rc2 = Y.pr_rec_h[it.ch0 + k];
-      if(rc2.rsv >= 0)
-      {
-        const long ci = rc2.rsv & 0xfffff, cn = rc2.rsv >> 20;
-        if(cn < 1 || ci + cn > (long)g) return fail("a child's workgroups do not precede their parent", g);
-      }
-      if(rc2.dst_off < 0 || (size_t)(rc2.dst_off + rc2.npad) > Y.pr_dst_h.size()) return fail("destination list out of range", g);
-      if(rc2.u_off < 0 || rc2.u_off + rc2.npad > H.uscr_size) return fail("a child's update matrix outside the scratch", g);
-      for(long e = 0; e < rc2.npad; e++)
-      {
-        const long d = Y.pr_dst_h[(size_t)(rc2.dst_off + e)];
-        if(it.sliced || it.jsp >= 0) { if(d >= pan + (it.sliced ? (it.eA & 1) + (it.eB - it.eA) : sym_w_linear(mb, it.jsp)) + 1) return fail("a destination behind the workgroup's LDS", g); }
-        else if(!(d & 0x8000) ? d >= pan + 1 : (d & 0x7fff) > ntri) return fail("a destination outside panel / update matrix", g);
-        else if((d & 0x8000) && it.rsv2 > 1 && ((d & 0x7fff) < it.eA || (d & 0x7fff) >= it.eB)) return fail("an HBM replica adds to an entry it does not own", g);
-      }
-    }
-    const bool last = g + 1 == Y.pr_item_h.size() || Y.pr_item_h[g + 1].rep == 0;
-    if(last && mb > 0 && it.u_off >= 0)
-      for(long t = 0; t < T; t++) if(covered[(size_t)t] != 1) return fail("a tile column of the update matrix is not formed exactly once", g);
-  }
-  const long v[] = { (long)Y.pr_level0, (long)(H.fw_lvl_ptr[H.nlevels] - (Y.pr_level0 < H.nlevels ? H.fw_lvl_ptr[Y.pr_level0] : H.fw_lvl_ptr[H.nlevels])),
-                     (long)Y.pr_nwg, (long)Y.pr_lds, nsliced, nhbm };
-  for(int i = 0; i < nstats && i < 6; i++) stats[i] = v[i];
+  if(sym_analyze(H, N, M, colptr, rowidx, 0, M, err, sizeof(err))) { dlg_set_error("symbolic analysis: %s", err); return DLG_ERR_ARG; }
+  const RegionKnobs K = region_knobs_env(ncu);
+  FacLevels L;
+  if(fac_level_params(H, L, err, sizeof(err))) { dlg_set_error("%s", err); return DLG_ERR_ARG; }
+  const RegionPlan R = region_plan(H, L, 1, H.nlevels - 1, K);
+  long checked[2];
+  if(region_check(H, R, checked, err, sizeof(err))) { dlg_set_error("%s", err); return DLG_ERR_STATE; }
+  const long v[] = { (long)R.level0, (long)(H.fw_lvl_ptr[H.nlevels] - H.fw_lvl_ptr[std::min(R.level0, H.nlevels)]),
+                     (long)R.nwg, (long)R.lds, checked[0], checked[1], (long)region_plan_hash(R), (long)fac_levels_hash(L) };
+  for(int i = 0; i < nstats && i < 8; i++) stats[i] = v[i];
   return DLG_OK;
 }

@@ -533,10 +533,10 @@ extern "C" int dlg_sparse_schedule(dlg_backend_t* b, int* n_levels, int* persist
 {
   if(!b || !b->sym) { dlg_set_error("no symbolic analysis yet"); return DLG_ERR_STATE; }
   const SparseSym* Y = b->sym; const SymHost& H = Y->H;
-  const bool on = Y->pr_level0 < H.nlevels;
+  const bool on = Y->top.level0 < H.nlevels;
   if(n_levels) *n_levels = H.nlevels;
-  if(persist_level0) *persist_level0 = on ? Y->pr_level0 : -1;
-  if(persist_items) *persist_items = on ? H.fw_lvl_ptr[H.nlevels] - H.fw_lvl_ptr[Y->pr_level0] : 0;
+  if(persist_level0) *persist_level0 = on ? Y->top.level0 : -1;
+  if(persist_items) *persist_items = on ? H.fw_lvl_ptr[H.nlevels] - H.fw_lvl_ptr[Y->top.level0] : 0;
   return DLG_OK;
 }
 

@@ -1,5 +1,6 @@
 // sparse_internal.h -- shared by the DOGLEG_SPARSE translation units:
 //   sparse_assemble.hip   K1 Jt*x, K3/K8 |Jv|^2, K4 JtJ assembly into the supernode panels
+//   sparse_region.cpp     K5's host-only planner: per-level launch parameters, the one-launch regions' schedule and its check
 //   sparse_factor.hip     K5 level-scheduled supernodal Cholesky (panel factorisation + updates)
 //   sparse_solve.hip      K6 triangular solves
 //   sparse_host.hip       pattern set-up (symbolic phase, uploads, buffers), orchestration
@@ -17,13 +18,14 @@
 #pragma once
 #include "dlg_internal.h"
 #include "sparse_symbolic.h"
+#include "sparse_region.h"
 
 namespace {
 constexpr int JFL_SEG = 16;             // workgroups per long Jt*x list (k_jtx_fin2_long)
 constexpr int NV_CHUNK = 2048;          // non-zeros per workgroup of the |Jv|^2 kernel
 
 constexpr int TPB = 256;
-constexpr int LDS_BUDGET = 147456;      // bytes of dynamic LDS we allow a workgroup
+constexpr int LDS_BUDGET = SYM_LDS_BUDGET;      // bytes of dynamic LDS we allow a workgroup
 constexpr int FAC_LDS_BUDGET = SYM_FAC_LDS_BUDGET;  // the panel factorisation takes (almost) all 160 KB of a CU; the rest is its static LDS
 
 __device__ __forceinline__ double wave_sum(double v)
@@ -64,6 +66,14 @@ template <class T> int upload(T*& dev, const std::vector<T>& h)
 // one work unit of k_update_gather, flat (everything the kernel needs before its first barrier behind ONE load)
 struct GatherUnit { int64_t lt, part; int s0, s1, nrows_t, nc; };
 struct SolveItem { int c0, w, nrows, rowoff; int64_t lx; int bd0, nbd; int pflag, rsv; };    // pflag: the parent's workgroup in the persistent backward launch (-1: none); rsv: pre-multiplied block sweep
+
+// a one-launch region of the factorisation on the device (sparse_region.h: RegionPlan; level0 >= H.nlevels: none)
+struct PrRegion
+{
+  int level0 = 1 << 30, level1 = -1, lds = 0, stage = 0, nwg = 0;
+  FwItem* item = nullptr; MfChild* rec = nullptr; uint16_t* dst = nullptr;   // work items (supernode x replica), the region's copy of the children records
+  int* flag = nullptr; int epoch = 0;   // one flag per workgroup (+ the fork gate): the epoch of the launch that finished it
+};
 
 struct SparseSym
 {
@@ -121,8 +131,8 @@ struct SparseSym
   // sharded rows: positions of the structural non-zeros of JtJ in Lx (what the all-reduce carries)
   uint32_t* ar_idx = nullptr; double* ar_buf = nullptr; size_t ar_n = 0;
   // per-level launch parameters
-  std::vector<int> fac_lds;     // bytes of LDS for the factor kernel of a level (0: panels stay in HBM)
-  std::vector<int> upd_lds, upd_nw, slv_lds, bwd_lds, fac_nt, upd_coop, syrk_lds, syrk_nt, syrk_kc, bwd_nt, syrk_fused, fin_ny, fac_stage, bwd_top, bwd_bd, bwd_pmx, fac_leaf;
+  FacLevels fac;                // the factor and update kernels' (sparse_region.h)
+  std::vector<int> slv_lds, bwd_lds, bwd_nt, bwd_bd, bwd_pmx;
   // subtree partition (part_nranks > 1): what is summed over the ranks between the last level below
   // the cut and the first one above it -- segments of Lx (panels above the cut) and of uscr (update
   // matrices that cross the cut), packed into red_buf --, and the 0/1 mask that makes the solution
@@ -146,14 +156,9 @@ struct SparseSym
   int64_t touch_off = 0, touch_n = 0;    // stretch of Lx with the leaf panels (sparse_touch_factor)
   int bw_level0 = 1 << 30, bw_lds = 0, bw_n = 0;   // persistent top region of the backward solve (sparse_solve_setup)
   SolveItem* slv_item_pr = nullptr; int* bwd_flag = nullptr; int bwd_epoch = 0; double* bwd_xh = nullptr;   // (bwd_xh: x of the region as its own arrival signal, two sets)
-  int pr_stage = 0; double* pr_acc = nullptr;   // ... childless supernodes stage their update matrix; shadow scratch for the ones kept in HBM
-  int pr_level0 = 1 << 30, pr_lds = 0;   // persistent top region of the factorisation: first level, LDS bytes (sparse_factor_setup)
-  int* fac_flag = nullptr; int fac_epoch = 0;   // one flag per workgroup of the region: the epoch of the launch that finished it
-  FwItem* pr_item = nullptr; MfChild* pr_rec = nullptr; uint16_t* pr_dst = nullptr; int pr_nwg = 0;
-  // a subtree partition's second one-launch region: the rank's own levels pr2_level0 .. pr2_level1 (= the cut)
-  int pr2_level0 = 1 << 30, pr2_level1 = -1, pr2_lds = 0, pr2_stage = 0, pr2_nwg = 0; int* fac2_flag = nullptr; int fac2_epoch = 0;
-  FwItem* pr2_item = nullptr; MfChild* pr2_rec = nullptr; uint16_t* pr2_dst = nullptr;
-  std::vector<FwItem> pr_item_h; std::vector<MfChild> pr_rec_h; std::vector<uint16_t> pr_dst_h;   // ... on the host (plan-only set-up: dlg_sparse_region_probe)   // the region's work items (supernode x replica) and its copy of the children records
+  // one-launch regions of the factorisation (sparse_factor_setup): the top of the tree and, with a subtree partition, the
+  // rank's own levels up to the cut; the shadow scratch both use for update matrices that are summed in HBM
+  PrRegion top, lo; double* pr_acc = nullptr;
   // fin on the side: flags [A: Jt*x final / augmented row on its way, B: partial-sum stages done], their epoch, the
   // epoch the main stream still has to wait for (0: nothing owed), whether the schedule allows it at all
   // partial clears (sparse_assemble.hip, clear_panels): the ranges of a panel buffer outside the merged leaves' panels,
@@ -162,7 +167,6 @@ struct SparseSym
   int64_t* aug_of_var = nullptr; char* jf_listed = nullptr;      // by variable: where its augmented-row entry lies; its Jt*x comes from a record list
   int aug_fused_epoch = 0; const double* spec_aug_fused = nullptr;   // the Jt*x sums of the last evaluation set the augmented rows (epoch of their word)
   int* fin_flag = nullptr; int fin_epoch = 0, fin_side_owed = 0; bool fin_side_sched_ok = false; hipStream_t fin_main = nullptr;
-  bool fac_b16 = false;         // panel_factor_b16 where the panel has at most 512 rows
   int bwd_xb_cap = 12288;       // below rows of a supernode staged in LDS by the backward solve
   double* diag_mm = nullptr; int n_diag_mm = 0;   // [supernode][min, max] of the diagonal of L (k_solve_bwd_level), read by the step kernels
   std::vector<void*> allocs;
@@ -176,6 +180,6 @@ int sparse_eval_assemble(dlg_backend* b, int s, int* done);   // K1 + K4 in one 
 int sparse_assemble_finish(dlg_backend* b);                   // ... its JtJ partial-sum stages (deferred behind the fetch of Jt*x)
 int sparse_zero_spare(dlg_backend* b, hipStream_t ordered_for);                        // clear the swapped-out panel buffer behind the step's fetch
 void sparse_spec_invalidate(dlg_backend* b, int s);                 // subtree partition: the sum over the ranks at the cut
-int sparse_factor_setup(dlg_backend* b, bool plan_only = false);   // per-level launch parameters of K5
+int sparse_factor_setup(dlg_backend* b);   // per-level launch parameters of K5
 int sparse_factor_levels(dlg_backend* b, int part = 0);      // K5 launches (no synchronisation); part 1: the leaf level only where the rest can follow later (fac_pending), part 2: that rest
 int sparse_solve_setup(dlg_backend* b);                      // per-level launch parameters of K6

@@ -655,8 +655,6 @@ __global__ void __launch_bounds__(TPB) k_mask_vec(double* __restrict__ v, const 
 
 } // namespace
 
-// per-level launch parameters of the solve kernels
-static long env_int_solve(const char* n, long d) { const char* v = getenv(n); return v ? atol(v) : d; }
 #ifdef DLG_FL_PROFILE
 extern "C" void dlg_bw_profile_dump(int nlevels)
 {
@@ -695,39 +693,45 @@ int sparse_touch_factor(dlg_backend* b, hipStream_t st)
   DLG_LAUNCH_CHECK();
   return DLG_OK;
 }
+// the backward solve's record of supernode s; rsv and pflag are the caller's
+static SolveItem solve_item(const SymHost& H, int s)
+{
+  SolveItem it;
+  it.c0 = H.sn_c0[s]; it.w = H.sn_c0[s+1] - H.sn_c0[s]; it.nrows = H.sn_rowptr[s+1] - H.sn_rowptr[s];
+  it.rowoff = H.sn_rowptr[s]; it.lx = H.sn_lx[s]; it.bd0 = H.sn_bd_ptr[s]; it.nbd = H.sn_bd_ptr[s+1] - H.sn_bd_ptr[s];
+  it.pflag = -1; it.rsv = 0;
+  return it;
+}
+
+// per-level launch parameters of the solve kernels
 int sparse_solve_setup(dlg_backend* b)
 {
   SparseSym* Y = b->sym;
   const SymHost& H = Y->H;
   // below rows of a supernode that the backward solve stages in LDS (96 KB of x); beyond that it gathers x from HBM
-  const long xb_cap = env_int_solve("DOGLEG_AMD_BWD_XB_CAP", 12288);
+  const long xb_cap = env_int("DOGLEG_AMD_BWD_XB_CAP", 12288);
   Y->bwd_xb_cap = (int)xb_cap;
-  Y->slv_lds.assign(H.nlevels, 0); Y->bwd_lds.assign(H.nlevels, 0); Y->bwd_nt.assign(H.nlevels, 512); Y->bwd_top.assign(H.nlevels, 0); Y->bwd_bd.assign(H.nlevels, 0); Y->bwd_pmx.assign(H.nlevels, 0);
+  Y->slv_lds.assign(H.nlevels, 0); Y->bwd_lds.assign(H.nlevels, 0); Y->bwd_nt.assign(H.nlevels, 512); Y->bwd_bd.assign(H.nlevels, 0); Y->bwd_pmx.assign(H.nlevels, 0);
   for(int l = 0; l < H.nlevels; l++)
   {
-    long maxw = 0, mb = 0, mbt = 0, wmax_all = 0;
+    long maxw = 0, mb = 0;
     for(int i = H.lvl_ptr[l]; i < H.lvl_ptr[l+1]; i++)
     {
       const int s = H.lvl_sn[i];
       const long wv = H.sn_c0[s+1] - H.sn_c0[s], nr = H.sn_rowptr[s+1] - H.sn_rowptr[s];
       if(wv > maxw) maxw = wv;
-      wmax_all = std::max(wmax_all, wv);
       // xb (x at the below rows, unless there are more of them than xb_cap: those supernodes gather x
       // from HBM), xs, diagonal blocks, rhs, mat-vec partial sums
       const long rb = nr - wv - 1;
       const long need = (rb <= xb_cap ? rb + 3 : 0) + 256 + ((wv + 7)/8)*64 + 16 + 8*256;
       if(need > mb) mb = need;
-      // + the top block, for the supernodes that read it (not the block-diagonal ones)
-      if(H.sn_bd_ptr[s+1] == H.sn_bd_ptr[s]) mbt = std::max(mbt, need + wv*(wv | 1));
     }
-    mbt = std::max(mbt, mb);
-    if(wmax_all > 256) { dlg_set_error("supernode of width %ld is too wide for the backward-solve kernel", wmax_all); return DLG_ERR_ARG; }
+    if(maxw > 256) { dlg_set_error("supernode of width %ld is too wide for the backward-solve kernel", maxw); return DLG_ERR_ARG; }
     Y->slv_lds[l] = (int)(maxw*(maxw | 1)*8);
     if(Y->slv_lds[l] > LDS_BUDGET) { dlg_set_error("supernode of width %ld is too wide for the solve kernels", maxw); return DLG_ERR_ARG; }
     if(mb*8 > LDS_BUDGET) { dlg_set_error("supernode too large for the backward-solve kernel (%ld doubles)", mb); return DLG_ERR_ARG; }
-    // the top block rides in LDS when every supernode of the level has room for it
-    Y->bwd_top[l] = 0;     // (the top block staged in LDS was measured slower than its prefetch from HBM, rounds 2 - 5: k_solve_bwd_level keeps the path, nothing selects it)
-    Y->bwd_lds[l] = (int)((Y->bwd_top[l] ? mbt : mb)*8);
+    // (the top block staged in LDS, bit 0 of k_solve_bwd_level's mode, was measured slower than its prefetch from HBM: no launch selects it)
+    Y->bwd_lds[l] = (int)(mb*8);
     Y->bwd_pmx[l] = 0;
     {
       // room for the pre-multiplied operands of the block sweep (k_solve_bwd_level: premul), [nblk][8][w16] per supernode
@@ -757,9 +761,8 @@ int sparse_solve_setup(dlg_backend* b)
     {
       const int s = H.xl_sn[k];
       SolveItem& it = items[k];
-      it.c0 = H.sn_c0[s]; it.w = H.sn_c0[s+1] - H.sn_c0[s]; it.nrows = H.sn_rowptr[s+1] - H.sn_rowptr[s];
-      it.rowoff = H.sn_rowptr[s]; it.lx = H.sn_lx[s]; it.bd0 = H.sn_bd_ptr[s]; it.nbd = H.sn_bd_ptr[s+1] - H.sn_bd_ptr[s];
-      it.pflag = -1; it.rsv = Y->bwd_pmx[H.sn_level[s]] ? 1 : 0;
+      it = solve_item(H, s);
+      it.rsv = Y->bwd_pmx[H.sn_level[s]] ? 1 : 0;
       if(it.nbd > 0)
       {
         // block-diagonal top: rsv = the common width of the members (0: they differ)
@@ -803,12 +806,12 @@ int sparse_solve_setup(dlg_backend* b)
   {
     int ncu = 256;
     { int dev = 0; if(hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev); }
-    const int cap = (int)env_int_solve("DOGLEG_AMD_PERSIST_MAX", 2*ncu);
+    const int cap = env_int("DOGLEG_AMD_PERSIST_MAX", 2*ncu);
     int total = 0, l0 = H.nlevels, ldsb = 0;
     for(int l = H.nlevels - 1; l >= 1; l--)
     {
       const int n = H.xl_ptr[l+1] - H.xl_ptr[l];
-      if(n == 0 || total + n > cap || Y->bwd_nt[l] != 512 || Y->bwd_bd[l] || Y->bwd_top[l]) break;
+      if(n == 0 || total + n > cap || Y->bwd_nt[l] != 512 || Y->bwd_bd[l]) break;
       total += n; l0 = l; ldsb = std::max(ldsb, Y->bwd_lds[l]);
     }
 
@@ -820,10 +823,8 @@ int sparse_solve_setup(dlg_backend* b)
         for(int k = H.xl_ptr[l]; k < H.xl_ptr[l+1]; k++)
         {
           const int s = H.xl_sn[k];
-          SolveItem it;
-          it.c0 = H.sn_c0[s]; it.w = H.sn_c0[s+1] - H.sn_c0[s]; it.nrows = H.sn_rowptr[s+1] - H.sn_rowptr[s];
-          it.rowoff = H.sn_rowptr[s]; it.lx = H.sn_lx[s]; it.bd0 = H.sn_bd_ptr[s]; it.nbd = H.sn_bd_ptr[s+1] - H.sn_bd_ptr[s];
-          it.rsv = Y->bwd_pmx[l] ? 1 : 0; it.pflag = -1;
+          SolveItem it = solve_item(H, s);
+          it.rsv = Y->bwd_pmx[l] ? 1 : 0;
           if(it.nbd > 0) it.rsv = 0;          // (a block-diagonal top in the region: rsv would mean the members' width; 0 = look it up)
           // the parent: the supernode of the first below row (the last row is the augmented one)
           if(it.nrows - it.w - 1 > 0)
@@ -839,26 +840,40 @@ int sparse_solve_setup(dlg_backend* b)
       Y->bw_level0 = l0; Y->bw_n = (int)items.size(); Y->bw_lds = std::max(ldsb, 84*1024);
       DLG_CHECK(upload(Y->slv_item_pr, items)); Y->allocs.push_back(Y->slv_item_pr);
       // x of the region as its own signal (k_solve_bwd_level, xh): two sets, every entry a sentinel until it is stored
-      if(true)
-      {
-        std::vector<unsigned long long> empty(2*(size_t)H.N, 0x7FF8DEADBEEF0002ull);
-        DLG_HIP(hipMalloc(&Y->bwd_xh, sizeof(double)*empty.size())); Y->allocs.push_back(Y->bwd_xh);
-        DLG_HIP(hipMemcpy(Y->bwd_xh, empty.data(), sizeof(double)*empty.size(), hipMemcpyHostToDevice));
-      }
+      std::vector<unsigned long long> empty(2*(size_t)H.N, 0x7FF8DEADBEEF0002ull);
+      DLG_HIP(hipMalloc(&Y->bwd_xh, sizeof(double)*empty.size())); Y->allocs.push_back(Y->bwd_xh);
+      DLG_HIP(hipMemcpy(Y->bwd_xh, empty.data(), sizeof(double)*empty.size(), hipMemcpyHostToDevice));
       DLG_HIP(hipMalloc(&Y->bwd_flag, sizeof(int)*items.size())); Y->allocs.push_back(Y->bwd_flag);
       DLG_HIP(hipMemsetAsync(Y->bwd_flag, 0, sizeof(int)*items.size(), b->stream));
       Y->bwd_epoch = 0;
     }
   }
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_fwd_level),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_bwd_level<256, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_bwd_level<256, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
-  DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_bwd_level<512, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
+  for(const void* k : { (const void*)&k_solve_fwd_level, (const void*)&k_solve_bwd_level<256, false>,
+                        (const void*)&k_solve_bwd_level<256, true>, (const void*)&k_solve_bwd_level<512, false> })
+    DLG_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
   return DLG_OK;
+}
+
+// where a backward launch that starts at level l leaves its supernodes' [min, max] of the diagonal of L (null: nowhere)
+static double* bwd_diag_mm(const dlg_backend* b, int l)
+{
+  const SparseSym* Y = b->sym;
+  return (Y->diag_mm && !b->knobs.ei_jpass) ? Y->diag_mm + 16*(size_t)Y->H.xl_ptr[l] : (double*)nullptr;
+}
+// the one dispatch over the instantiations of k_solve_bwd_level: the supernodes `items` of level l (a region: its first
+// level); bd: every supernode of the launch has a block-diagonal top (the lean variant, 256 threads only)
+static void launch_bwd_level(dlg_backend* b, int nt, bool bd, int grid, int lds, const SolveItem* items, double* out, int use_aug,
+                             int l, int* flag, int epoch, double* xh, int nxh)
+{
+  SparseSym* Y = b->sym;
+  double* mm = bwd_diag_mm(b, l);
+#define DLG_BW_LAUNCH(...) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_solve_bwd_level<__VA_ARGS__>), dim3(grid), dim3(nt), lds, b->stream, \
+                                              items, Y->sn_rows, Y->perm, Y->Lx, Y->ywork, out, use_aug, Y->sn_bd_col, 256*l, Y->bwd_xb_cap, \
+                                              flag, epoch, Y->d_info, dlg_handoff(b, 1 << 21), xh, nxh, mm)
+  if(nt == 256 && bd) DLG_BW_LAUNCH(256, true);
+  else if(nt == 256) DLG_BW_LAUNCH(256, false);
+  else { nt = 512; DLG_BW_LAUNCH(512, false); }
+#undef DLG_BW_LAUNCH
 }
 
 // K6: out = (L L')^-1 rhs in the original variable order
@@ -887,32 +902,13 @@ int sparse_solve(dlg_backend* b, const double* rhs, double* out)
   {
     // the persistent top region: its levels in one launch, workgroups from the root down (sparse_solve_setup)
     DlgRegionTurn turn(b);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_solve_bwd_level<512, false>), dim3(Y->bw_n), dim3(512), Y->bw_lds, st,
-                       Y->slv_item_pr, Y->sn_rows, Y->perm, Y->Lx, Y->ywork, out, use_aug, Y->sn_bd_col,
-                       256*Y->bw_level0, Y->bwd_xb_cap, Y->bwd_flag, ++Y->bwd_epoch, Y->d_info, dlg_handoff(b, 1 << 21), Y->bwd_xh, H.N,
-                       (Y->diag_mm && !b->knobs.ei_jpass) ? Y->diag_mm + 16*(size_t)H.xl_ptr[Y->bw_level0] : (double*)nullptr);
+    launch_bwd_level(b, 512, false, Y->bw_n, Y->bw_lds, Y->slv_item_pr, out, use_aug, Y->bw_level0, Y->bwd_flag, ++Y->bwd_epoch, Y->bwd_xh, H.N);
     ltop = Y->bw_level0 - 1;
   }
   for(int l = ltop; l >= 0; l--)
   {
     const int n = H.xl_ptr[l+1] - H.xl_ptr[l];
-    // thread = row of the diagonal block: 256 threads when every supernode of a populous level is
-    // narrow (more workgroups per CU), else 512
-    if(n > 0 && Y->bwd_nt[l] == 256 && Y->bwd_bd[l])
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_solve_bwd_level<256, true>), dim3(n), dim3(256), Y->bwd_lds[l], st,
-                         Y->slv_item + H.xl_ptr[l], Y->sn_rows, Y->perm, Y->Lx, Y->ywork, out, use_aug, Y->sn_bd_col,
-                         Y->bwd_top[l] + 256*l, Y->bwd_xb_cap, (int*)nullptr, 0, Y->d_info, dlg_handoff(b, 1 << 21), (double*)nullptr, 0,
-                         (Y->diag_mm && !b->knobs.ei_jpass) ? Y->diag_mm + 16*(size_t)H.xl_ptr[l] : (double*)nullptr);
-    else if(n > 0 && Y->bwd_nt[l] == 256)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_solve_bwd_level<256, false>), dim3(n), dim3(256), Y->bwd_lds[l], st,
-                         Y->slv_item + H.xl_ptr[l], Y->sn_rows, Y->perm, Y->Lx, Y->ywork, out, use_aug, Y->sn_bd_col,
-                         Y->bwd_top[l] + 256*l, Y->bwd_xb_cap, (int*)nullptr, 0, Y->d_info, dlg_handoff(b, 1 << 21), (double*)nullptr, 0,
-                         (Y->diag_mm && !b->knobs.ei_jpass) ? Y->diag_mm + 16*(size_t)H.xl_ptr[l] : (double*)nullptr);
-    else if(n > 0)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_solve_bwd_level<512, false>), dim3(n), dim3(512), Y->bwd_lds[l], st,
-                         Y->slv_item + H.xl_ptr[l], Y->sn_rows, Y->perm, Y->Lx, Y->ywork, out, use_aug, Y->sn_bd_col,
-                         Y->bwd_top[l] + 256*l, Y->bwd_xb_cap, (int*)nullptr, 0, Y->d_info, dlg_handoff(b, 1 << 21), (double*)nullptr, 0,
-                         (Y->diag_mm && !b->knobs.ei_jpass) ? Y->diag_mm + 16*(size_t)H.xl_ptr[l] : (double*)nullptr);
+    if(n > 0) launch_bwd_level(b, Y->bwd_nt[l], Y->bwd_bd[l], n, Y->bwd_lds[l], Y->slv_item + H.xl_ptr[l], out, use_aug, l, (int*)nullptr, 0, (double*)nullptr, 0);
   }
   DLG_LAUNCH_CHECK();
   if(H.part_nranks > 1)

@@ -12,6 +12,12 @@
 #include <queue>
 #include <array>
 
+int env_int(const char* name, int dflt)
+{
+  const char* s = getenv(name);
+  return (s && *s) ? atoi(s) : dflt;
+}
+
 namespace {
 
 constexpr int VB_MAX   = 8;       // max variables per var-block (<= 64 lanes per 8x8 output block)
@@ -21,11 +27,6 @@ constexpr int MAXCH_JTX = 2048;
 constexpr int PANEL_CAP = 16384;  // doubles: supernode panels up to this size are factored in LDS
 constexpr int SN_WMAX  = 256;     // max supernode width
 
-int env_int(const char* name, int dflt)
-{
-  const char* s = getenv(name);
-  return (s && *s) ? atoi(s) : dflt;
-}
 // doubles: a row slice (top block + its rows) of a larger panel; as much of the 160 KB LDS as a
 // single workgroup can get, so that fewer slices repeat the factorisation of the top block
 static int slice_cap() { return env_int("DOGLEG_AMD_SLICE_CAP", SYM_FAC_LDS_BUDGET/8 - 40); }

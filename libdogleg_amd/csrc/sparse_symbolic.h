@@ -148,6 +148,9 @@ static_assert(sizeof(AsmFin2) == 24, "AsmFin2 layout");
 // into slot `part` of the partial buffer instead of the destination
 struct SymTask { int32_t blk, c0, c1, part, var0, nI; };   // var0 / nI: copied from the out-block (one dependent load less)
 
+// an integer knob from the environment; unset or EMPTY: dflt (the factor and solve set-up used to read an empty value as 0)
+int env_int(const char* name, int dflt);
+constexpr int SYM_LDS_BUDGET = 147456;      // bytes of dynamic LDS the update and solve kernels allow a workgroup
 // LDS bytes a factor workgroup may use: (almost) all 160 KB of a CU, the rest is its static LDS
 constexpr int SYM_FAC_LDS_BUDGET = 163840 - 3584 - 8704;      // (static LDS of the factor kernel: its own words + panel_factor_b16's hand-off buffers)
 

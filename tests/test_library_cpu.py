@@ -372,6 +372,126 @@ def test_one_launch_region_schedule_invariants(shape, ncu, monkeypatch):
         monkeypatch.delenv(knob)
 
 
+# The schedule of the one-launch region and the per-level launch parameters of the factorisation, pinned bit for bit:
+# shape (seed 11) -> (level_params_hash, {CUs: schedule_hash under each of _REGION_KNOBS}).  The literals were produced by
+# the set-up code as it stood before the planner moved to sparse_region.cpp (the same hash added to its probe, nothing else).
+_REGION_KNOBS = (None, ("DOGLEG_AMD_FRONT_REPLICAS", "1"), ("DOGLEG_AMD_NO_FRONT_SLICES", "1"), ("DOGLEG_AMD_PERSIST_MAX", "3"))
+_REGION_KW = {(833, 15000, 250000): dict(scale_decades=4.0, n_zero_cols=3)}
+_REGION_HASHES = {
+    (49, 900, 10000): (0x333b848517a32945, {
+        256: (0x326b590a32d9185e, 0x70c58b34c19d29a5, 0x4c81fc5572e6cd7, 0x85ff7d46b93fa5d4),
+        64: (0x326b590a32d9185e, 0x70c58b34c19d29a5, 0x4c81fc5572e6cd7, 0x85ff7d46b93fa5d4),
+    }),
+    (99, 1800, 20000): (0xba8e82bdc66c367a, {
+        256: (0xcc0d6b20c48c0603, 0x494b9475902aad8, 0x86cc3f11aa9c9b29, 0x768e908f52d85f0e),
+        64: (0xcc0d6b20c48c0603, 0x494b9475902aad8, 0x86cc3f11aa9c9b29, 0x768e908f52d85f0e),
+    }),
+    (199, 3000, 30000): (0x22f1eb75a2c3699, {
+        256: (0x1f1948b3d5d148ea, 0xdafb7f7f66e49649, 0x7d015f0c776266ec, 0x5d250adda8309ba7),
+        64: (0xa2807df0e24bae0, 0xdafb7f7f66e49649, 0x7ba90210648bccc9, 0x5d250adda8309ba7),
+    }),
+    (499, 9000, 100000): (0xc964bc1e7c6dd4ec, {
+        256: (0x21e99ac484e03af8, 0x5351d94e0dc4df78, 0x793a71e47be5293a, 0x6ccc7847d97b071a),
+        64: (0xf0152a0407c0896b, 0x5351d94e0dc4df78, 0xd93fa4170d887b39, 0x6ccc7847d97b071a),
+    }),
+    (2499, 45000, 500000): (0xa647c3c90a236a63, {
+        256: (0x61b7ecdc3dbda781, 0x10f88cf952fd21a4, 0x28911526ea5ef954, 0xc9c9dc680ba7251e),
+        64: (0xfe2360a10a4a1370, 0xa4834725e4a7e66b, 0xb6bcf5b63f7d5d40, 0xc9c9dc680ba7251e),
+    }),
+    (833, 15000, 250000): (0x6abc9502c289e5f, {
+        256: (0x330ee472dd1709a7, 0x366a698f0b698db8, 0xa3434c6c32bb3677, 0x29272c3a73b4af50),
+        64: (0x330ee472dd1709a7, 0x366a698f0b698db8, 0xa3434c6c32bb3677, 0x29272c3a73b4af50),
+    }),
+}
+_region_patterns = {}
+
+
+def _region_pattern(shape):
+    if shape not in _region_patterns:
+        prob = oa.BAProblem(*shape, seed=11, **_REGION_KW.get(shape, {}))
+        _region_patterns[shape] = (prob.N, prob.M) + tuple(prob.pattern())
+    return _region_patterns[shape]
+
+
+def _set_knob(monkeypatch, knob):
+    for k in _REGION_KNOBS[1:]:
+        monkeypatch.delenv(k[0], raising=False)
+    if knob:
+        monkeypatch.setenv(*knob)
+
+
+def test_one_launch_region_schedule_is_pinned(monkeypatch):
+    """Every field of every work item, children record and destination of the region, and every per-level launch
+    parameter, hashed (dlg_sparse_region_probe: schedule_hash, level_params_hash) and compared with what the set-up
+    code produced before it was taken apart: six patterns x 256 / 64 CUs x {default, one replica, no slices,
+    DOGLEG_AMD_PERSIST_MAX=3 (which shortens the region of every pattern: it starts at level 2, 7, 4, 5, 7, 26
+    instead of 1, 6, 1, 1, 1, 18)}.  The set holds the three forms of a work item: whole update matrix in LDS, a slice
+    of it in LDS (up to 663 workgroups: config #4 at 256 CUs), and summed in HBM (up to 23 update matrices: config #4
+    without slices) -- among the latter the HBM replicas (rsv2 > 1, not sliced, jsp < 0), e.g. 8 workgroups of
+    (49, 900, 10000) and 40 of (833, 15000, 250000) with the default knobs; the assertion finds them where nothing is
+    sliced, (99, 1800, 20000) with one replica: 5 workgroups for 4 supernodes."""
+    wrong, sliced, hbm, hbm_replicas = [], 0, 0, 0
+    for shape, (lvl_hash, by_ncu) in _REGION_HASHES.items():
+        N, M, Jp, Ji = _region_pattern(shape)
+        for ncu, hashes in by_ncu.items():
+            for knob, want in zip(_REGION_KNOBS, hashes):
+                _set_knob(monkeypatch, knob)
+                st = capi.region_probe(N, M, Jp, Ji, ncu)
+                sliced = max(sliced, st["sliced_workgroups"])
+                hbm = max(hbm, st["hbm_update_matrices"])
+                # with slices allowed a replica either keeps a slice (counted above) or owns a stretch in HBM: more
+                # workgroups than supernodes and none sliced can only be the latter
+                if knob != _REGION_KNOBS[2] and st["sliced_workgroups"] == 0 and st["hbm_update_matrices"] > 0:
+                    hbm_replicas = max(hbm_replicas, st["workgroups"] - st["supernodes"])
+                if (st["schedule_hash"], st["level_params_hash"]) != (want, lvl_hash):
+                    wrong.append((shape, ncu, knob, hex(st["schedule_hash"]), hex(st["level_params_hash"])))
+    assert not wrong, wrong
+    assert sliced > 0 and hbm > 0 and hbm_replicas > 0
+
+
+def _sanitizing_compiler(tmp):
+    """the first of g++ / clang++ / ROCm's clang++ that links and runs a sanitized program"""
+    from libdogleg_amd import build as B
+    hello = tmp / "hello.cpp"
+    hello.write_text("#include <vector>\nint main(){std::vector<int> v(3); return v[2];}\n")
+    for cc in ("g++", "clang++", os.path.join(os.path.dirname(B.HIPCC), "amdclang++")):
+        try:
+            subprocess.run([cc] + _SAN_FLAGS + [str(hello), "-o", str(tmp / "hello")], check=True, capture_output=True)
+            subprocess.run([str(tmp / "hello")], check=True, capture_output=True)
+            return cc
+        except (OSError, subprocess.CalledProcessError):
+            continue
+    return None
+
+
+_SAN_FLAGS = ["-std=c++17", "-O0", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread"]
+
+
+def test_region_planner_is_clean_under_sanitizers(tmp_path, monkeypatch):
+    """The symbolic phase, the planner and its check as a stand-alone program (tests/c/region_plan_main.cpp: plain C++,
+    no HIP) under AddressSanitizer and UndefinedBehaviorSanitizer: exit status 0, nothing reported, and the hashes
+    the library computes for the same pattern, CUs and knobs."""
+    cc = _sanitizing_compiler(tmp_path)
+    if cc is None:
+        pytest.skip("no compiler here links a program with -fsanitize=address,undefined")
+    csrc = os.path.join(ROOT, "libdogleg_amd", "csrc")
+    exe = str(tmp_path / "region_plan_main")
+    subprocess.run([cc] + _SAN_FLAGS + ["-I", csrc, os.path.join(ROOT, "tests", "c", "region_plan_main.cpp"),
+                                        os.path.join(csrc, "sparse_symbolic.cpp"), os.path.join(csrc, "sparse_region.cpp"),
+                                        "-o", exe], check=True)
+    for shape in list(_REGION_HASHES)[:3]:
+        N, M, Jp, Ji = _region_pattern(shape)
+        pat = tmp_path / "pattern.bin"
+        np.concatenate([[N, M], Jp, Ji]).astype(np.int32).tofile(pat)
+        for ncu in (256, 64):
+            for knob in _REGION_KNOBS:
+                _set_knob(monkeypatch, knob)
+                r = subprocess.run([exe, str(pat), str(ncu)], capture_output=True, text=True)
+                assert r.returncode == 0 and r.stderr == "", (shape, ncu, knob, r.returncode, r.stderr[-2000:])
+                st = capi.region_probe(N, M, Jp, Ji, ncu)
+                assert [int(h, 16) for h in r.stdout.split()] == [st["schedule_hash"], st["level_params_hash"]], (shape, ncu, knob)
+
+
 def test_subtree_partition_rows_form_closed_subtrees():
     """the property the partition rests on: a rank's rows touch only its own subtrees' variables and
     the replicated ones -- so J_r' J_r of rank r is zero in every (variable of another rank, *) entry"""
