@@ -240,7 +240,7 @@ int  dlg_point_eval_early(dlg_backend_t* b, int slot, const double* x_dev, const
  * The value itself needs no pass over J where the Gauss-Newton system (JtJ + lambda I) gn = -Jt x was solved with a factor
  * whose pivots span less than 212x and whose estimated error along gn, eps (max L_ii)^2 |gn|^2 / -<Jt x, gn>, is at most
  * 1e-12: |J gn|^2 = -<Jt x, gn> - lambda |gn|^2, <J cauchy, J gn> = -<cauchy, Jt x> - lambda <cauchy, gn>, |J cauchy|^2 is
- * the Cauchy step's own scalar (backend.hip: ident_norm2_Jstep; within about 2e-12 of the exact value, dlg_internal.h:
+ * the Cauchy step's own scalar (step.hip: ident_norm2_Jstep; within about 2e-12 of the exact value, dlg_internal.h:
  * IDENT_ERR_MAX).  The step kernel decides on the device, the pass over J that is on the stream returns at once.  A wider
  * pivot range (config #5: 3.5e6 at lambda = 1e-10), an ill-conditioned system along gn, several ranks: the pass over J.
  * DOGLEG_AMD_EI_JPASS=1: always the pass over J. */

@@ -662,34 +662,42 @@ class Backend:
             self._pnew = np.ctypeslib.as_array(C.cast(self._pnew_ptr, C.POINTER(C.c_double)), shape=(self.N,))
         return self._pnew
 
-    def step(self, frm, to, kind, trustregion, want_p=True, tail=True):
+    def _pnew_dest(self, want_p, p_out):
+        """where p_new goes: p_out (a caller's float64 array of N, e.g. pageable memory), else this object's
+        page-locked buffer, else (want_p false) nowhere"""
+        if not want_p:
+            return None
+        if p_out is None:
+            return self._pnew_buffer()
+        assert p_out.dtype == np.float64 and p_out.shape == (self.N,) and p_out.flags["C_CONTIGUOUS"]
+        return p_out
+
+    def step(self, frm, to, kind, trustregion, want_p=True, tail=True, p_out=None):
         """make_step + expected_improvement behind one synchronisation:
         (|step|^2, k, max|step|, expected improvement, p_new); p_new as in make_step"""
         n2, k, am, ei = C.c_double(), C.c_double(), C.c_double(), C.c_double()
-        if want_p:
-            self._pnew_buffer()
+        dst = self._pnew_dest(want_p, p_out)
         _ck(self.L.dlg_step(self.h, frm, to, kind, trustregion, C.byref(n2), C.byref(k), C.byref(am),
-                            C.byref(ei), dptr(self._pnew) if want_p else None), "step")
+                            C.byref(ei), dptr(dst) if want_p else None), "step")
         e = ei.value
         if tail and self.step_tail_pending():
             e = self.step_tail()                # set_defer_tail: the value (and a page-locked p_new) complete here
-        return n2.value, k.value, am.value, e, (self._pnew if want_p else None)
+        return n2.value, k.value, am.value, e, dst
 
-    def take_step(self, frm, to, trustregion, lam=0.0, want_p=True, tail=True):
+    def take_step(self, frm, to, trustregion, lam=0.0, want_p=True, tail=True, p_out=None):
         """Cauchy + Gauss-Newton + the choice of step + step + expected improvement behind one
         synchronisation: (lambda, dict(n2c, n2g, kind, n2s, k, amax, ei), p_new)"""
         l = C.c_double(lam)
         out = (C.c_double * 7)()
-        if want_p:
-            self._pnew_buffer()
+        dst = self._pnew_dest(want_p, p_out)
         _ck(self.L.dlg_take_step(self.h, frm, to, trustregion, C.byref(l), out,
-                                 dptr(self._pnew) if want_p else None), "take_step")
+                                 dptr(dst) if want_p else None), "take_step")
         keys = ("n2c", "n2g", "kind", "n2s", "k", "amax", "ei")
         r = dict(zip(keys, [float(v) for v in out]))
         r["kind"] = int(r["kind"])
         if tail and self.step_tail_pending():
             r["ei"] = self.step_tail()          # set_defer_tail: the value (and a page-locked p_new) complete here
-        return l.value, r, (self._pnew if want_p else None)
+        return l.value, r, dst
 
     def run_steps(self, frm, to, nsteps, x_ptrs, J_ptrs, first_copy, trustregion, lam0=0.0):
         """nsteps x (bind the next resident copy, eval, take_step) in one C call (dlg_run_steps): returns
@@ -822,18 +830,14 @@ class Backend:
         _ck(self.L.dlg_covariance_entries_stats(self.h, C.byref(t), C.byref(a), C.byref(f)), "covariance_entries_stats")
         return t.value, a.value, f.value
 
-    def make_step(self, frm, to, kind, trustregion, want_p=True):
+    def make_step(self, frm, to, kind, trustregion, want_p=True, p_out=None):
         """p_new comes back in a page-locked buffer owned by this object (as the driver's operating
-        points are): it is overwritten by the next call -- copy it to keep it."""
+        points are): it is overwritten by the next call -- copy it to keep it.  p_out: a caller's array instead."""
         n2, k, am = C.c_double(), C.c_double(), C.c_double()
-        if want_p and self._pnew is None:
-            self._pnew_ptr = self.L.dlg_host_alloc(8 * self.N)
-            if not self._pnew_ptr:
-                raise DlgError(self.L.dlg_last_error().decode())
-            self._pnew = np.ctypeslib.as_array(C.cast(self._pnew_ptr, C.POINTER(C.c_double)), shape=(self.N,))
+        dst = self._pnew_dest(want_p, p_out)
         _ck(self.L.dlg_make_step(self.h, frm, to, kind, trustregion, C.byref(n2), C.byref(k),
-                                 C.byref(am), dptr(self._pnew) if want_p else None), "make_step")
-        return n2.value, k.value, am.value, (self._pnew if want_p else None)
+                                 C.byref(am), dptr(dst) if want_p else None), "make_step")
+        return n2.value, k.value, am.value, dst
 
     def expected_improvement(self, frm, to):
         a = C.c_double()

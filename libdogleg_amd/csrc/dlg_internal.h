@@ -46,7 +46,7 @@ struct DlgSlot
   const double* x_bound = nullptr;   // device-resident inputs (dlg_point_bind_device)
   const double* J_bound = nullptr;
   double  norm2_x = 0, norm2_cauchy = 0, norm2_gn = 0, norm2_jtx = 0;
-  // the expected improvement from the solved system (backend.hip, ident_norm2_Jstep): |J Jt_x|^2 of the Cauchy step, <Jt_x, gn>,
+  // the expected improvement from the solved system (step.hip, ident_norm2_Jstep): |J Jt_x|^2 of the Cauchy step, <Jt_x, gn>,
   // and whether the factor the Gauss-Newton step came from allows it (pivot ratio)
   double  Jg2 = 0, g_dot_gn = 0, a_dot_gn = 0, ident_lam = 0; bool ident_ok = false;      // (ident_norm2_Jstep: <Jt x, gn>, <cauchy, gn>, the lambda gn was solved at)
   bool    have_inputs = false, have_Jtx = false, have_cauchy = false, have_gn = false;
@@ -90,27 +90,25 @@ struct dlg_backend
   // scalar return path: kernels write d_scal, one D2H into pinned h_scal
   double* d_scal = nullptr;
   double* h_scal = nullptr;
-  const double* fold_p_src = nullptr; double* fold_p_dst = nullptr; bool p_copied = false;   // ... and p_new to a page-locked destination
   int* fork_gate = nullptr; int fork_gate_epoch = 0;      // dlg_fork_gate
-  int fold_scal = 0; bool scal_copied = false;   // dlg_take_step: its last kernel (K8-sparse) copies d_scal to h_scal itself
   // The expected improvement's pass over J (K8) behind the host's decision point (dlg_backend_set_defer_tail): the value is
   // first used after the NEXT evaluation (dogleg.c:1427 -- takeStepFrom only needs max|step| to tell "done", 1289-1296), so
-  // dlg_take_step's synchronisation rides on the step kernel (fold_scal_k7: it takes the scalars to the host), K8 follows on
+  // dlg_take_step's synchronisation rides on the step kernel (StepLaunch::nscal: it takes the scalars to the host), K8 follows on
   // the same stream while the host is on its way back, its partial sums (and p_new) land in page-locked memory and
   // dlg_step_tail adds them up -- behind a wait of its own only if the host has not waited for anything enqueued behind K8
-  // since (sync_mark against tail_mark: the evaluation of the trial point is such a wait).
-  bool defer_tail = false, tail_pending = false, tail_mode = false;
-  int fold_scal_k7 = 0, tail_nb = 0;
+  // since (sync_mark against tail_mark: the evaluation of the trial point is such a wait).  tail_*: between the step call and
+  // dlg_step_tail, which may be several C calls later.
+  bool defer_tail = false, tail_pending = false;
+  int tail_nb = 0;
   double tail_inner = 0.0, tail_value = 0.0;
   double* h_tail = nullptr; int h_tail_cap = 0;
   unsigned long sync_mark = 0, tail_mark = 0;
   bool factor_doomed = false; // sparse_factorize found the factorisation doomed at its look at the diagonal and enqueued nothing else (the lambda loops go on at once)
-  bool kout_host = false;     // (dlg_step behind the decision point: k_interpolate's k straight into the page-locked scalars)
   // The expected improvement WITHOUT its pass over J (K8): with (JtJ + lambda I) gn = -Jt_x solved, |J step|^2 of all three
   // kinds of step is a combination of N-vector dot products (ident_norm2_Jstep).  The step kernel decides on the device
   // (d_scal[IDENT_SLOT] = 1: the factor allows it, 2: the step is the Cauchy step, which needs no factor, 0: neither;
   // [IDENT_SLOT + 1] = the pivot ratio, [IDENT_SLOT + 4] = <cauchy - gn, cauchy>) and the pass over J that is on the stream
-  // behind it returns at once (k8_skip); the host reads the same word and forms the value, and a retry from the cached
+  // behind it returns at once (StepLaunch::skip); the host reads the same word and forms the value, and a retry from the cached
   // vectors (dlg_step) takes the word's 1 along (DlgSlot::ident_ok).  DOGLEG_AMD_EI_JPASS=1: always the pass over J.
   // The factor allows it where its pivot ratio is at most IDENT_RATIO_MAX AND the estimate of the value's relative error,
   // eps (max L_ii)^2 |gn|^2 / -<Jt x, gn>, is at most IDENT_ERR_MAX.  The error is gn' r with r the residual of the solve:
@@ -122,11 +120,11 @@ struct dlg_backend
   static constexpr int IDENT_SLOT = 3, GB_SLOT = 13;     // free slots of dlg_take_step's scalar block
   static constexpr double IDENT_RATIO_MAX = 212.0;
   static constexpr double IDENT_ERR_MAX = 1e-12;
-  bool ident_launched = false, ident_predict = false; const double* k8_skip = nullptr;      // ident_predict: the last step's pass over J was let go by the device
+  bool ident_predict = false;      // the last step's pass over J was let go by the device: the NEXT dlg_take_step may not launch it at all
   bool ei_from_system = false; double pivot_ratio = NAN;   // dlg_backend_ei_source: how the last value handed out was formed
   int ei_flip = 0, ei_count = 0;                           // DOGLEG_AMD_DEBUG_EI_FLIP (test hook)
   bool tail_ident = false, tail_no_fold = false; double tail_nJs = 0.0;     // (tail_no_fold: the K8 on the stream carries no p_new)
-  bool p_side_pending = false;          // p_new of a step behind the decision point is on its way on the copy stream (ev_copy)
+  bool p_side_pending = false;          // p_new of a step behind the decision point is on its way on the copy stream (ev_copy): until dlg_step_tail / the next call that writes p
   // Work the CALLER has for the stream that does not depend on a step's scalars (dlg_backend_set_between): enqueued from
   // inside dlg_take_step / dlg_step, between the step's last launch and the host's wait for it -- the device model's
   // kernels for the trial point, the first pass over the next point's J (dlg_point_eval_early).  The host's turn-round
@@ -211,7 +209,7 @@ struct dlg_backend
 
   // optional per-phase timing with HIP events on b->stream (dlg_backend_set_profiling)
   bool profiling = false;
-  hipEvent_t attach_stop = nullptr; bool stop_attached = false, ext_events = true;      // DLG_LAUNCH_LAST
+  bool ext_events = true;     // events may ride on launches (DLG_LAUNCH_TIMED, DLG_LAUNCH_LAST)
   int prof_every = 1; unsigned prof_tick[DLG_PROF_COUNT] = {};      // every n-th occurrence of a timed phase carries events
   unsigned prof_mask = 0;     // the phases that are timed (bit = DLG_PROF_*)
   struct ProfPair { hipEvent_t a, b; int id; bool cond; bool cont = false; };
@@ -255,11 +253,27 @@ bool dlg_prof_pair(dlg_backend* b, int id, hipEvent_t* e0, hipEvent_t* e1);
   do { hipEvent_t dlg_e0 = nullptr, dlg_e1 = nullptr; \
        if(dlg_prof_pair(b_, id_, &dlg_e0, &dlg_e1)) hipExtLaunchKernelGGL(kernel, grid, block, shm, st, dlg_e0, dlg_e1, 0, __VA_ARGS__); \
        else hipLaunchKernelGGL(kernel, grid, block, shm, st, __VA_ARGS__); } while(0)
-// The event the host is going to wait for, attached to the last kernel of what it waits for (attach_stop set by the
-// caller around the launch; stop_attached: the launch took it): no record behind the kernel.
-#define DLG_LAUNCH_LAST(b_, kernel, grid, block, shm, st, ...) \
-  do { if((b_)->attach_stop) { hipExtLaunchKernelGGL(kernel, grid, block, shm, st, (hipEvent_t)nullptr, (b_)->attach_stop, 0, __VA_ARGS__); (b_)->stop_attached = true; } \
+// The event the host is going to wait for (ev_, or null: a plain launch), attached to the last kernel of what it waits
+// for: no record behind the kernel.
+#define DLG_LAUNCH_LAST(ev_, kernel, grid, block, shm, st, ...) \
+  do { hipEvent_t dlg_ev = (ev_); \
+       if(dlg_ev) hipExtLaunchKernelGGL(kernel, grid, block, shm, st, (hipEvent_t)nullptr, dlg_ev, 0, __VA_ARGS__); \
        else hipLaunchKernelGGL(kernel, grid, block, shm, st, __VA_ARGS__); } while(0)
+// What a step function (step.hip) asks ONE launch to carry beyond its arguments, and what the launcher did about it.  A
+// default-constructed value is a plain launch.  The launcher decides: it takes the event and the scalars along only where
+// its partial sums found page-locked room, and says so -- the caller reads the answer here, nothing travels on dlg_backend.
+struct StepLaunch
+{
+  hipEvent_t stop = nullptr;      // the event the host is going to wait for rides on the launch (DLG_LAUNCH_LAST)
+  int nscal = 0;                  // the launch copies d_scal[0 .. nscal) to the page-locked h_scal (it is the last one of the step)
+  const double* p_src = nullptr; double* p_dst = nullptr;   // ... and p_new to a page-locked destination (its device address), a slice per workgroup
+  const double* skip = nullptr;   // device word; not 0: the pass over J returns at once (the step kernel's verdict, IDENT_SLOT)
+  bool tail = false;              // K8 behind the decision point: partial sums to h_tail, dlg_step_tail adds them
+  bool k_host = false;            // k_interpolate's k straight into the page-locked scalars (nobody fetches device scalars behind this step)
+  // filled in by the launcher
+  bool attached = false, scal_copied = false, p_copied = false;
+  bool ident = false;             // k_take_step: the step kernel was asked for its verdict on the value from the solved system
+};
 
 // rows of the measurement vector owned by this rank
 static inline int dlg_mloc(const dlg_backend* b) { return b->mloc; }
@@ -281,6 +295,11 @@ static inline void dlg_fork_gate(dlg_backend* b, int* gate, int epoch)
 
 // fetch the first n scalars of d_scal to the host (synchronises the stream)
 int dlg_fetch_scalars(dlg_backend* b, int n);
+// between backend.hip and step.hip: a valid backend and slot; the doubles of a slot's J; what step_prepare enqueued ahead
+// for a step that is not going to be taken is dropped (every entry point that works on other state calls it first)
+int dlg_check_slot(dlg_backend* b, int s);
+size_t dlg_j_doubles(const dlg_backend* b);
+int dlg_step_unprepare(dlg_backend* b);
 
 // what a kernel of a one-launch region needs to report a wait that gave up
 struct DlgHandoff { int* status; int spins; int skew; };
@@ -304,11 +323,11 @@ int dlg_check_handoff(dlg_backend* b);
 // --------------------------------------------------------- kernels_vec.hip --
 // out[0] = sum x[i]^2 ; out[1] = max |x[i]|   (deterministic two-stage)
 int k_norm2_absmax(dlg_backend* b, const double* x, int n, double* out2);
-// ... of two vectors behind one launch
+// ... of two vectors behind one launch (*on_host: it was one launch, the host adds all four; `stop` then rode on it)
 int k_norm2_absmax_pair(dlg_backend* b, const double* x1, int n1, double* out1, const double* x2, int n2, double* out2,
-                        bool* on_host = nullptr);
+                        bool* on_host = nullptr, hipEvent_t stop = nullptr);
 // out[0] = <x,y>
-int k_inner(dlg_backend* b, const double* x, const double* y, int n, double* out);
+int k_inner(dlg_backend* b, const double* x, const double* y, int n, double* out, StepLaunch& L);
 // Cauchy finish: g2 = |g|^2 (host), Jg2 = *Jg2_dev; k = -g2/Jg2;
 // cauchy = k*g ; out[0] = k*k*g2
 int k_cauchy_finish(dlg_backend* b, const double* g, double g2, const double* Jg2_dev, double* cauchy,
@@ -319,14 +338,14 @@ int k_scaled_step(dlg_backend* b, const double* v, double s, const double* p, do
 // interpolation (dogleg.c:964-987): out = {norm2_step, k, max|step|}
 int k_interpolate(dlg_backend* b, const double* a, const double* bb, double norm2a,
                   double trustregion, const double* p, double* step, double* p_new, int n,
-                  double* out3);
+                  double* out3, const StepLaunch& L);
 // gn = -u ; out[0] = norm2(gn)
 int k_negate_norm2(dlg_backend* b, double* v, int n, double* out);
 // step chosen on the device (dogleg.c:1192-1256): out_n2_max[0] = |step|^2, [2] = max|step|; out3 = {kind, k, |gn|^2}
 int k_negate_interp1(dlg_backend* b, double* gn, const double* cauchy, int n, double* gnpart, int* nb, const double* mm = nullptr, int nmm = 0, long mm_stride = 2);
 int k_take_step(dlg_backend* b, const double* cauchy, const double* gn, const double* gnpart, int nbg,
                 const double* n2c_dev, double trustregion, const double* p, double* step, double* p_new, int n,
-                double* out_n2_max, double* out3, const double* Jtx, double* out_inner,
+                double* out_n2_max, double* out3, const double* Jtx, double* out_inner, StepLaunch& L,
                 double* out_gb = nullptr, double* ident_out = nullptr, bool have_mm = false, bool ident_gn = false, double ratio_max = 0.0,
                 double g2 = 0.0, double err_max = 0.0);
 // generic deterministic final reduction of `np` partials (sum) into out[0]
@@ -353,7 +372,7 @@ void dense_launch_potrf_diag_trsm(hipStream_t st, double* A, int lda, int kb, in
                                   int* flag, int epoch, const DlgHandoff& ho);
 void dense_destroy(dlg_backend* b);
 int dense_eval(dlg_backend* b, int slot);                       // K1
-int dense_norm2_Jv(dlg_backend* b, int slot, const double* v, double* out_dev); // K3/K8
+int dense_norm2_Jv(dlg_backend* b, int slot, const double* v, double* out_dev, StepLaunch& L); // K3/K8
 int dense_factorize(dlg_backend* b, int slot, double lambda, int* ok);          // K4+K5
 bool dense_factor_ok(const dlg_backend* b);      // pivot flag of the last factorisation (after a sync)
 int dense_solve(dlg_backend* b, const double* rhs, double* out);                // K6 (no negate)
@@ -377,7 +396,7 @@ void sparse_spec_invalidate(dlg_backend* b, int s);
 bool sparse_spec_is(const dlg_backend* b, int s, const double* J);     // the second panel buffer holds slot s's assembly from the values at J
 // K3/K8; kind_if_factor_failed (device scalar holding the kind of step, or null): the pass is skipped when the
 // factorisation on the stream failed and the step is not the Cauchy step to the edge
-int sparse_norm2_Jv(dlg_backend* b, int slot, const double* v, double* out_dev, const double* kind_if_factor_failed = nullptr);
+int sparse_norm2_Jv(dlg_backend* b, int slot, const double* v, double* out_dev, const double* kind_if_factor_failed, StepLaunch& L);
 int sparse_factorize(dlg_backend* b, int slot, double lambda, int* ok);          // K4+K5 (b->factor_ahead: K5 up to the leaf level only, sparse_factorize_rest owes the rest)
 int sparse_factorize_rest(dlg_backend* b, bool* was_pending);
 bool sparse_factor_pending(const dlg_backend* b);                     // the levels above the leaves of a factorisation enqueued ahead

@@ -902,26 +902,26 @@ int dense_eval(dlg_backend* b, int s)
   return DLG_OK;
 }
 
-int dense_norm2_Jv(dlg_backend* b, int s, const double* v, double* out_dev)
+int dense_norm2_Jv(dlg_backend* b, int s, const double* v, double* out_dev, StepLaunch& L)
 {
   DlgSlot& S = b->slot[s];
   const int M = dlg_mloc(b);
   int g = dlg_cdiv(M, 4); if(g > 2048) g = 2048; if(g < 1) g = 1;
   // K8 behind the decision point (dlg_take_step, dlg_backend_set_defer_tail): the partial sums go to page-locked memory,
   // dlg_step_tail adds them; p_new rides along
-  if(b->tail_mode)
+  if(L.tail)
     if(double* hp = dlg_tail_partials(b, g))
     {
       hipLaunchKernelGGL(k_norm2_Jv_part, dim3(g), dim3(TPB), 0, b->stream, S.Jin(), v, M, b->N, hp,
-                         b->fold_p_src, b->fold_p_dst, (int)b->N, b->k8_skip);
+                         L.p_src, L.p_dst, (int)b->N, L.skip);
       DLG_LAUNCH_CHECK();
-      b->p_copied = b->fold_p_src != nullptr;
+      L.p_copied = L.p_src != nullptr;
       return DLG_OK;
     }
   DLG_CHECK(dlg_ensure_partials(b, 8192));
   double* part = b->d_part + 5120;          // behind the regions of the vector reductions (kernels_vec.hip)
   hipLaunchKernelGGL(k_norm2_Jv_part, dim3(g), dim3(TPB), 0, b->stream, S.Jin(), v, M, b->N, part,
-                     (const double*)nullptr, (double*)nullptr, 0, b->k8_skip);
+                     (const double*)nullptr, (double*)nullptr, 0, L.skip);
   DLG_LAUNCH_CHECK();
   return k_reduce_sum(b, part, g, out_dev);
 }

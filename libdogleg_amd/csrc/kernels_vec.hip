@@ -262,7 +262,7 @@ __global__ void __launch_bounds__(TPB) k_part_take_step(const double* __restrict
   __shared__ double sh[16];
   __shared__ double s_l2, s_negc, s_n2g, s_skip, s_ratio;
   __shared__ double s_gn[MAXB];
-  // The expected improvement from the solved system (K8 without its pass over J, backend.hip: ident_norm2_Jstep): allowed
+  // The expected improvement from the solved system (K8 without its pass over J, step.hip: ident_norm2_Jstep): allowed
   // by the host (one rank) and by the factor itself, from the pairs of pivots the backward solve left per supernode
   // (mmpart: their partial minima / maxima, k_part_negate_interp1): the ratio of its largest to its smallest pivot, and
   // the estimate of the value's relative error below (dlg_backend::IDENT_ERR_MAX).
@@ -508,7 +508,7 @@ int k_norm2_absmax(dlg_backend* b, const double* x, int n, double* out2)
 // (|x1|^2, max|x1|) -> out1[0..1] and (|x2|^2, max|x2|) -> out2[0..1] behind one launch where the second
 // stages run on the host (dlg_host_partials); else two calls of k_norm2_absmax
 int k_norm2_absmax_pair(dlg_backend* b, const double* x1, int n1, double* out1, const double* x2, int n2, double* out2,
-                        bool* on_host)
+                        bool* on_host, hipEvent_t stop)
 {
   if(on_host) *on_host = false;
   const int g1 = grid_for(n1), g2 = grid_for(n2);
@@ -518,7 +518,7 @@ int k_norm2_absmax_pair(dlg_backend* b, const double* x1, int n1, double* out1, 
     double* hp2 = hp1 ? dlg_host_partials(b, out2, g2, 1, 1, 1) : nullptr;
     if(hp1 && hp2)
     {
-      DLG_LAUNCH_LAST(b, k_part_norm2_absmax2, dim3(g1 + g2), dim3(TPB), 0, b->stream, x1, n1, hp1, g1, x2, n2, hp2);
+      DLG_LAUNCH_LAST(stop, k_part_norm2_absmax2, dim3(g1 + g2), dim3(TPB), 0, b->stream, x1, n1, hp1, g1, x2, n2, hp2);
       DLG_LAUNCH_CHECK();
       if(on_host) *on_host = true;             // all four scalars are summed on the host (dlg_resolve_pending)
       return DLG_OK;
@@ -528,13 +528,17 @@ int k_norm2_absmax_pair(dlg_backend* b, const double* x1, int n1, double* out1, 
   DLG_CHECK(k_norm2_absmax(b, x1, n1, out1));
   return k_norm2_absmax(b, x2, n2, out2);
 }
-int k_inner(dlg_backend* b, const double* x, const double* y, int n, double* out)
+int k_inner(dlg_backend* b, const double* x, const double* y, int n, double* out, StepLaunch& L)
 {
   const int g = grid_for(n);
   DLG_CHECK(dlg_ensure_partials(b, 4*MAXB));
   if(double* hp = dlg_host_partials(b, out, g, 1, 0, 1))
-  { DLG_LAUNCH_LAST(b, k_part_inner, dim3(g), dim3(TPB), 0, b->stream, x, y, n, hp); DLG_LAUNCH_CHECK(); return DLG_OK; }      // (attach_stop: the launch the host waits for, dlg_step)
-  b->attach_stop = nullptr;
+  {
+    DLG_LAUNCH_LAST(L.stop, k_part_inner, dim3(g), dim3(TPB), 0, b->stream, x, y, n, hp);      // (L.stop: the launch the host waits for, dlg_step)
+    DLG_LAUNCH_CHECK();
+    L.attached = L.stop != nullptr;
+    return DLG_OK;
+  }
   hipLaunchKernelGGL(k_part_inner, dim3(g), dim3(TPB), 0, b->stream, x, y, n, b->d_part);
   hipLaunchKernelGGL(k_final, dim3(1), dim3(TPB), 0, b->stream, b->d_part, g, 1, 0, out, 1);
   DLG_LAUNCH_CHECK();
@@ -567,7 +571,7 @@ int k_scaled_step(dlg_backend* b, const double* v, double s, const double* p, do
 }
 int k_interpolate(dlg_backend* b, const double* a, const double* bb, double norm2a,
                   double trustregion, const double* p, double* step, double* p_new, int n,
-                  double* out3)
+                  double* out3, const StepLaunch& L)
 {
   const int g = grid_for(n);
   DLG_CHECK(dlg_ensure_partials(b, 4*MAXB));
@@ -576,9 +580,9 @@ int k_interpolate(dlg_backend* b, const double* a, const double* bb, double norm
   hipLaunchKernelGGL(k_part_interp1, dim3(g), dim3(TPB), 0, b->stream, a, bb, n, b->d_part);
   double* part2 = b->d_part + 2*g;
   double* hp = dlg_host_partials(b, out3, g, 1, 1, 2);
-  // (kout_host: the caller fetches no device scalars behind this step -- dlg_step with K8 behind the decision point --: k goes
+  // (L.k_host: the caller fetches no device scalars behind this step -- dlg_step with K8 behind the decision point --: k goes
   // straight to its place in the page-locked block)
-  double* kout = (b->kout_host && hp && out3 >= b->d_scal && out3 + 3 <= b->d_scal + dlg_backend::NSCAL) ? b->h_scal + ((out3 + 1) - b->d_scal) : out3 + 1;
+  double* kout = (L.k_host && hp && out3 >= b->d_scal && out3 + 3 <= b->d_scal + dlg_backend::NSCAL) ? b->h_scal + ((out3 + 1) - b->d_scal) : out3 + 1;
   hipLaunchKernelGGL(k_part_interp2, dim3(g), dim3(TPB), 0, b->stream, a, bb, b->d_part, g, norm2a,
                      trustregion*trustregion, p, step, p_new, n, hp ? hp : part2, kout);
   if(!hp) hipLaunchKernelGGL(k_final, dim3(1), dim3(TPB), 0, b->stream, part2, g, 1, 1, out3, 2);
@@ -607,7 +611,7 @@ int k_negate_interp1(dlg_backend* b, double* gn, const double* cauchy, int n, do
 // err_max: the largest estimated relative error of the value from the solved system trusted (k_part_take_step)
 int k_take_step(dlg_backend* b, const double* cauchy, const double* gn, const double* gnpart, int nbg,
                 const double* n2c_dev, double trustregion, const double* p, double* step, double* p_new, int n,
-                double* out_n2_max, double* out3, const double* Jtx, double* out_inner,
+                double* out_n2_max, double* out3, const double* Jtx, double* out_inner, StepLaunch& L,
                 double* out_gb, double* ident_out, bool have_mm, bool ident_gn, double ratio_max, double g2, double err_max)
 {
   const int g = grid_for(n);
@@ -621,15 +625,14 @@ int k_take_step(dlg_backend* b, const double* cauchy, const double* gn, const do
   // (<Jt x, gn> only where the host adds the partial sums: the identity is a single-rank matter)
   double* hb = (hg && out_gb) ? dlg_host_partials(b, out_gb, g, 1, 0, 1) : nullptr;
   if(!hb) ident_out = nullptr;
-  // (fold_scal_k7: this is the launch the host waits for -- it takes the scalars along and carries the event)
-  const bool fold = hp && hg && b->fold_scal_k7 > 0 && b->fold_scal_k7 <= TPB && b->h_scal && out3 >= b->d_scal && out3 + 3 <= b->d_scal + b->fold_scal_k7;
-  if(!fold) b->attach_stop = nullptr;
-  DLG_LAUNCH_LAST(b, k_part_take_step, dim3(g), dim3(TPB), 0, b->stream, cauchy, gn, (const double*)b->d_part, g, gnpart, nbg,
+  // (L.nscal: this is the launch the host waits for -- it takes the scalars along and carries the event)
+  const bool fold = hp && hg && L.nscal > 0 && L.nscal <= TPB && b->h_scal && out3 >= b->d_scal && out3 + 3 <= b->d_scal + L.nscal;
+  DLG_LAUNCH_LAST(fold ? L.stop : (hipEvent_t)nullptr, k_part_take_step, dim3(g), dim3(TPB), 0, b->stream, cauchy, gn, (const double*)b->d_part, g, gnpart, nbg,
                   n2c_dev, trustregion, p, step, p_new, n, hp ? hp : part2, out3, Jtx, gp,
-                  fold ? (const double*)b->d_scal : (const double*)nullptr, b->h_scal, fold ? b->fold_scal_k7 : 0,
+                  fold ? (const double*)b->d_scal : (const double*)nullptr, b->h_scal, fold ? L.nscal : 0,
                   hb, have_mm ? gnpart + 2*MAXB : (const double*)nullptr, have_mm ? nbg : 0, ident_gn ? 1 : 0, ratio_max, g2, err_max, ident_out);
-  b->ident_launched = ident_out != nullptr;
-  if(fold) b->scal_copied = true;
+  L.ident = ident_out != nullptr;
+  L.scal_copied = fold; L.attached = fold && L.stop;
   if(!hp) hipLaunchKernelGGL(k_final, dim3(1), dim3(TPB), 0, b->stream, part2, g, 1, 1, out_n2_max, 2);
   if(!hg) hipLaunchKernelGGL(k_final, dim3(1), dim3(TPB), 0, b->stream, gp, g, 1, 0, out_inner, 1);
   DLG_LAUNCH_CHECK();

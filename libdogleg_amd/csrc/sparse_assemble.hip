@@ -1129,7 +1129,7 @@ int sparse_eval(dlg_backend* b, int s)
 }
 
 // K3 / K8
-int sparse_norm2_Jv(dlg_backend* b, int s, const double* v, double* out_dev, const double* kind_if_factor_failed)
+int sparse_norm2_Jv(dlg_backend* b, int s, const double* v, double* out_dev, const double* kind_if_factor_failed, StepLaunch& L)
 {
   SparseSym* Y = b->sym;
   if(!Y) { dlg_set_error("dlg_sparse_set_pattern must be called first"); return DLG_ERR_STATE; }
@@ -1138,19 +1138,18 @@ int sparse_norm2_Jv(dlg_backend* b, int s, const double* v, double* out_dev, con
   if(g == 0) { DLG_HIP(hipMemsetAsync(out_dev, 0, sizeof(double), b->stream)); return DLG_OK; }
   // K8 inside dlg_take_step: only the host reads the sum -- the workgroups' partial sums go straight to
   // pinned host memory and are added there behind the step's one synchronisation (no second-stage launch)
-  // (tail_mode without a kind: K8 of a step from cached vectors, dlg_step -- no factorisation of this call to look at)
-  if(kind_if_factor_failed || b->tail_mode)
-    if(double* hp = b->tail_mode ? dlg_tail_partials(b, g) : dlg_host_partials(b, out_dev, g, 1, 0, 1))
+  // (L.tail without a kind: K8 of a step from cached vectors, dlg_step -- no factorisation of this call to look at)
+  if(kind_if_factor_failed || L.tail)
+    if(double* hp = L.tail ? dlg_tail_partials(b, g) : dlg_host_partials(b, out_dev, g, 1, 0, 1))
     {
-      const bool fold = b->fold_scal > 0 && b->fold_scal <= TPB && b->h_scal;
-      if(!fold) b->attach_stop = nullptr;
-      DLG_LAUNCH_LAST(b, k_norm2_Jv, dim3(g), dim3(TPB), 0, b->stream, Y->nv_chunk, Y->Jp, Y->Ji, S.Jin(), v, hp,
+      const bool fold = L.nscal > 0 && L.nscal <= TPB && b->h_scal;      // (the step's last launch: the scalars, the event and p_new go with it)
+      DLG_LAUNCH_LAST(fold ? L.stop : (hipEvent_t)nullptr, k_norm2_Jv, dim3(g), dim3(TPB), 0, b->stream, Y->nv_chunk, Y->Jp, Y->Ji, S.Jin(), v, hp,
                       kind_if_factor_failed ? (const int*)Y->d_info : (const int*)nullptr, kind_if_factor_failed, (int)Y->nnz_loc,
-                      fold ? (const double*)b->d_scal : (const double*)nullptr, b->h_scal, (int)b->fold_scal,
-                      (fold || b->tail_mode) ? b->fold_p_src : (const double*)nullptr, b->fold_p_dst, (int)b->N, b->k8_skip);
+                      fold ? (const double*)b->d_scal : (const double*)nullptr, b->h_scal, L.nscal,
+                      (fold || L.tail) ? L.p_src : (const double*)nullptr, L.p_dst, (int)b->N, L.skip);
       DLG_LAUNCH_CHECK();
-      if(fold) b->scal_copied = true;
-      if(fold || b->tail_mode) b->p_copied = b->fold_p_src != nullptr;
+      L.scal_copied = fold; L.attached = fold && L.stop;
+      L.p_copied = (fold || L.tail) && L.p_src;
       return DLG_OK;
     }
   DLG_CHECK(dlg_ensure_partials(b, 5120 + (size_t)g));
@@ -1189,7 +1188,7 @@ int sparse_assemble_finish(dlg_backend* b)
   return DLG_OK;
 }
 // ---- fin on the side ------------------------------------------------------------------------------------------
-// An evaluation whose point is factorised at once (backend.hip, step_prepare) had, between the assembly kernel and the
+// An evaluation whose point is factorised at once (step.hip, step_prepare) had, between the assembly kernel and the
 // leaf level of the factorisation, on ONE stream: the Jt*x record sums, the norm kernel the host waits for, a gap behind
 // it (a kernel somebody listens to holds the next dispatch back), and the two partial-sum stages of JtJ -- 35 us of
 // small kernels of which the leaf level needs only Jt*x (for the augmented row).  The stages write blocks of the

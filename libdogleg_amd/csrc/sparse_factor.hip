@@ -1269,7 +1269,7 @@ int sparse_factor_levels(dlg_backend* b, int part)
   SparseSym* Y = b->sym;
   const SymHost& H = Y->H;
   hipStream_t st = b->stream;
-  // A factorisation enqueued ahead of the caller's decision (backend.hip, step_prepare) comes in two parts where its
+  // A factorisation enqueued ahead of the caller's decision (step.hip, step_prepare) comes in two parts where its
   // first launch is a level of its own: part 1 = that launch (the leaf level), part 2 = everything behind it.  Same
   // launches in the same order on the same stream as part 0.
   const bool split = Y->top.level0 > 0 && H.nlevels >= 2 && H.part_nranks <= 1 && H.fw_lvl_ptr[1] > H.fw_lvl_ptr[0];

@@ -635,7 +635,7 @@ const double* sparse_pivot_minmax(const dlg_backend* b, int* n)
   *n = b->sym ? b->sym->n_diag_mm : 0;
   return (b->sym && b->sym->n_diag_mm > 0) ? b->sym->diag_mm : nullptr;
 }
-// A factorisation enqueued ahead of the caller's decision (backend.hip, step_prepare) takes the place of the held
+// A factorisation enqueued ahead of the caller's decision (step.hip, step_prepare) takes the place of the held
 // one: the held panels stay in the other buffer (sparse_assemble swaps, the buffer is cleared only behind the
 // next step) and come back if the caller turns to the held factor after all (a rejected trial point).
 void sparse_hold_factor(dlg_backend* b)
@@ -661,7 +661,7 @@ int sparse_restore_factor(dlg_backend* b, bool* restored, bool rearm)
   return DLG_OK;
 }
 bool sparse_factor_ok(const dlg_backend* b) { return *b->sym->h_info == 0x7fffffff; }
-// The factorisation and the solve enqueued ahead of the caller's decision (backend.hip, step_prepare) are not going to
+// The factorisation and the solve enqueued ahead of the caller's decision (step.hip, step_prepare) are not going to
 // be used -- the trial point was rejected: their launches that have not started yet return behind their first
 // barrier, exactly as they do behind a failed pivot (k_factor_level, k_update_*, k_solve_bwd_level look at the
 // pivot flag; the one-launch regions still raise their flags, nothing waits for a workgroup that gave up).  The

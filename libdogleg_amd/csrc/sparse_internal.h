@@ -126,7 +126,7 @@ struct SparseSym
   // intact_J, assembled with intact_lambda) are what the next attempt of the lambda loop factors (sparse_assemble)
   double* intact_Lx = nullptr; const double* intact_J = nullptr; int intact_slot = -1; double intact_lambda = 0.0;
   const double* fac_J = nullptr; int fac_slot = -1;      // the inputs of the last sparse_factorize
-  bool fac_pending = false;                   // sparse_factor_levels(b, 1) launched the leaf level only: part 2 is owed (backend.hip, step_prepare)
+  bool fac_pending = false;                   // sparse_factor_levels(b, 1) launched the leaf level only: part 2 is owed (step.hip, step_prepare)
   size_t nnz_loc = 0;
   // sharded rows: positions of the structural non-zeros of JtJ in Lx (what the all-reduce carries)
   uint32_t* ar_idx = nullptr; double* ar_buf = nullptr; size_t ar_n = 0;

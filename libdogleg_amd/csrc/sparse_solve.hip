@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(BWD_NT, BD_ONLY ? 4 : 1) k_solve_bwd_level(con
   __shared__ int s_skip;
   // (mm: smallest / largest diagonal entry of this supernode's part of L, a pair per WAVE that holds diagonal entries
   // ([workgroup][8][2]; no LDS, no barrier: the waves store their own) -- the step kernel turns them into the pivot ratio
-  // that decides whether the expected improvement may come from the solved system, backend.hip)
+  // that decides whether the expected improvement may come from the solved system, step.hip)
   double dmin = 1e300, dmax = 0.0;
   if(threadIdx.x == 0) s_skip = *info != 0x7fffffff;      // the factor is that of a failed factorisation: its solution is never used
   constexpr int NW = BWD_NT/64;
