@@ -473,6 +473,75 @@ int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned
  * Returns the number of entries written (at most n, at most 5). */
 int dogleg_amd_batch_uncertainty_last_stats(double* out, int n);
 
+/* ---- extension (not in the reference): the Jacobian of a DEVICE callback checked against central differences, on the
+ * device.  dogleg_testGradient* above take host callbacks, one variable a call.  Here the whole Jacobian is compared, and
+ * on a sparse problem the variables that share no measurement row are perturbed together (Curtis, Powell, Reid): a
+ * first-fit colouring of the variables over the pattern gives the groups, 15 of them on a problem with 15 entries a row
+ * whatever Nstate is, and the check costs 2 * ncolours evaluations of the callback.
+ *
+ * The arithmetic is that of dogleg_testGradient (reference dogleg.c:352-522): for a group G, x0, J0 at
+ * p0 - delta/2 sum_{v in G} e_v and x1, J1 at p0 + delta/2 sum_{v in G} e_v; for a declared entry (row r, variable v in G)
+ * observed = (x1[r] - x0[r]) / delta, reported = (J0 + J1) / 2 at that entry, err = |reported - observed|, relative error
+ * err / ((|reported| + |observed|) / 2), 0 / 0 = 0.  An entry is bad when err > atol + rtol (|reported| + |observed|) / 2
+ * or when one of the four values is not finite.  delta <= 0 selects the reference's 1e-6; rtol and atol are the caller's
+ * (negative or NaN: refused).
+ *
+ * A row with NO declared entry in G must not move: where x1[r] != x0[r] the pair (row, group) is counted in noutside and
+ * reported in `bad` with var = -1 - (index of the group), reported = 0 and its observed.
+ *
+ * All per-group work is enqueued on one stream (a kernel that perturbs p, the callback twice, the compare kernels), with
+ * one synchronisation and one download at the end.  Buffers live for the call only. */
+typedef struct
+{
+  long long nchecked;     /* Jacobian entries compared                                                   */
+  long long nbad;         /* err > atol + rtol (|rep| + |obs|) / 2, or a non-finite x / J involved        */
+  long long nnonfinite;   /* of those: non-finite                                                        */
+  long long noutside;     /* sparse: (row, colour) pairs with NO declared entry whose x moved (obs != 0) */
+  double max_error, max_error_relative;   /* over the finite entries; 0 / 0 = 0 as in the reference       */
+  int worst_var, worst_meas; double worst_reported, worst_observed;   /* an entry attaining max_error     */
+  int ncolours, evaluations;              /* callback invocations = 2 ncolours                            */
+} dogleg_amd_jacobian_report_t;
+typedef struct { int problem, var, meas; double reported, observed; } dogleg_amd_jacobian_entry_t;
+#define DOGLEG_AMD_JACOBIAN_ONE_AT_A_TIME 1   /* flags: every variable its own group on a sparse problem too */
+
+/* the groups: colour[v] of the first-fit colouring in natural variable order (v takes the smallest colour that no
+ * variable before it sharing a row with it holds; a variable in no row gets 0).  Host only.  Returns the number of
+ * colours, or -1 (message) on a bad pattern: see dogleg_optimize_device2 for the pattern's contract. */
+int dogleg_amd_jacobian_colouring(unsigned Nstate, unsigned Nmeas, const int* Jt_colptr, const int* Jt_rowidx,
+                                  int* colour /* [Nstate] out */);
+/* p0 on the host.  The pattern as dogleg_optimize_device2 takes it; NJnnz == 0 and NULL pattern pointers: dense, every
+ * variable its own group.  var_error[Nstate] (or NULL): the largest finite err per variable.  bad[max_bad] (or NULL)
+ * receives min(nbad + noutside, max_bad) records, sorted by (meas, var); which survive beyond max_bad is unspecified.
+ * worst_var is -1 when no finite entry was compared.  Returns the number of records written to bad, or -1 (message;
+ * outputs untouched when the arguments are refused: a NULL p0 / f / report, zero sizes, a pattern that disagrees with
+ * NJnnz or whose row indices do not ascend within a column, a negative or NaN rtol / atol, a set communicator). */
+int dogleg_amd_check_jacobian_device(const double* p0, unsigned Nstate, unsigned Nmeas, unsigned NJnnz,
+                                     const int* Jt_colptr, const int* Jt_rowidx,
+                                     dogleg_callback_device_t* f, void* cookie,
+                                     double delta, double rtol, double atol, int flags,
+                                     dogleg_amd_jacobian_report_t* report,
+                                     double* var_error /* [Nstate] max err per variable, or NULL */,
+                                     dogleg_amd_jacobian_entry_t* bad, int max_bad);
+/* the same for a batch callback: column v of all B problems in one pair of evaluations (2 Nstate invocations whatever B
+ * is, every live byte 1).  reports[b] is problem b's and does not depend on B or on its neighbours; bad records carry the
+ * problem, sorted by (problem, meas, var); *nbad_total (or NULL) receives the number written.  0 / -1; refused as above,
+ * and Nstate above DOGLEG_AMD_BATCH_MAX_NSTATE. */
+int dogleg_amd_check_jacobian_device_batch(const double* p0 /* [B][Nstate] */, unsigned B, unsigned Nstate, unsigned Nmeas,
+                                           dogleg_callback_device_batch_t* f, void* cookie,
+                                           double delta, double rtol, double atol,
+                                           dogleg_amd_jacobian_report_t* reports /* [B] */,
+                                           dogleg_amd_jacobian_entry_t* bad, int max_bad, long long* nbad_total);
+/* dogleg_testGradient for a device callback: the same table on stdout for variable `var` (two evaluations, one compare
+ * launch, one download; the print on the host). */
+void dogleg_amd_testGradient_device(unsigned var, const double* p0, unsigned Nstate, unsigned Nmeas, unsigned NJnnz,
+                                    const int* Jt_colptr, const int* Jt_rowidx, dogleg_callback_device_t* f, void* cookie);
+/* measurement: the calling thread's last check: out[0] = callback invocations, out[1] = kernel launches of the library,
+ * out[2] = stream synchronisations, out[3] = copies on the stream; counted where they are issued; and, if
+ * DOGLEG_AMD_CHECK_TIMING=1 was set for a dogleg_amd_check_jacobian_device call (three events a group on the stream),
+ * out[4] = ms in the callback's kernels, out[5] = ms in the library's compare kernels.  Returns the number of entries
+ * written (at most n, at most 6). */
+int dogleg_amd_check_jacobian_last_stats(double* out, int n);  /* callback calls, library launches, syncs, copies */
+
 #ifdef __cplusplus
 }
 #endif

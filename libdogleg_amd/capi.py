@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult,
+from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, JacobianReport, JacobianEntry,
                           CB_SPARSE, CB_DENSE, CB_PRODUCTS, dptr, iptr)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,6 +64,8 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_query_covariance",
     "dogleg_amd_optimize_dense_batch", "dogleg_amd_batch_last_stats",
     "dogleg_amd_dense_batch_uncertainty", "dogleg_amd_batch_uncertainty_last_stats",
+    "dogleg_amd_jacobian_colouring", "dogleg_amd_check_jacobian_device", "dogleg_amd_check_jacobian_device_batch",
+    "dogleg_amd_testGradient_device", "dogleg_amd_check_jacobian_last_stats",
 ]
 
 _lib = None
@@ -217,6 +219,16 @@ def lib():
     if hasattr(L, "dogleg_amd_dense_batch_uncertainty"):
         L.dogleg_amd_dense_batch_uncertainty.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, V, V, D, D, D, D, D, C.c_int, I]
         L.dogleg_amd_batch_uncertainty_last_stats.argtypes = [D, C.c_int]
+    if hasattr(L, "dogleg_amd_check_jacobian_device"):
+        JR, JE = C.POINTER(JacobianReport), C.POINTER(JacobianEntry)
+        L.dogleg_amd_jacobian_colouring.argtypes = [C.c_uint, C.c_uint, I, I, I]
+        L.dogleg_amd_check_jacobian_device.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, I, I, V, V, C.c_double, C.c_double,
+                                                       C.c_double, C.c_int, JR, D, JE, C.c_int]
+        L.dogleg_amd_check_jacobian_device_batch.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, V, V, C.c_double, C.c_double,
+                                                             C.c_double, JR, JE, C.c_int, C.POINTER(C.c_longlong)]
+        L.dogleg_amd_testGradient_device.argtypes = [C.c_uint, D, C.c_uint, C.c_uint, C.c_uint, I, I, V, V]
+        L.dogleg_amd_testGradient_device.restype = None
+        L.dogleg_amd_check_jacobian_last_stats.argtypes = [D, C.c_int]
     L.dogleg_amd_last_solve_timing.argtypes = [D, I]
     L.dlg_point_gather_device.argtypes = [V, C.c_int, V, V, I]
     L.dogleg_setMaxIterations.argtypes = [C.c_int]
@@ -331,6 +343,55 @@ def batch_uncertainty_last_stats():
     out = (C.c_double * 5)()
     lib().dogleg_amd_batch_uncertainty_last_stats(out, 5)
     return dict(launches=int(out[0]), syncs=int(out[1]), copies=int(out[2]), ms_callback=out[3], ms_library=out[4])
+
+
+def jacobian_colouring(N, M, Jp, Ji):
+    """dogleg_amd_jacobian_colouring (host only): (ncolours or -1, colour[N]) of the first-fit colouring of a Jt pattern"""
+    Jp = np.ascontiguousarray(Jp, dtype=np.int32)
+    Ji = np.ascontiguousarray(Ji, dtype=np.int32)
+    colour = np.full(N, -1, dtype=np.int32)
+    return lib().dogleg_amd_jacobian_colouring(N, M, iptr(Jp), iptr(Ji), iptr(colour)), colour
+
+
+def check_jacobian_device(p0, N, M, nnz, Jp, Ji, cb, cookie, delta=0.0, rtol=0.0, atol=0.0, flags=0, max_bad=64,
+                          want_var_error=True):
+    """dogleg_amd_check_jacobian_device.  nnz == 0: dense (Jp, Ji ignored).  cb: address of a dogleg_callback_device_t.
+    Returns dict(rc, report (the fields of dogleg_amd_jacobian_report_t), var_error (N,) or None, bad: list of
+    (problem, var, meas, reported, observed))."""
+    L = lib()
+    p0 = np.ascontiguousarray(p0, dtype=np.float64)
+    if nnz > 0:
+        Jp = np.ascontiguousarray(Jp, dtype=np.int32)
+        Ji = np.ascontiguousarray(Ji, dtype=np.int32)
+    rep = JacobianReport()
+    ve = np.zeros(N) if want_var_error else None
+    bad = (JacobianEntry * max(max_bad, 1))()
+    rc = L.dogleg_amd_check_jacobian_device(dptr(p0), N, M, nnz, iptr(Jp) if nnz > 0 else None, iptr(Ji) if nnz > 0 else None,
+                                            cb, cookie, delta, rtol, atol, flags, C.byref(rep),
+                                            dptr(ve) if want_var_error else None, bad, max_bad)
+    return dict(rc=rc, report=rep.asdict(), var_error=ve, bad=[bad[k].astuple() for k in range(max(rc, 0))])
+
+
+def check_jacobian_device_batch(p0s, N, M, cb, cookie, delta=0.0, rtol=0.0, atol=0.0, max_bad=64):
+    """dogleg_amd_check_jacobian_device_batch at the points p0s (B, N).  cb: address of a dogleg_callback_device_batch_t.
+    Returns dict(rc, reports: list of dicts, one per problem, bad: list of (problem, var, meas, reported, observed))."""
+    L = lib()
+    p = np.ascontiguousarray(p0s, dtype=np.float64).reshape(-1, N)
+    B = p.shape[0]
+    reps = (JacobianReport * max(B, 1))()
+    bad = (JacobianEntry * max(max_bad, 1))()
+    n = C.c_longlong(0)
+    rc = L.dogleg_amd_check_jacobian_device_batch(dptr(p), B, N, M, cb, cookie, delta, rtol, atol, reps, bad, max_bad, C.byref(n))
+    return dict(rc=rc, reports=[reps[b].asdict() for b in range(B)], bad=[bad[k].astuple() for k in range(n.value)])
+
+
+def check_jacobian_last_stats():
+    """{callbacks, launches, syncs, copies, ms_callback, ms_library} of the calling thread's last Jacobian check (the
+    times: DOGLEG_AMD_CHECK_TIMING=1, single problem)"""
+    out = (C.c_double * 6)()
+    lib().dogleg_amd_check_jacobian_last_stats(out, 6)
+    return dict(callbacks=int(out[0]), launches=int(out[1]), syncs=int(out[2]), copies=int(out[3]), ms_callback=out[4],
+                ms_library=out[5])
 
 
 SYM_STAT_NAMES = ["var_blocks", "supernodes", "levels", "nnz_JtJ_lower", "nnz_L", "panel_doubles",

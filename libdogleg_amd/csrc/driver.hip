@@ -24,6 +24,8 @@
 #include "../../include/dlg_backend.h"
 #include "../../include/dlg_trace.h"
 #include "dense_batch.h"
+#include "gradcheck.h"
+#include "gradcheck_plan.h"
 
 #define MSG(...) do { fprintf(stderr, "libdogleg_amd: " __VA_ARGS__); fputc('\n', stderr); } while(0)
 #define VERBOSE(c, ...) do { if((c)->pub.parameters->debug && !(c)->pub.parameters->debug_vnlog) MSG(__VA_ARGS__); } while(0)
@@ -1548,6 +1550,104 @@ int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned
   return dlg_dense_batch_uncertainty_run(p, B, Nstate, Nmeas, f, cookie, lambda, covariance, variances, factors, scale, fs, status);
 }
 int dogleg_amd_batch_uncertainty_last_stats(double* out, int n) { return out ? dlg_dense_batch_uncertainty_last_stats(out, n) : 0; }
+
+// ---- extension (not in the reference): the Jacobian of a device callback against central differences (gradcheck.hip)
+namespace {
+constexpr double GRADTEST_DELTA = 1e-6;             // dogleg.c:352
+bool one_rank_only(const char* who)
+{
+  const char* ws = getenv("DOGLEG_AMD_WORLD_SIZE");
+  if(!t_comm.set && !(ws && atoi(ws) > 1)) return true;
+  MSG("%s: one rank only (a communicator is set: dogleg_amd_clear_communicator)", who);
+  return false;
+}
+// the pattern arguments of a device callback's entry points: NJnnz == 0 with NULL pointers is dense
+bool device_pattern_ok(const char* who, unsigned int Nstate, unsigned int Nmeas, unsigned int NJnnz, const int* colptr,
+                       const int* rowidx)
+{
+  if(Nstate > 0x7fffffffu || Nmeas > 0x7fffffffu - 1 || NJnnz > 0x7fffffffu)
+  { MSG("%s: Nstate = %u, Nmeas = %u, NJnnz = %u: beyond the index range", who, Nstate, Nmeas, NJnnz); return false; }
+  if(NJnnz == 0)
+  {
+    if(colptr || rowidx) { MSG("%s: NJnnz = 0 selects the dense path, which takes no pattern", who); return false; }
+    return true;
+  }
+  if(!colptr || !rowidx) { MSG("%s: NJnnz = %u needs Jt_colptr and Jt_rowidx", who, NJnnz); return false; }
+  char err[512];
+  if(gradcheck_check_pattern((int)Nstate, (int)Nmeas, (long)NJnnz, colptr, rowidx, err, sizeof(err)))
+  { MSG("%s: %s", who, err); return false; }
+  return true;
+}
+bool tolerances_ok(const char* who, double rtol, double atol)
+{
+  if(rtol >= 0.0 && atol >= 0.0) return true;
+  MSG("%s: rtol = %g, atol = %g: both must be given and non-negative", who, rtol, atol);
+  return false;
+}
+} // namespace
+int dogleg_amd_jacobian_colouring(unsigned Nstate, unsigned Nmeas, const int* Jt_colptr, const int* Jt_rowidx, int* colour)
+{
+  const char* who = "dogleg_amd_jacobian_colouring";
+  if(!colour || Nstate == 0 || Nmeas == 0 || Nstate > 0x7fffffffu || Nmeas > 0x7fffffffu - 1)
+  { MSG("%s: Nstate = %u, Nmeas = %u and colour must be given", who, Nstate, Nmeas); return -1; }
+  char err[512];
+  if(gradcheck_check_pattern((int)Nstate, (int)Nmeas, -1, Jt_colptr, Jt_rowidx, err, sizeof(err)))
+  { MSG("%s: %s", who, err); return -1; }
+  return gradcheck_colour((int)Nstate, (int)Nmeas, Jt_colptr, Jt_rowidx, colour);
+}
+int dogleg_amd_check_jacobian_device(const double* p0, unsigned Nstate, unsigned Nmeas, unsigned NJnnz,
+                                     const int* Jt_colptr, const int* Jt_rowidx, dogleg_callback_device_t* f, void* cookie,
+                                     double delta, double rtol, double atol, int flags,
+                                     dogleg_amd_jacobian_report_t* report, double* var_error,
+                                     dogleg_amd_jacobian_entry_t* bad, int max_bad)
+{
+  const char* who = "dogleg_amd_check_jacobian_device";
+  if(!p0 || !f || !report) { MSG("%s: p0, the callback and report must be given", who); return -1; }
+  if(Nstate == 0 || Nmeas == 0) { MSG("%s: Nstate = %u, Nmeas = %u: neither may be 0", who, Nstate, Nmeas); return -1; }
+  if(!tolerances_ok(who, rtol, atol) || !device_pattern_ok(who, Nstate, Nmeas, NJnnz, Jt_colptr, Jt_rowidx)) return -1;
+  if(!one_rank_only(who)) return -1;
+  return dlg_gradcheck_run(p0, Nstate, Nmeas, NJnnz, Jt_colptr, Jt_rowidx, f, cookie, delta > 0.0 ? delta : GRADTEST_DELTA,
+                           rtol, atol, flags, report, var_error, bad, max_bad);
+}
+int dogleg_amd_check_jacobian_device_batch(const double* p0, unsigned B, unsigned Nstate, unsigned Nmeas,
+                                           dogleg_callback_device_batch_t* f, void* cookie,
+                                           double delta, double rtol, double atol, dogleg_amd_jacobian_report_t* reports,
+                                           dogleg_amd_jacobian_entry_t* bad, int max_bad, long long* nbad_total)
+{
+  const char* who = "dogleg_amd_check_jacobian_device_batch";
+  if(!p0 || !f || !reports) { MSG("%s: p0, the callback and reports must be given", who); return -1; }
+  if(B == 0 || Nstate == 0 || Nmeas == 0) { MSG("%s: B = %u, Nstate = %u, Nmeas = %u: none may be 0", who, B, Nstate, Nmeas); return -1; }
+  if(Nstate > DOGLEG_AMD_BATCH_MAX_NSTATE)
+  {
+    MSG("%s: Nstate = %u, a batch takes at most %d variables (larger problems: dogleg_amd_check_jacobian_device)", who, Nstate,
+        DOGLEG_AMD_BATCH_MAX_NSTATE);
+    return -1;
+  }
+  if(B > 0x7fffffffu/4 || Nmeas > 0x7fffffffu/(Nstate + 1))
+  { MSG("%s: B = %u problems of %u x %u: beyond the index range of the batch kernels", who, B, Nmeas, Nstate); return -1; }
+  if(!tolerances_ok(who, rtol, atol) || !one_rank_only(who)) return -1;
+  return dlg_gradcheck_batch_run(p0, B, Nstate, Nmeas, f, cookie, delta > 0.0 ? delta : GRADTEST_DELTA, rtol, atol, reports, bad,
+                                 max_bad, nbad_total);
+}
+void dogleg_amd_testGradient_device(unsigned var, const double* p0, unsigned Nstate, unsigned Nmeas, unsigned NJnnz,
+                                    const int* Jt_colptr, const int* Jt_rowidx, dogleg_callback_device_t* f, void* cookie)
+{
+  const char* who = "dogleg_amd_testGradient_device";
+  if(!p0 || !f || Nmeas == 0 || var >= Nstate) { MSG("%s: bad arguments", who); return; }
+  if(!device_pattern_ok(who, Nstate, Nmeas, NJnnz, Jt_colptr, Jt_rowidx) || !one_rank_only(who)) return;
+  std::vector<double> table(2*(size_t)Nmeas);
+  if(dlg_gradcheck_table(var, p0, Nstate, Nmeas, NJnnz, Jt_colptr, Jt_rowidx, f, cookie, GRADTEST_DELTA, table.data())) return;
+  // the table of dogleg_testGradient (gradtest.cpp: report)
+  printf("# ivar imeasurement gradient_reported gradient_observed error error_relative\n");
+  for(unsigned int m = 0; m < Nmeas; m++)
+  {
+    const double rep = table[2*(size_t)m], observed = table[2*(size_t)m + 1];
+    const double sum = fabs(rep) + fabs(observed), err = fabs(rep - observed);
+    printf("%d %d %.6g %.6g %.6g %.6g\n", (int)var, (int)m, rep, observed, err, sum == 0.0 ? 0.0 : err/(sum/2.0));
+  }
+  fflush(stdout);
+}
+int dogleg_amd_check_jacobian_last_stats(double* out, int n) { return out ? dlg_gradcheck_last_stats(out, n) : 0; }
 // what the library keeps between solves (the idle backend with its device memory, page-locked host buffers)
 void dogleg_amd_release_cache(void)
 {

@@ -124,6 +124,29 @@ class BatchResult(C.Structure):
     ]
 
 
+class JacobianReport(C.Structure):
+    """dogleg_amd_jacobian_report_t (include/dogleg.h)."""
+    _fields_ = [
+        ("nchecked", C.c_longlong), ("nbad", C.c_longlong), ("nnonfinite", C.c_longlong), ("noutside", C.c_longlong),
+        ("max_error", C.c_double), ("max_error_relative", C.c_double),
+        ("worst_var", C.c_int), ("worst_meas", C.c_int), ("worst_reported", C.c_double), ("worst_observed", C.c_double),
+        ("ncolours", C.c_int), ("evaluations", C.c_int),
+    ]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class JacobianEntry(C.Structure):
+    """dogleg_amd_jacobian_entry_t (include/dogleg.h)."""
+    _fields_ = [("problem", C.c_int), ("var", C.c_int), ("meas", C.c_int), ("reported", C.c_double), ("observed", C.c_double)]
+
+    def astuple(self):
+        return (self.problem, self.var, self.meas, self.reported, self.observed)
+
+
+JACOBIAN_ONE_AT_A_TIME = 1
+
 # dogleg_callback_device_batch_t
 CB_DEVICE_BATCH = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p)
 
