@@ -1,0 +1,339 @@
+// api_extensions.cpp -- the entry points of dogleg.h that never enter the trust-region loop: they check their
+// arguments and forward to the backend (outliers, covariance: the factor held for a context's point) or to a solver of
+// their own (dense_batch.hip, gradcheck.hip).  No HIP call.
+#include <cmath>
+#include <cstdlib>
+#include <vector>
+#include "driver_internal.h"
+#include "dense_batch.h"
+#include "gradcheck.h"
+#include "gradcheck_plan.h"
+
+namespace {
+
+// ---- outliers (dogleg.h; reference dogleg.c:2294-3149).  The leverage blocks come from the device (dlg_backend.h:
+// dlg_feature_leverage); what is left here is the host logic around them.
+bool outlier_ready(dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx, const char* who)
+{
+  if(!point || !ctx) { MSG("%s(): no point or context", who); return false; }
+  if(!point->have_x) { MSG("%s() needs x, but it isn't available", who); return false; }
+  if(!point->have_J) { MSG("%s() needs J, but it isn't available", who); return false; }
+  if(ctx->solve_type == DOGLEG_DENSE_PRODUCTS) { MSG("%s() is not available with DENSE_PRODUCTS: there is no J", who); return false; }
+  return dogleg_computeJtJfactorization(point, ctx);
+}
+// a backend call that needs the factor of the point's slot: if the factor held is another slot's, factorise again and retry
+template <class F> bool with_point_factor(dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx, const char* what, F call)
+{
+  int rc = call();
+  if(rc == DLG_ERR_STATE)
+  {
+    point->have_factorization = false;
+    if(!dogleg_computeJtJfactorization(point, ctx)) return false;
+    rc = call();
+  }
+  return be_ok(rc, what);
+}
+// *scale <= 0: Nn / (4 (Nstate + 1) |x|^2 / (Nn - Nstate - 1)), Nn the measurements that are not outliers
+void outlier_scale(double* scale, const dogleg_solverContext_t* ctx, int NoutlierFeatures, int featureSize, double norm2_x)
+{
+  if(*scale > 0.0) return;
+  const int nn = ctx->Nmeasurements - NoutlierFeatures*featureSize;
+  *scale = (double)nn / (4.0*((double)(ctx->Nstate + 1)*norm2_x/(double)(nn - ctx->Nstate - 1)));
+}
+
+// ---- covariance: what the reference's users get from cholmod_solve on ctx->factorization with unit right-hand sides
+bool cov_ready(dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx, const char* who)
+{
+  if(!point || !ctx) { MSG("%s(): no point or context", who); return false; }
+  const Driver* d = D(ctx);
+  if(d->sharded && d->nranks > 1) { MSG("%s() works on one rank only (this context has %d)", who, d->nranks); return false; }
+  return dogleg_computeJtJfactorization(point, ctx);
+}
+
+// ---- a batch of small dense problems: the shape every batch entry point takes
+bool batch_shape_ok(const char* who, unsigned int B, unsigned int Nstate, unsigned int Nmeas, const char* larger)
+{
+  if(B == 0 || Nstate == 0 || Nmeas == 0) { MSG("%s: B = %u, Nstate = %u, Nmeas = %u: none may be 0", who, B, Nstate, Nmeas); return false; }
+  if(Nstate > DOGLEG_AMD_BATCH_MAX_NSTATE)
+  {
+    MSG("%s: Nstate = %u, the batch kernels take at most %d variables (larger problems: %s)", who, Nstate,
+        DOGLEG_AMD_BATCH_MAX_NSTATE, larger);
+    return false;
+  }
+  if(B > 0x7fffffffu/4 || Nmeas > 0x7fffffffu/(Nstate + 1))
+  { MSG("%s: B = %u problems of %u x %u: beyond the index range of the batch kernels", who, B, Nmeas, Nstate); return false; }
+  return true;
+}
+
+// ---- the Jacobian of a device callback against central differences
+constexpr double GRADTEST_DELTA = 1e-6;             // dogleg.c:352
+// the pattern arguments of a device callback's entry points: NJnnz == 0 with NULL pointers is dense
+bool device_pattern_ok(const char* who, unsigned int Nstate, unsigned int Nmeas, unsigned int NJnnz, const int* colptr,
+                       const int* rowidx)
+{
+  if(Nstate > 0x7fffffffu || Nmeas > 0x7fffffffu - 1 || NJnnz > 0x7fffffffu)
+  { MSG("%s: Nstate = %u, Nmeas = %u, NJnnz = %u: beyond the index range", who, Nstate, Nmeas, NJnnz); return false; }
+  if(NJnnz == 0)
+  {
+    if(colptr || rowidx) { MSG("%s: NJnnz = 0 selects the dense path, which takes no pattern", who); return false; }
+    return true;
+  }
+  if(!colptr || !rowidx) { MSG("%s: NJnnz = %u needs Jt_colptr and Jt_rowidx", who, NJnnz); return false; }
+  char err[512];
+  if(gradcheck_check_pattern((int)Nstate, (int)Nmeas, (long)NJnnz, colptr, rowidx, err, sizeof(err)))
+  { MSG("%s: %s", who, err); return false; }
+  return true;
+}
+bool tolerances_ok(const char* who, double rtol, double atol)
+{
+  if(rtol >= 0.0 && atol >= 0.0) return true;
+  MSG("%s: rtol = %g, atol = %g: both must be given and non-negative", who, rtol, atol);
+  return false;
+}
+
+} // namespace
+
+extern "C" {
+
+bool dogleg_getOutliernessFactors(double* factors, double* scale, int featureSize, int Nfeatures,
+                                  int NoutlierFeatures, dogleg_operatingPoint_t* point,
+                                  dogleg_solverContext_t* ctx)
+{
+  if(featureSize <= 1) featureSize = 1;
+  if(featureSize > 2) { MSG("dogleg_getOutliernessFactors(): featureSize > 2 is not implemented (got %d)", featureSize); return false; }
+  if(!factors || !scale || Nfeatures < 0) { MSG("dogleg_getOutliernessFactors(): bad arguments"); return false; }
+  if(!outlier_ready(point, ctx, "dogleg_getOutliernessFactors")) return false;
+  if((long)Nfeatures*featureSize > (long)ctx->Nmeasurements)
+  { MSG("dogleg_getOutliernessFactors(): %d features of size %d exceed %d measurements", Nfeatures, featureSize, ctx->Nmeasurements); return false; }
+  outlier_scale(scale, ctx, NoutlierFeatures, featureSize, point->norm2_x);
+  Driver* d = D(ctx);
+  const double sc = *scale;
+  return with_point_factor(point, ctx, "outlierness factors",
+                           [&]{ return dlg_outlierness_factors(d->be, slot_of(d, point), featureSize, Nfeatures, sc, factors); });
+}
+
+bool dogleg_markOutliers(struct dogleg_outliers_t* markedOutliers, double* scale, int* Noutliers,
+                         double (getConfidence)(int i_feature_exclude), int featureSize, int Nfeatures,
+                         dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx)
+{
+  if(featureSize <= 1) featureSize = 1;
+  if(!markedOutliers || !Noutliers || !getConfidence || Nfeatures < 0) { MSG("dogleg_markOutliers(): bad arguments"); return false; }
+  std::vector<double> factors((size_t)Nfeatures);
+  if(!dogleg_getOutliernessFactors(factors.data(), scale, featureSize, Nfeatures, *Noutliers, point, ctx)) return false;
+  // candidates have a factor of at least 1; one is an outlier if leaving it out costs little confidence
+  const double confidence0 = getConfidence(-1);
+  if(confidence0 < 0.0) return false;
+  Driver* d = D(ctx);
+  VERBOSE(d, "Initial confidence: %g", confidence0);
+  bool markedAny = false;
+  *Noutliers = 0;
+  for(int i = 0; i < Nfeatures; i++)
+  {
+    if(markedOutliers[i].marked) { (*Noutliers)++; continue; }
+    if(factors[i] < 1.0) continue;
+    const double confidence = getConfidence(i);
+    if(confidence < 0.0) return false;
+    const double drop = 1.0 - confidence/confidence0;
+    if(drop < 0.05)
+    {
+      markedOutliers[i].marked = 1;
+      markedAny = true;
+      (*Noutliers)++;
+      VERBOSE(d, "Feature %d has outlierness factor %f. Culling produces a confidence: %g. relative loss: %g... YES an outlier; confidence drops little",
+              i, factors[i], confidence, drop);
+    }
+    else
+      VERBOSE(d, "Feature %d has outlierness factor %f. Culling produces a confidence: %g. relative loss: %g... NOT an outlier: confidence drops too much",
+              i, factors[i], confidence, drop);
+  }
+  return markedAny;
+}
+
+void dogleg_reportOutliers(double (getConfidence)(int i_feature_exclude), double* scale, int featureSize,
+                           int Nfeatures, int Noutliers, dogleg_operatingPoint_t* point,
+                           dogleg_solverContext_t* ctx)
+{
+  if(featureSize <= 1) featureSize = 1;
+  if(!getConfidence || Nfeatures < 0) { MSG("dogleg_reportOutliers(): bad arguments"); return; }
+  std::vector<double> factors((size_t)Nfeatures, 0.0);
+  (void)dogleg_getOutliernessFactors(factors.data(), scale, featureSize, Nfeatures, Noutliers, point, ctx);   // (a failure is reported, not fatal)
+  MSG("## Outlier statistics");
+  MSG("# i_feature outlier_factor confidence_drop_relative_if_removed");
+  const double confidence_full = getConfidence(-1);
+  for(int i = 0; i < Nfeatures; i++)
+  {
+    const double confidence = getConfidence(i);
+    MSG("%5d %9.3g %9.3g", i, factors[i], 1.0 - confidence/confidence_full);
+  }
+}
+
+double dogleg_getOutliernessTrace_newFeature_sparse(const double* JqueryFeature, int istateActive,
+                                                    int NstateActive, int featureSize, int NoutlierFeatures,
+                                                    dogleg_operatingPoint_t* point,
+                                                    dogleg_solverContext_t* ctx)
+{
+  const char* who = "dogleg_getOutliernessTrace_newFeature_sparse";
+  if(point && !point->have_x) { MSG("%s() needs x, but it isn't available", who); return -1.0; }
+  if(point && !point->have_J) { MSG("%s() needs J, but it isn't available", who); return -1.0; }
+  if(featureSize != 2) { MSG("%s(): only featureSize 2 is implemented (got %d)", who, featureSize); return -1.0; }
+  if(!JqueryFeature || NstateActive < 1) { MSG("%s(): bad arguments", who); return -1.0; }
+  if(!outlier_ready(point, ctx, who)) return -1.0;
+  Driver* d = D(ctx);
+  double A[3];
+  if(!with_point_factor(point, ctx, "leverage of a query feature",
+                        [&]{ return dlg_leverage_query(d->be, slot_of(d, point), JqueryFeature, istateActive, NstateActive, 2, A); }))
+    return -1.0;
+  // Mq = I + A; tr Mq^-1 = tr(Mq) / det(Mq)
+  const double m00 = 1.0 + A[0], m01 = A[1], m11 = 1.0 + A[2];
+  const double trace_inv = (m00 + m11)/(m00*m11 - m01*m01);
+  double scale = -1.0;
+  outlier_scale(&scale, ctx, NoutlierFeatures, featureSize, point->norm2_x);
+  return scale*(2.0 - trace_inv);
+}
+
+// ---- extension (not in the reference): covariance blocks from the factor held on the device (dlg_backend.h:
+// dlg_covariance_blocks)
+int dogleg_amd_covariance_blocks(double* out, int nreq, const int* r0, const int* nr, const int* c0, const int* nc,
+                                 dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx)
+{
+  const char* who = "dogleg_amd_covariance_blocks";
+  if(nreq < 0 || (nreq > 0 && (!out || !r0 || !nr || !c0 || !nc))) { MSG("%s(): bad arguments", who); return -1; }
+  if(!cov_ready(point, ctx, who)) return -1;
+  Driver* d = D(ctx);
+  return with_point_factor(point, ctx, "covariance blocks",
+                           [&]{ return dlg_covariance_blocks(d->be, slot_of(d, point), nreq, r0, nr, c0, nc, out); }) ? 0 : -1;
+}
+
+int dogleg_amd_marginal_variances(double* var, dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx)
+{
+  const char* who = "dogleg_amd_marginal_variances";
+  if(!var) { MSG("%s(): bad arguments", who); return -1; }
+  if(!cov_ready(point, ctx, who)) return -1;
+  Driver* d = D(ctx);
+  return with_point_factor(point, ctx, "marginal variances",
+                           [&]{ return dlg_marginal_variances(d->be, slot_of(d, point), var); }) ? 0 : -1;
+}
+
+int dogleg_amd_covariance_entries(double* out, long n, const int* row, const int* col,
+                                  dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx)
+{
+  const char* who = "dogleg_amd_covariance_entries";
+  if(n < 0 || (n > 0 && (!out || !row || !col))) { MSG("%s(): bad arguments", who); return -1; }
+  if(!cov_ready(point, ctx, who)) return -1;
+  Driver* d = D(ctx);
+  return with_point_factor(point, ctx, "covariance entries",
+                           [&]{ return dlg_covariance_entries(d->be, slot_of(d, point), n, row, col, out); }) ? 0 : -1;
+}
+
+int dogleg_amd_query_covariance(double* out, int nq, const int* qrow, const int* rowptr, const int* var,
+                                const double* val, int Nobservations,
+                                dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx)
+{
+  const char* who = "dogleg_amd_query_covariance";
+  if(nq < 0 || (nq > 0 && (!out || !qrow || !rowptr || !var || !val))) { MSG("%s(): bad arguments", who); return -1; }
+  if(!cov_ready(point, ctx, who)) return -1;
+  Driver* d = D(ctx);
+  return with_point_factor(point, ctx, "query covariance",
+                           [&]{ return dlg_query_covariance(d->be, slot_of(d, point), nq, qrow, rowptr, var, val, Nobservations, out); }) ? 0 : -1;
+}
+
+// ---- extension (not in the reference): a batch of small dense problems, the dog-leg loop on the device (dense_batch.hip)
+int dogleg_amd_optimize_dense_batch(double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                    dogleg_callback_device_batch_t* f, void* cookie,
+                                    const dogleg_parameters2_t* parameters, dogleg_amd_batch_result_t* results)
+{
+  const char* who = "dogleg_amd_optimize_dense_batch";
+  if(!p || !f || !results) { MSG("%s: p, the callback and results must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || !one_rank_only(who)) return -1;
+  return dlg_dense_batch_run(p, B, Nstate, Nmeas, f, cookie, parameters ? parameters : &g_params, results);
+}
+int dogleg_amd_batch_last_stats(double* out, int n) { return out ? dlg_dense_batch_last_stats(out, n) : 0; }
+int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                       dogleg_callback_device_batch_t* f, void* cookie,
+                                       double* lambda, double* covariance, double* variances, double* factors,
+                                       double* scale, int featureSize, int* status)
+{
+  const char* who = "dogleg_amd_dense_batch_uncertainty";
+  if(!p || !f || !status) { MSG("%s: p, the callback and status must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2")) return -1;
+  if(featureSize > 2) { MSG("%s: featureSize = %d: only 1 and 2 are supported", who, featureSize); return -1; }
+  const int fs = featureSize <= 1 ? 1 : 2;
+  if(!covariance && !variances && !factors) { MSG("%s: none of covariance, variances, factors is asked for", who); return -1; }
+  if(factors && !scale) { MSG("%s: factors need scale", who); return -1; }
+  if(factors && Nmeas/(unsigned int)fs == 0) { MSG("%s: Nmeas = %u holds no feature of size %d", who, Nmeas, fs); return -1; }
+  if(factors && Nmeas <= Nstate + 1)
+    for(unsigned int b = 0; b < B; b++)
+      if(!(scale[b] > 0.0))
+      {
+        MSG("%s: scale[%u] <= 0 is to be computed, which needs Nmeas > Nstate + 1 (%u, %u)", who, b, Nmeas, Nstate);
+        return -1;
+      }
+  if(!one_rank_only(who)) return -1;
+  return dlg_dense_batch_uncertainty_run(p, B, Nstate, Nmeas, f, cookie, lambda, covariance, variances, factors, scale, fs, status);
+}
+int dogleg_amd_batch_uncertainty_last_stats(double* out, int n) { return out ? dlg_dense_batch_uncertainty_last_stats(out, n) : 0; }
+
+// ---- extension (not in the reference): the Jacobian of a device callback against central differences (gradcheck.hip)
+int dogleg_amd_jacobian_colouring(unsigned Nstate, unsigned Nmeas, const int* Jt_colptr, const int* Jt_rowidx, int* colour)
+{
+  const char* who = "dogleg_amd_jacobian_colouring";
+  if(!colour || Nstate == 0 || Nmeas == 0 || Nstate > 0x7fffffffu || Nmeas > 0x7fffffffu - 1)
+  { MSG("%s: Nstate = %u, Nmeas = %u and colour must be given", who, Nstate, Nmeas); return -1; }
+  char err[512];
+  if(gradcheck_check_pattern((int)Nstate, (int)Nmeas, -1, Jt_colptr, Jt_rowidx, err, sizeof(err)))
+  { MSG("%s: %s", who, err); return -1; }
+  return gradcheck_colour((int)Nstate, (int)Nmeas, Jt_colptr, Jt_rowidx, colour);
+}
+int dogleg_amd_check_jacobian_device(const double* p0, unsigned Nstate, unsigned Nmeas, unsigned NJnnz,
+                                     const int* Jt_colptr, const int* Jt_rowidx, dogleg_callback_device_t* f, void* cookie,
+                                     double delta, double rtol, double atol, int flags,
+                                     dogleg_amd_jacobian_report_t* report, double* var_error,
+                                     dogleg_amd_jacobian_entry_t* bad, int max_bad)
+{
+  const char* who = "dogleg_amd_check_jacobian_device";
+  if(!p0 || !f || !report) { MSG("%s: p0, the callback and report must be given", who); return -1; }
+  if(Nstate == 0 || Nmeas == 0) { MSG("%s: Nstate = %u, Nmeas = %u: neither may be 0", who, Nstate, Nmeas); return -1; }
+  if(!tolerances_ok(who, rtol, atol) || !device_pattern_ok(who, Nstate, Nmeas, NJnnz, Jt_colptr, Jt_rowidx)) return -1;
+  if(!one_rank_only(who)) return -1;
+  return dlg_gradcheck_run(p0, Nstate, Nmeas, NJnnz, Jt_colptr, Jt_rowidx, f, cookie, delta > 0.0 ? delta : GRADTEST_DELTA,
+                           rtol, atol, flags, report, var_error, bad, max_bad);
+}
+int dogleg_amd_check_jacobian_device_batch(const double* p0, unsigned B, unsigned Nstate, unsigned Nmeas,
+                                           dogleg_callback_device_batch_t* f, void* cookie,
+                                           double delta, double rtol, double atol, dogleg_amd_jacobian_report_t* reports,
+                                           dogleg_amd_jacobian_entry_t* bad, int max_bad, long long* nbad_total)
+{
+  const char* who = "dogleg_amd_check_jacobian_device_batch";
+  if(!p0 || !f || !reports) { MSG("%s: p0, the callback and reports must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "dogleg_amd_check_jacobian_device")) return -1;
+  if(!tolerances_ok(who, rtol, atol) || !one_rank_only(who)) return -1;
+  return dlg_gradcheck_batch_run(p0, B, Nstate, Nmeas, f, cookie, delta > 0.0 ? delta : GRADTEST_DELTA, rtol, atol, reports, bad,
+                                 max_bad, nbad_total);
+}
+void dogleg_amd_testGradient_device(unsigned var, const double* p0, unsigned Nstate, unsigned Nmeas, unsigned NJnnz,
+                                    const int* Jt_colptr, const int* Jt_rowidx, dogleg_callback_device_t* f, void* cookie)
+{
+  const char* who = "dogleg_amd_testGradient_device";
+  if(!p0 || !f || Nmeas == 0 || var >= Nstate) { MSG("%s: bad arguments", who); return; }
+  if(!device_pattern_ok(who, Nstate, Nmeas, NJnnz, Jt_colptr, Jt_rowidx) || !one_rank_only(who)) return;
+  std::vector<double> table(2*(size_t)Nmeas);
+  if(dlg_gradcheck_table(var, p0, Nstate, Nmeas, NJnnz, Jt_colptr, Jt_rowidx, f, cookie, GRADTEST_DELTA, table.data())) return;
+  // the table of dogleg_testGradient (gradtest.cpp: report)
+  printf("# ivar imeasurement gradient_reported gradient_observed error error_relative\n");
+  for(unsigned int m = 0; m < Nmeas; m++)
+  {
+    const double rep = table[2*(size_t)m], observed = table[2*(size_t)m + 1];
+    const double sum = fabs(rep) + fabs(observed), err = fabs(rep - observed);
+    printf("%d %d %.6g %.6g %.6g %.6g\n", (int)var, (int)m, rep, observed, err, sum == 0.0 ? 0.0 : err/(sum/2.0));
+  }
+  fflush(stdout);
+}
+int dogleg_amd_check_jacobian_last_stats(double* out, int n) { return out ? dlg_gradcheck_last_stats(out, n) : 0; }
+
+// ---- extension (not in the reference): the device backend behind a returned context, for
+// dlg_solve_with_factor / dlg_point_download on the resident factor and vectors
+dlg_backend_t* dogleg_amd_backend(dogleg_solverContext_t* ctx) { return ctx ? D(ctx)->be : nullptr; }
+int dogleg_amd_point_slot(dogleg_solverContext_t* ctx, const dogleg_operatingPoint_t* point)
+{ return (ctx && point) ? slot_of(D(ctx), point) : -1; }
+
+} // extern "C"

@@ -2,7 +2,7 @@
 #pragma once
 #include "../../include/dogleg.h"
 
-// arguments checked by the caller (driver.hip: dogleg_amd_optimize_dense_batch); 0 / -1 with a message on stderr
+// arguments checked by the caller (api_extensions.cpp: dogleg_amd_optimize_dense_batch); 0 / -1 with a message on stderr
 int  dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int M,
                          dogleg_callback_device_batch_t* f, void* cookie,
                          const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results);

@@ -442,7 +442,7 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
     scale = A.scale[b];
     if(!(scale > 0.0))
     {
-      // NoutlierFeatures = 0 (driver.hip: outlier_scale); NaN for a problem that failed on a non-finite x
+      // NoutlierFeatures = 0 (api_extensions.cpp: outlier_scale); NaN for a problem that failed on a non-finite x
       scale = (double)M/(4.0*((double)(N + 1)*n2x/(double)(M - N - 1)));
       if(lane == 0) A.scale[b] = scale;
     }

@@ -1,5 +1,5 @@
 // gradcheck.h -- the Jacobian check of gradcheck.hip as the driver sees it (not installed).  The arguments are checked
-// by the caller (driver.hip: dogleg_amd_check_jacobian_device*); 0 or more / -1 with a message on stderr.
+// by the caller (api_extensions.cpp: dogleg_amd_check_jacobian_device*); 0 or more / -1 with a message on stderr.
 #pragma once
 #include "../../include/dogleg.h"
 

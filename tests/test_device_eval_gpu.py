@@ -125,7 +125,7 @@ def test_returned_context_of_a_device_solve(gpu):
 
 @pytest.mark.parametrize("overlap", [True, False], ids=["comparison beside the evaluation", "comparison first"])
 def test_a_backend_taken_over_serves_the_same_and_another_pattern_of_its_shape(gpu, overlap, monkeypatch):
-    """Between solves the library keeps one idle backend with its pattern and schedules (driver.hip: park / take over).  The
+    """Between solves the library keeps one idle backend with its pattern and schedules (driver_cache.hip: park / take over).  The
     next solve of the SAME shape compares its pattern with the backend's -- on a thread of its own, beside the first
     evaluation, which is made with the backend's schedules (round 5; DOGLEG_AMD_NO_PATTERN_OVERLAP: first, as before).
     Three solves in a row, same (N, M, nnz): pattern A, A again (taken over as it is), then B (another pattern: the

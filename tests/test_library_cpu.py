@@ -259,15 +259,22 @@ def test_gradient_check_tool_on_the_sample_problem(mode):
 
 def test_host_side_compiles_against_a_real_cholmod_header(tmp_path):
     """VERDICT r1 item 8 / INTEGRATION.md: where SuiteSparse is installed <cholmod.h> is used instead
-    of include/dogleg_cholmod_compat.h.  The driver (host pass of driver.hip) and a user translation
+    of include/dogleg_cholmod_compat.h.  The driver (the host pass of every file of it that sees a
+    dogleg_solverContext_t, driver_internal.h: driver.hip, driver_cache.hip, driver_comm.cpp, driver_records.cpp,
+    api_extensions.cpp) and a user translation
     unit must compile against CHOLMOD's public struct shapes: no by-value cholmod_factor with
     compat-only fields, the backend pointer lives in the driver."""
     inc = os.path.join(ROOT, "tests", "c", "cholmod_shape")
     hipcc = "/opt/rocm/bin/hipcc"
-    drv = os.path.join(ROOT, "libdogleg_amd", "csrc", "driver.hip")
-    r = subprocess.run([hipcc, "-std=c++17", "--offload-arch=gfx950", "--cuda-host-only", "-fsyntax-only",
-                        "-I", inc, drv], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    csrc = os.path.join(ROOT, "libdogleg_amd", "csrc")
+    users = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".cpp"))
+             and "driver_internal.h" in open(os.path.join(csrc, f)).read()]
+    assert {"driver.hip", "driver_cache.hip", "driver_comm.cpp", "driver_records.cpp", "api_extensions.cpp"} <= set(users)
+    for f in users:
+        lang = ["--offload-arch=gfx950", "--cuda-host-only"] if f.endswith(".hip") else ["-x", "c++"]
+        r = subprocess.run([hipcc, "-std=c++17"] + lang + ["-fsyntax-only", "-I", inc, os.path.join(csrc, f)],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, (f, r.stderr[-3000:])
     r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", inc,
                         os.path.join(ROOT, "tests", "c", "real_cholmod_host.cpp")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -490,6 +497,25 @@ def test_region_planner_is_clean_under_sanitizers(tmp_path, monkeypatch):
                 assert r.returncode == 0 and r.stderr == "", (shape, ncu, knob, r.returncode, r.stderr[-2000:])
                 st = capi.region_probe(N, M, Jp, Ji, ncu)
                 assert [int(h, 16) for h in r.stdout.split()] == [st["schedule_hash"], st["level_params_hash"]], (shape, ncu, knob)
+
+
+def test_id_file_rendezvous_is_clean_under_sanitizers(tmp_path):
+    """The id file of the multi-GPU environment contract as a stand-alone program (tests/c/id_file_main.cpp: it links
+    id_file.cpp alone -- plain C++, no HIP, no backend) under AddressSanitizer and UndefinedBehaviorSanitizer: publish then
+    wait, a file of another run id (the wait runs out), a truncated file, a file one byte too long."""
+    cc = _sanitizing_compiler(tmp_path)
+    if cc is None:
+        pytest.skip("no compiler here links a program with -fsanitize=address,undefined")
+    csrc = os.path.join(ROOT, "libdogleg_amd", "csrc")
+    exe = str(tmp_path / "id_file_main")
+    subprocess.run([cc] + _SAN_FLAGS + ["-I", csrc, os.path.join(ROOT, "tests", "c", "id_file_main.cpp"),
+                                        os.path.join(csrc, "id_file.cpp"), "-o", exe], check=True)
+    work = tmp_path / "ids"
+    work.mkdir()
+    r = subprocess.run([exe, str(work)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout == "ok\n", (r.returncode, r.stdout, r.stderr[-2000:])
+    # (the library's messages of the waits that ran out, nothing from a sanitizer)
+    assert all(l.startswith("libdogleg_amd: ") for l in r.stderr.splitlines()), r.stderr[-2000:]
 
 
 def test_subtree_partition_rows_form_closed_subtrees():
