@@ -136,7 +136,9 @@ def test_ba_lambda_path(gpu):
     compare_traces(trg, tro, step_tol=1e-7)     # lambda=1e-10 systems are ill-conditioned by design
 
 
-@pytest.mark.parametrize("env", [
+# the kernels and supernode cuts that the default schedule does not pick on a bundle-adjustment pattern (the knobs are
+# read when the pattern is set); test_factor_users_zoo_gpu.py runs the users of the held factor under the same list
+FALLBACK_ENVS = [
     {"DOGLEG_AMD_ASM_MFMA": "0"},                                   # LDS assembly kernel k_assemble for every column block
     {"DOGLEG_AMD_ASM_MFMA": "2"},                                   # MFMA assembly with the masked transient stores (shapes that do not fit one round of lanes)
     {"DOGLEG_AMD_SYRK_MIN": "0", "DOGLEG_AMD_NO_UPDATE_MFMA": "1"},  # k_update_coop instead of SYRK+gather / MFMA updates
@@ -157,10 +159,14 @@ def test_ba_lambda_path(gpu):
     {"DOGLEG_AMD_NO_PREMUL": "1"},                                  # backward block sweep with the operands multiplied in the loop
     {"DOGLEG_AMD_NO_LEAF_KERNEL": "1"},                             # merged leaves through the general factor kernel
     {"DOGLEG_AMD_FRONT_REPLICAS": "3"},                             # another replica count in the one-launch region
-], ids=["lds-assembly", "mfma-assembly-masked-stores", "coop-update", "mfma-update", "syrk-unfused", "no-rider", "small-slices", "no-multifrontal",
+]
+FALLBACK_IDS = ["lds-assembly", "mfma-assembly-masked-stores", "coop-update", "mfma-update", "syrk-unfused", "no-rider", "small-slices", "no-multifrontal",
         "multifrontal-from-leaves", "multifrontal-128", "multifrontal-256", "device-finals",
         "bwd-x-from-hbm", "no-overlap", "no-persistent-top", "deep-persistent-top",
-        "separate-jtx", "no-premul", "no-leaf-kernel", "replica-counts"])
+        "separate-jtx", "no-premul", "no-leaf-kernel", "replica-counts"]
+
+
+@pytest.mark.parametrize("env", FALLBACK_ENVS, ids=FALLBACK_IDS)
 def test_fallback_kernels_match_oracle(gpu, env, monkeypatch):
     """the kernels the default schedule does not pick on a bundle-adjustment pattern stay correct:
     the schedule knobs are read when the pattern is set"""
