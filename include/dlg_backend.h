@@ -167,6 +167,13 @@ int  dlg_sparse_region_probe(int N, int M, const int* colptr, const int* rowidx,
  * parents through flags) or -1 if there is none; the workgroups of that launch */
 int  dlg_sparse_schedule(dlg_backend_t* b, int* n_levels, int* persist_level0, int* persist_items);
 
+/* the merged leaves' rows below their member blocks: a leaf launch of the factorisation in the lean mode stores the
+ * augmented row only and leaves the others as the assembly wrote them; the entry points that use the held factor
+ * form L_below there first, once (DOGLEG_AMD_LEAF_STORE_ROWS=1: the leaf launch stores every row).
+ * stats[] = {leaf launches in the lean mode, runs of that materialisation, 1 if the current factor's rows are the
+ * assembly's still, levels of the pattern whose leaf launch may run lean}, as many as nstats asks for */
+int  dlg_sparse_leaf_rows_stats(dlg_backend_t* b, long* stats, int nstats);
+
 /* host-only symbolic phase on a pattern (no GPU): stats[] = {var-blocks,
  * supernodes, levels, nnz(tril JtJ), nnz(L), panel doubles, factor flops, max
  * panel, assembly tasks, update items, relpos entries, output blocks,

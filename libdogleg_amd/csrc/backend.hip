@@ -621,6 +621,10 @@ int dlg_factor_user_begin(dlg_backend* b, int s, const char* who, unsigned needs
   if((needs & DLG_NEEDS_J) && !b->slot[s].have_inputs) { dlg_set_error("%s needs x and J of slot %d", who, s); return DLG_ERR_STATE; }
   if(b->factor_slot != s) { dlg_set_error("%s: no factorization of slot %d is held", who, s); return DLG_ERR_STATE; }
   if((needs & DLG_NEEDS_PATTERN) && b->type == DLG_SPARSE && !b->sym) { dlg_set_error("%s: no sparse pattern", who); return DLG_ERR_STATE; }
+  // (the held factor's merged leaves as every user reads them: L_below stored, once per held factor -- sparse_factor.hip.
+  // Every reader of those rows in sparse_multi.hip and sparse_selinv.hip runs behind this prelude; the one that can be
+  // reached without it, sparse_solve with a right-hand side of its own, asks for the rows itself.)
+  if(b->type == DLG_SPARSE) DLG_CHECK(sparse_leaf_rows_materialize(b));
   return DLG_OK;
 }
 

@@ -404,6 +404,7 @@ int sparse_norm2_chunks(const dlg_backend* b);
 int dense_norm2_chunks(const dlg_backend* b);
 bool sparse_factor_ok(const dlg_backend* b);     // pivot flag of the last factorisation (after a sync)
 int sparse_solve(dlg_backend* b, const double* rhs, double* out);                // K6
+int sparse_leaf_rows_materialize(dlg_backend* b);       // the current factor's merged leaves: L_below stored where the lean leaf launch left W (idempotent; no pattern: nothing)
 void sparse_hold_factor(dlg_backend* b);
 bool sparse_would_look(const dlg_backend* b, double lambda);      // sparse_factorize(lambda) would look at the diagonal first (and ask the host at once)
 bool sparse_note_breakdown(dlg_backend* b);           // a factorisation broke down (the host knows): sparse_factorize looks at the diagonal first from now on (lambda = 0); true: stopped by that look, the panels are the assembly's still

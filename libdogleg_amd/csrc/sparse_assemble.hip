@@ -1278,6 +1278,7 @@ static int clear_panels(dlg_backend* b, double* Lx, hipStream_t st)
   SparseSym* Y = b->sym;
   const SymHost& H = Y->H;
   const bool known = Lx == Y->lz_ok[0] || Lx == Y->lz_ok[1];
+  Y->leaf_rows.assembled(Lx);
   if(known && Y->clr_partial_ok && !b->sharded() && H.part_nranks <= 1)
   {
     hipLaunchKernelGGL(k_clear_ranges, dim3(64, Y->n_clr), dim3(TPB), 0, st, Lx, Y->clr_off, Y->clr_len);
@@ -1301,6 +1302,7 @@ static int assemble_launch(dlg_backend* b, const double* Jv, double* Lx = nullpt
   DLG_CHECK(sparse_assemble_finish(b));             // (an earlier assembly's partial sums live in the buffers this one fills)
   DLG_CHECK(sparse_fin_side_gate(b));               // (... and stages still running on the second stream read them)
   if(!Lx) Lx = Y->Lx;
+  Y->leaf_rows.assembled(Lx);                       // (the rows below the leaves' member blocks are a new point's W: leaf_rows_state.h)
   if(!zeroed) DLG_CHECK(clear_panels(b, Lx, st));
   const int nt = (int)H.asm_ctask.size(), nmt = (int)H.asm_mtask.size();
   if(nt > 0 || nmt > 0)

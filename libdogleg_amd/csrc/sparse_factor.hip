@@ -285,7 +285,8 @@ __global__ void __launch_bounds__(NT, LEAF ? 4 : 1) k_factor_level(const FwItem*
                                                      double* __restrict__ top_scr,
                                                      int* __restrict__ info,
                                                      double* uscr, int mode,
-                                                     int* pr_flag, int pr_epoch, DlgHandoff ho, int64_t pr_acc)
+                                                     int* pr_flag, int pr_epoch, DlgHandoff ho, int64_t pr_acc,
+                                                     double* __restrict__ leaf_rd)
 {
   extern __shared__ __attribute__((aligned(16))) double P[];
   __shared__ int sbad, s_skip;
@@ -297,6 +298,11 @@ __global__ void __launch_bounds__(NT, LEAF ? 4 : 1) k_factor_level(const FwItem*
 #endif
   const bool stage_leaf_u = (mode & 4) != 0;    // childless supernodes may stage U in LDS too (host: no occupancy loss)
   const bool b16 = (mode & 16) != 0;            // panel_factor_b16 (blocks of 16, the diagonal tile in registers)
+  // FMODE_LEAN_ROWS (LEAF only): of the rows below the member blocks only the augmented row goes back to the panel -- the
+  // others stay the assembly's W, whose one reader inside a step, the backward solve, takes L_below' x = L_tt^-1 (W' x)
+  // from them (k_solve_bwd_level: rows_raw); the members' reciprocal pivots are left in leaf_rd for the readers that
+  // need L_below itself (k_leaf_rows_materialize)
+  const bool lean_rows = LEAF && (mode & 32) != 0;
   mode &= 3;
   const FwItem it = items[blockIdx.x];
   const int r0 = it.r0, w = it.w, nrows = it.nrows;
@@ -537,6 +543,15 @@ __global__ void __launch_bounds__(NT, LEAF ? 4 : 1) k_factor_level(const FwItem*
     }
     __syncthreads();
   }
+  if(LEAF && cmp && lean_rows)
+  {
+    for(int j = tid; j < w; j += NT)
+    {
+      G[(size_t)j*nrows + (nloc - 1 + shift)] = Pb[(nloc - 1) + j*ldp];
+      leaf_rd[it.col0 + j] = s_rdiag[j];
+    }
+  }
+  else
   for(int i = row0c + tid - cp_g*cp_rows; i < nloc && cp_g < cp_ng && store_panel; i += cp_rows)
   {
     // rows below the top block go back to the panel; the top block too unless the supernode is
@@ -580,6 +595,47 @@ __global__ void __launch_bounds__(TPB) k_copy_top(const int* __restrict__ ms_sn,
   double* G = Lx + sn_lx[s];
   const double* T = top_scr + sn_top[s];
   for(int e = threadIdx.x; e < w*w; e += TPB) { const int j = e / w, i = e - j*w; G[i + (size_t)j*nrows] = T[e]; }
+}
+
+// L_below = W L_tt^-T of the merged leaves a lean leaf launch left as W (k_factor_level, FMODE_LEAN_ROWS), for the readers
+// of the factor other than the backward solve.  One workgroup per leaf: the rows below the member blocks into the leaf
+// kernel's LDS image, the factored member blocks from the panel and their reciprocal pivots from leaf_rd (what the leaf
+// launch held in LDS at this point), bd_compact_rows -- the arithmetic and the bits of the write-back the leaf launch
+// left out --, and the rows go back.  The augmented row (the last one) is the factorisation's already: not stored.
+template <int NT>
+__global__ void __launch_bounds__(NT) k_leaf_rows_materialize(const FwItem* __restrict__ items,
+                                                              double* __restrict__ Lx, const double* __restrict__ leaf_rd,
+                                                              const int* __restrict__ info)
+{
+  // (the factor is that of a factorisation that broke down or was given up: its leaf workgroups left before they factored
+  // a member -- nothing here is a factor's, and the panels stay what sparse_assemble may take over; see k_copy_top)
+  if(*info != 0x7fffffff) return;
+  extern __shared__ __attribute__((aligned(16))) double P[];
+  constexpr int DS = 4;                        // (the leaf instantiation's: members of at most 4 columns)
+  __shared__ int s_mcol[68];
+  __shared__ double s_rdiag[64];
+  const FwItem it = items[blockIdx.x];
+  const int w = it.w, nrows = it.nrows, tid = threadIdx.x;
+  // (every item of a lean level is an unsliced block-diagonal panel of at most 64 columns whose members have one common
+  // width of at most 4, it.bdw: fac_level_params, L.leaf -- the leaf instantiation's own premise)
+  double* G = Lx + it.lx;
+  const int mb = nrows - w, ldp = (mb + 1) & ~1;
+  double* Pb = P - w;
+  double* Dg = P + ldp*w;
+  for(int m = tid; m <= it.nbd; m += NT) s_mcol[m] = (m < it.nbd) ? m*it.bdw : w;
+  for(int j = tid; j < w; j += NT) s_rdiag[j] = leaf_rd[it.col0 + j];
+  __syncthreads();
+  for(int m = tid; m < it.nbd; m += NT)
+  {
+    const int c0 = s_mcol[m], nb = s_mcol[m + 1] - c0;
+    for(int c = 0; c < nb; c++)
+      for(int q = 0; q <= c && q < DS; q++) Dg[(c0 + c)*DS + q] = G[(c0 + c) + (size_t)(c0 + q)*nrows];
+  }
+  for(int e = tid; e < mb*w; e += NT) { const int j = e / mb, i = e - j*mb; P[i + j*ldp] = G[(size_t)j*nrows + w + i]; }
+  __syncthreads();
+  bd_compact_rows<NT, DS>(Pb, ldp, nrows, w, tid, it.nbd, s_mcol, s_rdiag, Dg, it.bdw);
+  __syncthreads();
+  for(int e = tid; e < (mb - 1)*w; e += NT) { const int j = e / (mb - 1), i = e - j*(mb - 1); G[(size_t)j*nrows + w + i] = P[i + j*ldp]; }
 }
 
 // cooperative variant of the update for heavy sources (wide panels): the whole
@@ -1124,10 +1180,11 @@ __global__ void __launch_bounds__(TPB) k_update_fin(int f0, const int* __restric
 // the one dispatch over the instantiations of k_factor_level (leaf: the lean one, 256 threads only; the compiler
 // lays the kernels out in the order they are first named: <256> in front of <256, true>)
 static void launch_factor_level(int nt, bool leaf, int grid, int lds, hipStream_t st, const SparseSym* Y, const FwItem* items,
-                                const MfChild* rec, const uint16_t* dst, int fmode, int* fl, int ep, DlgHandoff ho, int64_t pacc)
+                                const MfChild* rec, const uint16_t* dst, int fmode, int* fl, int ep, DlgHandoff ho, int64_t pacc,
+                                double* leaf_rd = nullptr)
 {
 #define DLG_FL_LAUNCH(...) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_factor_level<__VA_ARGS__>), dim3(grid), dim3(nt), lds, st, \
-                                              items, rec, Y->sn_bd_col, dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, fl, ep, ho, pacc)
+                                              items, rec, Y->sn_bd_col, dst, Y->Lx, Y->top_scr, Y->d_info, Y->uscr, fmode, fl, ep, ho, pacc, leaf_rd)
   if(nt == 128) DLG_FL_LAUNCH(128);
   else if(nt == 256 && !leaf) DLG_FL_LAUNCH(256);
   else if(nt == 256) DLG_FL_LAUNCH(256, true);
@@ -1135,6 +1192,7 @@ static void launch_factor_level(int nt, bool leaf, int grid, int lds, hipStream_
 #undef DLG_FL_LAUNCH
 }
 constexpr int FMODE_B16 = 16;      // panel_factor_b16 where the panel has at most 512 rows: every launch asks for it
+constexpr int FMODE_LEAN_ROWS = 32;      // a level of merged leaves: the rows below the member blocks stay the assembly's (k_factor_level: lean_rows)
 
 // the levels of region R, the first of which is l, in one launch (its epoch is the caller's: ++R.epoch)
 static void launch_region(dlg_backend* b, const PrRegion& R, int l)
@@ -1210,11 +1268,28 @@ int sparse_factor_setup(dlg_backend* b)
   }
   DLG_CHECK(region_flags(b, Y->top));
   DLG_CHECK(region_flags(b, Y->lo));
+  // The levels whose leaf launch may leave the rows below the member blocks as the assembly wrote them: the lean
+  // instantiation, launched on its own (not inside a region), and nothing of the level's updates reads those rows from the
+  // panel -- the update matrices come out of the launch's LDS copy (syrk_fused) or there are none.
+  // DOGLEG_AMD_LEAF_STORE_ROWS=1: no level does (the write-back of all rows, for A/B runs and the tests).
+  // (sparse_solve_setup, which runs behind this, takes a level back whose backward launch could not honour it)
+  const bool store_rows = env_int("DOGLEG_AMD_LEAF_STORE_ROWS", 0) != 0, sym_debug = getenv("DOGLEG_AMD_SYM_DEBUG") != nullptr;
+  Y->leaf_lean.assign(H.nlevels, 0);
+  for(int l = 0; l < H.nlevels && !store_rows; l++)
+  {
+    const bool own_launch = l < Y->top.level0 && !(l >= Y->lo.level0 && l <= Y->lo.level1);
+    const int nu = H.uw_lvl_ptr[l+1] - H.uw_lvl_ptr[l];
+    const bool rows_unread = nu == 0 || (H.upd_syrk[l] && Y->fac.upd_nw[l] > 0 && Y->fac.syrk_fused[l]);
+    Y->leaf_lean[l] = (Y->fac.leaf[l] && own_launch && rows_unread) ? 1 : 0;
+    if(sym_debug) fprintf(stderr, "factor level %d: lean leaf rows %d\n", l, (int)Y->leaf_lean[l]);
+  }
+  if(!Y->leaf_rd) { DLG_HIP(hipMalloc(&Y->leaf_rd, sizeof(double)*2*(size_t)std::max(1, H.N))); Y->allocs.push_back(Y->leaf_rd); }
+  Y->leaf_rows.reset();
   // the kernels that ask for more dynamic LDS than the default: the first four the factor budget, the rest the common one
   const void* const big_lds[] = { (const void*)&k_factor_level<128>, (const void*)&k_factor_level<256>, (const void*)&k_factor_level<256, true>,
-                                  (const void*)&k_factor_level<512>, (const void*)&k_update_level, (const void*)&k_update_syrk<256>,
+                                  (const void*)&k_factor_level<512>, (const void*)&k_leaf_rows_materialize<256>, (const void*)&k_update_level, (const void*)&k_update_syrk<256>,
                                   (const void*)&k_update_syrk<1024>, (const void*)&k_update_gather<TPB>, (const void*)&k_update_mfma };
-  for(int i = 0; i < 9; i++) DLG_HIP(hipFuncSetAttribute(big_lds[i], hipFuncAttributeMaxDynamicSharedMemorySize, i < 4 ? FAC_LDS_BUDGET : LDS_BUDGET));
+  for(int i = 0; i < 10; i++) DLG_HIP(hipFuncSetAttribute(big_lds[i], hipFuncAttributeMaxDynamicSharedMemorySize, i < 5 ? FAC_LDS_BUDGET : LDS_BUDGET));
   return DLG_OK;
 }
 
@@ -1319,9 +1394,15 @@ int sparse_factor_levels(dlg_backend* b, int part)
     }
     if(n > 0 && !launched_before)
     {
-      const int fmode = ((l >= H.mf_level0) ? 2 : Y->fac.syrk_fused[l]) + 4*Y->fac.stage[l] + FMODE_B16 + 256*(l & 31);
+      // (a level of merged leaves that may keep its rows below as the assembly's: the buffer's state says so from here on,
+      // whatever becomes of this factorisation -- a workgroup that gives up has not touched its rows either)
+      const int rd_slot = Y->leaf_lean[l] ? Y->leaf_rows.slot(Y->Lx) : -1;
+      const bool lean = rd_slot >= 0;
+      const int fmode = ((l >= H.mf_level0) ? 2 : Y->fac.syrk_fused[l]) + 4*Y->fac.stage[l] + FMODE_B16 + (lean ? FMODE_LEAN_ROWS : 0) + 256*(l & 31);
       launch_factor_level(Y->fac.nt[l], Y->fac.leaf[l], n, Y->fac.lds[l], st, Y, Y->fw_item + H.fw_lvl_ptr[l], Y->mf_rec, Y->mf_dst,
-                          fmode, (int*)nullptr, 0, DlgHandoff{nullptr, 0, 0}, (int64_t)0);
+                          fmode, (int*)nullptr, 0, DlgHandoff{nullptr, 0, 0}, (int64_t)0, lean ? Y->leaf_rd + (size_t)rd_slot*H.N : (double*)nullptr);
+      if(lean) Y->leaf_rows.factored_lean(Y->Lx);
+      else if(Y->fac.leaf[l]) Y->leaf_rows.factored_full(Y->Lx);
     }
     if(part == 1 && split && l == 0) { Y->fac_pending = true; DLG_LAUNCH_CHECK(); return DLG_OK; }
     // (behind the leaf level's factor kernel, in front of its updates: the gather kernel looks at the word itself,
@@ -1375,6 +1456,38 @@ int sparse_factor_levels(dlg_backend* b, int part)
     hipLaunchKernelGGL(k_copy_top, dim3((unsigned)H.ms_sn.size()), dim3(TPB), 0, st, Y->ms_sn, Y->sn_c0,
                        Y->sn_rowptr, Y->sn_lx, Y->sn_top, Y->Lx, Y->top_scr, (const int*)Y->d_info);
   DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
+
+// The readers of the merged leaves' L_below other than the backward solve are behind this: dlg_factor_user_begin calls it for
+// the blocked solves, the reach sweeps and the selected inverse, sparse_solve for the forward solve of another right-hand side: where the current factor's leaf launch
+// ran lean, L_below is stored over W now, on the backend's stream, once (the buffer's state says when: leaf_rows_state.h).
+int sparse_leaf_rows_materialize(dlg_backend* b)
+{
+  SparseSym* Y = b->sym;
+  if(!Y || !Y->Lx || !Y->leaf_rows.raw(Y->Lx)) return DLG_OK;
+  const SymHost& H = Y->H;
+  const int slot = Y->leaf_rows.slot(Y->Lx);
+  for(int l = 0; l < H.nlevels; l++)
+  {
+    const int n = H.fw_lvl_ptr[l+1] - H.fw_lvl_ptr[l];
+    if(!Y->leaf_lean[l] || n == 0) continue;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_leaf_rows_materialize<256>), dim3(n), dim3(256), Y->fac.lds[l], b->stream,
+                       Y->fw_item + H.fw_lvl_ptr[l], Y->Lx, Y->leaf_rd + (size_t)slot*H.N, (const int*)Y->d_info);
+  }
+  DLG_LAUNCH_CHECK();
+  Y->leaf_rows.materialize(Y->Lx);
+  return DLG_OK;
+}
+// {lean leaf launches, materialisations, 1 if the current factor's leaf rows are the assembly's still, levels that may run lean}
+extern "C" int dlg_sparse_leaf_rows_stats(dlg_backend_t* b, long* stats, int nstats)
+{
+  if(!b || !b->sym || !stats) { dlg_set_error("no symbolic analysis yet"); return DLG_ERR_STATE; }
+  const SparseSym* Y = b->sym;
+  long lean = 0;
+  for(char c : Y->leaf_lean) lean += c;
+  const long v[] = { Y->leaf_rows.lean_launches, Y->leaf_rows.materialized, Y->leaf_rows.raw(Y->Lx) ? 1L : 0L, lean };
+  for(int i = 0; i < nstats && i < 4; i++) stats[i] = v[i];
   return DLG_OK;
 }
 

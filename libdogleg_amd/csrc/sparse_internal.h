@@ -19,6 +19,7 @@
 #include "dlg_internal.h"
 #include "sparse_symbolic.h"
 #include "sparse_region.h"
+#include "leaf_rows_state.h"
 
 namespace {
 constexpr int JFL_SEG = 16;             // workgroups per long Jt*x list (k_jtx_fin2_long)
@@ -143,6 +144,12 @@ struct SparseSym
   int64_t* augpos = nullptr;            // Lx offset of the augmented-row entry of every column
   int *xl_sn = nullptr;
   double* held_Lx = nullptr; const double* held_aug = nullptr; double held_lambda = 0.0;   // sparse_hold_factor
+  // The lean leaf launch (sparse_factor.hip, FMODE_LEAN_ROWS) leaves the rows below the merged leaves' member blocks as
+  // the assembly wrote them: which buffer is in that state (leaf_rows_state.h), the levels whose leaf launch may run lean
+  // (sparse_factor_setup: leaf_lean), the reciprocal pivots of the leaves' columns the launch leaves behind for
+  // k_leaf_rows_materialize ([2][N]: a set per panel buffer, leaf_rows.slot).  The backward solve picks its formula from
+  // the buffer's state (leaf_rows.raw) and the level (leaf_lean), nothing else.
+  LeafRowsState leaf_rows; std::vector<char> leaf_lean; double* leaf_rd = nullptr;
   double cur_lambda = 0.0;              // of the factorisation being enqueued (the top panels get it after the sum)
   double *ms_scr = nullptr, *ms_y = nullptr; int ms_lds_f = 0, ms_lds_b = 0;     // multi-right-hand-side solves (sparse_multi.hip)
   // leverage blocks (sparse_multi.hip, sparse_leverage_reach): per chunk of 16 measurement rows, the supernodes on the paths

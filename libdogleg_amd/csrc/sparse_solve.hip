@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(BWD_NT, BD_ONLY ? 4 : 1) k_solve_bwd_level(con
                                                             double* __restrict__ out, int use_aug,
                                                             const int* __restrict__ sn_bd_col, int top_lds, int xb_cap,
                                                             int* pr_flag, int pr_epoch, const int* __restrict__ info, DlgHandoff ho,
-                                                            double* xh, int xh_n, double* __restrict__ mm)
+                                                            double* xh, int xh_n, double* __restrict__ mm, int rows_raw)
 {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ int s_skip;
@@ -428,6 +428,17 @@ __global__ void __launch_bounds__(BWD_NT, BD_ONLY ? 4 : 1) k_solve_bwd_level(con
       }
     }
   }
+  // rows_raw, the lean variant: the member's block for the forward substitution below is fetched again here (the mat-vec's
+  // operands are dead, the lines are in cache since round 2; kept in registers across the mat-vec it spilled), all of it
+  // at once and behind the barrier's shadow
+  double Lz[4][4];
+  if(LEAN && rows_raw)
+  {
+#pragma unroll
+    for(int a = 0; a < 4; a++)
+#pragma unroll
+      for(int b = 0; b <= a; b++) Lz[a][b] = (tid < nmem && a < nbm) ? L[(m0 + a) + (size_t)(m0 + b)*nrows] : (a == b ? 1.0 : 0.0);
+  }
   __syncthreads();
   BW_STAMP(3);
   if(tinv_on)
@@ -444,9 +455,29 @@ __global__ void __launch_bounds__(BWD_NT, BD_ONLY ? 4 : 1) k_solve_bwd_level(con
     {
       double sum = 0.0;
       for(int p = 0; p < mv_parts; p++) sum += xp[p*256 + tid];
-      xs[tid] = myrhs - sum;
+      // rows_raw: the rows below are the assembly's W still (the lean leaf launch of the factorisation, sparse_factor.hip):
+      // sum = (W' x_b) of this column, and L_below' x_b = L_tt^-1 (W' x_b) is one forward substitution per member, on the
+      // member's thread; the right-hand side waits in this column's own entry of xp (part 0: read by nobody else)
+      if(rows_raw) { xs[tid] = sum; xp[tid] = myrhs; }
+      else xs[tid] = myrhs - sum;
     }
     __syncthreads();
+    if(rows_raw && tid < nmem)
+    {
+      // (a lean level's members have at most 4 columns: fac_level_params, L.leaf.  The member's block is in registers:
+      // since round 2, or fetched again behind the mat-vec)
+      double z[4];
+#pragma unroll
+      for(int a = 0; a < 4; a++)
+      {
+        double v = (a < nbm) ? xs[m0 + a] : 0.0;
+#pragma unroll
+        for(int b = 0; b < a; b++) v -= (LEAN ? Lz[a][b] : Lm[a][b])*z[b];
+        z[a] = v/(LEAN ? Lz[a][a] : Lm[a][a]);
+      }
+#pragma unroll
+      for(int a = 0; a < 4; a++) if(a < nbm) xs[m0 + a] = xp[m0 + a] - z[a];
+    }
     if(LEAN)
     {
       // rolled loops, the solved unknowns stay in xs: few registers, the latency is hidden by the
@@ -848,6 +879,12 @@ int sparse_solve_setup(dlg_backend* b)
       Y->bwd_epoch = 0;
     }
   }
+  // A level may run lean in the factorisation (sparse_factor_setup: leaf_lean) only where THIS file's launch of it reads the
+  // rows as what they then are: a per-level launch (below the one-launch region) every supernode of which has a
+  // block-diagonal top (bwd_bd: the members' substitution is where rows_raw acts).  The two set-ups look at different
+  // lists (the rank's work items there, the level's supernodes here): a level they disagree on stores its rows.
+  for(int l = 0; l < H.nlevels; l++)
+    if(Y->leaf_lean[l] && (l >= Y->bw_level0 || !Y->bwd_bd[l])) Y->leaf_lean[l] = 0;
   for(const void* k : { (const void*)&k_solve_fwd_level, (const void*)&k_solve_bwd_level<256, false>,
                         (const void*)&k_solve_bwd_level<256, true>, (const void*)&k_solve_bwd_level<512, false> })
     DLG_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET));
@@ -867,9 +904,12 @@ static void launch_bwd_level(dlg_backend* b, int nt, bool bd, int grid, int lds,
 {
   SparseSym* Y = b->sym;
   double* mm = bwd_diag_mm(b, l);
+  // (a level of merged leaves whose rows below the member blocks the factorisation left as the assembly's; l of a region is
+  // its first level, which sparse_solve_setup never leaves lean)
+  const int rows_raw = (Y->leaf_lean[l] && Y->leaf_rows.raw(Y->Lx)) ? 1 : 0;
 #define DLG_BW_LAUNCH(...) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_solve_bwd_level<__VA_ARGS__>), dim3(grid), dim3(nt), lds, b->stream, \
                                               items, Y->sn_rows, Y->perm, Y->Lx, Y->ywork, out, use_aug, Y->sn_bd_col, 256*l, Y->bwd_xb_cap, \
-                                              flag, epoch, Y->d_info, dlg_handoff(b, 1 << 21), xh, nxh, mm)
+                                              flag, epoch, Y->d_info, dlg_handoff(b, 1 << 21), xh, nxh, mm, rows_raw)
   if(nt == 256 && bd) DLG_BW_LAUNCH(256, true);
   else if(nt == 256) DLG_BW_LAUNCH(256, false);
   else { nt = 512; DLG_BW_LAUNCH(512, false); }
@@ -886,6 +926,7 @@ int sparse_solve(dlg_backend* b, const double* rhs, double* out)
   const int use_aug = (Y->aug_rhs != nullptr && Y->aug_rhs == rhs) ? 1 : 0;
   if(H.part_nranks > 1 && !use_aug)
   { dlg_set_error("with a subtree partition only the right-hand side that rode along with the factorisation (Jt x) can be solved for"); return DLG_ERR_STATE; }
+  if(!use_aug) DLG_CHECK(sparse_leaf_rows_materialize(b));      // (the forward solve reads the leaves' L_below itself)
   for(int l = 0; l < H.nlevels && !use_aug; l++)
   {
     const int n = H.xl_ptr[l+1] - H.xl_ptr[l];
