@@ -180,12 +180,18 @@ def test_all_four_stops():
     db.close()
 
 
-def _zero_column_batch(prm, B=32, chosen=(3, 17, 30), zero_col=2):
-    from problems.batch import MODE_ZERO_COLUMN
-    N, M, seed0 = 6, 40, 1
+def zero_column_oracle(prm, B=32, chosen=(3, 17, 30), zero_col=2, shape=(6, 40), seed0=1):
+    """the oracle on the "default" problems seed0 .. seed0 + B - 1 of `shape`, column zero_col of J exactly zero in the chosen"""
+    N, M = shape
     eps, noise, spread, _ = SETS["default"]
-    orc = bo.solve_batch(M, N, range(seed0, seed0 + B), eps, noise, spread, prm, zero_cols={b: zero_col for b in chosen})
-    assert_margin(orc, "zero-column batch")
+    return bo.solve_batch(M, N, range(seed0, seed0 + B), eps, noise, spread, prm, zero_cols={b: zero_col for b in chosen})
+
+
+def _zero_column_batch(prm, B=32, chosen=(3, 17, 30), zero_col=2, shape=(6, 40)):
+    from problems.batch import MODE_ZERO_COLUMN
+    (N, M), seed0 = shape, 1
+    orc = zero_column_oracle(prm, B, chosen, zero_col, shape, seed0)
+    assert_margin(orc, f"zero-column batch {shape}")
     db = device_batch(N, M, range(seed0, seed0 + B), "default")
     mode = np.zeros(B, dtype=np.uint8)
     mode[list(chosen)] = MODE_ZERO_COLUMN

@@ -210,9 +210,12 @@ def test_one_callback_and_constant_launches():
 
 # ---------------------------------------------------------------- 5. the lambda loop
 def test_lambda_loop_on_a_zero_column():
+    check_lambda_loop_on_a_zero_column(6, 40, 2)
+
+
+def check_lambda_loop_on_a_zero_column(N, M, c, B=32, chosen=(3, 17, 30)):
     from problems.batch import MODE_ZERO_COLUMN
-    N, M, B, c = 6, 40, 32, 2
-    chosen = [3, 17, 30]
+    chosen = list(chosen)
     seeds = np.arange(1, 1 + B)
     db, p, _ = solved(N, M, seeds)
     lam0 = np.zeros(B)
