@@ -473,6 +473,57 @@ int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned
  * Returns the number of entries written (at most n, at most 5). */
 int dogleg_amd_batch_uncertainty_last_stats(double* out, int n);
 
+/* ---- the products form of a batch (the batch twin of dogleg_optimize_dense_products): the callback reduces over its
+ * measurements itself and hands back, for every LIVE problem, norm2(x), Jt x and JtJ.  Nmeas is not an argument: every
+ * problem may have its own number of measurements, the library never sees them, and nothing of size Nmeas is stored.
+ * B independent problems of Nstate variables advance together in rounds; every problem has its own trust region, lambda
+ * and stopping test, and problem b does exactly what dogleg_optimize_dense_products does on that problem alone with the
+ * same parameters: the same trial points, accept / reject decisions, trust-region updates, lambda schedule (0 -> 1e-10 ->
+ * x10, only when a factorisation the reference would attempt fails) and the same ways to stop.  A round is one call of
+ * the callback, one launch of the library and one 4-byte read-back, whatever B is.  The result struct, the status codes
+ * and the meanings of evaluations and iterations are those of dogleg_amd_optimize_dense_batch; dogleg_amd_batch_last_stats
+ * reports the calling thread's last batch solve of either form.
+ *
+ * All pointers are device memory; live_dev and hip_stream as in dogleg_callback_device_batch_t.
+ *   p_dev      in : [B][Nstate]
+ *   norm2x_dev out: [B]
+ *   xtJ_dev    out: [B][Nstate], Jt x
+ *   JtJ_dev    out: [B][S], the layout chosen by parameters->JtJ_packed / JtJ_upper as in the reference:
+ *     unpacked            S = Nstate^2, row-major.  ONLY the entries [i][j] with j >= i are read (the triangle the
+ *                         reference's dpotrf 'L' reads through its column-major view); the others are never read and
+ *                         need not be written.
+ *     packed and upper    S = Nstate (Nstate + 1) / 2, row-major upper triangle: row 0 (Nstate entries), row 1 from its
+ *                         diagonal (Nstate - 1 entries), ...
+ *     packed, not upper   refused with a message and -1, as the reference refuses it.
+ * DOGLEG_AMD_BATCH_FAILED also covers a non-finite norm2x, a non-finite entry of xtJ and a non-finite entry of JtJ among
+ * those that are read (every one of them is checked, off the diagonal too).
+ *
+ * Refused with a message and -1, p untouched, no device work: a NULL p / f / results, B or Nstate 0, Nstate above
+ * DOGLEG_AMD_BATCH_MAX_NSTATE, the packed lower layout, a set communicator (one rank only), device memory that does not
+ * fit (the message names the size): B * (1 + Nstate + S) doubles of callback output plus B * (Nstate * (Nstate + 11) / 2 + 8)
+ * doubles of state.  parameters == NULL: the process-global set (unpacked).
+ * What the products form does not give: outlierness factors (they need J; the reference's outlier API refuses
+ * DENSE_PRODUCTS for the same reason). */
+typedef void (dogleg_callback_device_batch_products_t)(const double* p_dev, double* norm2x_dev, double* xtJ_dev,
+                                                       double* JtJ_dev, const unsigned char* live_dev, unsigned int B,
+                                                       void* hip_stream, void* cookie);
+int dogleg_amd_optimize_dense_products_batch(double* p, unsigned int B, unsigned int Nstate,
+                                             dogleg_callback_device_batch_products_t* f, void* cookie,
+                                             const dogleg_parameters2_t* parameters,
+                                             dogleg_amd_batch_result_t* results);
+/* Sigma_b = (JtJ + lambda I)^-1 and its diagonal with the JtJ the products callback returns at p[b]: the contract of
+ * dogleg_amd_dense_batch_uncertainty for lambda, covariance, variances and status (one callback with every live byte 1,
+ * then one launch; the same lambda schedule; a negative or NaN lambda[b], or anything non-finite among what is read of
+ * problem b's norm2x, xtJ and JtJ, fails that problem alone and gives it NaN outputs; a problem's bits do not depend on B
+ * or on its neighbours).  Of parameters only JtJ_packed / JtJ_upper are read (NULL: the global set).  There are no
+ * outlierness factors and no scale: they need J.  Refused with a message and -1 before any device work, outputs
+ * untouched: a NULL p / f / status, B or Nstate 0, Nstate above DOGLEG_AMD_BATCH_MAX_NSTATE, the packed lower layout, both
+ * outputs NULL, a set communicator, device memory that does not fit.  dogleg_amd_batch_uncertainty_last_stats covers it. */
+int dogleg_amd_dense_products_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate,
+                                                dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                const dogleg_parameters2_t* parameters,
+                                                double* lambda, double* covariance, double* variances, int* status);
+
 /* ---- extension (not in the reference): the Jacobian of a DEVICE callback checked against central differences, on the
  * device.  dogleg_testGradient* above take host callbacks, one variable a call.  Here the whole Jacobian is compared, and
  * on a sparse problem the variables that share no measurement row are perturbed together (Curtis, Powell, Reid): a

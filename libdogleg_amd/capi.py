@@ -64,6 +64,7 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_query_covariance",
     "dogleg_amd_optimize_dense_batch", "dogleg_amd_batch_last_stats",
     "dogleg_amd_dense_batch_uncertainty", "dogleg_amd_batch_uncertainty_last_stats",
+    "dogleg_amd_optimize_dense_products_batch", "dogleg_amd_dense_products_batch_uncertainty",
     "dogleg_amd_jacobian_colouring", "dogleg_amd_check_jacobian_device", "dogleg_amd_check_jacobian_device_batch",
     "dogleg_amd_testGradient_device", "dogleg_amd_check_jacobian_last_stats",
 ]
@@ -220,6 +221,9 @@ def lib():
     if hasattr(L, "dogleg_amd_dense_batch_uncertainty"):
         L.dogleg_amd_dense_batch_uncertainty.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, V, V, D, D, D, D, D, C.c_int, I]
         L.dogleg_amd_batch_uncertainty_last_stats.argtypes = [D, C.c_int]
+    if hasattr(L, "dogleg_amd_optimize_dense_products_batch"):
+        L.dogleg_amd_optimize_dense_products_batch.argtypes = [D, C.c_uint, C.c_uint, V, V, PP, C.POINTER(BatchResult)]
+        L.dogleg_amd_dense_products_batch_uncertainty.argtypes = [D, C.c_uint, C.c_uint, V, V, PP, D, D, D, I]
     if hasattr(L, "dogleg_amd_check_jacobian_device"):
         JR, JE = C.POINTER(JacobianReport), C.POINTER(JacobianEntry)
         L.dogleg_amd_jacobian_colouring.argtypes = [C.c_uint, C.c_uint, I, I, I]
@@ -303,10 +307,47 @@ def optimize_dense_batch(p0s, N, M, cb, cookie, params=None):
     B = p.shape[0]
     res = (BatchResult * max(B, 1))()
     rc = L.dogleg_amd_optimize_dense_batch(dptr(p), B, N, M, cb, cookie, C.byref(params) if params is not None else None, res)
+    return rc, p, _batch_results(res, B)
+
+
+def _batch_results(res, B):
+    """a (BatchResult * n) array as a numpy record array of its first B entries"""
     dt = np.dtype(dict(names=[n for n, _ in BatchResult._fields_], formats=[np.dtype(t) for _, t in BatchResult._fields_],
                        offsets=[getattr(BatchResult, n).offset for n, _ in BatchResult._fields_],
                        itemsize=C.sizeof(BatchResult)))
-    return rc, p, np.frombuffer(res, dtype=dt)[:B].copy()
+    return np.frombuffer(res, dtype=dt)[:B].copy()
+
+
+def optimize_dense_products_batch(p0s, N, cb, cookie, params=None):
+    """dogleg_amd_optimize_dense_products_batch: p0s (B, N) start points, cb the address of a
+    dogleg_callback_device_batch_products_t; the layout of JtJ is params.JtJ_packed / JtJ_upper.  Returns (rc, p (B, N),
+    results) as optimize_dense_batch."""
+    L = lib()
+    p = np.array(p0s, dtype=np.float64, copy=True).reshape(-1, N)
+    B = p.shape[0]
+    res = (BatchResult * max(B, 1))()
+    rc = L.dogleg_amd_optimize_dense_products_batch(dptr(p), B, N, cb, cookie, C.byref(params) if params is not None else None,
+                                                    res)
+    return rc, p, _batch_results(res, B)
+
+
+def dense_products_batch_uncertainty(p, N, cb, cookie, params=None, lam=None, want=("cov", "var")):
+    """dogleg_amd_dense_products_batch_uncertainty at the points p (B, N).  lam: (B,) or None (NULL: start at 0); want: which
+    of "cov", "var" to ask for.  Returns dict(rc, status, lam (None if lam was None), cov (B, N, N) / var (B, N) as asked)."""
+    L = lib()
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, N)
+    B = p.shape[0]
+    out = dict(lam=None if lam is None else np.array(lam, dtype=np.float64, copy=True).reshape(B))
+    out["status"] = np.full(B, -1, dtype=np.int32)
+    if "cov" in want:
+        out["cov"] = np.zeros((B, N, N))
+    if "var" in want:
+        out["var"] = np.zeros((B, N))
+    opt = lambda k: dptr(out[k]) if out.get(k) is not None else None
+    out["rc"] = L.dogleg_amd_dense_products_batch_uncertainty(dptr(p), B, N, cb, cookie,
+                                                              C.byref(params) if params is not None else None,
+                                                              opt("lam"), opt("cov"), opt("var"), iptr(out["status"]))
+    return out
 
 
 def batch_last_stats():

@@ -65,6 +65,22 @@ bool batch_shape_ok(const char* who, unsigned int B, unsigned int Nstate, unsign
   return true;
 }
 
+// the products form: no Nmeas, and the layout of JtJ from the parameters (dogleg.c:597-601 refuses packed lower too)
+bool products_batch_ok(const char* who, unsigned int B, unsigned int Nstate, const dogleg_parameters2_t* prm)
+{
+  if(B == 0 || Nstate == 0) { MSG("%s: B = %u, Nstate = %u: neither may be 0", who, B, Nstate); return false; }
+  if(Nstate > DOGLEG_AMD_BATCH_MAX_NSTATE)
+  {
+    MSG("%s: Nstate = %u, the batch kernels take at most %d variables (larger problems: a loop over dogleg_optimize_dense_products)",
+        who, Nstate, DOGLEG_AMD_BATCH_MAX_NSTATE);
+    return false;
+  }
+  if(B > 0x7fffffffu/4) { MSG("%s: B = %u problems: beyond the index range of the batch kernels", who, B); return false; }
+  if(prm->JtJ_packed && !prm->JtJ_upper)
+  { MSG("%s: JtJ_packed without JtJ_upper (a packed lower triangle) is not supported: use the packed upper or the unpacked layout", who); return false; }
+  return true;
+}
+
 // ---- the Jacobian of a device callback against central differences
 constexpr double GRADTEST_DELTA = 1e-6;             // dogleg.c:352
 // the pattern arguments of a device callback's entry points: NJnnz == 0 with NULL pointers is dense
@@ -272,6 +288,31 @@ int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned
   return dlg_dense_batch_uncertainty_run(p, B, Nstate, Nmeas, f, cookie, lambda, covariance, variances, factors, scale, fs, status);
 }
 int dogleg_amd_batch_uncertainty_last_stats(double* out, int n) { return out ? dlg_dense_batch_uncertainty_last_stats(out, n) : 0; }
+
+// ---- the products form of the two: the callback hands back norm2(x), Jt x and JtJ, so there is no Nmeas
+int dogleg_amd_optimize_dense_products_batch(double* p, unsigned int B, unsigned int Nstate,
+                                             dogleg_callback_device_batch_products_t* f, void* cookie,
+                                             const dogleg_parameters2_t* parameters, dogleg_amd_batch_result_t* results)
+{
+  const char* who = "dogleg_amd_optimize_dense_products_batch";
+  if(!p || !f || !results) { MSG("%s: p, the callback and results must be given", who); return -1; }
+  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
+  if(!products_batch_ok(who, B, Nstate, prm) || !one_rank_only(who)) return -1;
+  return dlg_dense_products_batch_run(p, B, Nstate, f, cookie, prm, results);
+}
+int dogleg_amd_dense_products_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate,
+                                                dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                const dogleg_parameters2_t* parameters,
+                                                double* lambda, double* covariance, double* variances, int* status)
+{
+  const char* who = "dogleg_amd_dense_products_batch_uncertainty";
+  if(!p || !f || !status) { MSG("%s: p, the callback and status must be given", who); return -1; }
+  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
+  if(!products_batch_ok(who, B, Nstate, prm)) return -1;
+  if(!covariance && !variances) { MSG("%s: neither covariance nor variances is asked for", who); return -1; }
+  if(!one_rank_only(who)) return -1;
+  return dlg_dense_products_batch_uncertainty_run(p, B, Nstate, f, cookie, !prm->JtJ_packed, lambda, covariance, variances, status);
+}
 
 // ---- extension (not in the reference): the Jacobian of a device callback against central differences (gradcheck.hip)
 int dogleg_amd_jacobian_colouring(unsigned Nstate, unsigned Nmeas, const int* Jt_colptr, const int* Jt_rowidx, int* colour)

@@ -10,6 +10,14 @@ int  dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int
 int  dlg_dense_batch_uncertainty_run(const double* p, unsigned int B, unsigned int N, unsigned int M,
                                      dogleg_callback_device_batch_t* f, void* cookie, double* lambda, double* covariance,
                                      double* variances, double* factors, double* scale, int fs, int* status);
+// the products form of the two (dogleg_amd_optimize_dense_products_batch, dogleg_amd_dense_products_batch_uncertainty): the
+// layout of JtJ is prm->JtJ_packed (packed means packed upper here: the caller refused packed lower) / `unpacked`
+int  dlg_dense_products_batch_run(double* p, unsigned int B, unsigned int N, dogleg_callback_device_batch_products_t* f,
+                                  void* cookie, const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results);
+int  dlg_dense_products_batch_uncertainty_run(const double* p, unsigned int B, unsigned int N,
+                                              dogleg_callback_device_batch_products_t* f, void* cookie, bool unpacked,
+                                              double* lambda, double* covariance, double* variances, int* status);
+// the last call of either form
 int  dlg_dense_batch_uncertainty_last_stats(double* out, int n);
 // the device buffers, the stream, the page-locked counter and staging kept between calls (dogleg_amd_release_cache)
 void dlg_dense_batch_release();

@@ -17,6 +17,11 @@
 //
 // dogleg_amd_dense_batch_uncertainty (k_batch_uncertainty, below the round kernel): covariance, variances and outlierness
 // factors of every problem at given points, one callback and one launch, on the same sweep, Cholesky and cache.
+//
+// The products form (dogleg_amd_optimize_dense_products_batch, dogleg_amd_dense_products_batch_uncertainty): the callback
+// hands back norm2(x), Jt x and JtJ of every live problem, so there is no sweep.  A second front end (load_products) puts
+// the same three things where sweep_point leaves them; from evaluate_step on both forms run the same functions.  The
+// kernels are templates over the form: the J-form instantiations keep their arithmetic and their order of operations.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +46,16 @@ enum { F_CAUCHY = 1, F_GN = 2, F_EDGE = 4, F_STARTED = 8 };
 enum { SC_N2X, SC_TR, SC_LAMBDA, SC_N2C, SC_N2GN, SC_EI, SC_COUNT = 8 };
 enum { ST_FLAGS, ST_ITER, ST_EVAL, ST_STATUS, ST_COUNT = 4 };
 
+enum { FORM_J = 0, FORM_PRODUCTS = 1 };
+
+// what a products callback wrote: norm2(x) [B], Jt x [B][N], JtJ [B][S]; unpacked: S = N^2 row-major, of which the
+// entries [i][j], j >= i, are read; otherwise S = NP, row-major packed upper = the kernels' packed lower column-major
+struct ProductsDev
+{
+  const double* n2x; const double* xtJ; const double* JtJ;
+  int unpacked;
+};
+
 struct BatchDev
 {
   int B, N, M, NP;
@@ -49,6 +64,7 @@ struct BatchDev
   int* st; unsigned char* live; int* counter;
   int max_iterations;
   double trustregion0, dec_factor, dec_thr, inc_factor, inc_thr, jtx_thr, upd_thr, tr_thr;
+  ProductsDev P;               // FORM_PRODUCTS (x, J, M unused there)
 };
 
 template <int NMAX> struct BatchCfg
@@ -57,6 +73,12 @@ template <int NMAX> struct BatchCfg
   static constexpr int NE = (NP + 63)/64;                       // entries of JtJ a lane accumulates
   static constexpr int SCR = NP > BATCH_TILE + 64 ? NP : BATCH_TILE + 64;     // the factor; during the sweep: the tile and its x
   static constexpr int LDSW = NP + SCR + NMAX;                  // doubles of LDS per wavefront
+};
+// the same per form: the products form has no row tile, the second region holds the factor only
+template <int NMAX, int FORM> struct FormCfg
+{
+  static constexpr int SCR = FORM == FORM_J ? BatchCfg<NMAX>::SCR : BatchCfg<NMAX>::NP;
+  static constexpr int LDSW = BatchCfg<NMAX>::NP + SCR + NMAX;
 };
 
 // LDS of ONE wavefront written by some lanes and read by others: the hardware keeps a wave's LDS operations in
@@ -207,23 +229,78 @@ __device__ __forceinline__ double sweep_point(const double* Jb, const double* xb
   return n2x;
 }
 
-// one round of problem b; returns whether the problem is still live
+// the front end of the products form: what the callback wrote for problem b goes where sweep_point leaves its results.
+// Lane l copies the entries l, l + 64, ... of the packed triangle into SA (packed upper: the same bytes, coalesced;
+// unpacked: entry (ei, ej), ei >= ej, is G[ej][ei], the triangle the reference's dpotrf 'L' reads through its
+// column-major view, dogleg.c:802-806; the other triangle is never read).  finite: whether EVERYTHING read is finite --
+// an off-diagonal NaN of JtJ does not show on the diagonal the way a NaN of J does.
 template <int NMAX>
+__device__ __forceinline__ double load_products(const ProductsDev& P, int b, int N, int NP, int lane, double* SA,
+                                                double& g_out, bool& finite)
+{
+  using C = BatchCfg<NMAX>;
+  bool fin = true;
+  wsync();
+  if(P.unpacked)
+  {
+    int ei[C::NE], ej[C::NE];
+    packed_entries<NMAX>(N, NP, lane, ei, ej);
+    const double* Gb = P.JtJ + (size_t)b*N*N;
+#pragma unroll
+    for(int k = 0; k < C::NE; k++)
+      if(lane + 64*k < NP)
+      {
+        const double v = Gb[ej[k]*N + ei[k]];
+        fin = fin && isfinite(v);
+        SA[lane + 64*k] = v;
+      }
+  }
+  else
+  {
+    const double* Gb = P.JtJ + (size_t)b*NP;
+#pragma unroll
+    for(int k = 0; k < C::NE; k++)
+      if(lane + 64*k < NP)
+      {
+        const double v = Gb[lane + 64*k];
+        fin = fin && isfinite(v);
+        SA[lane + 64*k] = v;
+      }
+  }
+  wsync();
+  const double g = lane < N ? P.xtJ[(size_t)b*N + lane] : 0.0;
+  const double n2x = P.n2x[b];
+  finite = __all(fin && isfinite(g) && isfinite(n2x));
+  g_out = g;
+  return n2x;
+}
+
+// one round of problem b; returns whether the problem is still live
+template <int NMAX, int FORM>
 __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
 {
   using C = BatchCfg<NMAX>;
   const int N = A.N, M = A.M, NP = A.NP;
   double* SA = S;                      // JtJ of the point the step is taken from
   double* SL = S + C::NP;              // its factor; during the sweep the row tile
-  double* SV = SL + C::SCR;            // an N-vector
+  double* SV = SL + FormCfg<NMAX, FORM>::SCR;     // an N-vector
   const size_t bN = (size_t)b*N;
 
-  // ---- the sweep over the trial point's x and J: norm2(x), Jt x, JtJ ----
-  double gacc;
-  const double n2x = sweep_point<NMAX>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc);
-  // a non-finite x or J shows in norm2(x) or on the diagonal of JtJ
-  const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
-  const bool finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
+  double gacc, n2x;
+  bool finite;
+  if constexpr(FORM == FORM_J)
+  {
+    // ---- the sweep over the trial point's x and J: norm2(x), Jt x, JtJ ----
+    n2x = sweep_point<NMAX>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc);
+    // a non-finite x or J shows in norm2(x) or on the diagonal of JtJ
+    const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
+    finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
+  }
+  else
+  {
+    (void)M;
+    n2x = load_products<NMAX>(A.P, b, N, NP, lane, SA, gacc, finite);
+  }
 
   // ---- evaluate_step (dogleg.c:1303-1356) and the swap of the two points (1427-1470) ----
   int* st = A.st + (size_t)ST_COUNT*b; double* sc = A.sc + (size_t)SC_COUNT*b;
@@ -357,15 +434,16 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
   return status == 0;
 }
 
-template <int NMAX>
+template <int NMAX, int FORM>
 __global__ void __launch_bounds__(64*BATCH_WPB) k_batch_round(BatchDev A)
 {
-  __shared__ double lds[BATCH_WPB*BatchCfg<NMAX>::LDSW];
+  constexpr int LDSW = FormCfg<NMAX, FORM>::LDSW;
+  __shared__ double lds[BATCH_WPB*LDSW];
   __shared__ int s_live[BATCH_WPB];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x*BATCH_WPB + w;
   bool still = false;
-  if(b < A.B && A.live[b]) still = batch_problem<NMAX>(A, b, lane, lds + w*BatchCfg<NMAX>::LDSW);
+  if(b < A.B && A.live[b]) still = batch_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
   if(lane == 0) s_live[w] = still ? 1 : 0;
   __syncthreads();
   if(threadIdx.x == 0)
@@ -387,6 +465,7 @@ struct UncDev
   const double* x; const double* J;
   double *lam, *scale, *cov, *var, *fac;     // cov, var, fac (and scale with fac): nullptr where not asked for
   int* status;
+  ProductsDev P;               // FORM_PRODUCTS (x, J, M, fs, NF unused there; fac and scale nullptr: they need J)
 };
 
 // x' (B + B^2) x scale / 8 with B = (A_f - I)^-1, dogleg.h above dogleg_getOutliernessFactors (the arithmetic of
@@ -407,20 +486,27 @@ __device__ inline double factor2(double a00, double a01, double a11, double x0, 
   return (xBx + (v0*v0 + v1*v1)/(det*det))*k;
 }
 
-template <int NMAX>
+template <int NMAX, int FORM>
 __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
 {
   using C = BatchCfg<NMAX>;
   const int N = A.N, M = A.M, NP = A.NP;
   double* SA = S;                      // JtJ, then Sigma
   double* SL = S + C::NP;              // the row tile of the sweeps; between them the factor and its inverse
-  const double* Jb = A.J + (size_t)b*M*N;
-  const double* xb = A.x + (size_t)b*M;
+  const double* Jb = nullptr; const double* xb = nullptr;
 
-  double gacc;
-  const double n2x = sweep_point<NMAX>(Jb, xb, N, M, NP, lane, SA, SL, gacc);
-  const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
-  bool ok = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
+  double gacc, n2x;
+  bool ok;
+  if constexpr(FORM == FORM_J)
+  {
+    Jb = A.J + (size_t)b*M*N;
+    xb = A.x + (size_t)b*M;
+    n2x = sweep_point<NMAX>(Jb, xb, N, M, NP, lane, SA, SL, gacc);
+    const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
+    ok = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
+  }
+  else
+    n2x = load_products<NMAX>(A.P, b, N, NP, lane, SA, gacc, ok);
 
   // ---- the factorisation at lambda[b]; a pivot <= 0 moves lambda as the solve does (dogleg.c:634-820) ----
   double lam = A.lam[b];
@@ -496,7 +582,7 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
       const int i = e/N;
       A.cov[(size_t)b*N*N + e] = sym_at(SA, i, e - i*N, N);
     }
-  if(!A.fac) return;
+  if(FORM != FORM_J || !A.fac) return;
 
   // ---- the second sweep over J: tiles of T rows, row stride N | 1 in LDS (lanes read different rows: an odd stride keeps
   // them on different banks), lane t takes feature t of the tile: a = J_f Sigma J_f' against Sigma in LDS ----
@@ -564,13 +650,14 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
   }
 }
 
-template <int NMAX>
+template <int NMAX, int FORM>
 __global__ void __launch_bounds__(64*BATCH_WPB) k_batch_uncertainty(UncDev A)
 {
-  __shared__ double lds[BATCH_WPB*(BatchCfg<NMAX>::NP + BatchCfg<NMAX>::SCR)];
+  constexpr int LDSW = BatchCfg<NMAX>::NP + FormCfg<NMAX, FORM>::SCR;
+  __shared__ double lds[BATCH_WPB*LDSW];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x*BATCH_WPB + w;
-  if(b < A.B) unc_problem<NMAX>(A, b, lane, lds + w*(BatchCfg<NMAX>::NP + BatchCfg<NMAX>::SCR));
+  if(b < A.B) unc_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
 }
 
 __global__ void __launch_bounds__(256) k_batch_init(BatchDev A)
@@ -591,7 +678,7 @@ struct BatchCache
   hipStream_t stream = nullptr;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   int* h_counter = nullptr;
-  void* d_eval = nullptr; size_t eval_bytes = 0;      // x, J of the trial points
+  void* d_eval = nullptr; size_t eval_bytes = 0;      // x, J of the trial points; products form: norm2x | xtJ | JtJ
   void* d_state = nullptr; size_t state_bytes = 0;    // everything else
   void* h_stage = nullptr; size_t stage_bytes = 0;    // page-locked: what the uncertainty call uploads and reads back
 };
@@ -647,7 +734,7 @@ int cache_open(const char* who)
   }
   return 0;
 }
-// the two device buffers of the cache, grown to eval_bytes and state_bytes
+// the two device buffers of the cache, grown to eval_bytes and state_bytes (M == 0: the products form, for the message)
 bool cache_ensure(const char* who, unsigned int B, unsigned int N, unsigned int M, size_t eval_bytes, size_t state_bytes)
 {
   BatchCache& K = g_cache;
@@ -658,8 +745,10 @@ bool cache_ensure(const char* who, unsigned int B, unsigned int N, unsigned int 
     {
       (void)hipGetLastError(); *ptr = nullptr;
       dlg_set_error("%s: cannot allocate %zu bytes of device memory", who, want);
-      BMSG("%s: B = %u problems of %u x %u need %zu + %zu bytes of device memory: the allocation of %zu failed", who, B, M, N,
-           eval_bytes, state_bytes, want);
+      if(M) BMSG("%s: B = %u problems of %u x %u need %zu + %zu bytes of device memory: the allocation of %zu failed", who, B, M, N,
+                 eval_bytes, state_bytes, want);
+      else  BMSG("%s: B = %u problems of %u variables need %zu bytes of callback output + %zu bytes of state in device memory: "
+                 "the allocation of %zu failed", who, B, N, eval_bytes, state_bytes, want);
       return false;
     }
     *have = want;
@@ -668,33 +757,77 @@ bool cache_ensure(const char* who, unsigned int B, unsigned int N, unsigned int 
   return ensure(&K.d_eval, &K.eval_bytes, eval_bytes) && ensure(&K.d_state, &K.state_bytes, state_bytes);
 }
 
-int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f, void* cookie,
+// the callback of a call and what it writes: the J form (fJ: x, J of Nmeas = M rows) or the products form (fP: norm2x,
+// xtJ, JtJ; M is 0 there)
+struct BatchForm
+{
+  dogleg_callback_device_batch_t* fJ;
+  dogleg_callback_device_batch_products_t* fP;
+  bool unpacked;               // products: JtJ as N x N
+  bool products() const { return fP != nullptr; }
+  unsigned int S(unsigned int N) const { return unpacked ? N*N : N*(N + 1)/2; }
+};
+// where the products callback's three outputs lie in the evaluation buffer
+struct ProductsLayout { size_t n2_bytes, g_bytes, G_bytes; };
+ProductsLayout products_layout(const BatchForm& F, unsigned int B, unsigned int N)
+{
+  return { align256(sizeof(double)*(size_t)B), align256(sizeof(double)*(size_t)B*N), align256(sizeof(double)*(size_t)B*F.S(N)) };
+}
+ProductsDev products_dev(const BatchForm& F, const ProductsLayout& L, void* d_eval)
+{
+  ProductsDev P;
+  char* q = (char*)d_eval;
+  P.n2x = (double*)q; q += L.n2_bytes; P.xtJ = (double*)q; q += L.g_bytes; P.JtJ = (double*)q;
+  P.unpacked = F.unpacked ? 1 : 0;
+  return P;
+}
+
+template <int FORM> void launch_round(unsigned int N, dim3 grid, dim3 block, hipStream_t st, const BatchDev& A)
+{
+  if(N <= 8)       hipLaunchKernelGGL((k_batch_round<8, FORM>), grid, block, 0, st, A);
+  else if(N <= 16) hipLaunchKernelGGL((k_batch_round<16, FORM>), grid, block, 0, st, A);
+  else if(N <= 24) hipLaunchKernelGGL((k_batch_round<24, FORM>), grid, block, 0, st, A);
+  else             hipLaunchKernelGGL((k_batch_round<32, FORM>), grid, block, 0, st, A);
+}
+template <int FORM> void launch_uncertainty(unsigned int N, dim3 grid, dim3 block, hipStream_t st, const UncDev& A)
+{
+  if(N <= 8)       hipLaunchKernelGGL((k_batch_uncertainty<8, FORM>), grid, block, 0, st, A);
+  else if(N <= 16) hipLaunchKernelGGL((k_batch_uncertainty<16, FORM>), grid, block, 0, st, A);
+  else if(N <= 24) hipLaunchKernelGGL((k_batch_uncertainty<24, FORM>), grid, block, 0, st, A);
+  else             hipLaunchKernelGGL((k_batch_uncertainty<32, FORM>), grid, block, 0, st, A);
+}
+
+int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F, void* cookie,
                const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)
 {
-  const char* who = "dogleg_amd_optimize_dense_batch";
+  const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch" : "dogleg_amd_optimize_dense_batch";
   if(cache_open(who)) return -1;
   BatchCache& K = g_cache;
   const int NP = (int)(N*(N + 1)/2);
   // sizes in doubles first: B * M * (N + 1) can pass 2^64 bytes
-  const double eval_d = (double)B*(double)M*((double)N + 1.0);
+  const double eval_d = F.products() ? (double)B*(1.0 + N + F.S(N)) : (double)B*(double)M*((double)N + 1.0);
   const double state_d = (double)B*(5.0*N + NP + SC_COUNT + 1.0);
   if((eval_d + state_d)*8.0 > 1.0e15)
   {
     dlg_set_error("%s: %.3g bytes of device memory", who, (eval_d + state_d)*8.0);
-    BMSG("%s: B = %u problems of %u x %u need %.3g bytes of device memory", who, B, M, N, (eval_d + state_d)*8.0);
+    if(F.products()) BMSG("%s: B = %u problems of %u variables need %.3g bytes of device memory", who, B, N, (eval_d + state_d)*8.0);
+    else             BMSG("%s: B = %u problems of %u x %u need %.3g bytes of device memory", who, B, M, N, (eval_d + state_d)*8.0);
     return -1;
   }
   const size_t x_bytes = align256(sizeof(double)*(size_t)B*M), J_bytes = align256(sizeof(double)*(size_t)B*M*N);
   const size_t vec_bytes = align256(sizeof(double)*(size_t)B*N), G_bytes = align256(sizeof(double)*(size_t)B*NP);
   const size_t sc_bytes = align256(sizeof(double)*(size_t)B*SC_COUNT), st_bytes = align256(sizeof(int)*(size_t)B*ST_COUNT);
   const size_t live_bytes = align256(B);
-  const size_t eval_bytes = x_bytes + J_bytes, state_bytes = 5*vec_bytes + G_bytes + sc_bytes + st_bytes + live_bytes + 256;
+  const ProductsLayout PL = products_layout(F, B, N);
+  const size_t eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : x_bytes + J_bytes;
+  const size_t state_bytes = 5*vec_bytes + G_bytes + sc_bytes + st_bytes + live_bytes + 256;
   if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes)) return -1;
 
   BatchDev A;
   A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = NP;
   char* q = (char*)K.d_eval;
   A.x = (double*)q; q += x_bytes; A.J = (double*)q;
+  A.P = products_dev(F, PL, K.d_eval);
   q = (char*)K.d_state;
   A.p_before = (double*)q; q += vec_bytes; A.p_trial = (double*)q; q += vec_bytes; A.g = (double*)q; q += vec_bytes;
   A.cauchy = (double*)q; q += vec_bytes; A.gn = (double*)q; q += vec_bytes; A.JtJ = (double*)q; q += G_bytes;
@@ -727,12 +860,14 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg
     }
     BHIP(hipMemsetAsync(A.counter, 0, sizeof(int), st));
     if(timing) BHIP(hipEventRecord(K.ev[0], st));
-    f(A.p_trial, const_cast<double*>(A.x), const_cast<double*>(A.J), A.live, B, (void*)st, cookie);
+    if(F.products())
+      F.fP(A.p_trial, const_cast<double*>(A.P.n2x), const_cast<double*>(A.P.xtJ), const_cast<double*>(A.P.JtJ), A.live, B,
+           (void*)st, cookie);
+    else
+      F.fJ(A.p_trial, const_cast<double*>(A.x), const_cast<double*>(A.J), A.live, B, (void*)st, cookie);
     if(timing) BHIP(hipEventRecord(K.ev[1], st));
-    if(N <= 8)       hipLaunchKernelGGL(k_batch_round<8>, grid, block, 0, st, A);
-    else if(N <= 16) hipLaunchKernelGGL(k_batch_round<16>, grid, block, 0, st, A);
-    else if(N <= 24) hipLaunchKernelGGL(k_batch_round<24>, grid, block, 0, st, A);
-    else             hipLaunchKernelGGL(k_batch_round<32>, grid, block, 0, st, A);
+    if(F.products()) launch_round<FORM_PRODUCTS>(N, grid, block, st, A);
+    else             launch_round<FORM_J>(N, grid, block, st, A);
     BHIP(hipGetLastError());
     if(timing) BHIP(hipEventRecord(K.ev[2], st));
     BHIP(hipMemcpyAsync(K.h_counter, A.counter, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -766,19 +901,20 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg
   return 0;
 }
 
-int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f, void* cookie,
+int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F, void* cookie,
                double* lambda, double* covariance, double* variances, double* factors, double* scale, int fs, int* status)
 {
-  const char* who = "dogleg_amd_dense_batch_uncertainty";
+  const char* who = F.products() ? "dogleg_amd_dense_products_batch_uncertainty" : "dogleg_amd_dense_batch_uncertainty";
   double* const ts = t_unc_stats;              // kernel launches, synchronisations, copies + fills: counted where they happen
   for(int k = 0; k < 5; k++) ts[k] = 0.0;
   const unsigned int NF = M/(unsigned int)fs;
-  const double eval_d = (double)B*(double)M*((double)N + 1.0);
+  const double eval_d = F.products() ? (double)B*(1.0 + N + F.S(N)) : (double)B*(double)M*((double)N + 1.0);
   const double state_d = (double)B*((double)N + 3.0 + (variances ? N : 0.0) + (covariance ? (double)N*N : 0.0) + (factors ? NF : 0.0));
   if((eval_d + state_d)*8.0 > 1.0e15)
   {
     dlg_set_error("%s: %.3g bytes of device memory", who, (eval_d + state_d)*8.0);
-    BMSG("%s: B = %u problems of %u x %u need %.3g bytes of device memory", who, B, M, N, (eval_d + state_d)*8.0);
+    if(F.products()) BMSG("%s: B = %u problems of %u variables need %.3g bytes of device memory", who, B, N, (eval_d + state_d)*8.0);
+    else             BMSG("%s: B = %u problems of %u x %u need %.3g bytes of device memory", who, B, M, N, (eval_d + state_d)*8.0);
     return -1;
   }
   // (the arithmetic above needs no device: a call that cannot fit is refused before any device work)
@@ -793,7 +929,9 @@ int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, 
   const size_t fac_bytes = factors ? align256(sizeof(double)*(size_t)B*NF) : 0;
   const size_t o_lam = p_bytes, o_scale = o_lam + b_bytes, o_st = o_scale + b_bytes, o_var = o_st + st_bytes;
   const size_t o_cov = o_var + var_bytes, o_fac = o_cov + cov_bytes, io_bytes = o_fac + fac_bytes;
-  const size_t eval_bytes = x_bytes + J_bytes, state_bytes = io_bytes + align256(B);
+  const ProductsLayout PL = products_layout(F, B, N);
+  const size_t eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : x_bytes + J_bytes;
+  const size_t state_bytes = io_bytes + align256(B);
   if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes)) return -1;
   if(K.stage_bytes < io_bytes)
   {
@@ -811,6 +949,7 @@ int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, 
   UncDev A;
   A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = (int)(N*(N + 1)/2); A.fs = fs; A.NF = (int)NF;
   A.x = (double*)K.d_eval; A.J = (double*)((char*)K.d_eval + x_bytes);
+  A.P = products_dev(F, PL, K.d_eval);
   double* d_p = (double*)d;
   A.lam = (double*)(d + o_lam); A.scale = factors ? (double*)(d + o_scale) : nullptr; A.status = (int*)(d + o_st);
   A.var = variances ? (double*)(d + o_var) : nullptr; A.cov = covariance ? (double*)(d + o_cov) : nullptr;
@@ -827,13 +966,15 @@ int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, 
   BHIP(hipMemcpyAsync(d, h, o_st, hipMemcpyHostToDevice, st)); ts[2] += 1.0;
   BHIP(hipMemsetAsync(d_live, 1, B, st)); ts[2] += 1.0;
   if(timing) BHIP(hipEventRecord(K.ev[0], st));
-  f(d_p, const_cast<double*>(A.x), const_cast<double*>(A.J), d_live, B, (void*)st, cookie);
+  if(F.products())
+    F.fP(d_p, const_cast<double*>(A.P.n2x), const_cast<double*>(A.P.xtJ), const_cast<double*>(A.P.JtJ), d_live, B, (void*)st,
+         cookie);
+  else
+    F.fJ(d_p, const_cast<double*>(A.x), const_cast<double*>(A.J), d_live, B, (void*)st, cookie);
   if(timing) BHIP(hipEventRecord(K.ev[1], st));
   const dim3 grid((B + BATCH_WPB - 1)/BATCH_WPB), block(64*BATCH_WPB);
-  if(N <= 8)       hipLaunchKernelGGL(k_batch_uncertainty<8>, grid, block, 0, st, A);
-  else if(N <= 16) hipLaunchKernelGGL(k_batch_uncertainty<16>, grid, block, 0, st, A);
-  else if(N <= 24) hipLaunchKernelGGL(k_batch_uncertainty<24>, grid, block, 0, st, A);
-  else             hipLaunchKernelGGL(k_batch_uncertainty<32>, grid, block, 0, st, A);
+  if(F.products()) launch_uncertainty<FORM_PRODUCTS>(N, grid, block, st, A);
+  else             launch_uncertainty<FORM_J>(N, grid, block, st, A);
   BHIP(hipGetLastError()); ts[0] += 1.0;
   if(timing) BHIP(hipEventRecord(K.ev[2], st));
   BHIP(hipMemcpyAsync(h + o_lam, d + o_lam, io_bytes - o_lam, hipMemcpyDeviceToHost, st)); ts[2] += 1.0;
@@ -860,7 +1001,15 @@ int dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int 
                         void* cookie, const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)
 {
   std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = run_locked(p, B, N, M, f, cookie, prm, results);
+  const int rc = run_locked(p, B, N, M, BatchForm{f, nullptr, false}, cookie, prm, results);
+  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
+  return rc;
+}
+int dlg_dense_products_batch_run(double* p, unsigned int B, unsigned int N, dogleg_callback_device_batch_products_t* f,
+                                 void* cookie, const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)
+{
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int rc = run_locked(p, B, N, 0, BatchForm{nullptr, f, !prm->JtJ_packed}, cookie, prm, results);
   if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
   return rc;
 }
@@ -869,7 +1018,18 @@ int dlg_dense_batch_uncertainty_run(const double* p, unsigned int B, unsigned in
                                      double* variances, double* factors, double* scale, int fs, int* status)
 {
   std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = unc_locked(p, B, N, M, f, cookie, lambda, covariance, variances, factors, scale, fs, status);
+  const int rc = unc_locked(p, B, N, M, BatchForm{f, nullptr, false}, cookie, lambda, covariance, variances, factors, scale, fs,
+                            status);
+  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
+  return rc;
+}
+int dlg_dense_products_batch_uncertainty_run(const double* p, unsigned int B, unsigned int N,
+                                             dogleg_callback_device_batch_products_t* f, void* cookie, bool unpacked,
+                                             double* lambda, double* covariance, double* variances, int* status)
+{
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int rc = unc_locked(p, B, N, 0, BatchForm{nullptr, f, unpacked}, cookie, lambda, covariance, variances, nullptr, nullptr, 1,
+                            status);
   if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
   return rc;
 }

@@ -149,6 +149,9 @@ JACOBIAN_ONE_AT_A_TIME = 1
 
 # dogleg_callback_device_batch_t
 CB_DEVICE_BATCH = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p)
+# dogleg_callback_device_batch_products_t
+CB_DEVICE_BATCH_PRODUCTS = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p,
+                                       C.c_void_p)
 
 CB_SPARSE = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double),
                         C.POINTER(CholmodSparse), C.c_void_p)
