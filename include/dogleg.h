@@ -397,7 +397,8 @@ int dogleg_amd_query_covariance(double* out, int nq, const int* qrow, const int*
  *   hip_stream  : enqueue here, do not synchronise (as dogleg_callback_device_t)
  *
  * Limits (refused with a message and -1): B, Nstate or Nmeas 0, a NULL p / f / results, Nstate above
- * DOGLEG_AMD_BATCH_MAX_NSTATE (larger problems: a loop over dogleg_optimize_dense2), a set communicator (one rank only),
+ * DOGLEG_AMD_BATCH_MAX_NSTATE = 64, the width of a wavefront: one lane holds one variable (larger problems: a loop over
+ * dogleg_optimize_dense2), a set communicator (one rank only),
  * device memory: B * Nmeas * (Nstate + 1) doubles for x and J of the trial points, plus B * (Nstate * (Nstate + 11) / 2 + 8)
  * doubles of state (a call that does not fit fails with a message that names the size).  The debug / debug_vnlog bits of the parameters are ignored.  There is no returnContext: the
  * covariance and the outlierness factors of every problem come from dogleg_amd_dense_batch_uncertainty below; for the factor
@@ -405,7 +406,7 @@ int dogleg_amd_query_covariance(double* out, int nq, const int* qrow, const int*
 typedef void (dogleg_callback_device_batch_t)(const double* p_dev, double* x_dev, double* J_dev,
                                               const unsigned char* live_dev, unsigned int B,
                                               void* hip_stream, void* cookie);
-#define DOGLEG_AMD_BATCH_MAX_NSTATE     32
+#define DOGLEG_AMD_BATCH_MAX_NSTATE     64
 #define DOGLEG_AMD_BATCH_JTX            1   /* |Jt x|_inf <= Jt_x_threshold at the start or at an accepted point   */
 #define DOGLEG_AMD_BATCH_SMALL_STEP     2   /* max |step| <= update_threshold: that step is not applied             */
 #define DOGLEG_AMD_BATCH_TRUSTREGION    3   /* trustregion < trustregion_threshold after a rejected trial           */

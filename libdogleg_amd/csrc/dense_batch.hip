@@ -6,7 +6,8 @@
 // the host reads one counter of live problems (a 4-byte copy into page-locked memory).  Launches and synchronisations
 // per round: constant, whatever B is.
 //
-// One wavefront per problem, BATCH_WPB problems per workgroup.  The wave sweeps the problem's J ONCE (coalesced loads
+// One wavefront per problem, BatchCfg<NMAX>::WPB problems per workgroup (4 up to 32 variables, 2 in the class of 48,
+// 1 in the class of 64: the LDS a wavefront needs grows with the packed triangle).  The wave sweeps the problem's J ONCE (coalesced loads
 // of row tiles into LDS, the next tile's loads in flight while the current one is used): norm2(x), Jt x and the packed
 // lower triangle of JtJ come out of that sweep, JtJ in registers (lane l holds entries l, l + 64, ...), then in LDS.
 // Everything after it -- |J g|^2 = g' JtJ g, the packed Cholesky with the lambda loop, the two triangular solves, the
@@ -38,7 +39,6 @@ void dlg_set_error(const char* fmt, ...);
 
 namespace {
 
-constexpr int BATCH_WPB = 4;            // problems (wavefronts) per workgroup
 constexpr int BATCH_TILE = 256;         // doubles of J staged per tile (and 64 of x behind them)
 constexpr double LAMBDA_INITIAL = 1e-10;       // dogleg.c:138
 
@@ -73,6 +73,9 @@ template <int NMAX> struct BatchCfg
   static constexpr int NE = (NP + 63)/64;                       // entries of JtJ a lane accumulates
   static constexpr int SCR = NP > BATCH_TILE + 64 ? NP : BATCH_TILE + 64;     // the factor; during the sweep: the tile and its x
   static constexpr int LDSW = NP + SCR + NMAX;                  // doubles of LDS per wavefront
+  // problems (wavefronts) per workgroup: 18 688 B at most up to <32>, 38 400 B at <48>, 33 792 B at <64>, so that four
+  // workgroups of any class fit a CU's 160 KB
+  static constexpr int WPB = NMAX <= 32 ? 4 : NMAX <= 48 ? 2 : 1;
 };
 // the same per form: the products form has no row tile, the second region holds the factor only
 template <int NMAX, int FORM> struct FormCfg
@@ -435,13 +438,13 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
 }
 
 template <int NMAX, int FORM>
-__global__ void __launch_bounds__(64*BATCH_WPB) k_batch_round(BatchDev A)
+__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_round(BatchDev A)
 {
-  constexpr int LDSW = FormCfg<NMAX, FORM>::LDSW;
-  __shared__ double lds[BATCH_WPB*LDSW];
-  __shared__ int s_live[BATCH_WPB];
+  constexpr int LDSW = FormCfg<NMAX, FORM>::LDSW, WPB = BatchCfg<NMAX>::WPB;
+  __shared__ double lds[WPB*LDSW];
+  __shared__ int s_live[WPB];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int b = blockIdx.x*BATCH_WPB + w;
+  const int b = blockIdx.x*WPB + w;
   bool still = false;
   if(b < A.B && A.live[b]) still = batch_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
   if(lane == 0) s_live[w] = still ? 1 : 0;
@@ -449,7 +452,7 @@ __global__ void __launch_bounds__(64*BATCH_WPB) k_batch_round(BatchDev A)
   if(threadIdx.x == 0)
   {
     int n = 0;
-    for(int k = 0; k < BATCH_WPB; k++) n += s_live[k];
+    for(int k = 0; k < WPB; k++) n += s_live[k];
     if(n) atomicAdd(A.counter, n);
   }
 }
@@ -484,6 +487,37 @@ __device__ inline double factor2(double a00, double a01, double a11, double x0, 
   const double xBx = (x0*x0*j00 + 2.0*x0*x1*j01 + x1*x1*j11)/det;
   const double v0 = x0*j00 + x1*j01, v1 = x0*j01 + x1*j11;
   return (xBx + (v0*v0 + v1*v1)/(det*det))*k;
+}
+
+// the factor of one feature of one (r) or two rows (ra, ra + NS) of J against Sigma, packed in SA: a = J_f Sigma J_f', the
+// arithmetic and the order of operations of the second sweep of the classes up to 32 in unc_problem (which keeps its own
+// text: through these functions its instantiations come out with other registers), for the classes above
+__device__ inline double feature1(const double* SA, const double* r, int N, double x0, double kf)
+{
+  double a = 0.0;
+  int idx = 0;
+  for(int j = 0; j < N; j++)
+  {
+    const double rj = r[j], d = SA[idx++];
+    double t0 = 0.0;
+    for(int i = j + 1; i < N; i++) t0 += SA[idx++]*r[i];
+    a += rj*(d*rj + 2.0*t0);
+  }
+  return factor1(a, x0, kf);
+}
+__device__ inline double feature2(const double* SA, const double* ra, int NS, int N, double x0, double x1, double kf)
+{
+  const double* rb = ra + NS;
+  double a00 = 0.0, a01 = 0.0, a11 = 0.0;
+  int idx = 0;
+  for(int j = 0; j < N; j++)
+  {
+    const double aj = ra[j], bj = rb[j], d = SA[idx++];
+    double t0 = 0.0, t1 = 0.0;
+    for(int i = j + 1; i < N; i++) { const double s = SA[idx++]; t0 += s*ra[i]; t1 += s*rb[i]; }
+    a00 += aj*(d*aj + 2.0*t0); a01 += aj*(d*bj + t1) + bj*t0; a11 += bj*(d*bj + 2.0*t1);
+  }
+  return factor2(a00, a01, a11, x0, x1, kf);
 }
 
 template <int NMAX, int FORM>
@@ -587,6 +621,36 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
   // ---- the second sweep over J: tiles of T rows, row stride N | 1 in LDS (lanes read different rows: an odd stride keeps
   // them on different banks), lane t takes feature t of the tile: a = J_f Sigma J_f' against Sigma in LDS ----
   const int fs = A.fs, NF = A.NF, NS = N | 1, Mc = NF*fs;
+  if constexpr(NMAX > 32)
+  {
+    const double kf = scale/8.0;
+    double* tile = SL;
+    // the classes above 32 variables: the first sweep's tile would hold 4 to 7 rows, so 4 to 7 lanes of 64 would work.  The
+    // tile is the whole region the factor lay in, NP doubles: T = min(64, NP / (N | 1)) rows (24 .. 35 at <48>, 32 .. 42 at
+    // <64>), copied from global memory as it lies (coalesced) with no registers held across the features' loops
+    int T = min(64, C::SCR/NS);
+    if(fs == 2) T &= ~1;
+    for(int r0 = 0; r0 < Mc; r0 += T)
+    {
+      const int tc = min(T, Mc - r0), cnt = tc*N;
+      const double* Jt = Jb + (size_t)r0*N;
+      wsync();
+      for(int e = lane, r = lane/N, c = lane - r*N; e < cnt; e += 64)
+      {
+        tile[r*NS + c] = Jt[e];
+        c += 64;
+        while(c >= N) { c -= N; r++; }
+      }
+      wsync();
+      if(lane*fs < tc)
+      {
+        const size_t f = (size_t)(r0/fs + lane);
+        if(fs == 1) A.fac[(size_t)b*NF + f] = feature1(SA, tile + lane*NS, N, xb[r0 + lane], kf);
+        else        A.fac[(size_t)b*NF + f] = feature2(SA, tile + 2*lane*NS, NS, N, xb[r0 + 2*lane], xb[r0 + 2*lane + 1], kf);
+      }
+    }
+    return;
+  }
   int T = min(min(64, BATCH_TILE/N), (BATCH_TILE + 64)/NS);
   if(fs == 2) T &= ~1;
   constexpr int NL = BATCH_TILE/64;
@@ -651,12 +715,12 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
 }
 
 template <int NMAX, int FORM>
-__global__ void __launch_bounds__(64*BATCH_WPB) k_batch_uncertainty(UncDev A)
+__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_uncertainty(UncDev A)
 {
-  constexpr int LDSW = BatchCfg<NMAX>::NP + FormCfg<NMAX, FORM>::SCR;
-  __shared__ double lds[BATCH_WPB*LDSW];
+  constexpr int LDSW = BatchCfg<NMAX>::NP + FormCfg<NMAX, FORM>::SCR, WPB = BatchCfg<NMAX>::WPB;
+  __shared__ double lds[WPB*LDSW];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int b = blockIdx.x*BATCH_WPB + w;
+  const int b = blockIdx.x*WPB + w;
   if(b < A.B) unc_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
 }
 
@@ -782,19 +846,34 @@ ProductsDev products_dev(const BatchForm& F, const ProductsLayout& L, void* d_ev
   return P;
 }
 
-template <int FORM> void launch_round(unsigned int N, dim3 grid, dim3 block, hipStream_t st, const BatchDev& A)
+// the grid and the block follow the size class: BatchCfg<NMAX>::WPB problems per workgroup
+template <int NMAX, int FORM> void launch_round_class(hipStream_t st, const BatchDev& A)
 {
-  if(N <= 8)       hipLaunchKernelGGL((k_batch_round<8, FORM>), grid, block, 0, st, A);
-  else if(N <= 16) hipLaunchKernelGGL((k_batch_round<16, FORM>), grid, block, 0, st, A);
-  else if(N <= 24) hipLaunchKernelGGL((k_batch_round<24, FORM>), grid, block, 0, st, A);
-  else             hipLaunchKernelGGL((k_batch_round<32, FORM>), grid, block, 0, st, A);
+  constexpr int WPB = BatchCfg<NMAX>::WPB;
+  hipLaunchKernelGGL((k_batch_round<NMAX, FORM>), dim3((A.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
 }
-template <int FORM> void launch_uncertainty(unsigned int N, dim3 grid, dim3 block, hipStream_t st, const UncDev& A)
+template <int NMAX, int FORM> void launch_uncertainty_class(hipStream_t st, const UncDev& A)
 {
-  if(N <= 8)       hipLaunchKernelGGL((k_batch_uncertainty<8, FORM>), grid, block, 0, st, A);
-  else if(N <= 16) hipLaunchKernelGGL((k_batch_uncertainty<16, FORM>), grid, block, 0, st, A);
-  else if(N <= 24) hipLaunchKernelGGL((k_batch_uncertainty<24, FORM>), grid, block, 0, st, A);
-  else             hipLaunchKernelGGL((k_batch_uncertainty<32, FORM>), grid, block, 0, st, A);
+  constexpr int WPB = BatchCfg<NMAX>::WPB;
+  hipLaunchKernelGGL((k_batch_uncertainty<NMAX, FORM>), dim3((A.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
+}
+template <int FORM> void launch_round(unsigned int N, hipStream_t st, const BatchDev& A)
+{
+  if(N <= 8)       launch_round_class<8, FORM>(st, A);
+  else if(N <= 16) launch_round_class<16, FORM>(st, A);
+  else if(N <= 24) launch_round_class<24, FORM>(st, A);
+  else if(N <= 32) launch_round_class<32, FORM>(st, A);
+  else if(N <= 48) launch_round_class<48, FORM>(st, A);
+  else             launch_round_class<64, FORM>(st, A);
+}
+template <int FORM> void launch_uncertainty(unsigned int N, hipStream_t st, const UncDev& A)
+{
+  if(N <= 8)       launch_uncertainty_class<8, FORM>(st, A);
+  else if(N <= 16) launch_uncertainty_class<16, FORM>(st, A);
+  else if(N <= 24) launch_uncertainty_class<24, FORM>(st, A);
+  else if(N <= 32) launch_uncertainty_class<32, FORM>(st, A);
+  else if(N <= 48) launch_uncertainty_class<48, FORM>(st, A);
+  else             launch_uncertainty_class<64, FORM>(st, A);
 }
 
 int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F, void* cookie,
@@ -844,7 +923,6 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
   BHIP(hipMemcpyAsync(A.p_trial, p, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_batch_init, dim3((B + 255)/256), dim3(256), 0, st, A);
   BHIP(hipGetLastError());
-  const dim3 grid((B + BATCH_WPB - 1)/BATCH_WPB), block(64*BATCH_WPB);
   // a problem leaves a round finished or with a new trial point; rejected trials shrink the trust region until the
   // threshold stops them, so the rounds are bounded wherever the reference's own loop is.  The cap only keeps a
   // parameter set under which the reference would never return (a decrease factor >= 1) from holding the device.
@@ -866,8 +944,8 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
     else
       F.fJ(A.p_trial, const_cast<double*>(A.x), const_cast<double*>(A.J), A.live, B, (void*)st, cookie);
     if(timing) BHIP(hipEventRecord(K.ev[1], st));
-    if(F.products()) launch_round<FORM_PRODUCTS>(N, grid, block, st, A);
-    else             launch_round<FORM_J>(N, grid, block, st, A);
+    if(F.products()) launch_round<FORM_PRODUCTS>(N, st, A);
+    else             launch_round<FORM_J>(N, st, A);
     BHIP(hipGetLastError());
     if(timing) BHIP(hipEventRecord(K.ev[2], st));
     BHIP(hipMemcpyAsync(K.h_counter, A.counter, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -972,9 +1050,8 @@ int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, 
   else
     F.fJ(d_p, const_cast<double*>(A.x), const_cast<double*>(A.J), d_live, B, (void*)st, cookie);
   if(timing) BHIP(hipEventRecord(K.ev[1], st));
-  const dim3 grid((B + BATCH_WPB - 1)/BATCH_WPB), block(64*BATCH_WPB);
-  if(F.products()) launch_uncertainty<FORM_PRODUCTS>(N, grid, block, st, A);
-  else             launch_uncertainty<FORM_J>(N, grid, block, st, A);
+  if(F.products()) launch_uncertainty<FORM_PRODUCTS>(N, st, A);
+  else             launch_uncertainty<FORM_J>(N, st, A);
   BHIP(hipGetLastError()); ts[0] += 1.0;
   if(timing) BHIP(hipEventRecord(K.ev[2], st));
   BHIP(hipMemcpyAsync(h + o_lam, d + o_lam, io_bytes - o_lam, hipMemcpyDeviceToHost, st)); ts[2] += 1.0;

@@ -112,7 +112,7 @@ class TraceBuffer:
 
 
 BATCH_JTX, BATCH_SMALL_STEP, BATCH_TRUSTREGION, BATCH_MAX_ITERATIONS, BATCH_FAILED = 1, 2, 3, 4, 5
-BATCH_MAX_NSTATE = 32
+BATCH_MAX_NSTATE = 64
 BATCH_UNC_OK, BATCH_UNC_FAILED = 0, 1            # dogleg_amd_dense_batch_uncertainty's status
 
 

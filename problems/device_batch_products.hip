@@ -38,8 +38,9 @@ __host__ __device__ inline double urand(uint64_t seed, uint64_t stream, uint64_t
   return (double)(h >> 11) * (2.0/9007199254740992.0) - 1.0;
 }
 
-constexpr int WPB = 2;                   // problems (wavefronts) per workgroup
-constexpr int NSTATE_MAX = 32;           // DOGLEG_AMD_BATCH_MAX_NSTATE
+constexpr int NSTATE_MAX = 64;           // DOGLEG_AMD_BATCH_MAX_NSTATE
+// problems (wavefronts) per workgroup: a wavefront's tile is 64 (N | 1) + 64 doubles, 33 792 bytes at N = 64
+constexpr int wpb_of(int NMAX) { return NMAX <= 32 ? 2 : 1; }
 enum { LAYOUT_PACKED_UPPER = 0, LAYOUT_UNPACKED = 1, LAYOUT_UNPACKED_NAN_LOWER = 2 };
 enum { MODE_MODEL = 0, MODE_NAN = 1, MODE_ZERO_COLUMN = 2, MODE_NAN_OFFDIAGONAL = 3 };
 
@@ -75,11 +76,11 @@ __device__ inline void wsync()
 // first entry of column c of the packed lower triangle, column-major: the same bytes as the row-major packed upper
 __device__ inline int col_off(int c, int N) { return c*N - c*(c - 1)/2; }
 
-// NMAX: 8, 16, 24 or 32, the size class of N (how many entries of the triangle a lane holds)
+// NMAX: 8, 16, 24, 32, 48 or 64, the size class of N (how many entries of the triangle a lane holds)
 template <int NMAX>
-__global__ void __launch_bounds__(64*WPB) k_products_eval(EvalArgs A)
+__global__ void __launch_bounds__(64*wpb_of(NMAX)) k_products_eval(EvalArgs A)
 {
-  constexpr int NE = (NMAX*(NMAX + 1)/2 + 63)/64;
+  constexpr int NE = (NMAX*(NMAX + 1)/2 + 63)/64, WPB = wpb_of(NMAX);
   extern __shared__ double lds[];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x*WPB + w;
@@ -161,6 +162,13 @@ __global__ void __launch_bounds__(64*WPB) k_products_eval(EvalArgs A)
       if(i != j) G[i*N + j] = A.layout == LAYOUT_UNPACKED_NAN_LOWER ? nan("") : v;
     }
   }
+}
+// the grid, the block and the LDS follow the size class: at most 34 816 bytes (two problems of 32 variables)
+template <int NMAX> void launch_eval(const EvalArgs& A, hipStream_t st)
+{
+  constexpr int WPB = wpb_of(NMAX);
+  const size_t lds = sizeof(double)*(size_t)WPB*(64*(A.N | 1) + 64);
+  hipLaunchKernelGGL(k_products_eval<NMAX>, dim3((A.B + WPB - 1)/WPB), dim3(64*WPB), lds, st, A);
 }
 } // namespace
 
@@ -249,13 +257,13 @@ void synth_cb_device_batch_products(const double* p_dev, double* norm2x_dev, dou
   A.seed = P->d_seed; A.M = P->d_M; A.pstar = P->d_pstar; A.mode = P->d_mode; A.live = live_dev; A.p = p_dev;
   A.eps = P->eps; A.noise = P->noise; A.norm2x = norm2x_dev; A.xtJ = xtJ_dev; A.JtJ = JtJ_dev; A.nevals = P->d_nevals;
   const int N = P->N;
-  const size_t lds = sizeof(double)*(size_t)WPB*(64*(N | 1) + 64);       // at most 34 816 bytes
-  const dim3 grid((B + WPB - 1)/WPB), block(64*WPB);
   hipStream_t st = (hipStream_t)hip_stream;
-  if(N <= 8)       hipLaunchKernelGGL(k_products_eval<8>, grid, block, lds, st, A);
-  else if(N <= 16) hipLaunchKernelGGL(k_products_eval<16>, grid, block, lds, st, A);
-  else if(N <= 24) hipLaunchKernelGGL(k_products_eval<24>, grid, block, lds, st, A);
-  else             hipLaunchKernelGGL(k_products_eval<32>, grid, block, lds, st, A);
+  if(N <= 8)       launch_eval<8>(A, st);
+  else if(N <= 16) launch_eval<16>(A, st);
+  else if(N <= 24) launch_eval<24>(A, st);
+  else if(N <= 32) launch_eval<32>(A, st);
+  else if(N <= 48) launch_eval<48>(A, st);
+  else             launch_eval<64>(A, st);
 }
 
 } // extern "C"

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """tools/batch_bench.py -- dogleg_amd_optimize_dense_batch on batches of the dense device test problem.
 
-For the shapes (Nstate, Nmeas) = (6, 40) and (16, 96) and B = 1 ... 131072 problems (problems/batch.py, the default
-generator settings): wall time of the call (median and range of the repeats after warm-up calls), rounds, the time of a
+For the shapes (Nstate, Nmeas) = (6, 40) and (16, 96) and B = 1 ... 131072 problems, and for (48, 160) and (64, 200) -- the
+size classes above 32 variables -- at B = 1, 1024 and 16384 (problems/batch.py, the default generator settings): wall time of the call (median and range of the repeats after warm-up calls), rounds, the time of a
 round split into the callback's kernels and the library's (events on the stream, DOGLEG_AMD_BATCH_TIMING=1, in a call
 of its own), problems per second, and for the library's part the bytes it must move -- 8 Nmeas Nstate per evaluated
 problem, read once -- over its time, beside the 6.29 TB/s copy ceiling of the MI355X.
@@ -28,8 +28,9 @@ from libdogleg_amd import capi                      # noqa: E402
 from problems import DenseProblem, DeviceTwin       # noqa: E402
 from problems.batch import DeviceBatch              # noqa: E402
 
-SHAPES = [(6, 40), (16, 96)]
 BATCHES = [1, 64, 1024, 16384, 131072]
+WIDE_BATCHES = [1, 1024, 16384]
+SHAPES = [((6, 40), BATCHES), ((16, 96), BATCHES), ((48, 160), WIDE_BATCHES), ((64, 200), WIDE_BATCHES)]
 EPS, NOISE, SPREAD = 0.3, 0.01, 0.5
 HBM_COPY_TBS = 6.29
 
@@ -115,8 +116,8 @@ def main():
            f"(copy ceiling of the MI355X: {HBM_COPY_TBS} TB/s).", "",
            "| N | M | B | wall ms | rounds | callback us/round | library us/round | problems/s | library GB/s | of ceiling |",
            "|---|---|---|---|---|---|---|---|---|---|"]
-    for N, M in SHAPES:
-        for B in BATCHES:
+    for (N, M), batches in SHAPES:
+        for B in batches:
             if B > a.max_b:
                 continue
             r = measure(N, M, B, a.reps if B < 100000 else max(3, a.reps // 2))
@@ -130,7 +131,7 @@ def main():
             "Loop: dogleg_optimize_device2 (dense path, device callback, no trace), one problem per call, cache warm; the two legs "
             "alternated; oracle: the CPU restatement of the reference on one host core (single-thread baseline, not gated).", "",
             "| N | M | B | batch ms | loop ms | loop / batch | oracle, 1 core, ms |", "|---|---|---|---|---|---|---|"]
-    for N, M in SHAPES:
+    for (N, M), _ in SHAPES:
         c = comparison(N, M, 1024, 3)
         line = (f"| {N} | {M} | {c['B']} | {c['batch'] * 1e3:.2f} ({c['batch_rng'][0] * 1e3:.2f} .. {c['batch_rng'][1] * 1e3:.2f}) | "
                 f"{c['loop'] * 1e3:.0f} ({c['loop_rng'][0] * 1e3:.0f} .. {c['loop_rng'][1] * 1e3:.0f}) | {c['loop'] / c['batch']:.0f} x | "
