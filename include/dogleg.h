@@ -412,6 +412,10 @@ typedef void (dogleg_callback_device_batch_t)(const double* p_dev, double* x_dev
 #define DOGLEG_AMD_BATCH_TRUSTREGION    3   /* trustregion < trustregion_threshold after a rejected trial           */
 #define DOGLEG_AMD_BATCH_MAX_ITERATIONS 4   /* max_iterations accepted steps                                        */
 #define DOGLEG_AMD_BATCH_FAILED         5   /* non-finite x or J, lambda overflow, an undefined (NaN) gain ratio    */
+#define DOGLEG_AMD_BATCH_NOT_RUN        0   /* the device-resident entry points: active_dev[b] was 0                */
+/* The layout of this struct is part of the ABI: the device-resident entry points write it from a kernel as an array of
+ * structs.  40 bytes; the doubles at offsets 0, 8 and 16, the ints at offsets 24, 28 and 32 (4 bytes of padding at the
+ * end, never written). */
 typedef struct
 {
   double norm2_x;        /* at the returned p[b]; negative: this problem failed                     */
@@ -419,7 +423,7 @@ typedef struct
   double lambda;         /* its sticky damping when it stopped                                      */
   int    iterations;     /* accepted steps                                                          */
   int    evaluations;    /* times the callback's result for this problem was used                   */
-  int    status;         /* DOGLEG_AMD_BATCH_{JTX, SMALL_STEP, TRUSTREGION, MAX_ITERATIONS, FAILED} */
+  int    status;         /* DOGLEG_AMD_BATCH_{JTX, SMALL_STEP, TRUSTREGION, MAX_ITERATIONS, FAILED, NOT_RUN} */
 } dogleg_amd_batch_result_t;
 /* p: [B][Nstate] on the host, in = initial estimates, out = optima.  0, or -1 on bad arguments / no device /
  * allocation failure (message on stderr, p untouched).  A problem that fails is reported in its result (its p[b]
@@ -464,6 +468,7 @@ int dogleg_amd_batch_last_stats(double* out, int n);
 #define DOGLEG_AMD_BATCH_UNC_OK      0
 #define DOGLEG_AMD_BATCH_UNC_FAILED  1   /* non-finite x or J at p[b], or lambda overflowed before a factorisation succeeded */
                                          /* (also: a negative or NaN lambda[b] on input) */
+#define DOGLEG_AMD_BATCH_UNC_SKIPPED 2   /* the device-resident entry points: active_dev[b] was 0, nothing else written */
 int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
                                        dogleg_callback_device_batch_t* f, void* cookie,
                                        double* lambda, double* covariance, double* variances, double* factors,
@@ -524,6 +529,65 @@ int dogleg_amd_dense_products_batch_uncertainty(const double* p, unsigned int B,
                                                 dogleg_callback_device_batch_products_t* f, void* cookie,
                                                 const dogleg_parameters2_t* parameters,
                                                 double* lambda, double* covariance, double* variances, int* status);
+
+/* ---- device-resident batches: the four entry points above with every array in DEVICE memory, so that a batch whose start
+ * points come from a kernel and whose optima feed another kernel never passes through the host.  The callback types, the
+ * parameters, the size classes, the limits, the status codes, the layouts of all arrays and the bits of every result are
+ * those of the host-pointer twin.
+ *
+ * Common to the four:
+ *   *_dev       device-accessible memory of the current device: device, managed or registered / page-locked host memory.
+ *               Refused before any device work: a pointer of any other kind (pageable host memory among them), a device
+ *               allocation of another device, a device allocation that does not cover the bytes the call touches from
+ *               that pointer.
+ *   hip_stream  a hipStream_t, or NULL.  Non-NULL: every copy, the callback and every launch go onto that stream, behind
+ *               whatever was enqueued there before (the kernel that wrote p_dev, say), and the callback receives that
+ *               stream.  NULL: the library's own non-blocking stream, as the host-pointer entry points; the caller must have
+ *               finished writing the inputs.
+ *   The call blocks the host until its work is complete (the solve reads its 4-byte counter of live problems every round,
+ *   the uncertainty call synchronises once at its end).  Nothing else is copied between host and device and no page-locked
+ *   staging buffer is allocated.
+ *   active_dev  [B] bytes or NULL (all active).  active_dev[b] == 0: problem b is NOT RUN.  The callback sees the mask
+ *               through live_dev: the solve's live bytes start as the mask, the uncertainty call's live bytes are the mask.
+ *               An active problem's bits do not depend on the mask.  With no active problem the call returns 0, invokes
+ *               the callback at most once and writes nothing but the records of problems that are not run.
+ *
+ * The solve:
+ *   p_dev       [B][Nstate] in/out.  A problem that FAILED or is not run keeps its input bits.
+ *   results_dev [B] dogleg_amd_batch_result_t, an array of structs (the layout written above the typedef); only the six
+ *               fields are written.  Not run: {norm2_x -1, trustregion 0, lambda 0, iterations 0, evaluations 0,
+ *               status DOGLEG_AMD_BATCH_NOT_RUN}.
+ *   lambda_dev  [B] or NULL: results_dev[b].lambda as a contiguous array (0 where not run), the lambda_dev argument of the
+ *               uncertainty call below.
+ * dogleg_amd_batch_last_stats covers these solves.  Refused with a message and -1: what the host-pointer twin refuses, and
+ * the pointers described above. */
+int dogleg_amd_optimize_dense_batch_device(double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                           dogleg_callback_device_batch_t* f, void* cookie,
+                                           const dogleg_parameters2_t* parameters,
+                                           dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                           const unsigned char* active_dev, void* hip_stream);
+int dogleg_amd_optimize_dense_products_batch_device(double* p_dev, unsigned int B, unsigned int Nstate,
+                                                    dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                    const dogleg_parameters2_t* parameters,
+                                                    dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                    const unsigned char* active_dev, void* hip_stream);
+/* The uncertainty calls: the arguments of dogleg_amd_dense_batch_uncertainty / dogleg_amd_dense_products_batch_uncertainty,
+ * read and written where they lie.  A problem that is not run gets status_dev[b] = DOGLEG_AMD_BATCH_UNC_SKIPPED and nothing
+ * else: none of its outputs, its lambda_dev[b] or its scale_dev[b] is written.  One invocation of the callback and one
+ * launch, whatever B is; dogleg_amd_batch_uncertainty_last_stats reports launches 1, synchronisations 1 and at most 2 fills
+ * (the live bytes without a mask, the lambda scratch for a NULL lambda_dev).  Refused with a message and -1: what the
+ * host-pointer twin refuses, the pointers described above, and factors_dev together with Nmeas <= Nstate + 1 (whether every
+ * scale_dev[b] is given cannot be seen without a copy). */
+int dogleg_amd_dense_batch_uncertainty_device(const double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                              dogleg_callback_device_batch_t* f, void* cookie,
+                                              double* lambda_dev, double* covariance_dev, double* variances_dev,
+                                              double* factors_dev, double* scale_dev, int featureSize, int* status_dev,
+                                              const unsigned char* active_dev, void* hip_stream);
+int dogleg_amd_dense_products_batch_uncertainty_device(const double* p_dev, unsigned int B, unsigned int Nstate,
+                                                       dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                       const dogleg_parameters2_t* parameters,
+                                                       double* lambda_dev, double* covariance_dev, double* variances_dev,
+                                                       int* status_dev, const unsigned char* active_dev, void* hip_stream);
 
 /* ---- extension (not in the reference): the Jacobian of a DEVICE callback checked against central differences, on the
  * device.  dogleg_testGradient* above take host callbacks, one variable a call.  Here the whole Jacobian is compared, and

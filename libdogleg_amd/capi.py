@@ -65,6 +65,9 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_optimize_dense_batch", "dogleg_amd_batch_last_stats",
     "dogleg_amd_dense_batch_uncertainty", "dogleg_amd_batch_uncertainty_last_stats",
     "dogleg_amd_optimize_dense_products_batch", "dogleg_amd_dense_products_batch_uncertainty",
+    "dogleg_amd_optimize_dense_batch_device", "dogleg_amd_optimize_dense_products_batch_device",
+    "dogleg_amd_dense_batch_uncertainty_device", "dogleg_amd_dense_products_batch_uncertainty_device",
+    "dlg_batch_device_span_ok",          # (csrc/dense_batch.h: the pointer check of the four above, exported for the tests)
     "dogleg_amd_jacobian_colouring", "dogleg_amd_check_jacobian_device", "dogleg_amd_check_jacobian_device_batch",
     "dogleg_amd_testGradient_device", "dogleg_amd_check_jacobian_last_stats",
 ]
@@ -224,6 +227,13 @@ def lib():
     if hasattr(L, "dogleg_amd_optimize_dense_products_batch"):
         L.dogleg_amd_optimize_dense_products_batch.argtypes = [D, C.c_uint, C.c_uint, V, V, PP, C.POINTER(BatchResult)]
         L.dogleg_amd_dense_products_batch_uncertainty.argtypes = [D, C.c_uint, C.c_uint, V, V, PP, D, D, D, I]
+    if hasattr(L, "dogleg_amd_optimize_dense_batch_device"):
+        L.dogleg_amd_optimize_dense_batch_device.argtypes = [V, C.c_uint, C.c_uint, C.c_uint, V, V, PP, V, V, V, V]
+        L.dogleg_amd_optimize_dense_products_batch_device.argtypes = [V, C.c_uint, C.c_uint, V, V, PP, V, V, V, V]
+        L.dogleg_amd_dense_batch_uncertainty_device.argtypes = [V, C.c_uint, C.c_uint, C.c_uint, V, V, V, V, V, V, V, C.c_int,
+                                                                V, V, V]
+        L.dogleg_amd_dense_products_batch_uncertainty_device.argtypes = [V, C.c_uint, C.c_uint, V, V, PP, V, V, V, V, V, V]
+        L.dlg_batch_device_span_ok.argtypes = [V, C.c_size_t]
     if hasattr(L, "dogleg_amd_check_jacobian_device"):
         JR, JE = C.POINTER(JacobianReport), C.POINTER(JacobianEntry)
         L.dogleg_amd_jacobian_colouring.argtypes = [C.c_uint, C.c_uint, I, I, I]
@@ -385,6 +395,59 @@ def batch_uncertainty_last_stats():
     out = (C.c_double * 5)()
     lib().dogleg_amd_batch_uncertainty_last_stats(out, 5)
     return dict(launches=int(out[0]), syncs=int(out[1]), copies=int(out[2]), ms_callback=out[3], ms_library=out[4])
+
+
+def _dev(a):
+    """the device address of a DeviceArray, a raw address, or None"""
+    if a is None:
+        return None
+    return C.c_void_p(a.ptr if isinstance(a, DeviceArray) else int(a))
+
+
+def batch_device_span_ok(ptr, nbytes):
+    """dlg_batch_device_span_ok: whether the device-resident batch entry points accept [ptr, ptr + nbytes)"""
+    return bool(lib().dlg_batch_device_span_ok(_dev(ptr), nbytes))
+
+
+def optimize_dense_batch_device(p_dev, B, N, M, cb, cookie, params, results_dev, lambda_dev=None, active_dev=None, stream=None):
+    """dogleg_amd_optimize_dense_batch_device.  p_dev (B, N) doubles in/out, results_dev B dogleg_amd_batch_result_t,
+    lambda_dev B doubles or None, active_dev B bytes or None: DeviceArrays or raw device addresses; stream: a hipStream_t as
+    an integer, or None.  Returns rc."""
+    return lib().dogleg_amd_optimize_dense_batch_device(_dev(p_dev), B, N, M, cb, cookie,
+                                                        C.byref(params) if params is not None else None, _dev(results_dev),
+                                                        _dev(lambda_dev), _dev(active_dev), _dev(stream))
+
+
+def optimize_dense_products_batch_device(p_dev, B, N, cb, cookie, params, results_dev, lambda_dev=None, active_dev=None,
+                                         stream=None):
+    """dogleg_amd_optimize_dense_products_batch_device, the arguments as optimize_dense_batch_device.  Returns rc."""
+    return lib().dogleg_amd_optimize_dense_products_batch_device(_dev(p_dev), B, N, cb, cookie,
+                                                                 C.byref(params) if params is not None else None,
+                                                                 _dev(results_dev), _dev(lambda_dev), _dev(active_dev),
+                                                                 _dev(stream))
+
+
+def batch_results_from_device(results_dev, B):
+    """the record array of _batch_results from B dogleg_amd_batch_result_t in a DeviceArray"""
+    raw = results_dev.numpy().view(np.uint8)[:B * C.sizeof(BatchResult)]
+    return _batch_results((BatchResult * B).from_buffer_copy(raw.tobytes()), B)
+
+
+def dense_batch_uncertainty_device(p_dev, B, N, M, cb, cookie, status_dev, lambda_dev=None, cov_dev=None, var_dev=None,
+                                   factors_dev=None, scale_dev=None, fs=1, active_dev=None, stream=None):
+    """dogleg_amd_dense_batch_uncertainty_device: every array a DeviceArray or a raw device address (None: NULL).  Returns rc."""
+    return lib().dogleg_amd_dense_batch_uncertainty_device(_dev(p_dev), B, N, M, cb, cookie, _dev(lambda_dev), _dev(cov_dev),
+                                                           _dev(var_dev), _dev(factors_dev), _dev(scale_dev), fs,
+                                                           _dev(status_dev), _dev(active_dev), _dev(stream))
+
+
+def dense_products_batch_uncertainty_device(p_dev, B, N, cb, cookie, params, status_dev, lambda_dev=None, cov_dev=None,
+                                            var_dev=None, active_dev=None, stream=None):
+    """dogleg_amd_dense_products_batch_uncertainty_device, as dense_batch_uncertainty_device.  Returns rc."""
+    return lib().dogleg_amd_dense_products_batch_uncertainty_device(_dev(p_dev), B, N, cb, cookie,
+                                                                    C.byref(params) if params is not None else None,
+                                                                    _dev(lambda_dev), _dev(cov_dev), _dev(var_dev),
+                                                                    _dev(status_dev), _dev(active_dev), _dev(stream))
 
 
 def jacobian_colouring(N, M, Jp, Ji):

@@ -81,6 +81,37 @@ bool products_batch_ok(const char* who, unsigned int B, unsigned int Nstate, con
   return true;
 }
 
+// a *_dev argument of the device-resident batch entry points: memory a kernel of the current device may touch over `bytes`
+bool device_span_ok(const char* who, const char* name, const void* ptr, size_t bytes)
+{
+  if(dlg_batch_device_span_ok(ptr, bytes)) return true;
+  MSG("%s: %s = %p is not device-accessible memory of the current device that covers the %zu bytes this call touches there "
+      "(device, managed or registered host memory; host arrays go to the entry point without _device)", who, name, ptr, bytes);
+  return false;
+}
+
+// the arrays of a device-resident solve / uncertainty call of B problems (NF: features per problem; optional ones may be NULL)
+bool solve_spans_ok(const char* who, size_t B, size_t N, const double* p, const dogleg_amd_batch_result_t* results,
+                    const double* lambda, const unsigned char* active)
+{
+  return device_span_ok(who, "p_dev", p, sizeof(double)*B*N) &&
+         device_span_ok(who, "results_dev", results, sizeof(dogleg_amd_batch_result_t)*B) &&
+         (!lambda || device_span_ok(who, "lambda_dev", lambda, sizeof(double)*B)) &&
+         (!active || device_span_ok(who, "active_dev", active, B));
+}
+bool uncertainty_spans_ok(const char* who, size_t B, size_t N, size_t NF, const double* p, const int* status, const double* lambda,
+                          const double* covariance, const double* variances, const double* factors, const double* scale,
+                          const unsigned char* active)
+{
+  return device_span_ok(who, "p_dev", p, sizeof(double)*B*N) && device_span_ok(who, "status_dev", status, sizeof(int)*B) &&
+         (!lambda || device_span_ok(who, "lambda_dev", lambda, sizeof(double)*B)) &&
+         (!covariance || device_span_ok(who, "covariance_dev", covariance, sizeof(double)*B*N*N)) &&
+         (!variances || device_span_ok(who, "variances_dev", variances, sizeof(double)*B*N)) &&
+         (!factors || (device_span_ok(who, "factors_dev", factors, sizeof(double)*B*NF) &&
+                       device_span_ok(who, "scale_dev", scale, sizeof(double)*B))) &&
+         (!active || device_span_ok(who, "active_dev", active, B));
+}
+
 // ---- the Jacobian of a device callback against central differences
 constexpr double GRADTEST_DELTA = 1e-6;             // dogleg.c:352
 // the pattern arguments of a device callback's entry points: NJnnz == 0 with NULL pointers is dense
@@ -312,6 +343,82 @@ int dogleg_amd_dense_products_batch_uncertainty(const double* p, unsigned int B,
   if(!covariance && !variances) { MSG("%s: neither covariance nor variances is asked for", who); return -1; }
   if(!one_rank_only(who)) return -1;
   return dlg_dense_products_batch_uncertainty_run(p, B, Nstate, f, cookie, !prm->JtJ_packed, lambda, covariance, variances, status);
+}
+
+// ---- the device-resident twins of the four: the same checks, then the pointers, then dense_batch.hip
+int dogleg_amd_optimize_dense_batch_device(double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                           dogleg_callback_device_batch_t* f, void* cookie,
+                                           const dogleg_parameters2_t* parameters,
+                                           dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                           const unsigned char* active_dev, void* hip_stream)
+{
+  const char* who = "dogleg_amd_optimize_dense_batch_device";
+  if(!p_dev || !f || !results_dev) { MSG("%s: p_dev, the callback and results_dev must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || !one_rank_only(who)) return -1;
+  if(!solve_spans_ok(who, B, Nstate, p_dev, results_dev, lambda_dev, active_dev)) return -1;
+  return dlg_dense_batch_device_run(DlgBatchDeviceSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false,
+                                                        parameters ? parameters : &g_params, results_dev, lambda_dev, active_dev,
+                                                        hip_stream});
+}
+int dogleg_amd_optimize_dense_products_batch_device(double* p_dev, unsigned int B, unsigned int Nstate,
+                                                    dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                    const dogleg_parameters2_t* parameters,
+                                                    dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                    const unsigned char* active_dev, void* hip_stream)
+{
+  const char* who = "dogleg_amd_optimize_dense_products_batch_device";
+  if(!p_dev || !f || !results_dev) { MSG("%s: p_dev, the callback and results_dev must be given", who); return -1; }
+  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
+  if(!products_batch_ok(who, B, Nstate, prm) || !one_rank_only(who)) return -1;
+  if(!solve_spans_ok(who, B, Nstate, p_dev, results_dev, lambda_dev, active_dev)) return -1;
+  return dlg_dense_batch_device_run(DlgBatchDeviceSolve{p_dev, B, Nstate, 0, nullptr, f, cookie, !prm->JtJ_packed, prm,
+                                                        results_dev, lambda_dev, active_dev, hip_stream});
+}
+int dogleg_amd_dense_batch_uncertainty_device(const double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                              dogleg_callback_device_batch_t* f, void* cookie,
+                                              double* lambda_dev, double* covariance_dev, double* variances_dev,
+                                              double* factors_dev, double* scale_dev, int featureSize, int* status_dev,
+                                              const unsigned char* active_dev, void* hip_stream)
+{
+  const char* who = "dogleg_amd_dense_batch_uncertainty_device";
+  if(!p_dev || !f || !status_dev) { MSG("%s: p_dev, the callback and status_dev must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2")) return -1;
+  if(featureSize > 2) { MSG("%s: featureSize = %d: only 1 and 2 are supported", who, featureSize); return -1; }
+  const int fs = featureSize <= 1 ? 1 : 2;
+  if(!covariance_dev && !variances_dev && !factors_dev)
+  { MSG("%s: none of covariance_dev, variances_dev, factors_dev is asked for", who); return -1; }
+  if(factors_dev && !scale_dev) { MSG("%s: factors_dev needs scale_dev", who); return -1; }
+  if(factors_dev && Nmeas/(unsigned int)fs == 0) { MSG("%s: Nmeas = %u holds no feature of size %d", who, Nmeas, fs); return -1; }
+  if(factors_dev && Nmeas <= Nstate + 1)
+  {
+    MSG("%s: factors_dev with Nmeas <= Nstate + 1 (%u, %u): a scale_dev[b] <= 0 could not be computed, and whether there is one "
+        "cannot be seen without a copy", who, Nmeas, Nstate);
+    return -1;
+  }
+  if(!one_rank_only(who)) return -1;
+  if(!uncertainty_spans_ok(who, B, Nstate, Nmeas/(unsigned int)fs, p_dev, status_dev, lambda_dev, covariance_dev, variances_dev,
+                           factors_dev, scale_dev, active_dev)) return -1;
+  return dlg_dense_batch_uncertainty_device_run(DlgBatchDeviceUnc{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda_dev,
+                                                                  covariance_dev, variances_dev, factors_dev, scale_dev, fs,
+                                                                  status_dev, active_dev, hip_stream});
+}
+int dogleg_amd_dense_products_batch_uncertainty_device(const double* p_dev, unsigned int B, unsigned int Nstate,
+                                                       dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                       const dogleg_parameters2_t* parameters,
+                                                       double* lambda_dev, double* covariance_dev, double* variances_dev,
+                                                       int* status_dev, const unsigned char* active_dev, void* hip_stream)
+{
+  const char* who = "dogleg_amd_dense_products_batch_uncertainty_device";
+  if(!p_dev || !f || !status_dev) { MSG("%s: p_dev, the callback and status_dev must be given", who); return -1; }
+  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
+  if(!products_batch_ok(who, B, Nstate, prm)) return -1;
+  if(!covariance_dev && !variances_dev) { MSG("%s: neither covariance_dev nor variances_dev is asked for", who); return -1; }
+  if(!one_rank_only(who)) return -1;
+  if(!uncertainty_spans_ok(who, B, Nstate, 0, p_dev, status_dev, lambda_dev, covariance_dev, variances_dev, nullptr, nullptr,
+                           active_dev)) return -1;
+  return dlg_dense_batch_uncertainty_device_run(DlgBatchDeviceUnc{p_dev, B, Nstate, 0, nullptr, f, cookie, !prm->JtJ_packed,
+                                                                  lambda_dev, covariance_dev, variances_dev, nullptr, nullptr, 1,
+                                                                  status_dev, active_dev, hip_stream});
 }
 
 // ---- extension (not in the reference): the Jacobian of a device callback against central differences (gradcheck.hip)

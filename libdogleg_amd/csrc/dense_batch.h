@@ -1,5 +1,6 @@
 // dense_batch.h -- the batch solver of dense_batch.hip as the driver sees it (not installed).
 #pragma once
+#include <cstddef>
 #include "../../include/dogleg.h"
 
 // arguments checked by the caller (api_extensions.cpp: dogleg_amd_optimize_dense_batch); 0 / -1 with a message on stderr
@@ -17,6 +18,29 @@ int  dlg_dense_products_batch_run(double* p, unsigned int B, unsigned int N, dog
 int  dlg_dense_products_batch_uncertainty_run(const double* p, unsigned int B, unsigned int N,
                                               dogleg_callback_device_batch_products_t* f, void* cookie, bool unpacked,
                                               double* lambda, double* covariance, double* variances, int* status);
+// ---- the device-resident twins (dogleg_amd_*_batch_device): every array in device memory, active: [B] bytes or NULL,
+// stream: a hipStream_t or NULL (the cache's own).  Arguments and pointers checked by the caller.  One of fJ / fP is given;
+// Nmeas is 0 in the products form, whose layout of JtJ is `unpacked`
+struct DlgBatchDeviceSolve
+{
+  double* p; unsigned int B, N, M;
+  dogleg_callback_device_batch_t* fJ; dogleg_callback_device_batch_products_t* fP; void* cookie; bool unpacked;
+  const dogleg_parameters2_t* prm;
+  dogleg_amd_batch_result_t* results; double* lambda; const unsigned char* active; void* stream;
+};
+int  dlg_dense_batch_device_run(const DlgBatchDeviceSolve& a);
+struct DlgBatchDeviceUnc
+{
+  const double* p; unsigned int B, N, M;
+  dogleg_callback_device_batch_t* fJ; dogleg_callback_device_batch_products_t* fP; void* cookie; bool unpacked;
+  double *lambda, *covariance, *variances, *factors, *scale; int fs; int* status;
+  const unsigned char* active; void* stream;
+};
+int  dlg_dense_batch_uncertainty_device_run(const DlgBatchDeviceUnc& a);
+// whether a kernel of the current device may touch [ptr, ptr + bytes): device memory of this device whose allocation covers
+// the span, managed memory or registered / page-locked host memory.  Exported: the one place both pointer checks are made,
+// so that they can be tested without a launch on a bad pointer
+extern "C" int dlg_batch_device_span_ok(const void* ptr, size_t bytes);
 // the last call of either form
 int  dlg_dense_batch_uncertainty_last_stats(double* out, int n);
 // the device buffers, the stream, the page-locked counter and staging kept between calls (dogleg_amd_release_cache)

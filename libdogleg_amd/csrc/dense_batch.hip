@@ -23,6 +23,12 @@
 // hands back norm2(x), Jt x and JtJ of every live problem, so there is no sweep.  A second front end (load_products) puts
 // the same three things where sweep_point leaves them; from evaluate_step on both forms run the same functions.  The
 // kernels are templates over the form: the J-form instantiations keep their arithmetic and their order of operations.
+//
+// The device-resident twins (dogleg_amd_*_batch_device): the same rounds and the same launch of k_batch_uncertainty with every
+// array of the caller in device memory.  The solve takes its initial p by a copy within the device and ends in k_batch_finish,
+// which writes p, the result structs and lambda where the caller has them; the uncertainty kernel's per-output pointers point
+// at the caller's arrays.  An active mask is the initial value of the solve's live bytes and a wave-uniform return at the head
+// of k_batch_uncertainty.  k_batch_round is the same for both routes.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -469,6 +475,7 @@ struct UncDev
   double *lam, *scale, *cov, *var, *fac;     // cov, var, fac (and scale with fac): nullptr where not asked for
   int* status;
   ProductsDev P;               // FORM_PRODUCTS (x, J, M, fs, NF unused there; fac and scale nullptr: they need J)
+  const unsigned char* active; // [B] or nullptr (all): 0: problem b is skipped, only its status is written
 };
 
 // x' (B + B^2) x scale / 8 with B = (A_f - I)^-1, dogleg.h above dogleg_getOutliernessFactors (the arithmetic of
@@ -721,10 +728,18 @@ __global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_uncertainty(Un
   __shared__ double lds[WPB*LDSW];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x*WPB + w;
-  if(b < A.B) unc_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
+  if(b >= A.B) return;
+  // the mask: b is the wave's, so the whole wave leaves together
+  if(A.active && !A.active[b])
+  {
+    if(lane == 0) A.status[b] = DOGLEG_AMD_BATCH_UNC_SKIPPED;
+    return;
+  }
+  unc_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
 }
 
-__global__ void __launch_bounds__(256) k_batch_init(BatchDev A)
+// active: [B] or nullptr (all); a problem with active[b] == 0 starts, and stays, not live
+__global__ void __launch_bounds__(256) k_batch_init(BatchDev A, const unsigned char* active)
 {
   const int b = blockIdx.x*256 + threadIdx.x;
   if(b >= A.B) return;
@@ -732,7 +747,31 @@ __global__ void __launch_bounds__(256) k_batch_init(BatchDev A)
   for(int k = 0; k < SC_COUNT; k++) sc[k] = 0.0;
   sc[SC_TR] = A.trustregion0;
   for(int k = 0; k < ST_COUNT; k++) st[k] = 0;
-  A.live[b] = 1;
+  A.live[b] = active ? (active[b] ? 1 : 0) : 1;
+}
+
+// the end of a device-resident solve: the state of every problem into the caller's arrays (what run_locked does on the
+// host for the host-pointer entry points).  Thread t takes element t of p, [B][N] (coalesced stores; a problem that FAILED
+// or was not run keeps its input), and, for t < B, the record and the lambda of problem t.  A status of 0 after the last
+// round is a problem that never was live: every live problem leaves its last round with a status.
+__global__ void __launch_bounds__(256) k_batch_finish(BatchDev A, double* p, dogleg_amd_batch_result_t* results, double* lambda)
+{
+  const size_t t = (size_t)blockIdx.x*256 + threadIdx.x;
+  if(t >= (size_t)A.B*A.N) return;
+  {
+    const int status = A.st[(size_t)ST_COUNT*(t/A.N) + ST_STATUS];
+    if(status != DOGLEG_AMD_BATCH_NOT_RUN && status != DOGLEG_AMD_BATCH_FAILED) p[t] = A.p_before[t];
+  }
+  if(t >= (size_t)A.B) return;
+  const int* st = A.st + (size_t)ST_COUNT*t; const double* sc = A.sc + (size_t)SC_COUNT*t;
+  const int status = st[ST_STATUS];
+  const bool run = status != DOGLEG_AMD_BATCH_NOT_RUN;
+  dogleg_amd_batch_result_t& R = results[t];
+  const double lam = run ? sc[SC_LAMBDA] : 0.0;
+  R.norm2_x = !run || status == DOGLEG_AMD_BATCH_FAILED ? -1.0 : sc[SC_N2X];
+  R.trustregion = run ? sc[SC_TR] : 0.0; R.lambda = lam;
+  R.iterations = st[ST_ITER]; R.evaluations = st[ST_EVAL]; R.status = status;
+  if(lambda) lambda[t] = lam;
 }
 
 // ---- what is kept between calls ----
@@ -876,10 +915,11 @@ template <int FORM> void launch_uncertainty(unsigned int N, hipStream_t st, cons
   else             launch_uncertainty_class<64, FORM>(st, A);
 }
 
-int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F, void* cookie,
-               const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)
+// the cache opened and grown for B problems of N variables (M measurements; 0: the products form), and the kernels'
+// argument pointing into it
+int batch_setup(const char* who, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F,
+                const dogleg_parameters2_t* prm, BatchDev& A)
 {
-  const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch" : "dogleg_amd_optimize_dense_batch";
   if(cache_open(who)) return -1;
   BatchCache& K = g_cache;
   const int NP = (int)(N*(N + 1)/2);
@@ -902,7 +942,6 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
   const size_t state_bytes = 5*vec_bytes + G_bytes + sc_bytes + st_bytes + live_bytes + 256;
   if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes)) return -1;
 
-  BatchDev A;
   A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = NP;
   char* q = (char*)K.d_eval;
   A.x = (double*)q; q += x_bytes; A.J = (double*)q;
@@ -916,13 +955,17 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
   A.dec_factor = prm->trustregion_decrease_factor; A.dec_thr = prm->trustregion_decrease_threshold;
   A.inc_factor = prm->trustregion_increase_factor; A.inc_thr = prm->trustregion_increase_threshold;
   A.jtx_thr = prm->Jt_x_threshold; A.upd_thr = prm->update_threshold; A.tr_thr = prm->trustregion_threshold;
+  return 0;
+}
 
+// the rounds on stream st, from the initial p in A.p_trial and the initial live bytes to the round that leaves no problem
+// live: the callback, ONE launch and the 4-byte read-back of the counter per round.  Fills t_stats.
+int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* cookie, hipStream_t st)
+{
+  BatchCache& K = g_cache;
+  const unsigned int B = (unsigned int)A.B, N = (unsigned int)A.N;
   const bool timing = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
   if(timing) for(hipEvent_t& e : K.ev) if(!e) BHIP(hipEventCreate(&e));
-  hipStream_t st = K.stream;
-  BHIP(hipMemcpyAsync(A.p_trial, p, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_batch_init, dim3((B + 255)/256), dim3(256), 0, st, A);
-  BHIP(hipGetLastError());
   // a problem leaves a round finished or with a new trial point; rejected trials shrink the trust region until the
   // threshold stops them, so the rounds are bounded wherever the reference's own loop is.  The cap only keeps a
   // parameter set under which the reference would never return (a decrease factor >= 1) from holding the device.
@@ -959,6 +1002,21 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
     }
     if(*K.h_counter == 0) break;
   }
+  t_stats[0] = (double)rounds; t_stats[1] = ms_cb; t_stats[2] = ms_lib;
+  return 0;
+}
+
+int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F, void* cookie,
+               const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)
+{
+  const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch" : "dogleg_amd_optimize_dense_batch";
+  BatchDev A;
+  if(batch_setup(who, B, N, M, F, prm, A)) return -1;
+  hipStream_t st = g_cache.stream;
+  BHIP(hipMemcpyAsync(A.p_trial, p, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_batch_init, dim3((B + 255)/256), dim3(256), 0, st, A, (const unsigned char*)nullptr);
+  BHIP(hipGetLastError());
+  if(batch_rounds(who, F, A, cookie, st)) return -1;
   std::vector<double> sc((size_t)B*SC_COUNT), pb((size_t)B*N);
   std::vector<int> sti((size_t)B*ST_COUNT);
   BHIP(hipMemcpyAsync(sc.data(), A.sc, sizeof(double)*sc.size(), hipMemcpyDeviceToHost, st));
@@ -975,7 +1033,27 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
     R.iterations = sti[b*ST_COUNT + ST_ITER]; R.evaluations = sti[b*ST_COUNT + ST_EVAL]; R.status = status;
     if(!failed) memcpy(p + b*N, pb.data() + b*N, sizeof(double)*N);
   }
-  t_stats[0] = (double)rounds; t_stats[1] = ms_cb; t_stats[2] = ms_lib;
+  return 0;
+}
+
+// the device-resident solve: the initial p by a copy within the device, the mask as the initial live bytes, the rounds,
+// then k_batch_finish in place of the three downloads and the host's loop.  Everything on the caller's stream if given.
+int run_device_locked(const DlgBatchDeviceSolve& a)
+{
+  const BatchForm F{a.fJ, a.fP, a.unpacked};
+  const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch_device" : "dogleg_amd_optimize_dense_batch_device";
+  const unsigned int B = a.B, N = a.N;
+  BatchDev A;
+  if(batch_setup(who, B, N, a.M, F, a.prm, A)) return -1;
+  hipStream_t st = a.stream ? (hipStream_t)a.stream : g_cache.stream;
+  BHIP(hipMemcpyAsync(A.p_trial, a.p, sizeof(double)*(size_t)B*N, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(k_batch_init, dim3((B + 255)/256), dim3(256), 0, st, A, a.active);
+  BHIP(hipGetLastError());
+  if(batch_rounds(who, F, A, a.cookie, st)) return -1;
+  const size_t n = (size_t)B*N;
+  hipLaunchKernelGGL(k_batch_finish, dim3((unsigned int)((n + 255)/256)), dim3(256), 0, st, A, a.p, a.results, a.lambda);
+  BHIP(hipGetLastError());
+  BHIP(hipStreamSynchronize(st));
   return 0;
 }
 
@@ -1032,6 +1110,7 @@ int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, 
   A.lam = (double*)(d + o_lam); A.scale = factors ? (double*)(d + o_scale) : nullptr; A.status = (int*)(d + o_st);
   A.var = variances ? (double*)(d + o_var) : nullptr; A.cov = covariance ? (double*)(d + o_cov) : nullptr;
   A.fac = factors ? (double*)(d + o_fac) : nullptr;
+  A.active = nullptr;
   unsigned char* d_live = (unsigned char*)(d + io_bytes);
 
   memcpy(h, p, sizeof(double)*(size_t)B*N);
@@ -1072,6 +1151,69 @@ int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, 
   return 0;
 }
 
+// the device-resident uncertainty call: the kernel reads p, lambda and scale and writes every output where the caller has
+// them.  The cache holds x, J (or the products) and at most two small arrays: the live bytes, all 1, where no mask is given
+// (the mask itself is the callback's live_dev otherwise) and a zeroed lambda where the caller gives none.
+int unc_device_locked(const DlgBatchDeviceUnc& a)
+{
+  const BatchForm F{a.fJ, a.fP, a.unpacked};
+  const char* who = F.products() ? "dogleg_amd_dense_products_batch_uncertainty_device" : "dogleg_amd_dense_batch_uncertainty_device";
+  const unsigned int B = a.B, N = a.N, M = a.M;
+  double* const ts = t_unc_stats;
+  for(int k = 0; k < 5; k++) ts[k] = 0.0;
+  const unsigned int NF = M/(unsigned int)a.fs;
+  const double eval_d = F.products() ? (double)B*(1.0 + N + F.S(N)) : (double)B*(double)M*((double)N + 1.0);
+  if((eval_d + 2.0*B)*8.0 > 1.0e15)
+  {
+    dlg_set_error("%s: %.3g bytes of device memory", who, (eval_d + 2.0*B)*8.0);
+    if(F.products()) BMSG("%s: B = %u problems of %u variables need %.3g bytes of device memory", who, B, N, (eval_d + 2.0*B)*8.0);
+    else             BMSG("%s: B = %u problems of %u x %u need %.3g bytes of device memory", who, B, M, N, (eval_d + 2.0*B)*8.0);
+    return -1;
+  }
+  if(cache_open(who)) return -1;
+  BatchCache& K = g_cache;
+  const size_t x_bytes = align256(sizeof(double)*(size_t)B*M), J_bytes = align256(sizeof(double)*(size_t)B*M*N);
+  const size_t b_bytes = align256(sizeof(double)*(size_t)B);
+  const ProductsLayout PL = products_layout(F, B, N);
+  const size_t eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : x_bytes + J_bytes;
+  if(!cache_ensure(who, B, N, M, eval_bytes, b_bytes + align256(B))) return -1;
+  char* d = (char*)K.d_state;
+  UncDev A;
+  A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = (int)(N*(N + 1)/2); A.fs = a.fs; A.NF = (int)NF;
+  A.x = (double*)K.d_eval; A.J = (double*)((char*)K.d_eval + x_bytes);
+  A.P = products_dev(F, PL, K.d_eval);
+  A.lam = a.lambda ? a.lambda : (double*)d;
+  A.scale = a.factors ? a.scale : nullptr; A.status = a.status;
+  A.var = a.variances; A.cov = a.covariance; A.fac = a.factors;
+  A.active = a.active;
+  const unsigned char* d_live = a.active ? a.active : (const unsigned char*)(d + b_bytes);
+
+  const bool timing = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
+  if(timing) for(hipEvent_t& e : K.ev) if(!e) BHIP(hipEventCreate(&e));
+  hipStream_t st = a.stream ? (hipStream_t)a.stream : K.stream;
+  if(!a.lambda) { BHIP(hipMemsetAsync(d, 0, sizeof(double)*(size_t)B, st)); ts[2] += 1.0; }
+  if(!a.active) { BHIP(hipMemsetAsync(d + b_bytes, 1, B, st)); ts[2] += 1.0; }
+  if(timing) BHIP(hipEventRecord(K.ev[0], st));
+  if(F.products())
+    F.fP(a.p, const_cast<double*>(A.P.n2x), const_cast<double*>(A.P.xtJ), const_cast<double*>(A.P.JtJ), d_live, B, (void*)st,
+         a.cookie);
+  else
+    F.fJ(a.p, const_cast<double*>(A.x), const_cast<double*>(A.J), d_live, B, (void*)st, a.cookie);
+  if(timing) BHIP(hipEventRecord(K.ev[1], st));
+  if(F.products()) launch_uncertainty<FORM_PRODUCTS>(N, st, A);
+  else             launch_uncertainty<FORM_J>(N, st, A);
+  BHIP(hipGetLastError()); ts[0] += 1.0;
+  if(timing) BHIP(hipEventRecord(K.ev[2], st));
+  BHIP(hipStreamSynchronize(st)); ts[1] += 1.0;
+  if(timing)
+  {
+    float ta = 0.f, tc = 0.f;
+    BHIP(hipEventElapsedTime(&ta, K.ev[0], K.ev[1])); BHIP(hipEventElapsedTime(&tc, K.ev[1], K.ev[2]));
+    ts[3] = ta; ts[4] = tc;
+  }
+  return 0;
+}
+
 } // namespace
 
 int dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f,
@@ -1109,6 +1251,36 @@ int dlg_dense_products_batch_uncertainty_run(const double* p, unsigned int B, un
                             status);
   if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
   return rc;
+}
+int dlg_dense_batch_device_run(const DlgBatchDeviceSolve& a)
+{
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int rc = run_device_locked(a);
+  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
+  return rc;
+}
+int dlg_dense_batch_uncertainty_device_run(const DlgBatchDeviceUnc& a)
+{
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int rc = unc_device_locked(a);
+  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
+  return rc;
+}
+extern "C" int dlg_batch_device_span_ok(const void* ptr, size_t bytes)
+{
+  if(!ptr) return 0;
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof(at));
+  if(hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if(at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeHost) return 1;      // (host: registered / page-locked)
+  if(at.type != hipMemoryTypeDevice) return 0;                                       // unregistered host memory, arrays
+  int dev = -1;
+  if(hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if(at.device != dev) return 0;
+  hipDeviceptr_t base = nullptr; size_t size = 0;
+  if(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)const_cast<void*>(ptr)) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  const size_t off = (size_t)((const char*)ptr - (const char*)base);
+  return off <= size && bytes <= size - off ? 1 : 0;
 }
 int dlg_dense_batch_uncertainty_last_stats(double* out, int n)
 {
