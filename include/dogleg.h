@@ -589,6 +589,57 @@ int dogleg_amd_dense_products_batch_uncertainty_device(const double* p_dev, unsi
                                                        double* lambda_dev, double* covariance_dev, double* variances_dev,
                                                        int* status_dev, const unsigned char* active_dev, void* hip_stream);
 
+/* ---- covariance of per-problem query Jacobians of a batch: Var(q) = Jq Sigma_b Jq^T with Sigma_b = (JtJ + lambda I)^-1 of
+ * problem b at p[b], the batch twin of dogleg_amd_query_covariance.  Sigma_b is neither formed nor written: per problem the
+ * answer is Nq blocks of Qrows x Qrows.  Four entry points, mirroring the four uncertainty entry points above: the same
+ * callback types, size classes (Nstate <= DOGLEG_AMD_BATCH_MAX_NSTATE), lambda contract, status codes, stream rule, active
+ * mask and pointer checks.
+ *   Jq          [B][Nq][Qrows][Nstate], row-major: every problem has Nq >= 1 queries of Qrows rows, 1 <= Qrows <=
+ *               DOGLEG_AMD_BATCH_QUERY_MAX_ROWS (the limit of dogleg_amd_query_covariance).  Callers with ragged queries pad
+ *               with zero rows: a zero row of Jq gives a zero row and column of its block.
+ *   Nobservations (J form only) < 0: Jq Sigma_b Jq^T.  0 <= Nobservations <= Nmeas: the observations-only form
+ *               Jq Sigma_b J_obs^T J_obs Sigma_b Jq^T with J_obs the first Nobservations measurement rows of problem b, the
+ *               contract of dogleg_amd_query_covariance (0: exact zeros).  Nobservations > Nmeas is refused.  The products
+ *               form has no such argument: the form needs J.
+ *   out         [B][Nq][Qrows][Qrows] full, row-major, UNSCALED as every covariance output of this library (multiply by
+ *               sigma^2).  Every block is bitwise symmetric; in the plain form its diagonal is a sum of squares.
+ *   lambda      [B] in/out or NULL, and status [B]: as in dogleg_amd_dense_batch_uncertainty.  A FAILED problem gets NaN in
+ *               all of its out and does not disturb the others (the call still returns 0); a SKIPPED problem (active_dev[b]
+ *               == 0) has nothing but its status written.
+ * One call of the batch callback with every live byte 1 (or the mask), then ONE launch of the library whatever B and Nq
+ * are, one synchronisation; dogleg_amd_batch_uncertainty_last_stats covers these calls (the device twins: at most 2 fills).
+ * Problem b's output bits do not depend on B, on its position, on its neighbours or on the other queries.
+ * The host-pointer forms upload p, lambda and Jq and download out, lambda and status through the page-locked staging buffer
+ * of the uncertainty calls (8 B (Nstate + 2 + Nq Qrows (Nstate + Qrows)) bytes); the device forms copy nothing.
+ * Refused with a message and -1 before any device work, out / status untouched: a NULL p / f / Jq / out / status, B, Nstate,
+ * Nmeas, Nq or Qrows 0, Qrows above DOGLEG_AMD_BATCH_QUERY_MAX_ROWS, Nstate above DOGLEG_AMD_BATCH_MAX_NSTATE, Nobservations
+ * above Nmeas, the packed lower layout (products form), a set communicator, device memory that does not fit (the message
+ * names the size); the device twins also refuse the pointers described above "device-resident batches" (Jq_dev and out_dev
+ * with their full spans).
+ * Not covered: per-problem Nq / Qrows, queries of more than DOGLEG_AMD_BATCH_QUERY_MAX_ROWS rows, the observations-only form
+ * in the products form. */
+#define DOGLEG_AMD_BATCH_QUERY_MAX_ROWS 16
+int dogleg_amd_dense_batch_query_covariance(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                            dogleg_callback_device_batch_t* f, void* cookie, double* lambda,
+                                            const double* Jq, unsigned int Nq, unsigned int Qrows, int Nobservations,
+                                            double* out, int* status);
+int dogleg_amd_dense_products_batch_query_covariance(const double* p, unsigned int B, unsigned int Nstate,
+                                                     dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                     const dogleg_parameters2_t* parameters, double* lambda,
+                                                     const double* Jq, unsigned int Nq, unsigned int Qrows,
+                                                     double* out, int* status);
+int dogleg_amd_dense_batch_query_covariance_device(const double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                   dogleg_callback_device_batch_t* f, void* cookie, double* lambda_dev,
+                                                   const double* Jq_dev, unsigned int Nq, unsigned int Qrows, int Nobservations,
+                                                   double* out_dev, int* status_dev,
+                                                   const unsigned char* active_dev, void* hip_stream);
+int dogleg_amd_dense_products_batch_query_covariance_device(const double* p_dev, unsigned int B, unsigned int Nstate,
+                                                            dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                            const dogleg_parameters2_t* parameters, double* lambda_dev,
+                                                            const double* Jq_dev, unsigned int Nq, unsigned int Qrows,
+                                                            double* out_dev, int* status_dev,
+                                                            const unsigned char* active_dev, void* hip_stream);
+
 /* ---- extension (not in the reference): the Jacobian of a DEVICE callback checked against central differences, on the
  * device.  dogleg_testGradient* above take host callbacks, one variable a call.  Here the whole Jacobian is compared, and
  * on a sparse problem the variables that share no measurement row are perturbed together (Curtis, Powell, Reid): a

@@ -68,6 +68,8 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_optimize_dense_batch_device", "dogleg_amd_optimize_dense_products_batch_device",
     "dogleg_amd_dense_batch_uncertainty_device", "dogleg_amd_dense_products_batch_uncertainty_device",
     "dlg_batch_device_span_ok",          # (csrc/dense_batch.h: the pointer check of the four above, exported for the tests)
+    "dogleg_amd_dense_batch_query_covariance", "dogleg_amd_dense_products_batch_query_covariance",
+    "dogleg_amd_dense_batch_query_covariance_device", "dogleg_amd_dense_products_batch_query_covariance_device",
     "dogleg_amd_jacobian_colouring", "dogleg_amd_check_jacobian_device", "dogleg_amd_check_jacobian_device_batch",
     "dogleg_amd_testGradient_device", "dogleg_amd_check_jacobian_last_stats",
 ]
@@ -234,6 +236,12 @@ def lib():
                                                                 V, V, V]
         L.dogleg_amd_dense_products_batch_uncertainty_device.argtypes = [V, C.c_uint, C.c_uint, V, V, PP, V, V, V, V, V, V]
         L.dlg_batch_device_span_ok.argtypes = [V, C.c_size_t]
+    if hasattr(L, "dogleg_amd_dense_batch_query_covariance"):
+        U = C.c_uint
+        L.dogleg_amd_dense_batch_query_covariance.argtypes = [D, U, U, U, V, V, D, D, U, U, C.c_int, D, I]
+        L.dogleg_amd_dense_products_batch_query_covariance.argtypes = [D, U, U, V, V, PP, D, D, U, U, D, I]
+        L.dogleg_amd_dense_batch_query_covariance_device.argtypes = [V, U, U, U, V, V, V, V, U, U, C.c_int, V, V, V, V]
+        L.dogleg_amd_dense_products_batch_query_covariance_device.argtypes = [V, U, U, V, V, PP, V, V, U, U, V, V, V, V]
     if hasattr(L, "dogleg_amd_check_jacobian_device"):
         JR, JE = C.POINTER(JacobianReport), C.POINTER(JacobianEntry)
         L.dogleg_amd_jacobian_colouring.argtypes = [C.c_uint, C.c_uint, I, I, I]
@@ -448,6 +456,58 @@ def dense_products_batch_uncertainty_device(p_dev, B, N, cb, cookie, params, sta
                                                                     C.byref(params) if params is not None else None,
                                                                     _dev(lambda_dev), _dev(cov_dev), _dev(var_dev),
                                                                     _dev(status_dev), _dev(active_dev), _dev(stream))
+
+
+def _query_arrays(p, N, Jq, lam):
+    """(p (B, N), Jq (B, Nq, Q, N), the dict of outputs) of the host-pointer batch query calls"""
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, N)
+    B = p.shape[0]
+    Jq = np.ascontiguousarray(Jq, dtype=np.float64)
+    assert Jq.ndim == 4 and Jq.shape[0] == B and Jq.shape[3] == N, Jq.shape
+    out = dict(lam=None if lam is None else np.array(lam, dtype=np.float64, copy=True).reshape(B),
+               status=np.full(B, -1, dtype=np.int32), out=np.zeros((B, Jq.shape[1], Jq.shape[2], Jq.shape[2])))
+    return p, Jq, out
+
+
+def dense_batch_query_covariance(p, N, M, cb, cookie, Jq, lam=None, nobs=-1):
+    """dogleg_amd_dense_batch_query_covariance at the points p (B, N): Jq (B, Nq, Qrows, N); lam: (B,) or None (NULL: start at
+    0); nobs < 0: Jq Sigma Jq^T, otherwise the observations-only form over the first nobs measurements.  Returns dict(rc,
+    status, lam (None if lam was None), out (B, Nq, Qrows, Qrows))."""
+    p, Jq, out = _query_arrays(p, N, Jq, lam)
+    out["rc"] = lib().dogleg_amd_dense_batch_query_covariance(dptr(p), p.shape[0], N, M, cb, cookie,
+                                                              dptr(out["lam"]) if lam is not None else None, dptr(Jq),
+                                                              Jq.shape[1], Jq.shape[2], nobs, dptr(out["out"]), iptr(out["status"]))
+    return out
+
+
+def dense_products_batch_query_covariance(p, N, cb, cookie, Jq, params=None, lam=None):
+    """dogleg_amd_dense_products_batch_query_covariance, as dense_batch_query_covariance (the plain form only); the layout of
+    JtJ is params.JtJ_packed / JtJ_upper."""
+    p, Jq, out = _query_arrays(p, N, Jq, lam)
+    out["rc"] = lib().dogleg_amd_dense_products_batch_query_covariance(dptr(p), p.shape[0], N, cb, cookie,
+                                                                       C.byref(params) if params is not None else None,
+                                                                       dptr(out["lam"]) if lam is not None else None, dptr(Jq),
+                                                                       Jq.shape[1], Jq.shape[2], dptr(out["out"]),
+                                                                       iptr(out["status"]))
+    return out
+
+
+def dense_batch_query_covariance_device(p_dev, B, N, M, cb, cookie, Jq_dev, Nq, Q, out_dev, status_dev, nobs=-1, lambda_dev=None,
+                                        active_dev=None, stream=None):
+    """dogleg_amd_dense_batch_query_covariance_device: every array a DeviceArray or a raw device address (None: NULL).
+    Returns rc."""
+    return lib().dogleg_amd_dense_batch_query_covariance_device(_dev(p_dev), B, N, M, cb, cookie, _dev(lambda_dev), _dev(Jq_dev),
+                                                                Nq, Q, nobs, _dev(out_dev), _dev(status_dev), _dev(active_dev),
+                                                                _dev(stream))
+
+
+def dense_products_batch_query_covariance_device(p_dev, B, N, cb, cookie, params, Jq_dev, Nq, Q, out_dev, status_dev,
+                                                 lambda_dev=None, active_dev=None, stream=None):
+    """dogleg_amd_dense_products_batch_query_covariance_device, as dense_batch_query_covariance_device.  Returns rc."""
+    return lib().dogleg_amd_dense_products_batch_query_covariance_device(_dev(p_dev), B, N, cb, cookie,
+                                                                         C.byref(params) if params is not None else None,
+                                                                         _dev(lambda_dev), _dev(Jq_dev), Nq, Q, _dev(out_dev),
+                                                                         _dev(status_dev), _dev(active_dev), _dev(stream))
 
 
 def jacobian_colouring(N, M, Jp, Ji):

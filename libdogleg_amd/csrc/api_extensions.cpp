@@ -112,6 +112,35 @@ bool uncertainty_spans_ok(const char* who, size_t B, size_t N, size_t NF, const 
          (!active || device_span_ok(who, "active_dev", active, B));
 }
 
+// the queries of the batch query calls: Nq queries of Qrows rows per problem
+bool query_shape_ok(const char* who, unsigned int B, unsigned int Nq, unsigned int Qrows)
+{
+  if(Nq == 0 || Qrows == 0) { MSG("%s: Nq = %u, Qrows = %u: neither may be 0", who, Nq, Qrows); return false; }
+  if(Qrows > DOGLEG_AMD_BATCH_QUERY_MAX_ROWS)
+  {
+    MSG("%s: Qrows = %u, a query has at most %d rows (wider queries: dogleg_amd_dense_batch_uncertainty's covariance)", who, Qrows,
+        DOGLEG_AMD_BATCH_QUERY_MAX_ROWS);
+    return false;
+  }
+  if((double)B*(double)Nq*(double)Qrows > (double)(0x7fffffffu/DOGLEG_AMD_BATCH_MAX_NSTATE))
+  { MSG("%s: B = %u problems of %u queries of %u rows: beyond the index range of the batch kernels", who, B, Nq, Qrows); return false; }
+  return true;
+}
+bool observations_ok(const char* who, int Nobservations, unsigned int Nmeas)
+{
+  if(Nobservations < 0 || (unsigned int)Nobservations <= Nmeas) return true;
+  MSG("%s: Nobservations = %d exceeds Nmeas = %u (< 0 selects the plain form)", who, Nobservations, Nmeas);
+  return false;
+}
+bool query_spans_ok(const char* who, size_t B, size_t N, size_t Nq, size_t Q, const double* p, const int* status,
+                    const double* lambda, const double* Jq, const double* out, const unsigned char* active)
+{
+  return device_span_ok(who, "p_dev", p, sizeof(double)*B*N) && device_span_ok(who, "status_dev", status, sizeof(int)*B) &&
+         (!lambda || device_span_ok(who, "lambda_dev", lambda, sizeof(double)*B)) &&
+         device_span_ok(who, "Jq_dev", Jq, sizeof(double)*B*Nq*Q*N) && device_span_ok(who, "out_dev", out, sizeof(double)*B*Nq*Q*Q) &&
+         (!active || device_span_ok(who, "active_dev", active, B));
+}
+
 // ---- the Jacobian of a device callback against central differences
 constexpr double GRADTEST_DELTA = 1e-6;             // dogleg.c:352
 // the pattern arguments of a device callback's entry points: NJnnz == 0 with NULL pointers is dense
@@ -419,6 +448,64 @@ int dogleg_amd_dense_products_batch_uncertainty_device(const double* p_dev, unsi
   return dlg_dense_batch_uncertainty_device_run(DlgBatchDeviceUnc{p_dev, B, Nstate, 0, nullptr, f, cookie, !prm->JtJ_packed,
                                                                   lambda_dev, covariance_dev, variances_dev, nullptr, nullptr, 1,
                                                                   status_dev, active_dev, hip_stream});
+}
+
+// ---- Jq Sigma_b Jq' of per-problem query Jacobians: the four entry points beside the four uncertainty calls
+int dogleg_amd_dense_batch_query_covariance(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                            dogleg_callback_device_batch_t* f, void* cookie, double* lambda,
+                                            const double* Jq, unsigned int Nq, unsigned int Qrows, int Nobservations,
+                                            double* out, int* status)
+{
+  const char* who = "dogleg_amd_dense_batch_query_covariance";
+  if(!p || !f || !Jq || !out || !status) { MSG("%s: p, the callback, Jq, out and status must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2 and dogleg_amd_query_covariance")) return -1;
+  if(!query_shape_ok(who, B, Nq, Qrows) || !observations_ok(who, Nobservations, Nmeas) || !one_rank_only(who)) return -1;
+  return dlg_dense_batch_query_run(DlgBatchQuery{p, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda, Jq, Nq, Qrows,
+                                                 Nobservations, out, status, nullptr, nullptr});
+}
+int dogleg_amd_dense_products_batch_query_covariance(const double* p, unsigned int B, unsigned int Nstate,
+                                                     dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                     const dogleg_parameters2_t* parameters, double* lambda,
+                                                     const double* Jq, unsigned int Nq, unsigned int Qrows,
+                                                     double* out, int* status)
+{
+  const char* who = "dogleg_amd_dense_products_batch_query_covariance";
+  if(!p || !f || !Jq || !out || !status) { MSG("%s: p, the callback, Jq, out and status must be given", who); return -1; }
+  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
+  if(!products_batch_ok(who, B, Nstate, prm) || !query_shape_ok(who, B, Nq, Qrows) || !one_rank_only(who)) return -1;
+  return dlg_dense_batch_query_run(DlgBatchQuery{p, B, Nstate, 0, nullptr, f, cookie, !prm->JtJ_packed, lambda, Jq, Nq, Qrows, -1,
+                                                 out, status, nullptr, nullptr});
+}
+int dogleg_amd_dense_batch_query_covariance_device(const double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                   dogleg_callback_device_batch_t* f, void* cookie, double* lambda_dev,
+                                                   const double* Jq_dev, unsigned int Nq, unsigned int Qrows, int Nobservations,
+                                                   double* out_dev, int* status_dev,
+                                                   const unsigned char* active_dev, void* hip_stream)
+{
+  const char* who = "dogleg_amd_dense_batch_query_covariance_device";
+  if(!p_dev || !f || !Jq_dev || !out_dev || !status_dev)
+  { MSG("%s: p_dev, the callback, Jq_dev, out_dev and status_dev must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2 and dogleg_amd_query_covariance")) return -1;
+  if(!query_shape_ok(who, B, Nq, Qrows) || !observations_ok(who, Nobservations, Nmeas) || !one_rank_only(who)) return -1;
+  if(!query_spans_ok(who, B, Nstate, Nq, Qrows, p_dev, status_dev, lambda_dev, Jq_dev, out_dev, active_dev)) return -1;
+  return dlg_dense_batch_query_device_run(DlgBatchQuery{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda_dev, Jq_dev, Nq,
+                                                        Qrows, Nobservations, out_dev, status_dev, active_dev, hip_stream});
+}
+int dogleg_amd_dense_products_batch_query_covariance_device(const double* p_dev, unsigned int B, unsigned int Nstate,
+                                                            dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                            const dogleg_parameters2_t* parameters, double* lambda_dev,
+                                                            const double* Jq_dev, unsigned int Nq, unsigned int Qrows,
+                                                            double* out_dev, int* status_dev,
+                                                            const unsigned char* active_dev, void* hip_stream)
+{
+  const char* who = "dogleg_amd_dense_products_batch_query_covariance_device";
+  if(!p_dev || !f || !Jq_dev || !out_dev || !status_dev)
+  { MSG("%s: p_dev, the callback, Jq_dev, out_dev and status_dev must be given", who); return -1; }
+  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
+  if(!products_batch_ok(who, B, Nstate, prm) || !query_shape_ok(who, B, Nq, Qrows) || !one_rank_only(who)) return -1;
+  if(!query_spans_ok(who, B, Nstate, Nq, Qrows, p_dev, status_dev, lambda_dev, Jq_dev, out_dev, active_dev)) return -1;
+  return dlg_dense_batch_query_device_run(DlgBatchQuery{p_dev, B, Nstate, 0, nullptr, f, cookie, !prm->JtJ_packed, lambda_dev,
+                                                        Jq_dev, Nq, Qrows, -1, out_dev, status_dev, active_dev, hip_stream});
 }
 
 // ---- extension (not in the reference): the Jacobian of a device callback against central differences (gradcheck.hip)

@@ -37,6 +37,18 @@ struct DlgBatchDeviceUnc
   const unsigned char* active; void* stream;
 };
 int  dlg_dense_batch_uncertainty_device_run(const DlgBatchDeviceUnc& a);
+// dogleg_amd_dense_batch_query_covariance and its three twins behind the driver's checks.  One of fJ / fP is given; the
+// products form has M = 0 and no Nobservations (< 0: the plain form).  _run: host pointers (active and stream unused);
+// _device_run: every array in device memory
+struct DlgBatchQuery
+{
+  const double* p; unsigned int B, N, M;
+  dogleg_callback_device_batch_t* fJ; dogleg_callback_device_batch_products_t* fP; void* cookie; bool unpacked;
+  double* lambda; const double* Jq; unsigned int Nq, Qrows; int Nobservations; double* out; int* status;
+  const unsigned char* active; void* stream;
+};
+int  dlg_dense_batch_query_run(const DlgBatchQuery& a);
+int  dlg_dense_batch_query_device_run(const DlgBatchQuery& a);
 // whether a kernel of the current device may touch [ptr, ptr + bytes): device memory of this device whose allocation covers
 // the span, managed memory or registered / page-locked host memory.  Exported: the one place both pointer checks are made,
 // so that they can be tested without a launch on a bad pointer

@@ -19,6 +19,10 @@
 // dogleg_amd_dense_batch_uncertainty (k_batch_uncertainty, below the round kernel): covariance, variances and outlierness
 // factors of every problem at given points, one callback and one launch, on the same sweep, Cholesky and cache.
 //
+// dogleg_amd_dense_batch_query_covariance (k_batch_query, below the uncertainty kernel): Jq Sigma_b Jq' of caller-supplied
+// query Jacobians per problem, and the observations-only form, behind the same front half (factor_and_invert) in one launch;
+// Sigma itself is neither formed nor written.
+//
 // The products form (dogleg_amd_optimize_dense_products_batch, dogleg_amd_dense_products_batch_uncertainty): the callback
 // hands back norm2(x), Jt x and JtJ of every live problem, so there is no sweep.  A second front end (load_products) puts
 // the same three things where sweep_point leaves them; from evaluate_step on both forms run the same functions.  The
@@ -527,22 +531,19 @@ __device__ inline double feature2(const double* SA, const double* ra, int NS, in
   return factor2(a00, a01, a11, x0, x1, kf);
 }
 
-template <int NMAX, int FORM>
-__device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
+// the front half of a problem of the uncertainty and of the query kernel, one text for both: the sweep (or the products) into
+// SA, the finiteness test, the lambda loop on chol_packed in SL and, where that stands, X = L^-1 in place.  Between the two,
+// report(ok, lambda, norm2(x)) is the caller's: what it writes back of the factorisation and, for a problem that failed, the
+// NaN of its outputs.  Returns whether the factorisation stands.
+template <int NMAX, int FORM, class Report>
+__device__ __forceinline__ bool factor_and_invert(const UncDev& A, int b, int lane, double* SA, double* SL, Report report)
 {
-  using C = BatchCfg<NMAX>;
   const int N = A.N, M = A.M, NP = A.NP;
-  double* SA = S;                      // JtJ, then Sigma
-  double* SL = S + C::NP;              // the row tile of the sweeps; between them the factor and its inverse
-  const double* Jb = nullptr; const double* xb = nullptr;
-
   double gacc, n2x;
   bool ok;
   if constexpr(FORM == FORM_J)
   {
-    Jb = A.J + (size_t)b*M*N;
-    xb = A.x + (size_t)b*M;
-    n2x = sweep_point<NMAX>(Jb, xb, N, M, NP, lane, SA, SL, gacc);
+    n2x = sweep_point<NMAX>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc);
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     ok = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
   }
@@ -563,26 +564,8 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
     lam = lam == 0.0 ? LAMBDA_INITIAL : lam*10.0;
     if(!isfinite(lam)) ok = false;
   }
-  double scale = 0.0;
-  if(A.fac)
-  {
-    scale = A.scale[b];
-    if(!(scale > 0.0))
-    {
-      // NoutlierFeatures = 0 (api_extensions.cpp: outlier_scale); NaN for a problem that failed on a non-finite x
-      scale = (double)M/(4.0*((double)(N + 1)*n2x/(double)(M - N - 1)));
-      if(lane == 0) A.scale[b] = scale;
-    }
-  }
-  if(lane == 0) { A.lam[b] = lam; A.status[b] = ok ? DOGLEG_AMD_BATCH_UNC_OK : DOGLEG_AMD_BATCH_UNC_FAILED; }
-  if(!ok)
-  {
-    const double nan = __builtin_nan("");
-    if(A.var && lane < N) A.var[(size_t)b*N + lane] = nan;
-    if(A.cov) for(int e = lane; e < N*N; e += 64) A.cov[(size_t)b*N*N + e] = nan;
-    if(A.fac) for(int f = lane; f < A.NF; f += 64) A.fac[(size_t)b*A.NF + f] = nan;
-    return;
-  }
+  report(ok, lam, n2x);
+  if(!ok) return false;
 
   // ---- X = L^-1 in place, from the last column to the first (DTRTI2 'L'): column j of X is -X[j+1:, j+1:] L[j+1:, j] / L[j][j],
   // lane l takes row j + 1 + l ----
@@ -601,6 +584,47 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
     if(i < N) SL[jj + 1 + lane] = s;
     wsync();
   }
+  return true;
+}
+
+template <int NMAX, int FORM>
+__device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
+{
+  using C = BatchCfg<NMAX>;
+  const int N = A.N, M = A.M, NP = A.NP;
+  double* SA = S;                      // JtJ, then Sigma
+  double* SL = S + C::NP;              // the row tile of the sweeps; between them the factor and its inverse
+  const double* Jb = nullptr; const double* xb = nullptr;
+  if constexpr(FORM == FORM_J)
+  {
+    Jb = A.J + (size_t)b*M*N;
+    xb = A.x + (size_t)b*M;
+  }
+
+  double scale = 0.0;
+  const bool stands = factor_and_invert<NMAX, FORM>(A, b, lane, SA, SL, [&](bool ok, double lam, double n2x)
+  {
+    if(A.fac)
+    {
+      scale = A.scale[b];
+      if(!(scale > 0.0))
+      {
+        // NoutlierFeatures = 0 (api_extensions.cpp: outlier_scale); NaN for a problem that failed on a non-finite x
+        scale = (double)M/(4.0*((double)(N + 1)*n2x/(double)(M - N - 1)));
+        if(lane == 0) A.scale[b] = scale;
+      }
+    }
+    if(lane == 0) { A.lam[b] = lam; A.status[b] = ok ? DOGLEG_AMD_BATCH_UNC_OK : DOGLEG_AMD_BATCH_UNC_FAILED; }
+    if(!ok)
+    {
+      const double nan = __builtin_nan("");
+      if(A.var && lane < N) A.var[(size_t)b*N + lane] = nan;
+      if(A.cov) for(int e = lane; e < N*N; e += 64) A.cov[(size_t)b*N*N + e] = nan;
+      if(A.fac) for(int f = lane; f < A.NF; f += 64) A.fac[(size_t)b*A.NF + f] = nan;
+    }
+  });
+  if(!stands) return;
+
   // ---- Sigma = X' X, one lane per entry: Sigma[i][j] = sum over r >= i of X[r][i] X[r][j] (i >= j) ----
   {
     int ei[C::NE], ej[C::NE];
@@ -738,6 +762,162 @@ __global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_uncertainty(Un
   unc_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
 }
 
+// a . b over the wave, every lane ending with the same bits: the products are rounded before the butterfly.  (An FMA that took
+// its lane's product into the first level's sum would round differently in the two lanes of a pair.)
+__device__ inline double wave_dot(double a, double b)
+{
+#pragma clang fp contract(off)
+  double v = a*b;
+  for(int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ---- dogleg_amd_dense_batch_query_covariance: Var(q) = Jq Sigma_b Jq' of Nq caller-supplied query Jacobians of Q rows per
+// problem, ONE launch behind one call of the batch callback.  Per wave: factor_and_invert, then per query row c the forward
+// product z_c = X Jq_c' (lane i holds element i), and out[c][d] = z_c . z_d by the wave's butterfly sum: Sigma is never formed.
+// The observations-only (sandwich) form Jq Sigma J_obs' J_obs Sigma Jq' (J form, nobs >= 0): G = J_obs' J_obs by a sweep of its
+// own over the first nobs rows, Y_c = X' z_c (= Sigma Jq_c'), out[c][d] = Y_c' G Y_d.
+struct QueryDev
+{
+  UncDev U;                    // B, N, M, NP, x, J, P, lam, status, active; cov, var, fac, scale: nullptr
+  const double* Jq;            // [B][Nq][Q][N]
+  double* out;                 // [B][Nq][Q][Q]
+  int Nq, Q, nobs;             // nobs < 0: the plain form
+};
+
+// LDS of a wavefront of the query kernel: JtJ | the row tile, then the factor and X | an N-vector | G (J form) | the Q vectors
+// z (or Y) of one query.  The last lie in the region of JtJ, which nobody reads once the factorisation stands, where that
+// holds DOGLEG_AMD_BATCH_QUERY_MAX_ROWS rows (from <32> on), and in a region of their own below
+template <int NMAX, int FORM> struct QueryCfg
+{
+  using C = BatchCfg<NMAX>;
+  static constexpr int SCR = FormCfg<NMAX, FORM>::SCR;
+  static constexpr int GB = FORM == FORM_J ? C::NP : 0;
+  static constexpr int ZROWS = DOGLEG_AMD_BATCH_QUERY_MAX_ROWS*NMAX;
+  static constexpr int ZOWN = C::NP >= ZROWS ? 0 : ZROWS;
+  static constexpr int LDSW = C::NP + SCR + NMAX + GB + ZOWN;
+  static_assert(sizeof(double)*C::WPB*LDSW <= 65536, "k_batch_query: the wavefronts of a workgroup need more than 64 KB of LDS");
+};
+
+template <int NMAX, int FORM>
+__device__ void query_problem(const QueryDev& A, int b, int lane, double* S)
+{
+  using C = BatchCfg<NMAX>;
+  using QC = QueryCfg<NMAX, FORM>;
+  const UncDev& U = A.U;
+  const int N = U.N, Q = A.Q;
+  double* SA = S;                      // JtJ
+  double* SL = SA + C::NP;             // the row tile of the sweeps, then the factor and X = L^-1
+  double* SV = SL + QC::SCR;           // an N-vector, read at wave-uniform addresses
+  double* SG = SV + NMAX;              // G, packed as JtJ
+  double* SZ = QC::ZOWN ? SG + QC::GB : SA;       // z_c (sandwich form: Y_c), row c at c N
+  const size_t rows = (size_t)A.Nq*Q;
+  const double* Jqb = A.Jq + (size_t)b*rows*N;
+  double* ob = A.out + (size_t)b*rows*Q;
+
+  bool sandwich = false;
+  if constexpr(FORM == FORM_J)
+  {
+    sandwich = A.nobs >= 0;
+    if(sandwich)
+    {
+      // sweep_point over the first nobs rows: its JtJ is G (nobs = 0: no row is read, G is exactly 0)
+      double g;
+      (void)sweep_point<NMAX>(U.J + (size_t)b*U.M*N, U.x + (size_t)b*U.M, N, A.nobs, U.NP, lane, SG, SL, g);
+    }
+  }
+  const bool stands = factor_and_invert<NMAX, FORM>(U, b, lane, SA, SL, [&](bool ok, double lam, double)
+  {
+    if(lane == 0) { U.lam[b] = lam; U.status[b] = ok ? DOGLEG_AMD_BATCH_UNC_OK : DOGLEG_AMD_BATCH_UNC_FAILED; }
+    if(!ok)
+    {
+      const double nan = __builtin_nan("");
+      for(size_t e = lane; e < rows*Q; e += 64) ob[e] = nan;
+    }
+  });
+  if(!stands) return;
+
+  // the rows of Jq as they lie, lane i element i of a row (coalesced); the next row's load is in flight under the current
+  // row's product
+  double qn = lane < N ? Jqb[lane] : 0.0;
+  for(int q = 0; q < A.Nq; q++)
+  {
+    for(int c = 0; c < Q; c++)
+    {
+      const size_t r = (size_t)q*Q + c;
+      const double qv = qn;
+      if(r + 1 < rows) qn = lane < N ? Jqb[(r + 1)*N + lane] : 0.0;
+      wsync();
+      if(lane < N) SV[lane] = qv;
+      wsync();
+      // z = X Jq_c': lane i sums along row i of X (consecutive lanes read consecutive doubles of a column)
+      double z = 0.0;
+      if(lane < N)
+        for(int j = 0; j <= lane; j++) z += SL[col_off(j, N) + lane - j]*SV[j];
+      if(sandwich)
+      {
+        // Y = X' z: lane i sums along column i of X
+        wsync();
+        if(lane < N) SV[lane] = z;
+        wsync();
+        double y = 0.0;
+        if(lane < N)
+        {
+          const double* col = SL + col_off(lane, N) - lane;
+          for(int k = lane; k < N; k++) y += col[k]*SV[k];
+        }
+        z = y;
+      }
+      if(lane < N) SZ[c*N + lane] = z;
+    }
+    wsync();
+    // the triangle of the block, every entry once: the butterfly leaves the same bits in every lane, the lanes that own
+    // [c][d] and [d][c] store them -- a bitwise symmetric block whose diagonal (plain form) is a sum of squares
+    double* oq = ob + (size_t)q*Q*Q;
+    for(int d = 0; d < Q; d++)
+    {
+      double w = lane < N ? SZ[d*N + lane] : 0.0;
+      if(sandwich)
+      {
+        // w = G Y_d
+        wsync();
+        if(lane < N) SV[lane] = w;
+        wsync();
+        double t = 0.0;
+        if(lane < N)
+          for(int j = 0; j < N; j++) t += sym_at(SG, lane, j, N)*SV[j];
+        w = t;
+      }
+      for(int c = 0; c <= d; c++)
+      {
+        const double zc = lane < N ? SZ[c*N + lane] : 0.0;
+        const double s = wave_dot(zc, w);
+        const int e = c*Q + d, f = d*Q + c;
+        if(lane == (e & 63)) oq[e] = s;
+        if(c != d && lane == (f & 63)) oq[f] = s;
+      }
+    }
+    wsync();
+  }
+}
+
+template <int NMAX, int FORM>
+__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_query(QueryDev A)
+{
+  constexpr int LDSW = QueryCfg<NMAX, FORM>::LDSW, WPB = BatchCfg<NMAX>::WPB;
+  __shared__ double lds[WPB*LDSW];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x*WPB + w;
+  if(b >= A.U.B) return;
+  // the mask, as in k_batch_uncertainty
+  if(A.U.active && !A.U.active[b])
+  {
+    if(lane == 0) A.U.status[b] = DOGLEG_AMD_BATCH_UNC_SKIPPED;
+    return;
+  }
+  query_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
+}
+
 // active: [B] or nullptr (all); a problem with active[b] == 0 starts, and stays, not live
 __global__ void __launch_bounds__(256) k_batch_init(BatchDev A, const unsigned char* active)
 {
@@ -859,6 +1039,22 @@ bool cache_ensure(const char* who, unsigned int B, unsigned int N, unsigned int 
   };
   return ensure(&K.d_eval, &K.eval_bytes, eval_bytes) && ensure(&K.d_state, &K.state_bytes, state_bytes);
 }
+// the page-locked staging buffer of the host-pointer uncertainty and query calls, grown to io_bytes
+bool stage_ensure(const char* who, unsigned int B, unsigned int N, unsigned int M, size_t io_bytes)
+{
+  BatchCache& K = g_cache;
+  if(K.stage_bytes >= io_bytes) return true;
+  if(K.h_stage) { (void)hipHostFree(K.h_stage); K.h_stage = nullptr; K.stage_bytes = 0; }
+  if(hipHostMalloc(&K.h_stage, io_bytes) != hipSuccess)
+  {
+    (void)hipGetLastError(); K.h_stage = nullptr;
+    dlg_set_error("%s: cannot allocate %zu bytes of page-locked memory", who, io_bytes);
+    BMSG("%s: B = %u problems of %u x %u need %zu bytes of page-locked host memory: the allocation failed", who, B, M, N, io_bytes);
+    return false;
+  }
+  K.stage_bytes = io_bytes;
+  return true;
+}
 
 // the callback of a call and what it writes: the J form (fJ: x, J of Nmeas = M rows) or the products form (fP: norm2x,
 // xtJ, JtJ; M is 0 there)
@@ -895,6 +1091,20 @@ template <int NMAX, int FORM> void launch_uncertainty_class(hipStream_t st, cons
 {
   constexpr int WPB = BatchCfg<NMAX>::WPB;
   hipLaunchKernelGGL((k_batch_uncertainty<NMAX, FORM>), dim3((A.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
+}
+template <int NMAX, int FORM> void launch_query_class(hipStream_t st, const QueryDev& A)
+{
+  constexpr int WPB = BatchCfg<NMAX>::WPB;
+  hipLaunchKernelGGL((k_batch_query<NMAX, FORM>), dim3((A.U.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
+}
+template <int FORM> void launch_query(unsigned int N, hipStream_t st, const QueryDev& A)
+{
+  if(N <= 8)       launch_query_class<8, FORM>(st, A);
+  else if(N <= 16) launch_query_class<16, FORM>(st, A);
+  else if(N <= 24) launch_query_class<24, FORM>(st, A);
+  else if(N <= 32) launch_query_class<32, FORM>(st, A);
+  else if(N <= 48) launch_query_class<48, FORM>(st, A);
+  else             launch_query_class<64, FORM>(st, A);
 }
 template <int FORM> void launch_round(unsigned int N, hipStream_t st, const BatchDev& A)
 {
@@ -1088,19 +1298,7 @@ int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, 
   const ProductsLayout PL = products_layout(F, B, N);
   const size_t eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : x_bytes + J_bytes;
   const size_t state_bytes = io_bytes + align256(B);
-  if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes)) return -1;
-  if(K.stage_bytes < io_bytes)
-  {
-    if(K.h_stage) { (void)hipHostFree(K.h_stage); K.h_stage = nullptr; K.stage_bytes = 0; }
-    if(hipHostMalloc(&K.h_stage, io_bytes) != hipSuccess)
-    {
-      (void)hipGetLastError(); K.h_stage = nullptr;
-      dlg_set_error("%s: cannot allocate %zu bytes of page-locked memory", who, io_bytes);
-      BMSG("%s: B = %u problems of %u x %u need %zu bytes of page-locked host memory: the allocation failed", who, B, M, N, io_bytes);
-      return -1;
-    }
-    K.stage_bytes = io_bytes;
-  }
+  if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes) || !stage_ensure(who, B, N, M, io_bytes)) return -1;
   char* d = (char*)K.d_state; char* h = (char*)K.h_stage;
   UncDev A;
   A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = (int)(N*(N + 1)/2); A.fs = fs; A.NF = (int)NF;
@@ -1214,7 +1412,169 @@ int unc_device_locked(const DlgBatchDeviceUnc& a)
   return 0;
 }
 
+// ---- the query calls.  What both routes share: the sizes, the cache's x / J (or products) buffer and the kernel's argument
+// but for the pointers of the caller's arrays
+struct QuerySizes { size_t x_bytes, eval_bytes, Jq_bytes, out_bytes; };
+const char* query_who(const DlgBatchQuery& a, bool device)
+{
+  if(a.fP) return device ? "dogleg_amd_dense_products_batch_query_covariance_device" : "dogleg_amd_dense_products_batch_query_covariance";
+  return device ? "dogleg_amd_dense_batch_query_covariance_device" : "dogleg_amd_dense_batch_query_covariance";
+}
+// refused from the arithmetic alone, before the device is opened (extra_d: doubles of state beside x / J and the callback's output)
+bool query_sizes(const char* who, const DlgBatchQuery& a, const BatchForm& F, double extra_d, QuerySizes& S)
+{
+  const unsigned int B = a.B, N = a.N, M = a.M;
+  const double eval_d = F.products() ? (double)B*(1.0 + N + F.S(N)) : (double)B*(double)M*((double)N + 1.0);
+  const double rows_d = (double)B*(double)a.Nq*(double)a.Qrows;
+  const double need = (eval_d + extra_d)*8.0, Jq_d = rows_d*N*8.0, out_d = rows_d*a.Qrows*8.0;
+  if(need + Jq_d + out_d > 1.0e15)
+  {
+    dlg_set_error("%s: %.3g bytes of device memory", who, need + Jq_d + out_d);
+    BMSG("%s: B = %u problems of %u variables with %u queries of %u rows need %.3g bytes of device memory (%.3g of them for Jq, "
+         "%.3g for out)", who, B, N, a.Nq, a.Qrows, need + Jq_d + out_d, Jq_d, out_d);
+    return false;
+  }
+  const size_t rows = (size_t)B*a.Nq*a.Qrows;
+  const ProductsLayout PL = products_layout(F, B, N);
+  S.x_bytes = align256(sizeof(double)*(size_t)B*M);
+  S.eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : S.x_bytes + align256(sizeof(double)*(size_t)B*M*N);
+  S.Jq_bytes = align256(sizeof(double)*rows*N); S.out_bytes = align256(sizeof(double)*rows*a.Qrows);
+  return true;
+}
+QueryDev query_dev(const DlgBatchQuery& a, const BatchForm& F, const QuerySizes& S)
+{
+  BatchCache& K = g_cache;
+  QueryDev A;
+  UncDev& U = A.U;
+  U.B = (int)a.B; U.N = (int)a.N; U.M = (int)a.M; U.NP = (int)(a.N*(a.N + 1)/2); U.fs = 1; U.NF = 0;
+  U.x = (double*)K.d_eval; U.J = (double*)((char*)K.d_eval + S.x_bytes);
+  U.P = products_dev(F, products_layout(F, a.B, a.N), K.d_eval);
+  U.lam = nullptr; U.scale = nullptr; U.cov = nullptr; U.var = nullptr; U.fac = nullptr; U.status = nullptr; U.active = nullptr;
+  A.Jq = nullptr; A.out = nullptr;
+  A.Nq = (int)a.Nq; A.Q = (int)a.Qrows; A.nobs = F.products() ? -1 : a.Nobservations;
+  return A;
+}
+// the callback at d_p with the live bytes d_live, then the ONE launch, on st
+int query_enqueue(const char* who, const BatchForm& F, const QueryDev& A, const double* d_p, const unsigned char* d_live,
+                  void* cookie, hipStream_t st, bool timing)
+{
+  BatchCache& K = g_cache;
+  const UncDev& U = A.U;
+  const unsigned int B = (unsigned int)U.B;
+  if(timing) BHIP(hipEventRecord(K.ev[0], st));
+  if(F.products())
+    F.fP(d_p, const_cast<double*>(U.P.n2x), const_cast<double*>(U.P.xtJ), const_cast<double*>(U.P.JtJ), d_live, B, (void*)st, cookie);
+  else
+    F.fJ(d_p, const_cast<double*>(U.x), const_cast<double*>(U.J), d_live, B, (void*)st, cookie);
+  if(timing) BHIP(hipEventRecord(K.ev[1], st));
+  if(F.products()) launch_query<FORM_PRODUCTS>((unsigned int)U.N, st, A);
+  else             launch_query<FORM_J>((unsigned int)U.N, st, A);
+  BHIP(hipGetLastError()); t_unc_stats[0] += 1.0;
+  if(timing) BHIP(hipEventRecord(K.ev[2], st));
+  return 0;
+}
+int query_times(const char* who)
+{
+  BatchCache& K = g_cache;
+  float ta = 0.f, tc = 0.f;
+  BHIP(hipEventElapsedTime(&ta, K.ev[0], K.ev[1])); BHIP(hipEventElapsedTime(&tc, K.ev[1], K.ev[2]));
+  t_unc_stats[3] = ta; t_unc_stats[4] = tc;
+  return 0;
+}
+
+// host pointers.  Device (and staging) layout: p | Jq | lambda | status | out, then the live bytes; up: p .. lambda, down:
+// lambda .. out, one copy each
+int query_locked(const DlgBatchQuery& a)
+{
+  const BatchForm F{a.fJ, a.fP, a.unpacked};
+  const char* who = query_who(a, false);
+  const unsigned int B = a.B, N = a.N;
+  double* const ts = t_unc_stats;
+  for(int k = 0; k < 5; k++) ts[k] = 0.0;
+  QuerySizes S;
+  if(!query_sizes(who, a, F, (double)B*((double)N + 3.0), S)) return -1;
+  if(cache_open(who)) return -1;
+  BatchCache& K = g_cache;
+  const size_t p_bytes = align256(sizeof(double)*(size_t)B*N), b_bytes = align256(sizeof(double)*(size_t)B);
+  const size_t st_bytes = align256(sizeof(int)*(size_t)B);
+  const size_t o_Jq = p_bytes, o_lam = o_Jq + S.Jq_bytes, o_st = o_lam + b_bytes, o_out = o_st + st_bytes;
+  const size_t io_bytes = o_out + S.out_bytes;
+  if(!cache_ensure(who, B, N, a.M, S.eval_bytes, io_bytes + align256(B)) || !stage_ensure(who, B, N, a.M, io_bytes)) return -1;
+  char* d = (char*)K.d_state; char* h = (char*)K.h_stage;
+  QueryDev A = query_dev(a, F, S);
+  A.U.lam = (double*)(d + o_lam); A.U.status = (int*)(d + o_st);
+  A.Jq = (const double*)(d + o_Jq); A.out = (double*)(d + o_out);
+  unsigned char* d_live = (unsigned char*)(d + io_bytes);
+  const size_t rows = (size_t)B*a.Nq*a.Qrows;
+
+  memcpy(h, a.p, sizeof(double)*(size_t)B*N);
+  memcpy(h + o_Jq, a.Jq, sizeof(double)*rows*N);
+  if(a.lambda) memcpy(h + o_lam, a.lambda, sizeof(double)*B); else memset(h + o_lam, 0, sizeof(double)*B);
+
+  const bool timing = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
+  if(timing) for(hipEvent_t& e : K.ev) if(!e) BHIP(hipEventCreate(&e));
+  hipStream_t st = K.stream;
+  BHIP(hipMemcpyAsync(d, h, o_st, hipMemcpyHostToDevice, st)); ts[2] += 1.0;
+  BHIP(hipMemsetAsync(d_live, 1, B, st)); ts[2] += 1.0;
+  if(query_enqueue(who, F, A, (const double*)d, d_live, a.cookie, st, timing)) return -1;
+  BHIP(hipMemcpyAsync(h + o_lam, d + o_lam, io_bytes - o_lam, hipMemcpyDeviceToHost, st)); ts[2] += 1.0;
+  BHIP(hipStreamSynchronize(st)); ts[1] += 1.0;
+  if(timing && query_times(who)) return -1;
+  if(a.lambda) memcpy(a.lambda, h + o_lam, sizeof(double)*B);
+  memcpy(a.status, h + o_st, sizeof(int)*B);
+  memcpy(a.out, h + o_out, sizeof(double)*rows*a.Qrows);
+  return 0;
+}
+
+// device pointers: the kernel reads p, lambda and Jq and writes lambda, status and out where the caller has them.  Of the
+// cache: x / J (or the products), the live bytes where no mask is given and a zeroed lambda where the caller gives none
+int query_device_locked(const DlgBatchQuery& a)
+{
+  const BatchForm F{a.fJ, a.fP, a.unpacked};
+  const char* who = query_who(a, true);
+  const unsigned int B = a.B, N = a.N;
+  double* const ts = t_unc_stats;
+  for(int k = 0; k < 5; k++) ts[k] = 0.0;
+  QuerySizes S;
+  if(!query_sizes(who, a, F, 2.0*B, S)) return -1;
+  if(cache_open(who)) return -1;
+  BatchCache& K = g_cache;
+  const size_t b_bytes = align256(sizeof(double)*(size_t)B);
+  if(!cache_ensure(who, B, N, a.M, S.eval_bytes, b_bytes + align256(B))) return -1;
+  char* d = (char*)K.d_state;
+  QueryDev A = query_dev(a, F, S);
+  A.U.lam = a.lambda ? a.lambda : (double*)d;
+  A.U.status = a.status; A.U.active = a.active;
+  A.Jq = a.Jq; A.out = a.out;
+  const unsigned char* d_live = a.active ? a.active : (const unsigned char*)(d + b_bytes);
+
+  const bool timing = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
+  if(timing) for(hipEvent_t& e : K.ev) if(!e) BHIP(hipEventCreate(&e));
+  hipStream_t st = a.stream ? (hipStream_t)a.stream : K.stream;
+  if(!a.lambda) { BHIP(hipMemsetAsync(d, 0, sizeof(double)*(size_t)B, st)); ts[2] += 1.0; }
+  if(!a.active) { BHIP(hipMemsetAsync(d + b_bytes, 1, B, st)); ts[2] += 1.0; }
+  if(query_enqueue(who, F, A, a.p, d_live, a.cookie, st, timing)) return -1;
+  BHIP(hipStreamSynchronize(st)); ts[1] += 1.0;
+  if(timing && query_times(who)) return -1;
+  return 0;
+}
+
 } // namespace
+
+int dlg_dense_batch_query_run(const DlgBatchQuery& a)
+{
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int rc = query_locked(a);
+  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
+  return rc;
+}
+int dlg_dense_batch_query_device_run(const DlgBatchQuery& a)
+{
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int rc = query_device_locked(a);
+  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
+  return rc;
+}
 
 int dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f,
                         void* cookie, const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)

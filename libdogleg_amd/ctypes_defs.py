@@ -115,6 +115,7 @@ BATCH_JTX, BATCH_SMALL_STEP, BATCH_TRUSTREGION, BATCH_MAX_ITERATIONS, BATCH_FAIL
 BATCH_MAX_NSTATE = 64
 BATCH_UNC_OK, BATCH_UNC_FAILED = 0, 1            # dogleg_amd_dense_batch_uncertainty's status
 BATCH_NOT_RUN, BATCH_UNC_SKIPPED = 0, 2          # the device-resident entry points: a problem whose active byte is 0
+BATCH_QUERY_MAX_ROWS = 16                        # dogleg_amd_dense_batch_query_covariance: rows of a query
 
 
 class BatchResult(C.Structure):
