@@ -589,6 +589,59 @@ int dogleg_amd_dense_products_batch_uncertainty_device(const double* p_dev, unsi
                                                        double* lambda_dev, double* covariance_dev, double* variances_dev,
                                                        int* status_dev, const unsigned char* active_dev, void* hip_stream);
 
+/* ---- robust loss functions in the batch solve: every problem minimises F = sum_f rho(s_f), s_f = |x_f|^2, over its features
+ * (featureSize consecutive measurements from 0) in place of norm2(x), so that gross outliers lose their pull inside the solve.
+ * With w_f = rho'(s_f) at the point the sweep is made at, the dog-leg loop of dogleg_amd_optimize_dense_batch runs with
+ *   F = sum_f rho(s_f)        in place of norm2(x): the gain ratio (F_before - F_trial) / expected improvement, results[b].norm2_x
+ *   g = sum_f w_f J_f^T x_f   in place of Jt x:     the Cauchy step, the Jt_x_threshold test, the expected improvement
+ *   H = sum_f w_f J_f^T J_f   in place of JtJ:      the factorisation with lambda, |J g|^2, |J s|^2, the expected improvement
+ * and nothing else changed.  This is the first-order treatment (IRLS; Triggs' correction without its curvature term), what
+ * Ceres' corrector does for every loss with rho'' <= 0; all losses here have rho'' <= 0, so H stays positive semidefinite.
+ * A callback cannot supply this alone: rows scaled by sqrt(rho') give g and H, but the gain ratio must compare sum rho.
+ *   kind, with scale a > 0 and c = a^2:          rho(s)                        rho'(s)
+ *     DOGLEG_AMD_LOSS_TRIVIAL                    s                             1                (scale is ignored)
+ *     DOGLEG_AMD_LOSS_HUBER                      s <= c: s, else 2 a sqrt(s) - c       s <= c: 1, else a / sqrt(s)
+ *     DOGLEG_AMD_LOSS_SOFT_L1                    2 c (sqrt(1 + s/c) - 1)       1 / sqrt(1 + s/c)
+ *     DOGLEG_AMD_LOSS_CAUCHY                     c log1p(s/c)                  1 / (1 + s/c)
+ *   featureSize <= 1 means 1; sizes 1 to DOGLEG_AMD_BATCH_LOSS_MAX_FEATURESIZE = 4; Nmeas must be a multiple of it.
+ * The contract is that of dogleg_amd_optimize_dense_batch (and of its _device twin): the callback type and the live bytes, one
+ * callback, one launch and one 4-byte read-back per round, the status codes, the meaning of iterations and evaluations,
+ * dogleg_amd_batch_last_stats, and for the twin the pointer checks, the stream rule and the mask.
+ *   results[b].norm2_x  is F at the returned p[b] (NOT norm2(x)); negative: the problem failed.
+ *   weights     [B][Nmeas / featureSize] or NULL: rho'(s_f) at the returned p[b], in (0, 1]: what a caller thresholds to name
+ *               the outliers.  A FAILED problem gets NaN weights (and keeps its input p[b]); the weights of a problem that is not
+ *               run (active_dev[b] == 0) are not written.
+ * With DOGLEG_AMD_LOSS_TRIVIAL and featureSize 1 every result has the bits dogleg_amd_optimize_dense_batch gives (at other
+ * feature sizes the rows are summed in tiles of another height: norm2_x may differ in its last bits), and every weight is 1.
+ * Refused with a message and -1 before any device work, outputs untouched: what the plain twin refuses, a NULL loss, an unknown
+ * kind, a scale that is not finite and > 0 (unless TRIVIAL), featureSize above 4, Nmeas not a multiple of featureSize, a set
+ * communicator; the device twin also refuses weights_dev as it refuses the other pointers.  Device memory: the plain solve's,
+ * plus B * Nmeas / featureSize doubles.
+ * Not provided: the products form with a loss (it has no per-feature x); per-problem scales (normalise x in the callback);
+ * losses that are not concave in s (Tukey's biweight): H would need the curvature term; uncertainty and query calls that take a
+ * loss -- the recipe: call dogleg_amd_dense_batch_uncertainty / _query_covariance at the returned p with a callback that
+ * multiplies row r of x and J by sqrt(weights[b][r / featureSize]). */
+#define DOGLEG_AMD_LOSS_TRIVIAL 0
+#define DOGLEG_AMD_LOSS_HUBER   1
+#define DOGLEG_AMD_LOSS_SOFT_L1 2
+#define DOGLEG_AMD_LOSS_CAUCHY  3
+#define DOGLEG_AMD_BATCH_LOSS_MAX_FEATURESIZE 4
+typedef struct
+{
+  int    kind;           /* DOGLEG_AMD_LOSS_*                                              */
+  double scale;          /* a: residual norms |x_f| below it are treated as least squares  */
+  int    featureSize;    /* measurements per feature, 1 .. 4 (<= 1: 1)                     */
+} dogleg_amd_batch_loss_t;
+int dogleg_amd_optimize_dense_batch_robust(double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                           dogleg_callback_device_batch_t* f, void* cookie,
+                                           const dogleg_parameters2_t* parameters, const dogleg_amd_batch_loss_t* loss,
+                                           dogleg_amd_batch_result_t* results, double* weights);
+int dogleg_amd_optimize_dense_batch_robust_device(double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                  dogleg_callback_device_batch_t* f, void* cookie,
+                                                  const dogleg_parameters2_t* parameters, const dogleg_amd_batch_loss_t* loss,
+                                                  dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                  double* weights_dev, const unsigned char* active_dev, void* hip_stream);
+
 /* ---- covariance of per-problem query Jacobians of a batch: Var(q) = Jq Sigma_b Jq^T with Sigma_b = (JtJ + lambda I)^-1 of
  * problem b at p[b], the batch twin of dogleg_amd_query_covariance.  Sigma_b is neither formed nor written: per problem the
  * answer is Nq blocks of Qrows x Qrows.  Four entry points, mirroring the four uncertainty entry points above: the same

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, JacobianReport, JacobianEntry,
+from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, BatchLoss, JacobianReport, JacobianEntry,
                           CB_SPARSE, CB_DENSE, CB_PRODUCTS, dptr, iptr)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -68,6 +68,7 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_optimize_dense_batch_device", "dogleg_amd_optimize_dense_products_batch_device",
     "dogleg_amd_dense_batch_uncertainty_device", "dogleg_amd_dense_products_batch_uncertainty_device",
     "dlg_batch_device_span_ok",          # (csrc/dense_batch.h: the pointer check of the four above, exported for the tests)
+    "dogleg_amd_optimize_dense_batch_robust", "dogleg_amd_optimize_dense_batch_robust_device",
     "dogleg_amd_dense_batch_query_covariance", "dogleg_amd_dense_products_batch_query_covariance",
     "dogleg_amd_dense_batch_query_covariance_device", "dogleg_amd_dense_products_batch_query_covariance_device",
     "dogleg_amd_jacobian_colouring", "dogleg_amd_check_jacobian_device", "dogleg_amd_check_jacobian_device_batch",
@@ -236,6 +237,11 @@ def lib():
                                                                 V, V, V]
         L.dogleg_amd_dense_products_batch_uncertainty_device.argtypes = [V, C.c_uint, C.c_uint, V, V, PP, V, V, V, V, V, V]
         L.dlg_batch_device_span_ok.argtypes = [V, C.c_size_t]
+    if hasattr(L, "dogleg_amd_optimize_dense_batch_robust"):
+        LP = C.POINTER(BatchLoss)
+        L.dogleg_amd_optimize_dense_batch_robust.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, V, V, PP, LP,
+                                                             C.POINTER(BatchResult), D]
+        L.dogleg_amd_optimize_dense_batch_robust_device.argtypes = [V, C.c_uint, C.c_uint, C.c_uint, V, V, PP, LP, V, V, V, V, V]
     if hasattr(L, "dogleg_amd_dense_batch_query_covariance"):
         U = C.c_uint
         L.dogleg_amd_dense_batch_query_covariance.argtypes = [D, U, U, U, V, V, D, D, U, U, C.c_int, D, I]
@@ -433,6 +439,33 @@ def optimize_dense_products_batch_device(p_dev, B, N, cb, cookie, params, result
                                                                  C.byref(params) if params is not None else None,
                                                                  _dev(results_dev), _dev(lambda_dev), _dev(active_dev),
                                                                  _dev(stream))
+
+
+def optimize_dense_batch_robust(p0s, N, M, cb, cookie, loss, params=None, want_weights=True):
+    """dogleg_amd_optimize_dense_batch_robust: as optimize_dense_batch with loss a BatchLoss (None: NULL).  Returns (rc, p (B, N),
+    results, weights (B, M // max(featureSize, 1)) prefilled with -1, or None if not asked for); results["norm2_x"] is the
+    robust cost."""
+    L = lib()
+    p = np.array(p0s, dtype=np.float64, copy=True).reshape(-1, N)
+    B = p.shape[0]
+    res = (BatchResult * max(B, 1))()
+    fs = max(loss.featureSize, 1) if loss is not None else 1
+    w = np.full((B, M // fs), -1.0) if want_weights else None
+    rc = L.dogleg_amd_optimize_dense_batch_robust(dptr(p), B, N, M, cb, cookie, C.byref(params) if params is not None else None,
+                                                  C.byref(loss) if loss is not None else None, res,
+                                                  dptr(w) if w is not None else None)
+    return rc, p, _batch_results(res, B), w
+
+
+def optimize_dense_batch_robust_device(p_dev, B, N, M, cb, cookie, params, loss, results_dev, lambda_dev=None, weights_dev=None,
+                                       active_dev=None, stream=None):
+    """dogleg_amd_optimize_dense_batch_robust_device, the arguments as optimize_dense_batch_device; loss a BatchLoss (host),
+    weights_dev (B, M // featureSize) doubles or None.  Returns rc."""
+    return lib().dogleg_amd_optimize_dense_batch_robust_device(_dev(p_dev), B, N, M, cb, cookie,
+                                                               C.byref(params) if params is not None else None,
+                                                               C.byref(loss) if loss is not None else None, _dev(results_dev),
+                                                               _dev(lambda_dev), _dev(weights_dev), _dev(active_dev),
+                                                               _dev(stream))
 
 
 def batch_results_from_device(results_dev, B):

@@ -81,6 +81,24 @@ bool products_batch_ok(const char* who, unsigned int B, unsigned int Nstate, con
   return true;
 }
 
+// the loss of the robust batch solve
+bool batch_loss_ok(const char* who, const dogleg_amd_batch_loss_t* loss, unsigned int Nmeas)
+{
+  if(!loss) { MSG("%s: loss must be given (least squares: dogleg_amd_optimize_dense_batch, or DOGLEG_AMD_LOSS_TRIVIAL)", who); return false; }
+  if(loss->kind < DOGLEG_AMD_LOSS_TRIVIAL || loss->kind > DOGLEG_AMD_LOSS_CAUCHY)
+  { MSG("%s: loss->kind = %d is none of DOGLEG_AMD_LOSS_{TRIVIAL, HUBER, SOFT_L1, CAUCHY}", who, loss->kind); return false; }
+  if(loss->kind != DOGLEG_AMD_LOSS_TRIVIAL && !(std::isfinite(loss->scale) && loss->scale > 0.0))
+  { MSG("%s: loss->scale = %g must be finite and > 0", who, loss->scale); return false; }
+  if(loss->featureSize > DOGLEG_AMD_BATCH_LOSS_MAX_FEATURESIZE)
+  {
+    MSG("%s: loss->featureSize = %d: sizes 1 to %d are supported", who, loss->featureSize, DOGLEG_AMD_BATCH_LOSS_MAX_FEATURESIZE);
+    return false;
+  }
+  const unsigned int fs = loss->featureSize <= 1 ? 1u : (unsigned int)loss->featureSize;
+  if(Nmeas % fs) { MSG("%s: Nmeas = %u is not a multiple of loss->featureSize = %u", who, Nmeas, fs); return false; }
+  return true;
+}
+
 // a *_dev argument of the device-resident batch entry points: memory a kernel of the current device may touch over `bytes`
 bool device_span_ok(const char* who, const char* name, const void* ptr, size_t bytes)
 {
@@ -388,6 +406,35 @@ int dogleg_amd_optimize_dense_batch_device(double* p_dev, unsigned int B, unsign
   return dlg_dense_batch_device_run(DlgBatchDeviceSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false,
                                                         parameters ? parameters : &g_params, results_dev, lambda_dev, active_dev,
                                                         hip_stream});
+}
+// ---- the robust form of the solve and its device twin: the plain checks, then the loss, then (the twin) the pointers
+int dogleg_amd_optimize_dense_batch_robust(double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                           dogleg_callback_device_batch_t* f, void* cookie,
+                                           const dogleg_parameters2_t* parameters, const dogleg_amd_batch_loss_t* loss,
+                                           dogleg_amd_batch_result_t* results, double* weights)
+{
+  const char* who = "dogleg_amd_optimize_dense_batch_robust";
+  if(!p || !f || !results) { MSG("%s: p, the callback and results must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || !batch_loss_ok(who, loss, Nmeas) ||
+     !one_rank_only(who)) return -1;
+  return dlg_dense_batch_robust_run(p, B, Nstate, Nmeas, f, cookie, parameters ? parameters : &g_params, loss, results, weights);
+}
+int dogleg_amd_optimize_dense_batch_robust_device(double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                  dogleg_callback_device_batch_t* f, void* cookie,
+                                                  const dogleg_parameters2_t* parameters, const dogleg_amd_batch_loss_t* loss,
+                                                  dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                  double* weights_dev, const unsigned char* active_dev, void* hip_stream)
+{
+  const char* who = "dogleg_amd_optimize_dense_batch_robust_device";
+  if(!p_dev || !f || !results_dev) { MSG("%s: p_dev, the callback and results_dev must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || !batch_loss_ok(who, loss, Nmeas) ||
+     !one_rank_only(who)) return -1;
+  const size_t NF = Nmeas/(loss->featureSize <= 1 ? 1u : (unsigned int)loss->featureSize);
+  if(!solve_spans_ok(who, B, Nstate, p_dev, results_dev, lambda_dev, active_dev) ||
+     (weights_dev && !device_span_ok(who, "weights_dev", weights_dev, sizeof(double)*B*NF))) return -1;
+  return dlg_dense_batch_device_run(DlgBatchDeviceSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false,
+                                                        parameters ? parameters : &g_params, results_dev, lambda_dev, active_dev,
+                                                        hip_stream, loss, weights_dev});
 }
 int dogleg_amd_optimize_dense_products_batch_device(double* p_dev, unsigned int B, unsigned int Nstate,
                                                     dogleg_callback_device_batch_products_t* f, void* cookie,

@@ -7,6 +7,11 @@
 int  dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int M,
                          dogleg_callback_device_batch_t* f, void* cookie,
                          const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results);
+// dogleg_amd_optimize_dense_batch_robust: the same with a loss (checked by the caller: kind, scale, featureSize <= 4 that
+// divides M); weights: [B][M / featureSize] or NULL
+int  dlg_dense_batch_robust_run(double* p, unsigned int B, unsigned int N, unsigned int M,
+                                dogleg_callback_device_batch_t* f, void* cookie, const dogleg_parameters2_t* prm,
+                                const dogleg_amd_batch_loss_t* loss, dogleg_amd_batch_result_t* results, double* weights);
 // dogleg_amd_dense_batch_uncertainty behind the driver's checks (fs is 1 or 2 here); 0 / -1 with a message on stderr
 int  dlg_dense_batch_uncertainty_run(const double* p, unsigned int B, unsigned int N, unsigned int M,
                                      dogleg_callback_device_batch_t* f, void* cookie, double* lambda, double* covariance,
@@ -27,6 +32,7 @@ struct DlgBatchDeviceSolve
   dogleg_callback_device_batch_t* fJ; dogleg_callback_device_batch_products_t* fP; void* cookie; bool unpacked;
   const dogleg_parameters2_t* prm;
   dogleg_amd_batch_result_t* results; double* lambda; const unsigned char* active; void* stream;
+  const dogleg_amd_batch_loss_t* loss; double* weights;        // the robust form (J form only), or both NULL
 };
 int  dlg_dense_batch_device_run(const DlgBatchDeviceSolve& a);
 struct DlgBatchDeviceUnc

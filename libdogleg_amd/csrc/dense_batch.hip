@@ -66,6 +66,9 @@ struct ProductsDev
   int unpacked;
 };
 
+// the loss of a robust solve: c = a^2, fs rows a feature
+struct LossDev { int kind, fs; double a, c; };
+
 struct BatchDev
 {
   int B, N, M, NP;
@@ -75,6 +78,8 @@ struct BatchDev
   int max_iterations;
   double trustregion0, dec_factor, dec_thr, inc_factor, inc_thr, jtx_thr, upd_thr, tr_thr;
   ProductsDev P;               // FORM_PRODUCTS (x, J, M unused there)
+  LossDev L; int NF; double* wts;      // the robust form: NF = M / L.fs features, rho' at the point stepped from [B][NF]
+  int robust;                  // (host side: which kernel is launched)
 };
 
 template <int NMAX> struct BatchCfg
@@ -185,23 +190,70 @@ __device__ __forceinline__ void packed_entries(int N, int NP, int lane, int* ei,
   }
 }
 
+// rho(s) and w = rho'(s) of the loss L (dogleg.h: dogleg_amd_batch_loss_t); a NaN s gives NaN in both
+__device__ __forceinline__ void loss_eval(const LossDev& L, double s, double& rho, double& w)
+{
+  const double q = s/L.c;
+  switch(L.kind)
+  {
+  case DOGLEG_AMD_LOSS_HUBER:
+    if(s <= L.c) { rho = s; w = 1.0; }
+    else { const double r = sqrt(s); rho = 2.0*L.a*r - L.c; w = L.a/r; }
+    break;
+  case DOGLEG_AMD_LOSS_SOFT_L1:
+  {
+    // 2 c (r - 1) = 2 s / (r + 1): no cancellation for s << c
+    const double r = sqrt(1.0 + q);
+    rho = 2.0*s/(r + 1.0); w = 1.0/r;
+    break;
+  }
+  case DOGLEG_AMD_LOSS_CAUCHY:
+    rho = L.c*log1p(q); w = 1.0/(1.0 + q);
+    break;
+  default:
+    rho = s; w = 1.0;
+  }
+}
+// s of a feature of fs rows from x in memory: the products rounded, summed in the rows' order, as the sweep sums them
+__device__ __forceinline__ double feature_s(const double* xf, int fs)
+{
+#pragma clang fp contract(off)
+  double s = xf[0]*xf[0];
+  for(int k = 1; k < fs; k++) s += xf[k]*xf[k];
+  return s;
+}
+
 // the sweep over one point's x and J (xb: M, Jb: M x N row-major): returns norm2(x), leaves the packed lower triangle of
 // JtJ in SA and (Jt x)[lane] in gacc (eval_point, dogleg.c:1004-1083, and the rows' outer products dogleg.c:712-714).
 // tile: BATCH_TILE + 64 doubles of LDS.  Shared by the round and the uncertainty kernel: one order of operations.
-template <int NMAX>
+//
+// ROBUST: the same sweep with the loss L (first order: the curvature term of rho'' is left out, as Ceres' corrector does
+// for rho'' <= 0).  The tile height is a multiple of L.fs, so no feature straddles two tiles; the lane that holds x of row t
+// gets s of its feature by shuffles, evaluates rho and rho' and stages sqrt(w) x; every staged element of J is multiplied
+// by the sqrt(w) of its row (the element -> row map is the same for every tile).  The loop over the tile's rows is the plain
+// one.  Returns F.
+template <int NMAX, bool ROBUST = false>
 __device__ __forceinline__ double sweep_point(const double* Jb, const double* xb, int N, int M, int NP, int lane,
-                                              double* SA, double* tile, double& gacc_out)
+                                              double* SA, double* tile, double& gacc_out, const LossDev& L = LossDev())
 {
   using C = BatchCfg<NMAX>;
   double* xt = tile + BATCH_TILE;
   int ei[C::NE], ej[C::NE];
   packed_entries<NMAX>(N, NP, lane, ei, ej);
-  const int T = min(64, BATCH_TILE/N);
+  int T = min(64, BATCH_TILE/N);
   double acc[C::NE], gacc = 0.0, n2 = 0.0;
 #pragma unroll
   for(int k = 0; k < C::NE; k++) acc[k] = 0.0;
   constexpr int NL = BATCH_TILE/64;
   double v[NL], xv;
+  int rowof[NL], t0 = 0;       // ROBUST: the row of the tile element lane + 64 u; the first row of this lane's feature
+  if constexpr(ROBUST)
+  {
+    T -= T % L.fs;
+    t0 = lane - lane % L.fs;
+#pragma unroll
+    for(int u = 0; u < NL; u++) rowof[u] = min((lane + 64*u)/N, 63);     // (elements behind the tile's rows hold 0)
+  }
   {
     const int tc = min(T, M), cnt = tc*N;
 #pragma unroll
@@ -211,12 +263,46 @@ __device__ __forceinline__ double sweep_point(const double* Jb, const double* xb
   for(int r0 = 0; r0 < M; r0 += T)
   {
     const int tc = min(T, M - r0);
-    wsync();
+    if constexpr(ROBUST)
+    {
+      // sqrt(w) of this lane's row (1 behind the tile's rows) and the feature's rho, once a feature
+      double sw = 1.0;
+      // (the plain sweep's arithmetic, where the compiler contracts n2 += xv*xv; here the product is shared with the other
+      // branch and would not be contracted: hence spelled out, for the same bits)
+      if(L.kind == DOGLEG_AMD_LOSS_TRIVIAL) n2 = __builtin_fma(xv, xv, n2);
+      else
+      {
+        const double x2 = xv*xv;
+        double s = x2;
+        if(L.fs > 1)
+        {
+          // the rows of the feature in their order, in every one of its lanes: one s, one w a feature
+          s = __shfl(x2, t0, 64);
+          for(int k = 1; k < L.fs; k++) s += __shfl(x2, t0 + k, 64);
+        }
+        double rho, w;
+        loss_eval(L, s, rho, w);
+        if(lane < tc)
+        {
+          sw = sqrt(w);
+          if(lane == t0) n2 += rho;
+        }
+      }
+      wsync();
 #pragma unroll
-    for(int u = 0; u < NL; u++) tile[lane + 64*u] = v[u];
-    xt[lane] = xv;
-    wsync();
-    n2 += xv*xv;
+      for(int u = 0; u < NL; u++) tile[lane + 64*u] = v[u]*__shfl(sw, rowof[u], 64);
+      xt[lane] = sw*xv;
+      wsync();
+    }
+    else
+    {
+      wsync();
+#pragma unroll
+      for(int u = 0; u < NL; u++) tile[lane + 64*u] = v[u];
+      xt[lane] = xv;
+      wsync();
+      n2 += xv*xv;
+    }
     if(r0 + T < M)
     {
       const int r1 = r0 + T, tn = min(T, M - r1), cnt = tn*N;
@@ -289,7 +375,7 @@ __device__ __forceinline__ double load_products(const ProductsDev& P, int b, int
 }
 
 // one round of problem b; returns whether the problem is still live
-template <int NMAX, int FORM>
+template <int NMAX, int FORM, bool ROBUST>
 __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
 {
   using C = BatchCfg<NMAX>;
@@ -303,8 +389,8 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
   bool finite;
   if constexpr(FORM == FORM_J)
   {
-    // ---- the sweep over the trial point's x and J: norm2(x), Jt x, JtJ ----
-    n2x = sweep_point<NMAX>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc);
+    // ---- the sweep over the trial point's x and J: norm2(x), Jt x, JtJ (ROBUST: F, g, H in their places) ----
+    n2x = sweep_point<NMAX, ROBUST>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc, A.L);
     // a non-finite x or J shows in norm2(x) or on the diagonal of JtJ
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
@@ -365,6 +451,17 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
     }
     double* Gb = A.JtJ + (size_t)b*NP;
     for(int e = lane; e < NP; e += 64) Gb[e] = SA[e];
+    if constexpr(ROBUST)
+    {
+      // the weights of the point now stepped from: A.x still holds its x, so a rejected trial never needs them
+      const double* xb = A.x + (size_t)b*M; double* wb = A.wts + (size_t)b*A.NF;
+      for(int f = lane; f < A.NF; f += 64)
+      {
+        double rho, w;
+        loss_eval(A.L, feature_s(xb + (size_t)f*A.L.fs, A.L.fs), rho, w);
+        wb[f] = w;
+      }
+    }
     if(wave_max(fabs(g_r)) <= A.jtx_thr) status = DOGLEG_AMD_BATCH_JTX;
     else if(iters >= A.max_iterations) status = DOGLEG_AMD_BATCH_MAX_ITERATIONS;
   }
@@ -447,7 +544,7 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
   return status == 0;
 }
 
-template <int NMAX, int FORM>
+template <int NMAX, int FORM, bool ROBUST>
 __global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_round(BatchDev A)
 {
   constexpr int LDSW = FormCfg<NMAX, FORM>::LDSW, WPB = BatchCfg<NMAX>::WPB;
@@ -456,7 +553,7 @@ __global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_round(BatchDev
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x*WPB + w;
   bool still = false;
-  if(b < A.B && A.live[b]) still = batch_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
+  if(b < A.B && A.live[b]) still = batch_problem<NMAX, FORM, ROBUST>(A, b, lane, lds + w*LDSW);
   if(lane == 0) s_live[w] = still ? 1 : 0;
   __syncthreads();
   if(threadIdx.x == 0)
@@ -934,13 +1031,22 @@ __global__ void __launch_bounds__(256) k_batch_init(BatchDev A, const unsigned c
 // host for the host-pointer entry points).  Thread t takes element t of p, [B][N] (coalesced stores; a problem that FAILED
 // or was not run keeps its input), and, for t < B, the record and the lambda of problem t.  A status of 0 after the last
 // round is a problem that never was live: every live problem leaves its last round with a status.
-__global__ void __launch_bounds__(256) k_batch_finish(BatchDev A, double* p, dogleg_amd_batch_result_t* results, double* lambda)
+// The robust form (weights != nullptr; the grid covers [B][NF] too): thread t takes element t of the weights, NaN for a problem
+// that FAILED.
+__global__ void __launch_bounds__(256) k_batch_finish(BatchDev A, double* p, dogleg_amd_batch_result_t* results, double* lambda,
+                                                      double* weights)
 {
   const size_t t = (size_t)blockIdx.x*256 + threadIdx.x;
-  if(t >= (size_t)A.B*A.N) return;
+  if(t < (size_t)A.B*A.N)
   {
     const int status = A.st[(size_t)ST_COUNT*(t/A.N) + ST_STATUS];
     if(status != DOGLEG_AMD_BATCH_NOT_RUN && status != DOGLEG_AMD_BATCH_FAILED) p[t] = A.p_before[t];
+  }
+  if(weights && t < (size_t)A.B*A.NF)
+  {
+    const int status = A.st[(size_t)ST_COUNT*(t/A.NF) + ST_STATUS];
+    if(status == DOGLEG_AMD_BATCH_FAILED) weights[t] = __builtin_nan("");
+    else if(status != DOGLEG_AMD_BATCH_NOT_RUN) weights[t] = A.wts[t];
   }
   if(t >= (size_t)A.B) return;
   const int* st = A.st + (size_t)ST_COUNT*t; const double* sc = A.sc + (size_t)SC_COUNT*t;
@@ -1082,10 +1188,10 @@ ProductsDev products_dev(const BatchForm& F, const ProductsLayout& L, void* d_ev
 }
 
 // the grid and the block follow the size class: BatchCfg<NMAX>::WPB problems per workgroup
-template <int NMAX, int FORM> void launch_round_class(hipStream_t st, const BatchDev& A)
+template <int NMAX, int FORM, bool ROBUST> void launch_round_class(hipStream_t st, const BatchDev& A)
 {
   constexpr int WPB = BatchCfg<NMAX>::WPB;
-  hipLaunchKernelGGL((k_batch_round<NMAX, FORM>), dim3((A.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
+  hipLaunchKernelGGL((k_batch_round<NMAX, FORM, ROBUST>), dim3((A.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
 }
 template <int NMAX, int FORM> void launch_uncertainty_class(hipStream_t st, const UncDev& A)
 {
@@ -1106,14 +1212,14 @@ template <int FORM> void launch_query(unsigned int N, hipStream_t st, const Quer
   else if(N <= 48) launch_query_class<48, FORM>(st, A);
   else             launch_query_class<64, FORM>(st, A);
 }
-template <int FORM> void launch_round(unsigned int N, hipStream_t st, const BatchDev& A)
+template <int FORM, bool ROBUST = false> void launch_round(unsigned int N, hipStream_t st, const BatchDev& A)
 {
-  if(N <= 8)       launch_round_class<8, FORM>(st, A);
-  else if(N <= 16) launch_round_class<16, FORM>(st, A);
-  else if(N <= 24) launch_round_class<24, FORM>(st, A);
-  else if(N <= 32) launch_round_class<32, FORM>(st, A);
-  else if(N <= 48) launch_round_class<48, FORM>(st, A);
-  else             launch_round_class<64, FORM>(st, A);
+  if(N <= 8)       launch_round_class<8, FORM, ROBUST>(st, A);
+  else if(N <= 16) launch_round_class<16, FORM, ROBUST>(st, A);
+  else if(N <= 24) launch_round_class<24, FORM, ROBUST>(st, A);
+  else if(N <= 32) launch_round_class<32, FORM, ROBUST>(st, A);
+  else if(N <= 48) launch_round_class<48, FORM, ROBUST>(st, A);
+  else             launch_round_class<64, FORM, ROBUST>(st, A);
 }
 template <int FORM> void launch_uncertainty(unsigned int N, hipStream_t st, const UncDev& A)
 {
@@ -1126,16 +1232,18 @@ template <int FORM> void launch_uncertainty(unsigned int N, hipStream_t st, cons
 }
 
 // the cache opened and grown for B problems of N variables (M measurements; 0: the products form), and the kernels'
-// argument pointing into it
+// argument pointing into it.  loss: the robust form (checked by the caller), or nullptr
 int batch_setup(const char* who, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F,
-                const dogleg_parameters2_t* prm, BatchDev& A)
+                const dogleg_parameters2_t* prm, const dogleg_amd_batch_loss_t* loss, BatchDev& A)
 {
+  const unsigned int fs = loss ? (loss->featureSize <= 1 ? 1u : (unsigned int)loss->featureSize) : 1u;
+  const unsigned int NF = loss ? M/fs : 0;
   if(cache_open(who)) return -1;
   BatchCache& K = g_cache;
   const int NP = (int)(N*(N + 1)/2);
   // sizes in doubles first: B * M * (N + 1) can pass 2^64 bytes
   const double eval_d = F.products() ? (double)B*(1.0 + N + F.S(N)) : (double)B*(double)M*((double)N + 1.0);
-  const double state_d = (double)B*(5.0*N + NP + SC_COUNT + 1.0);
+  const double state_d = (double)B*(5.0*N + NP + SC_COUNT + 1.0 + NF);
   if((eval_d + state_d)*8.0 > 1.0e15)
   {
     dlg_set_error("%s: %.3g bytes of device memory", who, (eval_d + state_d)*8.0);
@@ -1149,7 +1257,8 @@ int batch_setup(const char* who, unsigned int B, unsigned int N, unsigned int M,
   const size_t live_bytes = align256(B);
   const ProductsLayout PL = products_layout(F, B, N);
   const size_t eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : x_bytes + J_bytes;
-  const size_t state_bytes = 5*vec_bytes + G_bytes + sc_bytes + st_bytes + live_bytes + 256;
+  const size_t wts_bytes = align256(sizeof(double)*(size_t)B*NF);
+  const size_t state_bytes = 5*vec_bytes + G_bytes + sc_bytes + st_bytes + live_bytes + 256 + wts_bytes;
   if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes)) return -1;
 
   A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = NP;
@@ -1160,7 +1269,10 @@ int batch_setup(const char* who, unsigned int B, unsigned int N, unsigned int M,
   A.p_before = (double*)q; q += vec_bytes; A.p_trial = (double*)q; q += vec_bytes; A.g = (double*)q; q += vec_bytes;
   A.cauchy = (double*)q; q += vec_bytes; A.gn = (double*)q; q += vec_bytes; A.JtJ = (double*)q; q += G_bytes;
   A.sc = (double*)q; q += sc_bytes; A.st = (int*)q; q += st_bytes; A.live = (unsigned char*)q; q += live_bytes;
-  A.counter = (int*)q;
+  A.counter = (int*)q; q += 256;
+  A.wts = loss ? (double*)q : nullptr; A.NF = (int)NF; A.robust = loss ? 1 : 0;
+  A.L.kind = loss ? loss->kind : DOGLEG_AMD_LOSS_TRIVIAL; A.L.fs = (int)fs;
+  A.L.a = loss && loss->kind != DOGLEG_AMD_LOSS_TRIVIAL ? loss->scale : 1.0; A.L.c = A.L.a*A.L.a;
   A.max_iterations = prm->max_iterations; A.trustregion0 = prm->trustregion0;
   A.dec_factor = prm->trustregion_decrease_factor; A.dec_thr = prm->trustregion_decrease_threshold;
   A.inc_factor = prm->trustregion_increase_factor; A.inc_thr = prm->trustregion_increase_threshold;
@@ -1197,8 +1309,9 @@ int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* c
     else
       F.fJ(A.p_trial, const_cast<double*>(A.x), const_cast<double*>(A.J), A.live, B, (void*)st, cookie);
     if(timing) BHIP(hipEventRecord(K.ev[1], st));
-    if(F.products()) launch_round<FORM_PRODUCTS>(N, st, A);
-    else             launch_round<FORM_J>(N, st, A);
+    if(F.products())   launch_round<FORM_PRODUCTS>(N, st, A);
+    else if(A.robust)  launch_round<FORM_J, true>(N, st, A);
+    else               launch_round<FORM_J>(N, st, A);
     BHIP(hipGetLastError());
     if(timing) BHIP(hipEventRecord(K.ev[2], st));
     BHIP(hipMemcpyAsync(K.h_counter, A.counter, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1216,12 +1329,15 @@ int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* c
   return 0;
 }
 
+// loss, weights: the robust form (weights: [B][NF] or nullptr), or both nullptr
 int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F, void* cookie,
-               const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)
+               const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results,
+               const dogleg_amd_batch_loss_t* loss = nullptr, double* weights = nullptr)
 {
-  const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch" : "dogleg_amd_optimize_dense_batch";
+  const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch" :
+                    loss ? "dogleg_amd_optimize_dense_batch_robust" : "dogleg_amd_optimize_dense_batch";
   BatchDev A;
-  if(batch_setup(who, B, N, M, F, prm, A)) return -1;
+  if(batch_setup(who, B, N, M, F, prm, loss, A)) return -1;
   hipStream_t st = g_cache.stream;
   BHIP(hipMemcpyAsync(A.p_trial, p, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_batch_init, dim3((B + 255)/256), dim3(256), 0, st, A, (const unsigned char*)nullptr);
@@ -1232,6 +1348,9 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
   BHIP(hipMemcpyAsync(sc.data(), A.sc, sizeof(double)*sc.size(), hipMemcpyDeviceToHost, st));
   BHIP(hipMemcpyAsync(sti.data(), A.st, sizeof(int)*sti.size(), hipMemcpyDeviceToHost, st));
   BHIP(hipMemcpyAsync(pb.data(), A.p_before, sizeof(double)*pb.size(), hipMemcpyDeviceToHost, st));
+  const size_t NF = (size_t)A.NF;
+  std::vector<double> wt(weights ? (size_t)B*NF : 0);
+  if(weights) BHIP(hipMemcpyAsync(wt.data(), A.wts, sizeof(double)*wt.size(), hipMemcpyDeviceToHost, st));
   BHIP(hipStreamSynchronize(st));
   for(size_t b = 0; b < B; b++)
   {
@@ -1242,6 +1361,11 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
     R.trustregion = sc[b*SC_COUNT + SC_TR]; R.lambda = sc[b*SC_COUNT + SC_LAMBDA];
     R.iterations = sti[b*ST_COUNT + ST_ITER]; R.evaluations = sti[b*ST_COUNT + ST_EVAL]; R.status = status;
     if(!failed) memcpy(p + b*N, pb.data() + b*N, sizeof(double)*N);
+    if(weights)
+    {
+      if(failed) for(size_t f = 0; f < NF; f++) weights[b*NF + f] = std::nan("");
+      else       memcpy(weights + b*NF, wt.data() + b*NF, sizeof(double)*NF);
+    }
   }
   return 0;
 }
@@ -1251,17 +1375,19 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
 int run_device_locked(const DlgBatchDeviceSolve& a)
 {
   const BatchForm F{a.fJ, a.fP, a.unpacked};
-  const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch_device" : "dogleg_amd_optimize_dense_batch_device";
+  const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch_device" :
+                    a.loss ? "dogleg_amd_optimize_dense_batch_robust_device" : "dogleg_amd_optimize_dense_batch_device";
   const unsigned int B = a.B, N = a.N;
   BatchDev A;
-  if(batch_setup(who, B, N, a.M, F, a.prm, A)) return -1;
+  if(batch_setup(who, B, N, a.M, F, a.prm, a.loss, A)) return -1;
   hipStream_t st = a.stream ? (hipStream_t)a.stream : g_cache.stream;
   BHIP(hipMemcpyAsync(A.p_trial, a.p, sizeof(double)*(size_t)B*N, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(k_batch_init, dim3((B + 255)/256), dim3(256), 0, st, A, a.active);
   BHIP(hipGetLastError());
   if(batch_rounds(who, F, A, a.cookie, st)) return -1;
-  const size_t n = (size_t)B*N;
-  hipLaunchKernelGGL(k_batch_finish, dim3((unsigned int)((n + 255)/256)), dim3(256), 0, st, A, a.p, a.results, a.lambda);
+  const size_t nw = a.loss && a.weights ? (size_t)B*A.NF : 0, n = (size_t)B*N > nw ? (size_t)B*N : nw;
+  hipLaunchKernelGGL(k_batch_finish, dim3((unsigned int)((n + 255)/256)), dim3(256), 0, st, A, a.p, a.results, a.lambda,
+                     a.loss ? a.weights : nullptr);
   BHIP(hipGetLastError());
   BHIP(hipStreamSynchronize(st));
   return 0;
@@ -1581,6 +1707,15 @@ int dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int 
 {
   std::lock_guard<std::mutex> lk(g_mu);
   const int rc = run_locked(p, B, N, M, BatchForm{f, nullptr, false}, cookie, prm, results);
+  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
+  return rc;
+}
+int dlg_dense_batch_robust_run(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f,
+                               void* cookie, const dogleg_parameters2_t* prm, const dogleg_amd_batch_loss_t* loss,
+                               dogleg_amd_batch_result_t* results, double* weights)
+{
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int rc = run_locked(p, B, N, M, BatchForm{f, nullptr, false}, cookie, prm, results, loss, weights);
   if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
   return rc;
 }

@@ -126,6 +126,15 @@ class BatchResult(C.Structure):
     ]
 
 
+LOSS_TRIVIAL, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY = 0, 1, 2, 3      # dogleg_amd_batch_loss_t.kind
+BATCH_LOSS_MAX_FEATURESIZE = 4
+
+
+class BatchLoss(C.Structure):
+    """dogleg_amd_batch_loss_t (include/dogleg.h)."""
+    _fields_ = [("kind", C.c_int), ("scale", C.c_double), ("featureSize", C.c_int)]
+
+
 class JacobianReport(C.Structure):
     """dogleg_amd_jacobian_report_t (include/dogleg.h)."""
     _fields_ = [
