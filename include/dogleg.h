@@ -642,6 +642,67 @@ int dogleg_amd_optimize_dense_batch_robust_device(double* p_dev, unsigned int B,
                                                   dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
                                                   double* weights_dev, const unsigned char* active_dev, void* hip_stream);
 
+/* ---- box bounds in the batch solve: every problem minimises norm2(x) (or, with a loss, F) subject to lower[b] <= p[b] <=
+ * upper[b], by an active-set dog-leg loop: variables on a bound whose gradient pushes outwards are held, the two steps are
+ * those of the free variables, the step chosen is clipped into the box, and a clipped step that the model does not like
+ * gives way to a Cauchy step cut at the first bound.  A callback cannot supply this alone (a reparameterisation changes the
+ * problem and its covariance and fails at the bound itself): the held set changes the Gauss-Newton system and the stopping
+ * test, the clipped step changes the expected improvement the gain ratio divides by.  The reference has no bounds.
+ * One problem, in the plain form's terms (with a loss read H, g, F for JtJ, Jt x, norm2(x), as in the robust form above):
+ *   1. Start.  p_i = min(max(p_i, lower_i), upper_i) before the first evaluation.  A problem with a NaN bound or with
+ *      lower_i > upper_i for any i is DOGLEG_AMD_BATCH_FAILED alone: evaluations 0, p[b] keeps its input bits, its held row is 0.
+ *   2. Held set, at the point stepped from (feasible by construction): i is held at lower if p_i == lower_i && g_i > 0, at
+ *      upper if p_i == upper_i && g_i < 0.  Equality is exact: the clamp of step 5 lands on the bound's bits.  The set is a
+ *      function of that point, its g and the bounds only: a rejected trial forms it again, nothing is stored for it.
+ *   3. Free gradient g_F: g with its held entries 0.  The Jt_x_threshold test is on |g_F|_inf (every variable held: 0, so the
+ *      problem stops with DOGLEG_AMD_BATCH_JTX before any division).  The Cauchy step is k g_F, k = -|g_F|^2 / (g_F' JtJ g_F).
+ *   4. Gauss-Newton step on the free set: in the copy of JtJ that is factorised, after lambda is added, every held row and
+ *      column gets zero off-diagonals and a diagonal of 1; the right-hand side is g_F, so the step is exactly 0 where held.
+ *      The factorisation, the lambda schedule and the choice among Cauchy-to-the-edge, Gauss-Newton and the interpolated
+ *      step are the plain solve's, on these two steps.
+ *   5. Clip.  trial_i = min(max(p_i + s_i, lower_i), upper_i); s'_i = s_i where nothing was clamped, bound_i - p_i where it
+ *      was.  With no component clamped nothing differs from the plain solve.  Expected improvement: -2 g's' - s'' JtJ s'.
+ *   6. Fallback, if some component was clamped and the expected improvement is <= 0 or max|s'| <= update_threshold:
+ *      d = t0 Cauchy with t0 = min(1, trustregion / |Cauchy|); alpha = min(1, min_i (far_i - p_i) / d_i) over the i with d_i != 0,
+ *      far_i = upper_i if d_i > 0, lower_i otherwise; the step is alpha d, clamped as in 5 (rounding only), with its own expected
+ *      improvement.  The step counts as one to the edge of the trust region iff |Cauchy| >= trustregion.  A free variable on a
+ *      bound has -g pointing inwards, so alpha > 0, and JtJ is positive semidefinite, so the improvement is > 0 up to rounding:
+ *      one that is <= 0 or not finite is DOGLEG_AMD_BATCH_FAILED.
+ *   7. update_threshold tests the step that is applied; the trial point is `trial`; the gain ratio, the trust-region update,
+ *      acceptance and what a rejected trial reuses are the plain solve's.
+ *   8. held[b] is the held set at the returned p[b].
+ * With bounds that clamp nothing (lower = upper = NULL, infinite entries, a box that is never met) every result has the bits of
+ * dogleg_amd_optimize_dense_batch (with a loss: of _robust), and held is all 0.
+ * The contract is that of dogleg_amd_optimize_dense_batch, _robust and their _device twins: the callback type and the live
+ * bytes, one callback, one launch and one 4-byte read-back per round, the result struct and the status codes (none is new),
+ * dogleg_amd_batch_last_stats, and for the twin the pointer checks (the three pointers inside *bounds, which itself is host
+ * memory, included), the stream rule and the mask (held of a problem that is not run is not written).
+ *   loss        NULL: least squares.  weights: as in the robust form; NULL unless a loss is given.
+ * Refused with a message and -1 before any device work, outputs untouched: what the plain (with a loss: the robust) twin refuses,
+ * a NULL bounds, weights without a loss; the device twin also refuses lower, upper and held as it refuses the other pointers.
+ * Device memory: the plain or robust solve's; the host-pointer form adds B Nstate doubles for each of lower and upper that
+ * is given (held is formed on the host from the returned point's p and g).
+ * Not provided: bounds in the products form; bounds in the uncertainty and query calls -- the recipe: call them at the returned
+ * p with a callback that zeroes the columns of J of the held variables and adds a unit row for each, using held; general
+ * linear constraints. */
+typedef struct
+{
+  const double*  lower;   /* [B][Nstate] or NULL: no lower bounds; -INFINITY entries allowed */
+  const double*  upper;   /* [B][Nstate] or NULL: no upper bounds; +INFINITY entries allowed */
+  unsigned char* held;    /* [B][Nstate] out or NULL: at the returned p[b]: 0 free, 1 held at lower, 2 held at upper */
+} dogleg_amd_batch_bounds_t;
+int dogleg_amd_optimize_dense_batch_bounded(double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                            dogleg_callback_device_batch_t* f, void* cookie,
+                                            const dogleg_parameters2_t* parameters, const dogleg_amd_batch_loss_t* loss,
+                                            const dogleg_amd_batch_bounds_t* bounds, dogleg_amd_batch_result_t* results,
+                                            double* weights);
+int dogleg_amd_optimize_dense_batch_bounded_device(double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                   dogleg_callback_device_batch_t* f, void* cookie,
+                                                   const dogleg_parameters2_t* parameters, const dogleg_amd_batch_loss_t* loss,
+                                                   const dogleg_amd_batch_bounds_t* bounds,
+                                                   dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                   double* weights_dev, const unsigned char* active_dev, void* hip_stream);
+
 /* ---- covariance of per-problem query Jacobians of a batch: Var(q) = Jq Sigma_b Jq^T with Sigma_b = (JtJ + lambda I)^-1 of
  * problem b at p[b], the batch twin of dogleg_amd_query_covariance.  Sigma_b is neither formed nor written: per problem the
  * answer is Nq blocks of Qrows x Qrows.  Four entry points, mirroring the four uncertainty entry points above: the same

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, BatchLoss, JacobianReport, JacobianEntry,
+from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, BatchLoss, BatchBounds, JacobianReport, JacobianEntry,
                           CB_SPARSE, CB_DENSE, CB_PRODUCTS, dptr, iptr)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -69,6 +69,7 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_dense_batch_uncertainty_device", "dogleg_amd_dense_products_batch_uncertainty_device",
     "dlg_batch_device_span_ok",          # (csrc/dense_batch.h: the pointer check of the four above, exported for the tests)
     "dogleg_amd_optimize_dense_batch_robust", "dogleg_amd_optimize_dense_batch_robust_device",
+    "dogleg_amd_optimize_dense_batch_bounded", "dogleg_amd_optimize_dense_batch_bounded_device",
     "dogleg_amd_dense_batch_query_covariance", "dogleg_amd_dense_products_batch_query_covariance",
     "dogleg_amd_dense_batch_query_covariance_device", "dogleg_amd_dense_products_batch_query_covariance_device",
     "dogleg_amd_jacobian_colouring", "dogleg_amd_check_jacobian_device", "dogleg_amd_check_jacobian_device_batch",
@@ -242,6 +243,12 @@ def lib():
         L.dogleg_amd_optimize_dense_batch_robust.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, V, V, PP, LP,
                                                              C.POINTER(BatchResult), D]
         L.dogleg_amd_optimize_dense_batch_robust_device.argtypes = [V, C.c_uint, C.c_uint, C.c_uint, V, V, PP, LP, V, V, V, V, V]
+    if hasattr(L, "dogleg_amd_optimize_dense_batch_bounded"):
+        LP, BP = C.POINTER(BatchLoss), C.POINTER(BatchBounds)
+        L.dogleg_amd_optimize_dense_batch_bounded.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, V, V, PP, LP, BP,
+                                                              C.POINTER(BatchResult), D]
+        L.dogleg_amd_optimize_dense_batch_bounded_device.argtypes = [V, C.c_uint, C.c_uint, C.c_uint, V, V, PP, LP, BP, V, V, V,
+                                                                     V, V]
     if hasattr(L, "dogleg_amd_dense_batch_query_covariance"):
         U = C.c_uint
         L.dogleg_amd_dense_batch_query_covariance.argtypes = [D, U, U, U, V, V, D, D, U, U, C.c_int, D, I]
@@ -466,6 +473,43 @@ def optimize_dense_batch_robust_device(p_dev, B, N, M, cb, cookie, params, loss,
                                                                C.byref(loss) if loss is not None else None, _dev(results_dev),
                                                                _dev(lambda_dev), _dev(weights_dev), _dev(active_dev),
                                                                _dev(stream))
+
+
+def optimize_dense_batch_bounded(p0s, N, M, cb, cookie, lower, upper, loss=None, params=None, want_weights=None,
+                                 want_held=True):
+    """dogleg_amd_optimize_dense_batch_bounded: as optimize_dense_batch with lower, upper (B, N) arrays or None (NULL) and loss a
+    BatchLoss or None (least squares).  Returns (rc, p (B, N), results, held (B, N) uint8 prefilled with 255 or None, weights
+    (B, M // max(featureSize, 1)) prefilled with -1 or None: asked for by default where a loss is given)."""
+    L = lib()
+    p = np.array(p0s, dtype=np.float64, copy=True).reshape(-1, N)
+    B = p.shape[0]
+    res = (BatchResult * max(B, 1))()
+    lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).reshape(B, N)
+    hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).reshape(B, N)
+    held = np.full((B, N), 255, dtype=np.uint8) if want_held else None
+    if want_weights is None:
+        want_weights = loss is not None
+    fs = max(loss.featureSize, 1) if loss is not None else 1
+    w = np.full((B, M // fs), -1.0) if want_weights else None
+    addr = lambda a: None if a is None else a.ctypes.data
+    bounds = BatchBounds(addr(lo), addr(hi), addr(held))
+    rc = L.dogleg_amd_optimize_dense_batch_bounded(dptr(p), B, N, M, cb, cookie, C.byref(params) if params is not None else None,
+                                                   C.byref(loss) if loss is not None else None, C.byref(bounds), res,
+                                                   dptr(w) if w is not None else None)
+    return rc, p, _batch_results(res, B), held, w
+
+
+def optimize_dense_batch_bounded_device(p_dev, B, N, M, cb, cookie, params, loss, lower_dev, upper_dev, held_dev, results_dev,
+                                        lambda_dev=None, weights_dev=None, active_dev=None, stream=None):
+    """dogleg_amd_optimize_dense_batch_bounded_device, the arguments as optimize_dense_batch_robust_device; lower_dev, upper_dev
+    (B, N) doubles and held_dev (B, N) bytes: DeviceArrays, raw addresses or None.  Returns rc."""
+    raw = lambda a: None if a is None else _dev(a).value
+    bounds = BatchBounds(raw(lower_dev), raw(upper_dev), raw(held_dev))
+    return lib().dogleg_amd_optimize_dense_batch_bounded_device(_dev(p_dev), B, N, M, cb, cookie,
+                                                                C.byref(params) if params is not None else None,
+                                                                C.byref(loss) if loss is not None else None, C.byref(bounds),
+                                                                _dev(results_dev), _dev(lambda_dev), _dev(weights_dev),
+                                                                _dev(active_dev), _dev(stream))
 
 
 def batch_results_from_device(results_dev, B):

@@ -99,6 +99,15 @@ bool batch_loss_ok(const char* who, const dogleg_amd_batch_loss_t* loss, unsigne
   return true;
 }
 
+// the bounds of the bounded batch solve: the struct must be given (its pointers may be NULL), weights belong to a loss
+bool batch_bounds_ok(const char* who, const dogleg_amd_batch_bounds_t* bounds, const dogleg_amd_batch_loss_t* loss,
+                     const double* weights)
+{
+  if(!bounds) { MSG("%s: bounds must be given (no bounds at all: lower = upper = NULL inside it, or the entry point without _bounded)", who); return false; }
+  if(weights && !loss) { MSG("%s: weights are those of a loss, and loss is NULL", who); return false; }
+  return true;
+}
+
 // a *_dev argument of the device-resident batch entry points: memory a kernel of the current device may touch over `bytes`
 bool device_span_ok(const char* who, const char* name, const void* ptr, size_t bytes)
 {
@@ -435,6 +444,42 @@ int dogleg_amd_optimize_dense_batch_robust_device(double* p_dev, unsigned int B,
   return dlg_dense_batch_device_run(DlgBatchDeviceSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false,
                                                         parameters ? parameters : &g_params, results_dev, lambda_dev, active_dev,
                                                         hip_stream, loss, weights_dev});
+}
+// ---- the bounded form and its device twin: the plain checks, the loss where one is given, the bounds, then (the twin) the pointers
+int dogleg_amd_optimize_dense_batch_bounded(double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                            dogleg_callback_device_batch_t* f, void* cookie,
+                                            const dogleg_parameters2_t* parameters, const dogleg_amd_batch_loss_t* loss,
+                                            const dogleg_amd_batch_bounds_t* bounds, dogleg_amd_batch_result_t* results,
+                                            double* weights)
+{
+  const char* who = "dogleg_amd_optimize_dense_batch_bounded";
+  if(!p || !f || !results) { MSG("%s: p, the callback and results must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || (loss && !batch_loss_ok(who, loss, Nmeas)) ||
+     !batch_bounds_ok(who, bounds, loss, weights) || !one_rank_only(who)) return -1;
+  return dlg_dense_batch_bounded_run(p, B, Nstate, Nmeas, f, cookie, parameters ? parameters : &g_params, loss, bounds, results,
+                                     weights);
+}
+int dogleg_amd_optimize_dense_batch_bounded_device(double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                   dogleg_callback_device_batch_t* f, void* cookie,
+                                                   const dogleg_parameters2_t* parameters, const dogleg_amd_batch_loss_t* loss,
+                                                   const dogleg_amd_batch_bounds_t* bounds,
+                                                   dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                   double* weights_dev, const unsigned char* active_dev, void* hip_stream)
+{
+  const char* who = "dogleg_amd_optimize_dense_batch_bounded_device";
+  if(!p_dev || !f || !results_dev) { MSG("%s: p_dev, the callback and results_dev must be given", who); return -1; }
+  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || (loss && !batch_loss_ok(who, loss, Nmeas)) ||
+     !batch_bounds_ok(who, bounds, loss, weights_dev) || !one_rank_only(who)) return -1;
+  const size_t NF = loss ? Nmeas/(loss->featureSize <= 1 ? 1u : (unsigned int)loss->featureSize) : 0;
+  const size_t BN = (size_t)B*Nstate;
+  if(!solve_spans_ok(who, B, Nstate, p_dev, results_dev, lambda_dev, active_dev) ||
+     (weights_dev && !device_span_ok(who, "weights_dev", weights_dev, sizeof(double)*B*NF)) ||
+     (bounds->lower && !device_span_ok(who, "bounds->lower", bounds->lower, sizeof(double)*BN)) ||
+     (bounds->upper && !device_span_ok(who, "bounds->upper", bounds->upper, sizeof(double)*BN)) ||
+     (bounds->held && !device_span_ok(who, "bounds->held", bounds->held, BN))) return -1;
+  return dlg_dense_batch_device_run(DlgBatchDeviceSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false,
+                                                        parameters ? parameters : &g_params, results_dev, lambda_dev, active_dev,
+                                                        hip_stream, loss, weights_dev, bounds});
 }
 int dogleg_amd_optimize_dense_products_batch_device(double* p_dev, unsigned int B, unsigned int Nstate,
                                                     dogleg_callback_device_batch_products_t* f, void* cookie,

@@ -12,6 +12,12 @@ int  dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int
 int  dlg_dense_batch_robust_run(double* p, unsigned int B, unsigned int N, unsigned int M,
                                 dogleg_callback_device_batch_t* f, void* cookie, const dogleg_parameters2_t* prm,
                                 const dogleg_amd_batch_loss_t* loss, dogleg_amd_batch_result_t* results, double* weights);
+// dogleg_amd_optimize_dense_batch_bounded: the same with box bounds (bounds given; lower / upper / held may be NULL) and,
+// where loss is given, the loss (checked as above; weights NULL without it)
+int  dlg_dense_batch_bounded_run(double* p, unsigned int B, unsigned int N, unsigned int M,
+                                 dogleg_callback_device_batch_t* f, void* cookie, const dogleg_parameters2_t* prm,
+                                 const dogleg_amd_batch_loss_t* loss, const dogleg_amd_batch_bounds_t* bounds,
+                                 dogleg_amd_batch_result_t* results, double* weights);
 // dogleg_amd_dense_batch_uncertainty behind the driver's checks (fs is 1 or 2 here); 0 / -1 with a message on stderr
 int  dlg_dense_batch_uncertainty_run(const double* p, unsigned int B, unsigned int N, unsigned int M,
                                      dogleg_callback_device_batch_t* f, void* cookie, double* lambda, double* covariance,
@@ -33,6 +39,7 @@ struct DlgBatchDeviceSolve
   const dogleg_parameters2_t* prm;
   dogleg_amd_batch_result_t* results; double* lambda; const unsigned char* active; void* stream;
   const dogleg_amd_batch_loss_t* loss; double* weights;        // the robust form (J form only), or both NULL
+  const dogleg_amd_batch_bounds_t* bounds;                     // the bounded form (J form only; its three pointers: device), or NULL
 };
 int  dlg_dense_batch_device_run(const DlgBatchDeviceSolve& a);
 struct DlgBatchDeviceUnc

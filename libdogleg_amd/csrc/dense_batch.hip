@@ -33,6 +33,11 @@
 // which writes p, the result structs and lambda where the caller has them; the uncertainty kernel's per-output pointers point
 // at the caller's arrays.  An active mask is the initial value of the solve's live bytes and a wave-uniform return at the head
 // of k_batch_uncertainty.  k_batch_round is the same for both routes.
+//
+// The bounded form (dogleg_amd_optimize_dense_batch_bounded and its _device twin): box bounds per problem by an active-set loop,
+// the eight steps above the prototype in dogleg.h.  BOUNDED is a template flag of batch_problem and k_batch_round beside ROBUST
+// (J form only); everything it adds lies behind the sweep, on the on-chip JtJ, g and the two cached steps, and needs no LDS of
+// its own.  k_batch_clamp (behind k_batch_init) clamps the start points; k_batch_finish, or run_locked on the host, forms held.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -80,6 +85,10 @@ struct BatchDev
   ProductsDev P;               // FORM_PRODUCTS (x, J, M unused there)
   LossDev L; int NF; double* wts;      // the robust form: NF = M / L.fs features, rho' at the point stepped from [B][NF]
   int robust;                  // (host side: which kernel is launched)
+  // the bounded form (behind everything above: the other kernels read their arguments where they did): lo, hi [B][N] or nullptr
+  // (no bound on that side), held [B][N] out or nullptr
+  const double *lo, *hi; unsigned char* held;
+  int bounded;                 // (host side: which kernel is launched)
 };
 
 template <int NMAX> struct BatchCfg
@@ -116,6 +125,33 @@ __device__ inline double wave_max(double v)
 {
   for(int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
   return v;
+}
+__device__ inline double wave_min(double v)
+{
+  for(int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// the bounded form (dogleg.h: dogleg_amd_batch_bounds_t).  Bit i of the held set: variable i sits on a bound, bit for bit, and
+// its gradient pushes outwards.  A function of the point stepped from, g and the bounds alone; every lane gets the whole mask
+__device__ __forceinline__ unsigned long long held_mask(double p, double g, double lo, double hi, int lane, int N)
+{
+  return __ballot(lane < N && ((p == lo && g > 0.0) || (p == hi && g < 0.0)));
+}
+// this lane's entry of an array of bounds [B][N], or `none` where there is no array or no variable
+__device__ __forceinline__ double bound_at(const double* bounds, size_t bN, int lane, int N, double none)
+{
+  return bounds && lane < N ? bounds[bN + lane] : none;
+}
+// p + s clamped into [lo, hi]; s becomes the step that was applied (untouched where nothing was clamped: then the sum is the
+// plain solve's).  Returns the point; clamped: whether this lane's component was
+__device__ __forceinline__ double clip_step(double p, double& s, double lo, double hi, bool& clamped)
+{
+  double t = p + s;
+  clamped = false;
+  if(t < lo) { t = lo; clamped = true; }
+  if(t > hi) { t = hi; clamped = true; }
+  if(clamped) s = t - p;
+  return t;
 }
 // first entry of column c of the packed lower triangle (column-major; the same bytes as the reference's row-major
 // packed upper, dogleg.c:788-790)
@@ -374,10 +410,14 @@ __device__ __forceinline__ double load_products(const ProductsDev& P, int b, int
   return n2x;
 }
 
-// one round of problem b; returns whether the problem is still live
-template <int NMAX, int FORM, bool ROBUST>
+// one round of problem b; returns whether the problem is still live.
+// BOUNDED (J form): box bounds by an active set, the eight steps above dogleg_amd_optimize_dense_batch_bounded in dogleg.h.
+// Everything it adds lies behind the sweep, on the on-chip JtJ, g and the two cached steps; the other instantiations keep
+// their text.
+template <int NMAX, int FORM, bool ROBUST, bool BOUNDED>
 __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
 {
+  static_assert(!BOUNDED || FORM == FORM_J, "bounds: the J form only");
   using C = BatchCfg<NMAX>;
   const int N = A.N, M = A.M, NP = A.NP;
   double* SA = S;                      // JtJ of the point the step is taken from
@@ -408,6 +448,9 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
   double n2x_b = sc[SC_N2X], tr = sc[SC_TR], lam = sc[SC_LAMBDA], n2c = sc[SC_N2C], n2gn = sc[SC_N2GN];
   double EI = sc[SC_EI];
   double p_r = 0.0, g_r = 0.0, ca_r = 0.0, gn_r = 0.0;
+  // BOUNDED: the held set of the point stepped from; this lane's bounds (none beyond N) are read where they are used, not
+  // kept in registers across the sweep and the factorisation
+  unsigned long long hm = 0;
   bool take = false;           // the trial point becomes the point to step from
   if(!finite) status = DOGLEG_AMD_BATCH_FAILED;
   else if(!(flags & F_STARTED)) take = true;
@@ -438,6 +481,8 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
         wsync();
         for(int e = lane; e < NP; e += 64) SA[e] = Gb[e];
         wsync();
+        // (the cached steps are those of this held set: it is recomputed, not stored)
+        if constexpr(BOUNDED) hm = held_mask(p_r, g_r, bound_at(A.lo, bN, lane, N, -INFINITY), bound_at(A.hi, bN, lane, N, INFINITY), lane, N);
       }
     }
   }
@@ -462,9 +507,21 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
         wb[f] = w;
       }
     }
-    if(wave_max(fabs(g_r)) <= A.jtx_thr) status = DOGLEG_AMD_BATCH_JTX;
+    double gmax;
+    if constexpr(BOUNDED)
+    {
+      // the stopping test is on the free gradient: 0 with every variable held
+      hm = held_mask(p_r, g_r, bound_at(A.lo, bN, lane, N, -INFINITY), bound_at(A.hi, bN, lane, N, INFINITY), lane, N);
+      gmax = wave_max((hm >> lane) & 1 ? 0.0 : fabs(g_r));
+    }
+    else gmax = wave_max(fabs(g_r));
+    if(gmax <= A.jtx_thr) status = DOGLEG_AMD_BATCH_JTX;
     else if(iters >= A.max_iterations) status = DOGLEG_AMD_BATCH_MAX_ITERATIONS;
   }
+  // the free gradient: g with its held entries 0 (the Cauchy step and the right-hand side of the Gauss-Newton step); the
+  // expected improvement keeps g
+  double gf_r = g_r;
+  if constexpr(BOUNDED) { if((hm >> lane) & 1) gf_r = 0.0; }
 
   // ---- take_step (dogleg.c:1172-1297) ----
   if(status == 0)
@@ -472,10 +529,10 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
     const double tr2 = tr*tr;
     if(!(flags & F_CAUCHY))
     {
-      const double g2 = wave_sum(g_r*g_r);
-      const double Jg2 = quad_form(SA, SV, g_r, N, lane);
+      const double g2 = wave_sum(gf_r*gf_r);
+      const double Jg2 = quad_form(SA, SV, gf_r, N, lane);
       const double k = -g2/Jg2;
-      n2c = k*k*g2; ca_r = k*g_r;
+      n2c = k*k*g2; ca_r = k*gf_r;
       if(lane < N) A.cauchy[bN + lane] = ca_r;
       flags |= F_CAUCHY;
     }
@@ -497,13 +554,28 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
           wsync();
           if(lam > 0.0 && lane < N) SL[col_off(lane, N)] += lam;
           wsync();
+          if constexpr(BOUNDED)
+          {
+            // the system on the free set: a held row and column is that of the identity, so that gn is exactly 0 there
+            if(hm)
+            {
+              int c = 0;
+              for(int e = lane; e < NP; e += 64)
+              {
+                while(e >= col_off(c + 1, N)) c++;
+                const int i = c + e - col_off(c, N);
+                if(((hm >> c) | (hm >> i)) & 1) SL[e] = i == c ? 1.0 : 0.0;
+              }
+              wsync();
+            }
+          }
           if(chol_packed(SL, N, lane)) break;
           lam = lam == 0.0 ? LAMBDA_INITIAL : lam*10.0;
           if(!isfinite(lam)) { status = DOGLEG_AMD_BATCH_FAILED; break; }
         }
         if(status == 0)
         {
-          gn_r = -solve_packed(SL, g_r, N, lane);
+          gn_r = -solve_packed(SL, gf_r, N, lane);
           if(lane >= N) gn_r = 0.0;
           n2gn = wave_sum(gn_r*gn_r);
           if(lane < N) A.gn[bN + lane] = gn_r;
@@ -526,7 +598,48 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
         }
       }
     }
-    if(status == 0)
+    // BOUNDED: the step clipped into the box.  With no component clamped the text below this block is the plain solve's
+    bool clipped = false;
+    if constexpr(BOUNDED)
+    {
+      if(status == 0)
+      {
+        const double lo_r = bound_at(A.lo, bN, lane, N, -INFINITY), hi_r = bound_at(A.hi, bN, lane, N, INFINITY);
+        bool cl;
+        double sc_r = s_r;
+        double t_r = clip_step(p_r, sc_r, lo_r, hi_r, cl);
+        clipped = __any(cl);
+        if(clipped)
+        {
+          s_r = sc_r;
+          double Js2 = quad_form(SA, SV, s_r, N, lane);
+          EI = -2.0*wave_sum(g_r*s_r) - Js2;
+          double smax = wave_max(fabs(s_r));
+          if(EI <= 0.0 || smax <= A.upd_thr)
+          {
+            // the clipped step is no descent step of the model, or no step at all: the Cauchy step, cut at the trust region,
+            // then at the first bound a free variable meets
+            const double d_r = fmin(1.0, tr/sqrt(n2c))*ca_r;
+            double a_r = 1.0;
+            if(lane < N && d_r != 0.0) a_r = ((d_r > 0.0 ? hi_r : lo_r) - p_r)/d_r;
+            const double alpha = fmin(1.0, wave_min(a_r));
+            s_r = alpha*d_r;
+            t_r = clip_step(p_r, s_r, lo_r, hi_r, cl);
+            Js2 = quad_form(SA, SV, s_r, N, lane);
+            EI = -2.0*wave_sum(g_r*s_r) - Js2;
+            smax = wave_max(fabs(s_r));
+            if(n2c >= tr2) flags |= F_EDGE; else flags &= ~F_EDGE;
+            if(!(EI > 0.0) || !isfinite(EI)) status = DOGLEG_AMD_BATCH_FAILED;
+          }
+          if(status == 0)
+          {
+            if(smax <= A.upd_thr) status = DOGLEG_AMD_BATCH_SMALL_STEP;
+            else if(lane < N) A.p_trial[bN + lane] = t_r;
+          }
+        }
+      }
+    }
+    if(!clipped && status == 0)
     {
       const double Js2 = quad_form(SA, SV, s_r, N, lane);
       EI = -2.0*wave_sum(g_r*s_r) - Js2;
@@ -544,7 +657,7 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
   return status == 0;
 }
 
-template <int NMAX, int FORM, bool ROBUST>
+template <int NMAX, int FORM, bool ROBUST, bool BOUNDED>
 __global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_round(BatchDev A)
 {
   constexpr int LDSW = FormCfg<NMAX, FORM>::LDSW, WPB = BatchCfg<NMAX>::WPB;
@@ -553,7 +666,7 @@ __global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_round(BatchDev
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x*WPB + w;
   bool still = false;
-  if(b < A.B && A.live[b]) still = batch_problem<NMAX, FORM, ROBUST>(A, b, lane, lds + w*LDSW);
+  if(b < A.B && A.live[b]) still = batch_problem<NMAX, FORM, ROBUST, BOUNDED>(A, b, lane, lds + w*LDSW);
   if(lane == 0) s_live[w] = still ? 1 : 0;
   __syncthreads();
   if(threadIdx.x == 0)
@@ -1027,12 +1140,47 @@ __global__ void __launch_bounds__(256) k_batch_init(BatchDev A, const unsigned c
   A.live[b] = active ? (active[b] ? 1 : 0) : 1;
 }
 
+// the start of a bounded solve, behind k_batch_init: the start point of every live problem clamped into its box.  A problem with
+// a NaN bound or lo > hi is FAILED here, alone: never live, no evaluation, its p not touched
+__global__ void __launch_bounds__(256) k_batch_clamp(BatchDev A)
+{
+  const int b = blockIdx.x*256 + threadIdx.x;
+  if(b >= A.B || !A.live[b]) return;
+  const size_t bN = (size_t)b*A.N;
+  bool ok = true;
+  for(int i = 0; i < A.N; i++)
+  {
+    const double lo = A.lo ? A.lo[bN + i] : -INFINITY, hi = A.hi ? A.hi[bN + i] : INFINITY;
+    if(!(lo <= hi)) ok = false;
+  }
+  if(!ok)
+  {
+    A.st[(size_t)ST_COUNT*b + ST_STATUS] = DOGLEG_AMD_BATCH_FAILED;
+    A.live[b] = 0;
+    return;
+  }
+  for(int i = 0; i < A.N; i++)
+  {
+    double p = A.p_trial[bN + i];
+    if(A.lo && p < A.lo[bN + i]) p = A.lo[bN + i];
+    if(A.hi && p > A.hi[bN + i]) p = A.hi[bN + i];
+    A.p_trial[bN + i] = p;
+  }
+}
+// 0 free, 1 held at lower, 2 held at upper: the held set at a point with the g of that point (held_mask, per element)
+__host__ __device__ inline unsigned char held_code(double p, double g, double lo, double hi)
+{
+  return p == lo && g > 0.0 ? 1 : p == hi && g < 0.0 ? 2 : 0;
+}
+
 // the end of a device-resident solve: the state of every problem into the caller's arrays (what run_locked does on the
 // host for the host-pointer entry points).  Thread t takes element t of p, [B][N] (coalesced stores; a problem that FAILED
 // or was not run keeps its input), and, for t < B, the record and the lambda of problem t.  A status of 0 after the last
 // round is a problem that never was live: every live problem leaves its last round with a status.
 // The robust form (weights != nullptr; the grid covers [B][NF] too): thread t takes element t of the weights, NaN for a problem
 // that FAILED.
+// The bounded form (A.held != nullptr): the held set at the returned point, from p, g and the bounds as the round kernel forms
+// it; all 0 for a problem that FAILED.
 __global__ void __launch_bounds__(256) k_batch_finish(BatchDev A, double* p, dogleg_amd_batch_result_t* results, double* lambda,
                                                       double* weights)
 {
@@ -1041,6 +1189,9 @@ __global__ void __launch_bounds__(256) k_batch_finish(BatchDev A, double* p, dog
   {
     const int status = A.st[(size_t)ST_COUNT*(t/A.N) + ST_STATUS];
     if(status != DOGLEG_AMD_BATCH_NOT_RUN && status != DOGLEG_AMD_BATCH_FAILED) p[t] = A.p_before[t];
+    if(A.held && status != DOGLEG_AMD_BATCH_NOT_RUN)
+      A.held[t] = status == DOGLEG_AMD_BATCH_FAILED ? 0 :
+                  held_code(A.p_before[t], A.g[t], A.lo ? A.lo[t] : -INFINITY, A.hi ? A.hi[t] : INFINITY);
   }
   if(weights && t < (size_t)A.B*A.NF)
   {
@@ -1188,10 +1339,10 @@ ProductsDev products_dev(const BatchForm& F, const ProductsLayout& L, void* d_ev
 }
 
 // the grid and the block follow the size class: BatchCfg<NMAX>::WPB problems per workgroup
-template <int NMAX, int FORM, bool ROBUST> void launch_round_class(hipStream_t st, const BatchDev& A)
+template <int NMAX, int FORM, bool ROBUST, bool BOUNDED> void launch_round_class(hipStream_t st, const BatchDev& A)
 {
   constexpr int WPB = BatchCfg<NMAX>::WPB;
-  hipLaunchKernelGGL((k_batch_round<NMAX, FORM, ROBUST>), dim3((A.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
+  hipLaunchKernelGGL((k_batch_round<NMAX, FORM, ROBUST, BOUNDED>), dim3((A.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
 }
 template <int NMAX, int FORM> void launch_uncertainty_class(hipStream_t st, const UncDev& A)
 {
@@ -1212,14 +1363,14 @@ template <int FORM> void launch_query(unsigned int N, hipStream_t st, const Quer
   else if(N <= 48) launch_query_class<48, FORM>(st, A);
   else             launch_query_class<64, FORM>(st, A);
 }
-template <int FORM, bool ROBUST = false> void launch_round(unsigned int N, hipStream_t st, const BatchDev& A)
+template <int FORM, bool ROBUST = false, bool BOUNDED = false> void launch_round(unsigned int N, hipStream_t st, const BatchDev& A)
 {
-  if(N <= 8)       launch_round_class<8, FORM, ROBUST>(st, A);
-  else if(N <= 16) launch_round_class<16, FORM, ROBUST>(st, A);
-  else if(N <= 24) launch_round_class<24, FORM, ROBUST>(st, A);
-  else if(N <= 32) launch_round_class<32, FORM, ROBUST>(st, A);
-  else if(N <= 48) launch_round_class<48, FORM, ROBUST>(st, A);
-  else             launch_round_class<64, FORM, ROBUST>(st, A);
+  if(N <= 8)       launch_round_class<8, FORM, ROBUST, BOUNDED>(st, A);
+  else if(N <= 16) launch_round_class<16, FORM, ROBUST, BOUNDED>(st, A);
+  else if(N <= 24) launch_round_class<24, FORM, ROBUST, BOUNDED>(st, A);
+  else if(N <= 32) launch_round_class<32, FORM, ROBUST, BOUNDED>(st, A);
+  else if(N <= 48) launch_round_class<48, FORM, ROBUST, BOUNDED>(st, A);
+  else             launch_round_class<64, FORM, ROBUST, BOUNDED>(st, A);
 }
 template <int FORM> void launch_uncertainty(unsigned int N, hipStream_t st, const UncDev& A)
 {
@@ -1233,8 +1384,10 @@ template <int FORM> void launch_uncertainty(unsigned int N, hipStream_t st, cons
 
 // the cache opened and grown for B problems of N variables (M measurements; 0: the products form), and the kernels'
 // argument pointing into it.  loss: the robust form (checked by the caller), or nullptr
+// nbounds: the bounded host-pointer form keeps that many arrays [B][N] of bounds (0 .. 2) behind the state; they come back in
+// A.lo (the first) and A.hi (the second) and the caller says which is which
 int batch_setup(const char* who, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F,
-                const dogleg_parameters2_t* prm, const dogleg_amd_batch_loss_t* loss, BatchDev& A)
+                const dogleg_parameters2_t* prm, const dogleg_amd_batch_loss_t* loss, BatchDev& A, int nbounds = 0)
 {
   const unsigned int fs = loss ? (loss->featureSize <= 1 ? 1u : (unsigned int)loss->featureSize) : 1u;
   const unsigned int NF = loss ? M/fs : 0;
@@ -1243,7 +1396,7 @@ int batch_setup(const char* who, unsigned int B, unsigned int N, unsigned int M,
   const int NP = (int)(N*(N + 1)/2);
   // sizes in doubles first: B * M * (N + 1) can pass 2^64 bytes
   const double eval_d = F.products() ? (double)B*(1.0 + N + F.S(N)) : (double)B*(double)M*((double)N + 1.0);
-  const double state_d = (double)B*(5.0*N + NP + SC_COUNT + 1.0 + NF);
+  const double state_d = (double)B*(5.0*N + NP + SC_COUNT + 1.0 + NF + (double)nbounds*N);
   if((eval_d + state_d)*8.0 > 1.0e15)
   {
     dlg_set_error("%s: %.3g bytes of device memory", who, (eval_d + state_d)*8.0);
@@ -1258,7 +1411,7 @@ int batch_setup(const char* who, unsigned int B, unsigned int N, unsigned int M,
   const ProductsLayout PL = products_layout(F, B, N);
   const size_t eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : x_bytes + J_bytes;
   const size_t wts_bytes = align256(sizeof(double)*(size_t)B*NF);
-  const size_t state_bytes = 5*vec_bytes + G_bytes + sc_bytes + st_bytes + live_bytes + 256 + wts_bytes;
+  const size_t state_bytes = 5*vec_bytes + G_bytes + sc_bytes + st_bytes + live_bytes + 256 + wts_bytes + (size_t)nbounds*vec_bytes;
   if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes)) return -1;
 
   A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = NP;
@@ -1271,6 +1424,9 @@ int batch_setup(const char* who, unsigned int B, unsigned int N, unsigned int M,
   A.sc = (double*)q; q += sc_bytes; A.st = (int*)q; q += st_bytes; A.live = (unsigned char*)q; q += live_bytes;
   A.counter = (int*)q; q += 256;
   A.wts = loss ? (double*)q : nullptr; A.NF = (int)NF; A.robust = loss ? 1 : 0;
+  q += wts_bytes;
+  A.lo = nbounds > 0 ? (const double*)q : nullptr; A.hi = nbounds > 1 ? (const double*)(q + vec_bytes) : nullptr;
+  A.held = nullptr; A.bounded = 0;
   A.L.kind = loss ? loss->kind : DOGLEG_AMD_LOSS_TRIVIAL; A.L.fs = (int)fs;
   A.L.a = loss && loss->kind != DOGLEG_AMD_LOSS_TRIVIAL ? loss->scale : 1.0; A.L.c = A.L.a*A.L.a;
   A.max_iterations = prm->max_iterations; A.trustregion0 = prm->trustregion0;
@@ -1310,6 +1466,7 @@ int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* c
       F.fJ(A.p_trial, const_cast<double*>(A.x), const_cast<double*>(A.J), A.live, B, (void*)st, cookie);
     if(timing) BHIP(hipEventRecord(K.ev[1], st));
     if(F.products())   launch_round<FORM_PRODUCTS>(N, st, A);
+    else if(A.bounded) { if(A.robust) launch_round<FORM_J, true, true>(N, st, A); else launch_round<FORM_J, false, true>(N, st, A); }
     else if(A.robust)  launch_round<FORM_J, true>(N, st, A);
     else               launch_round<FORM_J>(N, st, A);
     BHIP(hipGetLastError());
@@ -1329,21 +1486,37 @@ int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* c
   return 0;
 }
 
-// loss, weights: the robust form (weights: [B][NF] or nullptr), or both nullptr
+// loss, weights: the robust form (weights: [B][NF] or nullptr), or both nullptr.  bounds: the bounded form (host pointers; the
+// bounds that are given are uploaded behind the state), or nullptr
 int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F, void* cookie,
                const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results,
-               const dogleg_amd_batch_loss_t* loss = nullptr, double* weights = nullptr)
+               const dogleg_amd_batch_loss_t* loss = nullptr, double* weights = nullptr,
+               const dogleg_amd_batch_bounds_t* bounds = nullptr)
 {
   const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch" :
+                    bounds ? "dogleg_amd_optimize_dense_batch_bounded" :
                     loss ? "dogleg_amd_optimize_dense_batch_robust" : "dogleg_amd_optimize_dense_batch";
   BatchDev A;
-  if(batch_setup(who, B, N, M, F, prm, loss, A)) return -1;
+  const int nbounds = bounds ? (bounds->lower ? 1 : 0) + (bounds->upper ? 1 : 0) : 0;
+  if(batch_setup(who, B, N, M, F, prm, loss, A, nbounds)) return -1;
   hipStream_t st = g_cache.stream;
   BHIP(hipMemcpyAsync(A.p_trial, p, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_batch_init, dim3((B + 255)/256), dim3(256), 0, st, A, (const unsigned char*)nullptr);
   BHIP(hipGetLastError());
+  if(bounds)
+  {
+    // batch_setup left the first array in A.lo and the second in A.hi
+    A.bounded = 1;
+    if(bounds->upper && !bounds->lower) { A.hi = A.lo; A.lo = nullptr; }
+    if(A.lo) BHIP(hipMemcpyAsync(const_cast<double*>(A.lo), bounds->lower, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
+    if(A.hi) BHIP(hipMemcpyAsync(const_cast<double*>(A.hi), bounds->upper, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_batch_clamp, dim3((B + 255)/256), dim3(256), 0, st, A);
+    BHIP(hipGetLastError());
+  }
   if(batch_rounds(who, F, A, cookie, st)) return -1;
   std::vector<double> sc((size_t)B*SC_COUNT), pb((size_t)B*N);
+  std::vector<double> gb(bounds && bounds->held ? (size_t)B*N : 0);
+  if(!gb.empty()) BHIP(hipMemcpyAsync(gb.data(), A.g, sizeof(double)*gb.size(), hipMemcpyDeviceToHost, st));
   std::vector<int> sti((size_t)B*ST_COUNT);
   BHIP(hipMemcpyAsync(sc.data(), A.sc, sizeof(double)*sc.size(), hipMemcpyDeviceToHost, st));
   BHIP(hipMemcpyAsync(sti.data(), A.st, sizeof(int)*sti.size(), hipMemcpyDeviceToHost, st));
@@ -1366,6 +1539,10 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
       if(failed) for(size_t f = 0; f < NF; f++) weights[b*NF + f] = std::nan("");
       else       memcpy(weights + b*NF, wt.data() + b*NF, sizeof(double)*NF);
     }
+    if(!gb.empty())
+      for(size_t i = b*N; i < (b + 1)*N; i++)
+        bounds->held[i] = failed ? 0 : held_code(pb[i], gb[i], bounds->lower ? bounds->lower[i] : -INFINITY,
+                                                 bounds->upper ? bounds->upper[i] : INFINITY);
   }
   return 0;
 }
@@ -1376,6 +1553,7 @@ int run_device_locked(const DlgBatchDeviceSolve& a)
 {
   const BatchForm F{a.fJ, a.fP, a.unpacked};
   const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch_device" :
+                    a.bounds ? "dogleg_amd_optimize_dense_batch_bounded_device" :
                     a.loss ? "dogleg_amd_optimize_dense_batch_robust_device" : "dogleg_amd_optimize_dense_batch_device";
   const unsigned int B = a.B, N = a.N;
   BatchDev A;
@@ -1384,6 +1562,13 @@ int run_device_locked(const DlgBatchDeviceSolve& a)
   BHIP(hipMemcpyAsync(A.p_trial, a.p, sizeof(double)*(size_t)B*N, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(k_batch_init, dim3((B + 255)/256), dim3(256), 0, st, A, a.active);
   BHIP(hipGetLastError());
+  if(a.bounds)
+  {
+    // the caller's arrays, where they lie
+    A.bounded = 1; A.lo = a.bounds->lower; A.hi = a.bounds->upper; A.held = a.bounds->held;
+    hipLaunchKernelGGL(k_batch_clamp, dim3((B + 255)/256), dim3(256), 0, st, A);
+    BHIP(hipGetLastError());
+  }
   if(batch_rounds(who, F, A, a.cookie, st)) return -1;
   const size_t nw = a.loss && a.weights ? (size_t)B*A.NF : 0, n = (size_t)B*N > nw ? (size_t)B*N : nw;
   hipLaunchKernelGGL(k_batch_finish, dim3((unsigned int)((n + 255)/256)), dim3(256), 0, st, A, a.p, a.results, a.lambda,
@@ -1744,6 +1929,15 @@ int dlg_dense_products_batch_uncertainty_run(const double* p, unsigned int B, un
   std::lock_guard<std::mutex> lk(g_mu);
   const int rc = unc_locked(p, B, N, 0, BatchForm{nullptr, f, unpacked}, cookie, lambda, covariance, variances, nullptr, nullptr, 1,
                             status);
+  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
+  return rc;
+}
+int dlg_dense_batch_bounded_run(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f,
+                                void* cookie, const dogleg_parameters2_t* prm, const dogleg_amd_batch_loss_t* loss,
+                                const dogleg_amd_batch_bounds_t* bounds, dogleg_amd_batch_result_t* results, double* weights)
+{
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int rc = run_locked(p, B, N, M, BatchForm{f, nullptr, false}, cookie, prm, results, loss, weights, bounds);
   if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
   return rc;
 }

@@ -135,6 +135,11 @@ class BatchLoss(C.Structure):
     _fields_ = [("kind", C.c_int), ("scale", C.c_double), ("featureSize", C.c_int)]
 
 
+class BatchBounds(C.Structure):
+    """dogleg_amd_batch_bounds_t (include/dogleg.h): three addresses, each 0 for NULL."""
+    _fields_ = [("lower", C.c_void_p), ("upper", C.c_void_p), ("held", C.c_void_p)]
+
+
 class JacobianReport(C.Structure):
     """dogleg_amd_jacobian_report_t (include/dogleg.h)."""
     _fields_ = [
