@@ -50,35 +50,37 @@ bool cov_ready(dogleg_operatingPoint_t* point, dogleg_solverContext_t* ctx, cons
   return dogleg_computeJtJfactorization(point, ctx);
 }
 
-// ---- a batch of small dense problems: the shape every batch entry point takes
-bool batch_shape_ok(const char* who, unsigned int B, unsigned int Nstate, unsigned int Nmeas, const char* larger)
+// ---- a batch of small dense problems: the shape every batch entry point takes.  prm: the products form, which has no Nmeas and
+// takes the layout of JtJ from the parameters (dogleg.c:597-601 refuses packed lower too); nullptr: the J form
+bool batch_shape_ok(const char* who, unsigned int B, unsigned int Nstate, unsigned int Nmeas, const char* larger,
+                    const dogleg_parameters2_t* prm = nullptr)
 {
-  if(B == 0 || Nstate == 0 || Nmeas == 0) { MSG("%s: B = %u, Nstate = %u, Nmeas = %u: none may be 0", who, B, Nstate, Nmeas); return false; }
+  if(B == 0 || Nstate == 0 || (!prm && Nmeas == 0))
+  {
+    if(prm) MSG("%s: B = %u, Nstate = %u: neither may be 0", who, B, Nstate);
+    else    MSG("%s: B = %u, Nstate = %u, Nmeas = %u: none may be 0", who, B, Nstate, Nmeas);
+    return false;
+  }
   if(Nstate > DOGLEG_AMD_BATCH_MAX_NSTATE)
   {
     MSG("%s: Nstate = %u, the batch kernels take at most %d variables (larger problems: %s)", who, Nstate,
         DOGLEG_AMD_BATCH_MAX_NSTATE, larger);
     return false;
   }
-  if(B > 0x7fffffffu/4 || Nmeas > 0x7fffffffu/(Nstate + 1))
-  { MSG("%s: B = %u problems of %u x %u: beyond the index range of the batch kernels", who, B, Nmeas, Nstate); return false; }
-  return true;
-}
-
-// the products form: no Nmeas, and the layout of JtJ from the parameters (dogleg.c:597-601 refuses packed lower too)
-bool products_batch_ok(const char* who, unsigned int B, unsigned int Nstate, const dogleg_parameters2_t* prm)
-{
-  if(B == 0 || Nstate == 0) { MSG("%s: B = %u, Nstate = %u: neither may be 0", who, B, Nstate); return false; }
-  if(Nstate > DOGLEG_AMD_BATCH_MAX_NSTATE)
+  if(B > 0x7fffffffu/4 || (!prm && Nmeas > 0x7fffffffu/(Nstate + 1)))
   {
-    MSG("%s: Nstate = %u, the batch kernels take at most %d variables (larger problems: a loop over dogleg_optimize_dense_products)",
-        who, Nstate, DOGLEG_AMD_BATCH_MAX_NSTATE);
+    if(prm) MSG("%s: B = %u problems: beyond the index range of the batch kernels", who, B);
+    else    MSG("%s: B = %u problems of %u x %u: beyond the index range of the batch kernels", who, B, Nmeas, Nstate);
     return false;
   }
-  if(B > 0x7fffffffu/4) { MSG("%s: B = %u problems: beyond the index range of the batch kernels", who, B); return false; }
-  if(prm->JtJ_packed && !prm->JtJ_upper)
+  if(prm && prm->JtJ_packed && !prm->JtJ_upper)
   { MSG("%s: JtJ_packed without JtJ_upper (a packed lower triangle) is not supported: use the packed upper or the unpacked layout", who); return false; }
   return true;
+}
+// the shape of a request record a of either form (fJ or fP given); prm: defaulted.  larger_J: the J form's hint
+template <class Req> bool request_shape_ok(const char* who, const Req& a, const dogleg_parameters2_t* prm, const char* larger_J)
+{
+  return batch_shape_ok(who, a.B, a.N, a.M, a.fP ? "a loop over dogleg_optimize_dense_products" : larger_J, a.fP ? prm : nullptr);
 }
 
 // the loss of the robust batch solve
@@ -98,6 +100,11 @@ bool batch_loss_ok(const char* who, const dogleg_amd_batch_loss_t* loss, unsigne
   if(Nmeas % fs) { MSG("%s: Nmeas = %u is not a multiple of loss->featureSize = %u", who, Nmeas, fs); return false; }
   return true;
 }
+// features per problem under a (checked) loss; 0 without one
+size_t loss_features(const dogleg_amd_batch_loss_t* loss, unsigned int Nmeas)
+{
+  return loss ? Nmeas/(loss->featureSize <= 1 ? 1u : (unsigned int)loss->featureSize) : 0;
+}
 
 // the bounds of the bounded batch solve: the struct must be given (its pointers may be NULL), weights belong to a loss
 bool batch_bounds_ok(const char* who, const dogleg_amd_batch_bounds_t* bounds, const dogleg_amd_batch_loss_t* loss,
@@ -116,56 +123,119 @@ bool device_span_ok(const char* who, const char* name, const void* ptr, size_t b
       "(device, managed or registered host memory; host arrays go to the entry point without _device)", who, name, ptr, bytes);
   return false;
 }
-
-// the arrays of a device-resident solve / uncertainty call of B problems (NF: features per problem; optional ones may be NULL)
-bool solve_spans_ok(const char* who, size_t B, size_t N, const double* p, const dogleg_amd_batch_result_t* results,
-                    const double* lambda, const unsigned char* active)
+// an optional one
+bool device_span_ok_or_null(const char* who, const char* name, const void* ptr, size_t bytes)
 {
-  return device_span_ok(who, "p_dev", p, sizeof(double)*B*N) &&
-         device_span_ok(who, "results_dev", results, sizeof(dogleg_amd_batch_result_t)*B) &&
-         (!lambda || device_span_ok(who, "lambda_dev", lambda, sizeof(double)*B)) &&
-         (!active || device_span_ok(who, "active_dev", active, B));
-}
-bool uncertainty_spans_ok(const char* who, size_t B, size_t N, size_t NF, const double* p, const int* status, const double* lambda,
-                          const double* covariance, const double* variances, const double* factors, const double* scale,
-                          const unsigned char* active)
-{
-  return device_span_ok(who, "p_dev", p, sizeof(double)*B*N) && device_span_ok(who, "status_dev", status, sizeof(int)*B) &&
-         (!lambda || device_span_ok(who, "lambda_dev", lambda, sizeof(double)*B)) &&
-         (!covariance || device_span_ok(who, "covariance_dev", covariance, sizeof(double)*B*N*N)) &&
-         (!variances || device_span_ok(who, "variances_dev", variances, sizeof(double)*B*N)) &&
-         (!factors || (device_span_ok(who, "factors_dev", factors, sizeof(double)*B*NF) &&
-                       device_span_ok(who, "scale_dev", scale, sizeof(double)*B))) &&
-         (!active || device_span_ok(who, "active_dev", active, B));
+  return !ptr || device_span_ok(who, name, ptr, bytes);
 }
 
-// the queries of the batch query calls: Nq queries of Qrows rows per problem
-bool query_shape_ok(const char* who, unsigned int B, unsigned int Nq, unsigned int Qrows)
+// ---- the three kinds of batch request (dense_batch.h), each behind one function that makes every check of its entry points in
+// one order: the required pointers, the shape, what the kind adds, one rank only; then, and only on the device route, the spans
+// of the caller's arrays.  Nothing before the spans looks at a pointer's target.  who: the entry point
+enum SolveKind { SOLVE_PLAIN, SOLVE_ROBUST, SOLVE_BOUNDED };
+int batch_solve_entry(const char* who, SolveKind kind, DlgBatchSolve a)
 {
-  if(Nq == 0 || Qrows == 0) { MSG("%s: Nq = %u, Qrows = %u: neither may be 0", who, Nq, Qrows); return false; }
-  if(Qrows > DOGLEG_AMD_BATCH_QUERY_MAX_ROWS)
+  const char* dev = a.device ? "_dev" : "";
+  if(!a.p || !(a.fJ || a.fP) || !a.results) { MSG("%s: p%s, the callback and results%s must be given", who, dev, dev); return -1; }
+  if(!a.prm) a.prm = &g_params;
+  a.unpacked = a.fP && !a.prm->JtJ_packed;
+  if(!request_shape_ok(who, a, a.prm, "a loop over dogleg_optimize_dense2")) return -1;
+  if((kind == SOLVE_ROBUST || a.loss) && !batch_loss_ok(who, a.loss, a.M)) return -1;
+  if(kind == SOLVE_BOUNDED && !batch_bounds_ok(who, a.bounds, a.loss, a.weights)) return -1;
+  if(!one_rank_only(who)) return -1;
+  const size_t B = a.B, BN = B*a.N;
+  const dogleg_amd_batch_bounds_t none = {nullptr, nullptr, nullptr}, &bounds = a.bounds ? *a.bounds : none;
+  if(a.device &&
+     !(device_span_ok(who, "p_dev", a.p, sizeof(double)*BN) &&
+       device_span_ok(who, "results_dev", a.results, sizeof(dogleg_amd_batch_result_t)*B) &&
+       device_span_ok_or_null(who, "lambda_dev", a.lambda, sizeof(double)*B) &&
+       device_span_ok_or_null(who, "active_dev", a.active, B) &&
+       device_span_ok_or_null(who, "weights_dev", a.weights, sizeof(double)*B*loss_features(a.loss, a.M)) &&
+       device_span_ok_or_null(who, "bounds->lower", bounds.lower, sizeof(double)*BN) &&
+       device_span_ok_or_null(who, "bounds->upper", bounds.upper, sizeof(double)*BN) &&
+       device_span_ok_or_null(who, "bounds->held", bounds.held, BN))) return -1;
+  return dlg_dense_batch_solve(a);
+}
+// featureSize: as the caller gave it; a.fs is set here
+int batch_unc_entry(const char* who, DlgBatchUnc a, const dogleg_parameters2_t* parameters, int featureSize)
+{
+  const char* dev = a.device ? "_dev" : "";
+  if(!a.p || !(a.fJ || a.fP) || !a.status) { MSG("%s: p%s, the callback and status%s must be given", who, dev, dev); return -1; }
+  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
+  a.unpacked = a.fP && !prm->JtJ_packed;
+  if(!request_shape_ok(who, a, prm, "a loop over dogleg_optimize_dense2")) return -1;
+  if(featureSize > 2) { MSG("%s: featureSize = %d: only 1 and 2 are supported", who, featureSize); return -1; }
+  a.fs = featureSize <= 1 ? 1 : 2;
+  const unsigned int NF = a.M/(unsigned int)a.fs;
+  if(!a.covariance && !a.variances && !a.factors)
   {
-    MSG("%s: Qrows = %u, a query has at most %d rows (wider queries: dogleg_amd_dense_batch_uncertainty's covariance)", who, Qrows,
-        DOGLEG_AMD_BATCH_QUERY_MAX_ROWS);
-    return false;
+    if(a.fP) MSG("%s: neither covariance%s nor variances%s is asked for", who, dev, dev);
+    else     MSG("%s: none of covariance%s, variances%s, factors%s is asked for", who, dev, dev, dev);
+    return -1;
   }
-  if((double)B*(double)Nq*(double)Qrows > (double)(0x7fffffffu/DOGLEG_AMD_BATCH_MAX_NSTATE))
-  { MSG("%s: B = %u problems of %u queries of %u rows: beyond the index range of the batch kernels", who, B, Nq, Qrows); return false; }
-  return true;
+  if(a.factors && !a.scale)
+  {
+    if(a.device) MSG("%s: factors_dev needs scale_dev", who);
+    else         MSG("%s: factors need scale", who);
+    return -1;
+  }
+  if(a.factors && NF == 0) { MSG("%s: Nmeas = %u holds no feature of size %d", who, a.M, a.fs); return -1; }
+  // a scale[b] <= 0 is to be computed, which needs Nmeas > Nstate + 1: the host route looks for one, the device route cannot
+  if(a.factors && a.M <= a.N + 1)
+  {
+    if(a.device)
+    {
+      MSG("%s: factors_dev with Nmeas <= Nstate + 1 (%u, %u): a scale_dev[b] <= 0 could not be computed, and whether there is one "
+          "cannot be seen without a copy", who, a.M, a.N);
+      return -1;
+    }
+    for(unsigned int b = 0; b < a.B; b++)
+      if(!(a.scale[b] > 0.0))
+      {
+        MSG("%s: scale[%u] <= 0 is to be computed, which needs Nmeas > Nstate + 1 (%u, %u)", who, b, a.M, a.N);
+        return -1;
+      }
+  }
+  if(!one_rank_only(who)) return -1;
+  const size_t B = a.B, BN = B*a.N;
+  if(a.device &&
+     !(device_span_ok(who, "p_dev", a.p, sizeof(double)*BN) && device_span_ok(who, "status_dev", a.status, sizeof(int)*B) &&
+       device_span_ok_or_null(who, "lambda_dev", a.lambda, sizeof(double)*B) &&
+       device_span_ok_or_null(who, "covariance_dev", a.covariance, sizeof(double)*BN*a.N) &&
+       device_span_ok_or_null(who, "variances_dev", a.variances, sizeof(double)*BN) &&
+       (!a.factors || (device_span_ok(who, "factors_dev", a.factors, sizeof(double)*B*NF) &&
+                       device_span_ok(who, "scale_dev", a.scale, sizeof(double)*B))) &&
+       device_span_ok_or_null(who, "active_dev", a.active, B))) return -1;
+  return dlg_dense_batch_uncertainty(a);
 }
-bool observations_ok(const char* who, int Nobservations, unsigned int Nmeas)
+// Nq queries of Qrows rows per problem, Nobservations of the J form's Nmeas
+int batch_query_entry(const char* who, DlgBatchQuery a, const dogleg_parameters2_t* parameters)
 {
-  if(Nobservations < 0 || (unsigned int)Nobservations <= Nmeas) return true;
-  MSG("%s: Nobservations = %d exceeds Nmeas = %u (< 0 selects the plain form)", who, Nobservations, Nmeas);
-  return false;
-}
-bool query_spans_ok(const char* who, size_t B, size_t N, size_t Nq, size_t Q, const double* p, const int* status,
-                    const double* lambda, const double* Jq, const double* out, const unsigned char* active)
-{
-  return device_span_ok(who, "p_dev", p, sizeof(double)*B*N) && device_span_ok(who, "status_dev", status, sizeof(int)*B) &&
-         (!lambda || device_span_ok(who, "lambda_dev", lambda, sizeof(double)*B)) &&
-         device_span_ok(who, "Jq_dev", Jq, sizeof(double)*B*Nq*Q*N) && device_span_ok(who, "out_dev", out, sizeof(double)*B*Nq*Q*Q) &&
-         (!active || device_span_ok(who, "active_dev", active, B));
+  const char* dev = a.device ? "_dev" : "";
+  if(!a.p || !(a.fJ || a.fP) || !a.Jq || !a.out || !a.status)
+  { MSG("%s: p%s, the callback, Jq%s, out%s and status%s must be given", who, dev, dev, dev, dev); return -1; }
+  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
+  a.unpacked = a.fP && !prm->JtJ_packed;
+  if(!request_shape_ok(who, a, prm, "a loop over dogleg_optimize_dense2 and dogleg_amd_query_covariance")) return -1;
+  if(a.Nq == 0 || a.Qrows == 0) { MSG("%s: Nq = %u, Qrows = %u: neither may be 0", who, a.Nq, a.Qrows); return -1; }
+  if(a.Qrows > DOGLEG_AMD_BATCH_QUERY_MAX_ROWS)
+  {
+    MSG("%s: Qrows = %u, a query has at most %d rows (wider queries: dogleg_amd_dense_batch_uncertainty's covariance)", who, a.Qrows,
+        DOGLEG_AMD_BATCH_QUERY_MAX_ROWS);
+    return -1;
+  }
+  if((double)a.B*(double)a.Nq*(double)a.Qrows > (double)(0x7fffffffu/DOGLEG_AMD_BATCH_MAX_NSTATE))
+  { MSG("%s: B = %u problems of %u queries of %u rows: beyond the index range of the batch kernels", who, a.B, a.Nq, a.Qrows); return -1; }
+  if(a.Nobservations >= 0 && (unsigned int)a.Nobservations > a.M)
+  { MSG("%s: Nobservations = %d exceeds Nmeas = %u (< 0 selects the plain form)", who, a.Nobservations, a.M); return -1; }
+  if(!one_rank_only(who)) return -1;
+  const size_t B = a.B, rows = B*a.Nq*a.Qrows;
+  if(a.device &&
+     !(device_span_ok(who, "p_dev", a.p, sizeof(double)*B*a.N) && device_span_ok(who, "status_dev", a.status, sizeof(int)*B) &&
+       device_span_ok_or_null(who, "lambda_dev", a.lambda, sizeof(double)*B) &&
+       device_span_ok(who, "Jq_dev", a.Jq, sizeof(double)*rows*a.N) && device_span_ok(who, "out_dev", a.out, sizeof(double)*rows*a.Qrows) &&
+       device_span_ok_or_null(who, "active_dev", a.active, B))) return -1;
+  return dlg_dense_batch_query(a);
 }
 
 // ---- the Jacobian of a device callback against central differences
@@ -340,15 +410,14 @@ int dogleg_amd_query_covariance(double* out, int nq, const int* qrow, const int*
                            [&]{ return dlg_query_covariance(d->be, slot_of(d, point), nq, qrow, rowptr, var, val, Nobservations, out); }) ? 0 : -1;
 }
 
-// ---- extension (not in the reference): a batch of small dense problems, the dog-leg loop on the device (dense_batch.hip)
+// ---- extension (not in the reference): batches of small dense problems, the dog-leg loop on the device (dense_batch.hip).  Every
+// entry point fills the request record of its kind (dense_batch.h: p, B, N, M, fJ, fP, cookie, unpacked, then the kind's own
+// fields, active, stream, device) and hands it to the kind's checks above
 int dogleg_amd_optimize_dense_batch(double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
                                     dogleg_callback_device_batch_t* f, void* cookie,
                                     const dogleg_parameters2_t* parameters, dogleg_amd_batch_result_t* results)
 {
-  const char* who = "dogleg_amd_optimize_dense_batch";
-  if(!p || !f || !results) { MSG("%s: p, the callback and results must be given", who); return -1; }
-  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || !one_rank_only(who)) return -1;
-  return dlg_dense_batch_run(p, B, Nstate, Nmeas, f, cookie, parameters ? parameters : &g_params, results);
+  return batch_solve_entry(__func__, SOLVE_PLAIN, DlgBatchSolve{p, B, Nstate, Nmeas, f, nullptr, cookie, false, parameters, results});
 }
 int dogleg_amd_batch_last_stats(double* out, int n) { return out ? dlg_dense_batch_last_stats(out, n) : 0; }
 int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
@@ -356,23 +425,8 @@ int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned
                                        double* lambda, double* covariance, double* variances, double* factors,
                                        double* scale, int featureSize, int* status)
 {
-  const char* who = "dogleg_amd_dense_batch_uncertainty";
-  if(!p || !f || !status) { MSG("%s: p, the callback and status must be given", who); return -1; }
-  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2")) return -1;
-  if(featureSize > 2) { MSG("%s: featureSize = %d: only 1 and 2 are supported", who, featureSize); return -1; }
-  const int fs = featureSize <= 1 ? 1 : 2;
-  if(!covariance && !variances && !factors) { MSG("%s: none of covariance, variances, factors is asked for", who); return -1; }
-  if(factors && !scale) { MSG("%s: factors need scale", who); return -1; }
-  if(factors && Nmeas/(unsigned int)fs == 0) { MSG("%s: Nmeas = %u holds no feature of size %d", who, Nmeas, fs); return -1; }
-  if(factors && Nmeas <= Nstate + 1)
-    for(unsigned int b = 0; b < B; b++)
-      if(!(scale[b] > 0.0))
-      {
-        MSG("%s: scale[%u] <= 0 is to be computed, which needs Nmeas > Nstate + 1 (%u, %u)", who, b, Nmeas, Nstate);
-        return -1;
-      }
-  if(!one_rank_only(who)) return -1;
-  return dlg_dense_batch_uncertainty_run(p, B, Nstate, Nmeas, f, cookie, lambda, covariance, variances, factors, scale, fs, status);
+  return batch_unc_entry(__func__, DlgBatchUnc{p, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda, covariance, variances,
+                                               factors, scale, 0, status}, nullptr, featureSize);
 }
 int dogleg_amd_batch_uncertainty_last_stats(double* out, int n) { return out ? dlg_dense_batch_uncertainty_last_stats(out, n) : 0; }
 
@@ -381,52 +435,36 @@ int dogleg_amd_optimize_dense_products_batch(double* p, unsigned int B, unsigned
                                              dogleg_callback_device_batch_products_t* f, void* cookie,
                                              const dogleg_parameters2_t* parameters, dogleg_amd_batch_result_t* results)
 {
-  const char* who = "dogleg_amd_optimize_dense_products_batch";
-  if(!p || !f || !results) { MSG("%s: p, the callback and results must be given", who); return -1; }
-  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
-  if(!products_batch_ok(who, B, Nstate, prm) || !one_rank_only(who)) return -1;
-  return dlg_dense_products_batch_run(p, B, Nstate, f, cookie, prm, results);
+  return batch_solve_entry(__func__, SOLVE_PLAIN, DlgBatchSolve{p, B, Nstate, 0, nullptr, f, cookie, false, parameters, results});
 }
 int dogleg_amd_dense_products_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate,
                                                 dogleg_callback_device_batch_products_t* f, void* cookie,
                                                 const dogleg_parameters2_t* parameters,
                                                 double* lambda, double* covariance, double* variances, int* status)
 {
-  const char* who = "dogleg_amd_dense_products_batch_uncertainty";
-  if(!p || !f || !status) { MSG("%s: p, the callback and status must be given", who); return -1; }
-  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
-  if(!products_batch_ok(who, B, Nstate, prm)) return -1;
-  if(!covariance && !variances) { MSG("%s: neither covariance nor variances is asked for", who); return -1; }
-  if(!one_rank_only(who)) return -1;
-  return dlg_dense_products_batch_uncertainty_run(p, B, Nstate, f, cookie, !prm->JtJ_packed, lambda, covariance, variances, status);
+  return batch_unc_entry(__func__, DlgBatchUnc{p, B, Nstate, 0, nullptr, f, cookie, false, lambda, covariance, variances, nullptr,
+                                               nullptr, 0, status}, parameters, 1);
 }
 
-// ---- the device-resident twins of the four: the same checks, then the pointers, then dense_batch.hip
+// ---- the device-resident twins of the four
 int dogleg_amd_optimize_dense_batch_device(double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
                                            dogleg_callback_device_batch_t* f, void* cookie,
                                            const dogleg_parameters2_t* parameters,
                                            dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
                                            const unsigned char* active_dev, void* hip_stream)
 {
-  const char* who = "dogleg_amd_optimize_dense_batch_device";
-  if(!p_dev || !f || !results_dev) { MSG("%s: p_dev, the callback and results_dev must be given", who); return -1; }
-  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || !one_rank_only(who)) return -1;
-  if(!solve_spans_ok(who, B, Nstate, p_dev, results_dev, lambda_dev, active_dev)) return -1;
-  return dlg_dense_batch_device_run(DlgBatchDeviceSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false,
-                                                        parameters ? parameters : &g_params, results_dev, lambda_dev, active_dev,
-                                                        hip_stream});
+  return batch_solve_entry(__func__, SOLVE_PLAIN, DlgBatchSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, parameters,
+                                                                results_dev, lambda_dev, active_dev, hip_stream, nullptr, nullptr,
+                                                                nullptr, true});
 }
-// ---- the robust form of the solve and its device twin: the plain checks, then the loss, then (the twin) the pointers
+// ---- the robust form of the solve and its device twin
 int dogleg_amd_optimize_dense_batch_robust(double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
                                            dogleg_callback_device_batch_t* f, void* cookie,
                                            const dogleg_parameters2_t* parameters, const dogleg_amd_batch_loss_t* loss,
                                            dogleg_amd_batch_result_t* results, double* weights)
 {
-  const char* who = "dogleg_amd_optimize_dense_batch_robust";
-  if(!p || !f || !results) { MSG("%s: p, the callback and results must be given", who); return -1; }
-  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || !batch_loss_ok(who, loss, Nmeas) ||
-     !one_rank_only(who)) return -1;
-  return dlg_dense_batch_robust_run(p, B, Nstate, Nmeas, f, cookie, parameters ? parameters : &g_params, loss, results, weights);
+  return batch_solve_entry(__func__, SOLVE_ROBUST, DlgBatchSolve{p, B, Nstate, Nmeas, f, nullptr, cookie, false, parameters, results,
+                                                                 nullptr, nullptr, nullptr, loss, weights});
 }
 int dogleg_amd_optimize_dense_batch_robust_device(double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
                                                   dogleg_callback_device_batch_t* f, void* cookie,
@@ -434,30 +472,19 @@ int dogleg_amd_optimize_dense_batch_robust_device(double* p_dev, unsigned int B,
                                                   dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
                                                   double* weights_dev, const unsigned char* active_dev, void* hip_stream)
 {
-  const char* who = "dogleg_amd_optimize_dense_batch_robust_device";
-  if(!p_dev || !f || !results_dev) { MSG("%s: p_dev, the callback and results_dev must be given", who); return -1; }
-  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || !batch_loss_ok(who, loss, Nmeas) ||
-     !one_rank_only(who)) return -1;
-  const size_t NF = Nmeas/(loss->featureSize <= 1 ? 1u : (unsigned int)loss->featureSize);
-  if(!solve_spans_ok(who, B, Nstate, p_dev, results_dev, lambda_dev, active_dev) ||
-     (weights_dev && !device_span_ok(who, "weights_dev", weights_dev, sizeof(double)*B*NF))) return -1;
-  return dlg_dense_batch_device_run(DlgBatchDeviceSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false,
-                                                        parameters ? parameters : &g_params, results_dev, lambda_dev, active_dev,
-                                                        hip_stream, loss, weights_dev});
+  return batch_solve_entry(__func__, SOLVE_ROBUST, DlgBatchSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, parameters,
+                                                                 results_dev, lambda_dev, active_dev, hip_stream, loss, weights_dev,
+                                                                 nullptr, true});
 }
-// ---- the bounded form and its device twin: the plain checks, the loss where one is given, the bounds, then (the twin) the pointers
+// ---- the bounded form and its device twin (loss may be NULL)
 int dogleg_amd_optimize_dense_batch_bounded(double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
                                             dogleg_callback_device_batch_t* f, void* cookie,
                                             const dogleg_parameters2_t* parameters, const dogleg_amd_batch_loss_t* loss,
                                             const dogleg_amd_batch_bounds_t* bounds, dogleg_amd_batch_result_t* results,
                                             double* weights)
 {
-  const char* who = "dogleg_amd_optimize_dense_batch_bounded";
-  if(!p || !f || !results) { MSG("%s: p, the callback and results must be given", who); return -1; }
-  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || (loss && !batch_loss_ok(who, loss, Nmeas)) ||
-     !batch_bounds_ok(who, bounds, loss, weights) || !one_rank_only(who)) return -1;
-  return dlg_dense_batch_bounded_run(p, B, Nstate, Nmeas, f, cookie, parameters ? parameters : &g_params, loss, bounds, results,
-                                     weights);
+  return batch_solve_entry(__func__, SOLVE_BOUNDED, DlgBatchSolve{p, B, Nstate, Nmeas, f, nullptr, cookie, false, parameters, results,
+                                                                  nullptr, nullptr, nullptr, loss, weights, bounds});
 }
 int dogleg_amd_optimize_dense_batch_bounded_device(double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
                                                    dogleg_callback_device_batch_t* f, void* cookie,
@@ -466,20 +493,9 @@ int dogleg_amd_optimize_dense_batch_bounded_device(double* p_dev, unsigned int B
                                                    dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
                                                    double* weights_dev, const unsigned char* active_dev, void* hip_stream)
 {
-  const char* who = "dogleg_amd_optimize_dense_batch_bounded_device";
-  if(!p_dev || !f || !results_dev) { MSG("%s: p_dev, the callback and results_dev must be given", who); return -1; }
-  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2") || (loss && !batch_loss_ok(who, loss, Nmeas)) ||
-     !batch_bounds_ok(who, bounds, loss, weights_dev) || !one_rank_only(who)) return -1;
-  const size_t NF = loss ? Nmeas/(loss->featureSize <= 1 ? 1u : (unsigned int)loss->featureSize) : 0;
-  const size_t BN = (size_t)B*Nstate;
-  if(!solve_spans_ok(who, B, Nstate, p_dev, results_dev, lambda_dev, active_dev) ||
-     (weights_dev && !device_span_ok(who, "weights_dev", weights_dev, sizeof(double)*B*NF)) ||
-     (bounds->lower && !device_span_ok(who, "bounds->lower", bounds->lower, sizeof(double)*BN)) ||
-     (bounds->upper && !device_span_ok(who, "bounds->upper", bounds->upper, sizeof(double)*BN)) ||
-     (bounds->held && !device_span_ok(who, "bounds->held", bounds->held, BN))) return -1;
-  return dlg_dense_batch_device_run(DlgBatchDeviceSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false,
-                                                        parameters ? parameters : &g_params, results_dev, lambda_dev, active_dev,
-                                                        hip_stream, loss, weights_dev, bounds});
+  return batch_solve_entry(__func__, SOLVE_BOUNDED, DlgBatchSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, parameters,
+                                                                  results_dev, lambda_dev, active_dev, hip_stream, loss, weights_dev,
+                                                                  bounds, true});
 }
 int dogleg_amd_optimize_dense_products_batch_device(double* p_dev, unsigned int B, unsigned int Nstate,
                                                     dogleg_callback_device_batch_products_t* f, void* cookie,
@@ -487,13 +503,9 @@ int dogleg_amd_optimize_dense_products_batch_device(double* p_dev, unsigned int 
                                                     dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
                                                     const unsigned char* active_dev, void* hip_stream)
 {
-  const char* who = "dogleg_amd_optimize_dense_products_batch_device";
-  if(!p_dev || !f || !results_dev) { MSG("%s: p_dev, the callback and results_dev must be given", who); return -1; }
-  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
-  if(!products_batch_ok(who, B, Nstate, prm) || !one_rank_only(who)) return -1;
-  if(!solve_spans_ok(who, B, Nstate, p_dev, results_dev, lambda_dev, active_dev)) return -1;
-  return dlg_dense_batch_device_run(DlgBatchDeviceSolve{p_dev, B, Nstate, 0, nullptr, f, cookie, !prm->JtJ_packed, prm,
-                                                        results_dev, lambda_dev, active_dev, hip_stream});
+  return batch_solve_entry(__func__, SOLVE_PLAIN, DlgBatchSolve{p_dev, B, Nstate, 0, nullptr, f, cookie, false, parameters,
+                                                                results_dev, lambda_dev, active_dev, hip_stream, nullptr, nullptr,
+                                                                nullptr, true});
 }
 int dogleg_amd_dense_batch_uncertainty_device(const double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
                                               dogleg_callback_device_batch_t* f, void* cookie,
@@ -501,27 +513,9 @@ int dogleg_amd_dense_batch_uncertainty_device(const double* p_dev, unsigned int 
                                               double* factors_dev, double* scale_dev, int featureSize, int* status_dev,
                                               const unsigned char* active_dev, void* hip_stream)
 {
-  const char* who = "dogleg_amd_dense_batch_uncertainty_device";
-  if(!p_dev || !f || !status_dev) { MSG("%s: p_dev, the callback and status_dev must be given", who); return -1; }
-  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2")) return -1;
-  if(featureSize > 2) { MSG("%s: featureSize = %d: only 1 and 2 are supported", who, featureSize); return -1; }
-  const int fs = featureSize <= 1 ? 1 : 2;
-  if(!covariance_dev && !variances_dev && !factors_dev)
-  { MSG("%s: none of covariance_dev, variances_dev, factors_dev is asked for", who); return -1; }
-  if(factors_dev && !scale_dev) { MSG("%s: factors_dev needs scale_dev", who); return -1; }
-  if(factors_dev && Nmeas/(unsigned int)fs == 0) { MSG("%s: Nmeas = %u holds no feature of size %d", who, Nmeas, fs); return -1; }
-  if(factors_dev && Nmeas <= Nstate + 1)
-  {
-    MSG("%s: factors_dev with Nmeas <= Nstate + 1 (%u, %u): a scale_dev[b] <= 0 could not be computed, and whether there is one "
-        "cannot be seen without a copy", who, Nmeas, Nstate);
-    return -1;
-  }
-  if(!one_rank_only(who)) return -1;
-  if(!uncertainty_spans_ok(who, B, Nstate, Nmeas/(unsigned int)fs, p_dev, status_dev, lambda_dev, covariance_dev, variances_dev,
-                           factors_dev, scale_dev, active_dev)) return -1;
-  return dlg_dense_batch_uncertainty_device_run(DlgBatchDeviceUnc{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda_dev,
-                                                                  covariance_dev, variances_dev, factors_dev, scale_dev, fs,
-                                                                  status_dev, active_dev, hip_stream});
+  return batch_unc_entry(__func__, DlgBatchUnc{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda_dev, covariance_dev,
+                                               variances_dev, factors_dev, scale_dev, 0, status_dev, active_dev, hip_stream, true},
+                         nullptr, featureSize);
 }
 int dogleg_amd_dense_products_batch_uncertainty_device(const double* p_dev, unsigned int B, unsigned int Nstate,
                                                        dogleg_callback_device_batch_products_t* f, void* cookie,
@@ -529,17 +523,9 @@ int dogleg_amd_dense_products_batch_uncertainty_device(const double* p_dev, unsi
                                                        double* lambda_dev, double* covariance_dev, double* variances_dev,
                                                        int* status_dev, const unsigned char* active_dev, void* hip_stream)
 {
-  const char* who = "dogleg_amd_dense_products_batch_uncertainty_device";
-  if(!p_dev || !f || !status_dev) { MSG("%s: p_dev, the callback and status_dev must be given", who); return -1; }
-  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
-  if(!products_batch_ok(who, B, Nstate, prm)) return -1;
-  if(!covariance_dev && !variances_dev) { MSG("%s: neither covariance_dev nor variances_dev is asked for", who); return -1; }
-  if(!one_rank_only(who)) return -1;
-  if(!uncertainty_spans_ok(who, B, Nstate, 0, p_dev, status_dev, lambda_dev, covariance_dev, variances_dev, nullptr, nullptr,
-                           active_dev)) return -1;
-  return dlg_dense_batch_uncertainty_device_run(DlgBatchDeviceUnc{p_dev, B, Nstate, 0, nullptr, f, cookie, !prm->JtJ_packed,
-                                                                  lambda_dev, covariance_dev, variances_dev, nullptr, nullptr, 1,
-                                                                  status_dev, active_dev, hip_stream});
+  return batch_unc_entry(__func__, DlgBatchUnc{p_dev, B, Nstate, 0, nullptr, f, cookie, false, lambda_dev, covariance_dev,
+                                               variances_dev, nullptr, nullptr, 0, status_dev, active_dev, hip_stream, true},
+                         parameters, 1);
 }
 
 // ---- Jq Sigma_b Jq' of per-problem query Jacobians: the four entry points beside the four uncertainty calls
@@ -548,12 +534,8 @@ int dogleg_amd_dense_batch_query_covariance(const double* p, unsigned int B, uns
                                             const double* Jq, unsigned int Nq, unsigned int Qrows, int Nobservations,
                                             double* out, int* status)
 {
-  const char* who = "dogleg_amd_dense_batch_query_covariance";
-  if(!p || !f || !Jq || !out || !status) { MSG("%s: p, the callback, Jq, out and status must be given", who); return -1; }
-  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2 and dogleg_amd_query_covariance")) return -1;
-  if(!query_shape_ok(who, B, Nq, Qrows) || !observations_ok(who, Nobservations, Nmeas) || !one_rank_only(who)) return -1;
-  return dlg_dense_batch_query_run(DlgBatchQuery{p, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda, Jq, Nq, Qrows,
-                                                 Nobservations, out, status, nullptr, nullptr});
+  return batch_query_entry(__func__, DlgBatchQuery{p, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda, Jq, Nq, Qrows,
+                                                   Nobservations, out, status}, nullptr);
 }
 int dogleg_amd_dense_products_batch_query_covariance(const double* p, unsigned int B, unsigned int Nstate,
                                                      dogleg_callback_device_batch_products_t* f, void* cookie,
@@ -561,12 +543,8 @@ int dogleg_amd_dense_products_batch_query_covariance(const double* p, unsigned i
                                                      const double* Jq, unsigned int Nq, unsigned int Qrows,
                                                      double* out, int* status)
 {
-  const char* who = "dogleg_amd_dense_products_batch_query_covariance";
-  if(!p || !f || !Jq || !out || !status) { MSG("%s: p, the callback, Jq, out and status must be given", who); return -1; }
-  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
-  if(!products_batch_ok(who, B, Nstate, prm) || !query_shape_ok(who, B, Nq, Qrows) || !one_rank_only(who)) return -1;
-  return dlg_dense_batch_query_run(DlgBatchQuery{p, B, Nstate, 0, nullptr, f, cookie, !prm->JtJ_packed, lambda, Jq, Nq, Qrows, -1,
-                                                 out, status, nullptr, nullptr});
+  return batch_query_entry(__func__, DlgBatchQuery{p, B, Nstate, 0, nullptr, f, cookie, false, lambda, Jq, Nq, Qrows, -1, out, status},
+                           parameters);
 }
 int dogleg_amd_dense_batch_query_covariance_device(const double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
                                                    dogleg_callback_device_batch_t* f, void* cookie, double* lambda_dev,
@@ -574,14 +552,8 @@ int dogleg_amd_dense_batch_query_covariance_device(const double* p_dev, unsigned
                                                    double* out_dev, int* status_dev,
                                                    const unsigned char* active_dev, void* hip_stream)
 {
-  const char* who = "dogleg_amd_dense_batch_query_covariance_device";
-  if(!p_dev || !f || !Jq_dev || !out_dev || !status_dev)
-  { MSG("%s: p_dev, the callback, Jq_dev, out_dev and status_dev must be given", who); return -1; }
-  if(!batch_shape_ok(who, B, Nstate, Nmeas, "a loop over dogleg_optimize_dense2 and dogleg_amd_query_covariance")) return -1;
-  if(!query_shape_ok(who, B, Nq, Qrows) || !observations_ok(who, Nobservations, Nmeas) || !one_rank_only(who)) return -1;
-  if(!query_spans_ok(who, B, Nstate, Nq, Qrows, p_dev, status_dev, lambda_dev, Jq_dev, out_dev, active_dev)) return -1;
-  return dlg_dense_batch_query_device_run(DlgBatchQuery{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda_dev, Jq_dev, Nq,
-                                                        Qrows, Nobservations, out_dev, status_dev, active_dev, hip_stream});
+  return batch_query_entry(__func__, DlgBatchQuery{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda_dev, Jq_dev, Nq, Qrows,
+                                                   Nobservations, out_dev, status_dev, active_dev, hip_stream, true}, nullptr);
 }
 int dogleg_amd_dense_products_batch_query_covariance_device(const double* p_dev, unsigned int B, unsigned int Nstate,
                                                             dogleg_callback_device_batch_products_t* f, void* cookie,
@@ -590,14 +562,8 @@ int dogleg_amd_dense_products_batch_query_covariance_device(const double* p_dev,
                                                             double* out_dev, int* status_dev,
                                                             const unsigned char* active_dev, void* hip_stream)
 {
-  const char* who = "dogleg_amd_dense_products_batch_query_covariance_device";
-  if(!p_dev || !f || !Jq_dev || !out_dev || !status_dev)
-  { MSG("%s: p_dev, the callback, Jq_dev, out_dev and status_dev must be given", who); return -1; }
-  const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
-  if(!products_batch_ok(who, B, Nstate, prm) || !query_shape_ok(who, B, Nq, Qrows) || !one_rank_only(who)) return -1;
-  if(!query_spans_ok(who, B, Nstate, Nq, Qrows, p_dev, status_dev, lambda_dev, Jq_dev, out_dev, active_dev)) return -1;
-  return dlg_dense_batch_query_device_run(DlgBatchQuery{p_dev, B, Nstate, 0, nullptr, f, cookie, !prm->JtJ_packed, lambda_dev,
-                                                        Jq_dev, Nq, Qrows, -1, out_dev, status_dev, active_dev, hip_stream});
+  return batch_query_entry(__func__, DlgBatchQuery{p_dev, B, Nstate, 0, nullptr, f, cookie, false, lambda_dev, Jq_dev, Nq, Qrows, -1,
+                                                   out_dev, status_dev, active_dev, hip_stream, true}, parameters);
 }
 
 // ---- extension (not in the reference): the Jacobian of a device callback against central differences (gradcheck.hip)

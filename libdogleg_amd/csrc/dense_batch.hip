@@ -1,1215 +1,22 @@
-// dense_batch.hip -- dogleg_amd_optimize_dense_batch: B small dense problems of one shape, the whole dog-leg loop
-// (dogleg.c:1016-1022, 529-998, 1172-1476) per problem on the device.
-//
-// A round: the caller's batch callback evaluates x, J at the live problems' trial points (its kernels, on our stream),
-// then ONE launch of k_batch_round does for every live problem what eval_point + evaluate_step + take_step do, then
-// the host reads one counter of live problems (a 4-byte copy into page-locked memory).  Launches and synchronisations
-// per round: constant, whatever B is.
-//
-// One wavefront per problem, BatchCfg<NMAX>::WPB problems per workgroup (4 up to 32 variables, 2 in the class of 48,
-// 1 in the class of 64: the LDS a wavefront needs grows with the packed triangle).  The wave sweeps the problem's J ONCE (coalesced loads
-// of row tiles into LDS, the next tile's loads in flight while the current one is used): norm2(x), Jt x and the packed
-// lower triangle of JtJ come out of that sweep, JtJ in registers (lane l holds entries l, l + 64, ...), then in LDS.
-// Everything after it -- |J g|^2 = g' JtJ g, the packed Cholesky with the lambda loop, the two triangular solves, the
-// choice of step, |J s|^2 = s' JtJ s -- is wave-level code on that on-chip copy.  What a rejected trial needs again of
-// the point it started from (p, Jt x, the Cauchy and Gauss-Newton steps, JtJ: N (N + 11) / 2 doubles) lies in device
-// memory per problem; the J of a point is never read a second time and only one x / J buffer per problem exists.
-// Plain FMAs, no MFMA: DESIGN.md section 3, "Batches of small dense problems".
-//
-// dogleg_amd_dense_batch_uncertainty (k_batch_uncertainty, below the round kernel): covariance, variances and outlierness
-// factors of every problem at given points, one callback and one launch, on the same sweep, Cholesky and cache.
-//
-// dogleg_amd_dense_batch_query_covariance (k_batch_query, below the uncertainty kernel): Jq Sigma_b Jq' of caller-supplied
-// query Jacobians per problem, and the observations-only form, behind the same front half (factor_and_invert) in one launch;
-// Sigma itself is neither formed nor written.
-//
-// The products form (dogleg_amd_optimize_dense_products_batch, dogleg_amd_dense_products_batch_uncertainty): the callback
-// hands back norm2(x), Jt x and JtJ of every live problem, so there is no sweep.  A second front end (load_products) puts
-// the same three things where sweep_point leaves them; from evaluate_step on both forms run the same functions.  The
-// kernels are templates over the form: the J-form instantiations keep their arithmetic and their order of operations.
-//
-// The device-resident twins (dogleg_amd_*_batch_device): the same rounds and the same launch of k_batch_uncertainty with every
-// array of the caller in device memory.  The solve takes its initial p by a copy within the device and ends in k_batch_finish,
-// which writes p, the result structs and lambda where the caller has them; the uncertainty kernel's per-output pointers point
-// at the caller's arrays.  An active mask is the initial value of the solve's live bytes and a wave-uniform return at the head
-// of k_batch_uncertainty.  k_batch_round is the same for both routes.
-//
-// The bounded form (dogleg_amd_optimize_dense_batch_bounded and its _device twin): box bounds per problem by an active-set loop,
-// the eight steps above the prototype in dogleg.h.  BOUNDED is a template flag of batch_problem and k_batch_round beside ROBUST
-// (J form only); everything it adds lies behind the sweep, on the on-chip JtJ, g and the two cached steps, and needs no LDS of
-// its own.  k_batch_clamp (behind k_batch_init) clamps the start points; k_batch_finish, or run_locked on the host, forms held.
+// dense_batch.hip -- the host side of the batch solver: what is kept between calls (the cache), and one call path per kind of
+// request of dense_batch.h -- the solve (solve_locked: the rounds), and the uncertainty and query calls (evaluate_at: one
+// callback and ONE launch).  Each path serves the J and the products form, host arrays and the caller's device arrays.  The
+// kernels and what they compute: dense_batch_kernels.hip; their arguments and launchers: dense_batch_dev.h.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
-#include <cfloat>
 #include <mutex>
 #include <vector>
 #include "dense_batch.h"
+#include "dense_batch_dev.h"
 
 void dlg_set_error(const char* fmt, ...);
 
 #define BMSG(...) do { fprintf(stderr, "libdogleg_amd: " __VA_ARGS__); fputc('\n', stderr); } while(0)
 
 namespace {
-
-constexpr int BATCH_TILE = 256;         // doubles of J staged per tile (and 64 of x behind them)
-constexpr double LAMBDA_INITIAL = 1e-10;       // dogleg.c:138
-
-enum { F_CAUCHY = 1, F_GN = 2, F_EDGE = 4, F_STARTED = 8 };
-enum { SC_N2X, SC_TR, SC_LAMBDA, SC_N2C, SC_N2GN, SC_EI, SC_COUNT = 8 };
-enum { ST_FLAGS, ST_ITER, ST_EVAL, ST_STATUS, ST_COUNT = 4 };
-
-enum { FORM_J = 0, FORM_PRODUCTS = 1 };
-
-// what a products callback wrote: norm2(x) [B], Jt x [B][N], JtJ [B][S]; unpacked: S = N^2 row-major, of which the
-// entries [i][j], j >= i, are read; otherwise S = NP, row-major packed upper = the kernels' packed lower column-major
-struct ProductsDev
-{
-  const double* n2x; const double* xtJ; const double* JtJ;
-  int unpacked;
-};
-
-// the loss of a robust solve: c = a^2, fs rows a feature
-struct LossDev { int kind, fs; double a, c; };
-
-struct BatchDev
-{
-  int B, N, M, NP;
-  const double* x; const double* J;
-  double *p_before, *p_trial, *g, *cauchy, *gn, *JtJ, *sc;
-  int* st; unsigned char* live; int* counter;
-  int max_iterations;
-  double trustregion0, dec_factor, dec_thr, inc_factor, inc_thr, jtx_thr, upd_thr, tr_thr;
-  ProductsDev P;               // FORM_PRODUCTS (x, J, M unused there)
-  LossDev L; int NF; double* wts;      // the robust form: NF = M / L.fs features, rho' at the point stepped from [B][NF]
-  int robust;                  // (host side: which kernel is launched)
-  // the bounded form (behind everything above: the other kernels read their arguments where they did): lo, hi [B][N] or nullptr
-  // (no bound on that side), held [B][N] out or nullptr
-  const double *lo, *hi; unsigned char* held;
-  int bounded;                 // (host side: which kernel is launched)
-};
-
-template <int NMAX> struct BatchCfg
-{
-  static constexpr int NP = NMAX*(NMAX + 1)/2;
-  static constexpr int NE = (NP + 63)/64;                       // entries of JtJ a lane accumulates
-  static constexpr int SCR = NP > BATCH_TILE + 64 ? NP : BATCH_TILE + 64;     // the factor; during the sweep: the tile and its x
-  static constexpr int LDSW = NP + SCR + NMAX;                  // doubles of LDS per wavefront
-  // problems (wavefronts) per workgroup: 18 688 B at most up to <32>, 38 400 B at <48>, 33 792 B at <64>, so that four
-  // workgroups of any class fit a CU's 160 KB
-  static constexpr int WPB = NMAX <= 32 ? 4 : NMAX <= 48 ? 2 : 1;
-};
-// the same per form: the products form has no row tile, the second region holds the factor only
-template <int NMAX, int FORM> struct FormCfg
-{
-  static constexpr int SCR = FORM == FORM_J ? BatchCfg<NMAX>::SCR : BatchCfg<NMAX>::NP;
-  static constexpr int LDSW = BatchCfg<NMAX>::NP + SCR + NMAX;
-};
-
-// LDS of ONE wavefront written by some lanes and read by others: the hardware keeps a wave's LDS operations in
-// order, the compiler must not move them across this point
-__device__ inline void wsync()
-{
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-// butterfly sums: every lane ends with the same bits (a + b == b + a at every level)
-__device__ inline double wave_sum(double v)
-{
-  for(int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ inline double wave_max(double v)
-{
-  for(int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ inline double wave_min(double v)
-{
-  for(int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// the bounded form (dogleg.h: dogleg_amd_batch_bounds_t).  Bit i of the held set: variable i sits on a bound, bit for bit, and
-// its gradient pushes outwards.  A function of the point stepped from, g and the bounds alone; every lane gets the whole mask
-__device__ __forceinline__ unsigned long long held_mask(double p, double g, double lo, double hi, int lane, int N)
-{
-  return __ballot(lane < N && ((p == lo && g > 0.0) || (p == hi && g < 0.0)));
-}
-// this lane's entry of an array of bounds [B][N], or `none` where there is no array or no variable
-__device__ __forceinline__ double bound_at(const double* bounds, size_t bN, int lane, int N, double none)
-{
-  return bounds && lane < N ? bounds[bN + lane] : none;
-}
-// p + s clamped into [lo, hi]; s becomes the step that was applied (untouched where nothing was clamped: then the sum is the
-// plain solve's).  Returns the point; clamped: whether this lane's component was
-__device__ __forceinline__ double clip_step(double p, double& s, double lo, double hi, bool& clamped)
-{
-  double t = p + s;
-  clamped = false;
-  if(t < lo) { t = lo; clamped = true; }
-  if(t > hi) { t = hi; clamped = true; }
-  if(clamped) s = t - p;
-  return t;
-}
-// first entry of column c of the packed lower triangle (column-major; the same bytes as the reference's row-major
-// packed upper, dogleg.c:788-790)
-__device__ inline int col_off(int c, int N) { return c*N - c*(c - 1)/2; }
-__device__ inline double sym_at(const double* A, int i, int j, int N)
-{
-  return i >= j ? A[col_off(j, N) + i - j] : A[col_off(i, N) + j - i];
-}
-// v' A v, lane i holds v[i] (0 beyond N); V: N doubles of LDS
-__device__ inline double quad_form(const double* A, double* V, double v, int N, int lane)
-{
-  wsync();
-  if(lane < N) V[lane] = v;
-  wsync();
-  double r = 0.0;
-  if(lane < N)
-    for(int j = 0; j < N; j++) r += sym_at(A, lane, j, N)*V[j];
-  return wave_sum(r*v);
-}
-// DPPTRF 'L' on the packed triangle in LDS (right-looking, as the reference's LAPACK call dogleg.c:782): false where
-// a pivot is <= 0
-__device__ inline bool chol_packed(double* L, int N, int lane)
-{
-  for(int j = 0; j < N; j++)
-  {
-    const int jj = col_off(j, N), m = N - j - 1;
-    const double ajj = L[jj];
-    if(ajj <= 0.0) return false;
-    const double d = sqrt(ajj), inv = 1.0/d;
-    double ci = 0.0;
-    if(lane < m) ci = L[jj + 1 + lane]*inv;
-    wsync();
-    if(lane == 0) L[jj] = d;
-    if(lane < m) L[jj + 1 + lane] = ci;
-    wsync();
-    if(lane < m)
-      for(int c = 0; c <= lane; c++)
-        L[col_off(j + 1 + c, N) + lane - c] -= ci*L[jj + 1 + c];
-    wsync();
-  }
-  return true;
-}
-// (L L') u = rhs, lane i holds rhs[i] and gets u[i]
-__device__ inline double solve_packed(const double* L, double b, int N, int lane)
-{
-  for(int j = 0; j < N; j++)
-  {
-    const double bj = __shfl(b, j, 64)/L[col_off(j, N)];
-    if(lane == j) b = bj;
-    else if(lane > j && lane < N) b -= bj*L[col_off(j, N) + lane - j];
-  }
-  for(int j = N - 1; j >= 0; j--)
-  {
-    const double xj = __shfl(b, j, 64)/L[col_off(j, N)];
-    if(lane == j) b = xj;
-    else if(lane < j) b -= xj*L[col_off(lane, N) + j - lane];
-  }
-  return b;
-}
-
-// entry lane + 64 k of the packed triangle is (ei[k], ej[k]), ei >= ej; (0, 0) beyond NP
-template <int NMAX>
-__device__ __forceinline__ void packed_entries(int N, int NP, int lane, int* ei, int* ej)
-{
-#pragma unroll
-  for(int k = 0; k < BatchCfg<NMAX>::NE; k++)
-  {
-    const int e = lane + 64*k;
-    int c = 0;
-    if(e < NP) { while(e >= col_off(c + 1, N)) c++; }
-    ej[k] = c; ei[k] = e < NP ? c + e - col_off(c, N) : 0;
-  }
-}
-
-// rho(s) and w = rho'(s) of the loss L (dogleg.h: dogleg_amd_batch_loss_t); a NaN s gives NaN in both
-__device__ __forceinline__ void loss_eval(const LossDev& L, double s, double& rho, double& w)
-{
-  const double q = s/L.c;
-  switch(L.kind)
-  {
-  case DOGLEG_AMD_LOSS_HUBER:
-    if(s <= L.c) { rho = s; w = 1.0; }
-    else { const double r = sqrt(s); rho = 2.0*L.a*r - L.c; w = L.a/r; }
-    break;
-  case DOGLEG_AMD_LOSS_SOFT_L1:
-  {
-    // 2 c (r - 1) = 2 s / (r + 1): no cancellation for s << c
-    const double r = sqrt(1.0 + q);
-    rho = 2.0*s/(r + 1.0); w = 1.0/r;
-    break;
-  }
-  case DOGLEG_AMD_LOSS_CAUCHY:
-    rho = L.c*log1p(q); w = 1.0/(1.0 + q);
-    break;
-  default:
-    rho = s; w = 1.0;
-  }
-}
-// s of a feature of fs rows from x in memory: the products rounded, summed in the rows' order, as the sweep sums them
-__device__ __forceinline__ double feature_s(const double* xf, int fs)
-{
-#pragma clang fp contract(off)
-  double s = xf[0]*xf[0];
-  for(int k = 1; k < fs; k++) s += xf[k]*xf[k];
-  return s;
-}
-
-// the sweep over one point's x and J (xb: M, Jb: M x N row-major): returns norm2(x), leaves the packed lower triangle of
-// JtJ in SA and (Jt x)[lane] in gacc (eval_point, dogleg.c:1004-1083, and the rows' outer products dogleg.c:712-714).
-// tile: BATCH_TILE + 64 doubles of LDS.  Shared by the round and the uncertainty kernel: one order of operations.
-//
-// ROBUST: the same sweep with the loss L (first order: the curvature term of rho'' is left out, as Ceres' corrector does
-// for rho'' <= 0).  The tile height is a multiple of L.fs, so no feature straddles two tiles; the lane that holds x of row t
-// gets s of its feature by shuffles, evaluates rho and rho' and stages sqrt(w) x; every staged element of J is multiplied
-// by the sqrt(w) of its row (the element -> row map is the same for every tile).  The loop over the tile's rows is the plain
-// one.  Returns F.
-template <int NMAX, bool ROBUST = false>
-__device__ __forceinline__ double sweep_point(const double* Jb, const double* xb, int N, int M, int NP, int lane,
-                                              double* SA, double* tile, double& gacc_out, const LossDev& L = LossDev())
-{
-  using C = BatchCfg<NMAX>;
-  double* xt = tile + BATCH_TILE;
-  int ei[C::NE], ej[C::NE];
-  packed_entries<NMAX>(N, NP, lane, ei, ej);
-  int T = min(64, BATCH_TILE/N);
-  double acc[C::NE], gacc = 0.0, n2 = 0.0;
-#pragma unroll
-  for(int k = 0; k < C::NE; k++) acc[k] = 0.0;
-  constexpr int NL = BATCH_TILE/64;
-  double v[NL], xv;
-  int rowof[NL], t0 = 0;       // ROBUST: the row of the tile element lane + 64 u; the first row of this lane's feature
-  if constexpr(ROBUST)
-  {
-    T -= T % L.fs;
-    t0 = lane - lane % L.fs;
-#pragma unroll
-    for(int u = 0; u < NL; u++) rowof[u] = min((lane + 64*u)/N, 63);     // (elements behind the tile's rows hold 0)
-  }
-  {
-    const int tc = min(T, M), cnt = tc*N;
-#pragma unroll
-    for(int u = 0; u < NL; u++) v[u] = lane + 64*u < cnt ? Jb[lane + 64*u] : 0.0;
-    xv = lane < tc ? xb[lane] : 0.0;
-  }
-  for(int r0 = 0; r0 < M; r0 += T)
-  {
-    const int tc = min(T, M - r0);
-    if constexpr(ROBUST)
-    {
-      // sqrt(w) of this lane's row (1 behind the tile's rows) and the feature's rho, once a feature
-      double sw = 1.0;
-      // (the plain sweep's arithmetic, where the compiler contracts n2 += xv*xv; here the product is shared with the other
-      // branch and would not be contracted: hence spelled out, for the same bits)
-      if(L.kind == DOGLEG_AMD_LOSS_TRIVIAL) n2 = __builtin_fma(xv, xv, n2);
-      else
-      {
-        const double x2 = xv*xv;
-        double s = x2;
-        if(L.fs > 1)
-        {
-          // the rows of the feature in their order, in every one of its lanes: one s, one w a feature
-          s = __shfl(x2, t0, 64);
-          for(int k = 1; k < L.fs; k++) s += __shfl(x2, t0 + k, 64);
-        }
-        double rho, w;
-        loss_eval(L, s, rho, w);
-        if(lane < tc)
-        {
-          sw = sqrt(w);
-          if(lane == t0) n2 += rho;
-        }
-      }
-      wsync();
-#pragma unroll
-      for(int u = 0; u < NL; u++) tile[lane + 64*u] = v[u]*__shfl(sw, rowof[u], 64);
-      xt[lane] = sw*xv;
-      wsync();
-    }
-    else
-    {
-      wsync();
-#pragma unroll
-      for(int u = 0; u < NL; u++) tile[lane + 64*u] = v[u];
-      xt[lane] = xv;
-      wsync();
-      n2 += xv*xv;
-    }
-    if(r0 + T < M)
-    {
-      const int r1 = r0 + T, tn = min(T, M - r1), cnt = tn*N;
-      const double* Jn = Jb + (size_t)r1*N;
-#pragma unroll
-      for(int u = 0; u < NL; u++) v[u] = lane + 64*u < cnt ? Jn[lane + 64*u] : 0.0;
-      xv = lane < tn ? xb[r1 + lane] : 0.0;
-    }
-    for(int t = 0; t < tc; t++)
-    {
-      const double* row = tile + t*N;
-#pragma unroll
-      for(int k = 0; k < C::NE; k++) acc[k] += row[ei[k]]*row[ej[k]];
-      if(lane < N) gacc += row[lane]*xt[t];
-    }
-  }
-  const double n2x = wave_sum(n2);
-  wsync();
-#pragma unroll
-  for(int k = 0; k < C::NE; k++) if(lane + 64*k < NP) SA[lane + 64*k] = acc[k];
-  wsync();
-  gacc_out = gacc;
-  return n2x;
-}
-
-// the front end of the products form: what the callback wrote for problem b goes where sweep_point leaves its results.
-// Lane l copies the entries l, l + 64, ... of the packed triangle into SA (packed upper: the same bytes, coalesced;
-// unpacked: entry (ei, ej), ei >= ej, is G[ej][ei], the triangle the reference's dpotrf 'L' reads through its
-// column-major view, dogleg.c:802-806; the other triangle is never read).  finite: whether EVERYTHING read is finite --
-// an off-diagonal NaN of JtJ does not show on the diagonal the way a NaN of J does.
-template <int NMAX>
-__device__ __forceinline__ double load_products(const ProductsDev& P, int b, int N, int NP, int lane, double* SA,
-                                                double& g_out, bool& finite)
-{
-  using C = BatchCfg<NMAX>;
-  bool fin = true;
-  wsync();
-  if(P.unpacked)
-  {
-    int ei[C::NE], ej[C::NE];
-    packed_entries<NMAX>(N, NP, lane, ei, ej);
-    const double* Gb = P.JtJ + (size_t)b*N*N;
-#pragma unroll
-    for(int k = 0; k < C::NE; k++)
-      if(lane + 64*k < NP)
-      {
-        const double v = Gb[ej[k]*N + ei[k]];
-        fin = fin && isfinite(v);
-        SA[lane + 64*k] = v;
-      }
-  }
-  else
-  {
-    const double* Gb = P.JtJ + (size_t)b*NP;
-#pragma unroll
-    for(int k = 0; k < C::NE; k++)
-      if(lane + 64*k < NP)
-      {
-        const double v = Gb[lane + 64*k];
-        fin = fin && isfinite(v);
-        SA[lane + 64*k] = v;
-      }
-  }
-  wsync();
-  const double g = lane < N ? P.xtJ[(size_t)b*N + lane] : 0.0;
-  const double n2x = P.n2x[b];
-  finite = __all(fin && isfinite(g) && isfinite(n2x));
-  g_out = g;
-  return n2x;
-}
-
-// one round of problem b; returns whether the problem is still live.
-// BOUNDED (J form): box bounds by an active set, the eight steps above dogleg_amd_optimize_dense_batch_bounded in dogleg.h.
-// Everything it adds lies behind the sweep, on the on-chip JtJ, g and the two cached steps; the other instantiations keep
-// their text.
-template <int NMAX, int FORM, bool ROBUST, bool BOUNDED>
-__device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
-{
-  static_assert(!BOUNDED || FORM == FORM_J, "bounds: the J form only");
-  using C = BatchCfg<NMAX>;
-  const int N = A.N, M = A.M, NP = A.NP;
-  double* SA = S;                      // JtJ of the point the step is taken from
-  double* SL = S + C::NP;              // its factor; during the sweep the row tile
-  double* SV = SL + FormCfg<NMAX, FORM>::SCR;     // an N-vector
-  const size_t bN = (size_t)b*N;
-
-  double gacc, n2x;
-  bool finite;
-  if constexpr(FORM == FORM_J)
-  {
-    // ---- the sweep over the trial point's x and J: norm2(x), Jt x, JtJ (ROBUST: F, g, H in their places) ----
-    n2x = sweep_point<NMAX, ROBUST>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc, A.L);
-    // a non-finite x or J shows in norm2(x) or on the diagonal of JtJ
-    const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
-    finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
-  }
-  else
-  {
-    (void)M;
-    n2x = load_products<NMAX>(A.P, b, N, NP, lane, SA, gacc, finite);
-  }
-
-  // ---- evaluate_step (dogleg.c:1303-1356) and the swap of the two points (1427-1470) ----
-  int* st = A.st + (size_t)ST_COUNT*b; double* sc = A.sc + (size_t)SC_COUNT*b;
-  int flags = st[ST_FLAGS], iters = st[ST_ITER], status = 0;
-  const int evals = st[ST_EVAL] + 1;
-  double n2x_b = sc[SC_N2X], tr = sc[SC_TR], lam = sc[SC_LAMBDA], n2c = sc[SC_N2C], n2gn = sc[SC_N2GN];
-  double EI = sc[SC_EI];
-  double p_r = 0.0, g_r = 0.0, ca_r = 0.0, gn_r = 0.0;
-  // BOUNDED: the held set of the point stepped from; this lane's bounds (none beyond N) are read where they are used, not
-  // kept in registers across the sweep and the factorisation
-  unsigned long long hm = 0;
-  bool take = false;           // the trial point becomes the point to step from
-  if(!finite) status = DOGLEG_AMD_BATCH_FAILED;
-  else if(!(flags & F_STARTED)) take = true;
-  else
-  {
-    const double rho = (n2x_b - n2x)/EI;
-    if(rho != rho) status = DOGLEG_AMD_BATCH_FAILED;         // (the reference never leaves its retry loop there)
-    else
-    {
-      if(rho < A.dec_thr)
-      {
-        if(!(flags & F_EDGE)) tr = sqrt(n2gn);
-        tr *= A.dec_factor;
-      }
-      else if(rho > A.inc_thr && (flags & F_EDGE)) tr *= A.inc_factor;
-      if(rho > 0.0) { take = true; iters++; }
-      else if(tr < A.tr_thr) status = DOGLEG_AMD_BATCH_TRUSTREGION;
-      else
-      {
-        // rejected: again from the cached steps of the point before (no evaluation, no factorisation)
-        if(lane < N)
-        {
-          p_r = A.p_before[bN + lane]; g_r = A.g[bN + lane];
-          if(flags & F_CAUCHY) ca_r = A.cauchy[bN + lane];
-          if(flags & F_GN) gn_r = A.gn[bN + lane];
-        }
-        const double* Gb = A.JtJ + (size_t)b*NP;
-        wsync();
-        for(int e = lane; e < NP; e += 64) SA[e] = Gb[e];
-        wsync();
-        // (the cached steps are those of this held set: it is recomputed, not stored)
-        if constexpr(BOUNDED) hm = held_mask(p_r, g_r, bound_at(A.lo, bN, lane, N, -INFINITY), bound_at(A.hi, bN, lane, N, INFINITY), lane, N);
-      }
-    }
-  }
-  if(take)
-  {
-    flags = F_STARTED; n2x_b = n2x; g_r = gacc;
-    if(lane < N)
-    {
-      p_r = A.p_trial[bN + lane];
-      A.p_before[bN + lane] = p_r; A.g[bN + lane] = g_r;
-    }
-    double* Gb = A.JtJ + (size_t)b*NP;
-    for(int e = lane; e < NP; e += 64) Gb[e] = SA[e];
-    if constexpr(ROBUST)
-    {
-      // the weights of the point now stepped from: A.x still holds its x, so a rejected trial never needs them
-      const double* xb = A.x + (size_t)b*M; double* wb = A.wts + (size_t)b*A.NF;
-      for(int f = lane; f < A.NF; f += 64)
-      {
-        double rho, w;
-        loss_eval(A.L, feature_s(xb + (size_t)f*A.L.fs, A.L.fs), rho, w);
-        wb[f] = w;
-      }
-    }
-    double gmax;
-    if constexpr(BOUNDED)
-    {
-      // the stopping test is on the free gradient: 0 with every variable held
-      hm = held_mask(p_r, g_r, bound_at(A.lo, bN, lane, N, -INFINITY), bound_at(A.hi, bN, lane, N, INFINITY), lane, N);
-      gmax = wave_max((hm >> lane) & 1 ? 0.0 : fabs(g_r));
-    }
-    else gmax = wave_max(fabs(g_r));
-    if(gmax <= A.jtx_thr) status = DOGLEG_AMD_BATCH_JTX;
-    else if(iters >= A.max_iterations) status = DOGLEG_AMD_BATCH_MAX_ITERATIONS;
-  }
-  // the free gradient: g with its held entries 0 (the Cauchy step and the right-hand side of the Gauss-Newton step); the
-  // expected improvement keeps g
-  double gf_r = g_r;
-  if constexpr(BOUNDED) { if((hm >> lane) & 1) gf_r = 0.0; }
-
-  // ---- take_step (dogleg.c:1172-1297) ----
-  if(status == 0)
-  {
-    const double tr2 = tr*tr;
-    if(!(flags & F_CAUCHY))
-    {
-      const double g2 = wave_sum(gf_r*gf_r);
-      const double Jg2 = quad_form(SA, SV, gf_r, N, lane);
-      const double k = -g2/Jg2;
-      n2c = k*k*g2; ca_r = k*gf_r;
-      if(lane < N) A.cauchy[bN + lane] = ca_r;
-      flags |= F_CAUCHY;
-    }
-    double s_r = 0.0;
-    if(n2c >= tr2)
-    {
-      s_r = tr/sqrt(n2c)*ca_r;
-      flags |= F_EDGE;
-    }
-    else
-    {
-      if(!(flags & F_GN))
-      {
-        // the factorisation is attempted only here, so lambda moves only here (dogleg.c:634-820)
-        while(true)
-        {
-          wsync();
-          for(int e = lane; e < NP; e += 64) SL[e] = SA[e];
-          wsync();
-          if(lam > 0.0 && lane < N) SL[col_off(lane, N)] += lam;
-          wsync();
-          if constexpr(BOUNDED)
-          {
-            // the system on the free set: a held row and column is that of the identity, so that gn is exactly 0 there
-            if(hm)
-            {
-              int c = 0;
-              for(int e = lane; e < NP; e += 64)
-              {
-                while(e >= col_off(c + 1, N)) c++;
-                const int i = c + e - col_off(c, N);
-                if(((hm >> c) | (hm >> i)) & 1) SL[e] = i == c ? 1.0 : 0.0;
-              }
-              wsync();
-            }
-          }
-          if(chol_packed(SL, N, lane)) break;
-          lam = lam == 0.0 ? LAMBDA_INITIAL : lam*10.0;
-          if(!isfinite(lam)) { status = DOGLEG_AMD_BATCH_FAILED; break; }
-        }
-        if(status == 0)
-        {
-          gn_r = -solve_packed(SL, gf_r, N, lane);
-          if(lane >= N) gn_r = 0.0;
-          n2gn = wave_sum(gn_r*gn_r);
-          if(lane < N) A.gn[bN + lane] = gn_r;
-          flags |= F_GN;
-        }
-      }
-      if(status == 0)
-      {
-        if(n2gn <= tr2) { s_r = gn_r; flags &= ~F_EDGE; }
-        else
-        {
-          // dogleg.c:927-998
-          const double d = ca_r - gn_r;
-          const double l2 = wave_sum(d*d), neg_c = wave_sum(d*ca_r);
-          double disc = neg_c*neg_c - l2*(n2c - tr2);
-          if(disc < 0.0) disc = 0.0;
-          const double k = (neg_c + sqrt(disc))/l2;
-          s_r = ca_r + k*(gn_r - ca_r);
-          flags |= F_EDGE;
-        }
-      }
-    }
-    // BOUNDED: the step clipped into the box.  With no component clamped the text below this block is the plain solve's
-    bool clipped = false;
-    if constexpr(BOUNDED)
-    {
-      if(status == 0)
-      {
-        const double lo_r = bound_at(A.lo, bN, lane, N, -INFINITY), hi_r = bound_at(A.hi, bN, lane, N, INFINITY);
-        bool cl;
-        double sc_r = s_r;
-        double t_r = clip_step(p_r, sc_r, lo_r, hi_r, cl);
-        clipped = __any(cl);
-        if(clipped)
-        {
-          s_r = sc_r;
-          double Js2 = quad_form(SA, SV, s_r, N, lane);
-          EI = -2.0*wave_sum(g_r*s_r) - Js2;
-          double smax = wave_max(fabs(s_r));
-          if(EI <= 0.0 || smax <= A.upd_thr)
-          {
-            // the clipped step is no descent step of the model, or no step at all: the Cauchy step, cut at the trust region,
-            // then at the first bound a free variable meets
-            const double d_r = fmin(1.0, tr/sqrt(n2c))*ca_r;
-            double a_r = 1.0;
-            if(lane < N && d_r != 0.0) a_r = ((d_r > 0.0 ? hi_r : lo_r) - p_r)/d_r;
-            const double alpha = fmin(1.0, wave_min(a_r));
-            s_r = alpha*d_r;
-            t_r = clip_step(p_r, s_r, lo_r, hi_r, cl);
-            Js2 = quad_form(SA, SV, s_r, N, lane);
-            EI = -2.0*wave_sum(g_r*s_r) - Js2;
-            smax = wave_max(fabs(s_r));
-            if(n2c >= tr2) flags |= F_EDGE; else flags &= ~F_EDGE;
-            if(!(EI > 0.0) || !isfinite(EI)) status = DOGLEG_AMD_BATCH_FAILED;
-          }
-          if(status == 0)
-          {
-            if(smax <= A.upd_thr) status = DOGLEG_AMD_BATCH_SMALL_STEP;
-            else if(lane < N) A.p_trial[bN + lane] = t_r;
-          }
-        }
-      }
-    }
-    if(!clipped && status == 0)
-    {
-      const double Js2 = quad_form(SA, SV, s_r, N, lane);
-      EI = -2.0*wave_sum(g_r*s_r) - Js2;
-      // the terminal small step is neither applied nor evaluated (dogleg.c:1289-1296, 1403-1408)
-      if(wave_max(fabs(s_r)) <= A.upd_thr) status = DOGLEG_AMD_BATCH_SMALL_STEP;
-      else if(lane < N) A.p_trial[bN + lane] = p_r + s_r;
-    }
-  }
-  if(lane == 0)
-  {
-    sc[SC_N2X] = n2x_b; sc[SC_TR] = tr; sc[SC_LAMBDA] = lam; sc[SC_N2C] = n2c; sc[SC_N2GN] = n2gn; sc[SC_EI] = EI;
-    st[ST_FLAGS] = flags; st[ST_ITER] = iters; st[ST_EVAL] = evals; st[ST_STATUS] = status;
-    if(status != 0) A.live[b] = 0;
-  }
-  return status == 0;
-}
-
-template <int NMAX, int FORM, bool ROBUST, bool BOUNDED>
-__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_round(BatchDev A)
-{
-  constexpr int LDSW = FormCfg<NMAX, FORM>::LDSW, WPB = BatchCfg<NMAX>::WPB;
-  __shared__ double lds[WPB*LDSW];
-  __shared__ int s_live[WPB];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int b = blockIdx.x*WPB + w;
-  bool still = false;
-  if(b < A.B && A.live[b]) still = batch_problem<NMAX, FORM, ROBUST, BOUNDED>(A, b, lane, lds + w*LDSW);
-  if(lane == 0) s_live[w] = still ? 1 : 0;
-  __syncthreads();
-  if(threadIdx.x == 0)
-  {
-    int n = 0;
-    for(int k = 0; k < WPB; k++) n += s_live[k];
-    if(n) atomicAdd(A.counter, n);
-  }
-}
-
-// ---- dogleg_amd_dense_batch_uncertainty: Sigma_b = (JtJ + lambda I)^-1, its diagonal and the outlierness factors of every
-// problem at the points p[b], ONE launch behind one call of the batch callback.  Per wave: the sweep of the round kernel
-// (|x|^2, JtJ), the lambda loop on chol_packed, the factor inverted in place, Sigma = L^-T L^-1 into the LDS that held JtJ
-// (it is not needed once the factorisation stands: Sigma costs no LDS of its own), then a second sweep over J in which
-// one lane takes one feature.  No sum crosses lanes after the first sweep.
-struct UncDev
-{
-  int B, N, M, NP, fs, NF;
-  const double* x; const double* J;
-  double *lam, *scale, *cov, *var, *fac;     // cov, var, fac (and scale with fac): nullptr where not asked for
-  int* status;
-  ProductsDev P;               // FORM_PRODUCTS (x, J, M, fs, NF unused there; fac and scale nullptr: they need J)
-  const unsigned char* active; // [B] or nullptr (all): 0: problem b is skipped, only its status is written
-};
-
-// x' (B + B^2) x scale / 8 with B = (A_f - I)^-1, dogleg.h above dogleg_getOutliernessFactors (the arithmetic of
-// k_lev_finish, sparse_multi.hip)
-__device__ inline double factor1(double a, double x0, double k)
-{
-  const double den = 1.0 - a;
-  return fabs(den) < 1e-8 ? DBL_MAX : x0*x0/den*k;
-}
-__device__ inline double factor2(double a00, double a01, double a11, double x0, double x1, double k)
-{
-  const double m00 = a00 - 1.0, m01 = a01, m11 = a11 - 1.0;
-  const double det = m00*m11 - m01*m01;
-  if(fabs(det) < 1e-8) return DBL_MAX;
-  const double j00 = m11, j01 = -m01, j11 = m00;           // adjugate of A_f - I
-  const double xBx = (x0*x0*j00 + 2.0*x0*x1*j01 + x1*x1*j11)/det;
-  const double v0 = x0*j00 + x1*j01, v1 = x0*j01 + x1*j11;
-  return (xBx + (v0*v0 + v1*v1)/(det*det))*k;
-}
-
-// the factor of one feature of one (r) or two rows (ra, ra + NS) of J against Sigma, packed in SA: a = J_f Sigma J_f', the
-// arithmetic and the order of operations of the second sweep of the classes up to 32 in unc_problem (which keeps its own
-// text: through these functions its instantiations come out with other registers), for the classes above
-__device__ inline double feature1(const double* SA, const double* r, int N, double x0, double kf)
-{
-  double a = 0.0;
-  int idx = 0;
-  for(int j = 0; j < N; j++)
-  {
-    const double rj = r[j], d = SA[idx++];
-    double t0 = 0.0;
-    for(int i = j + 1; i < N; i++) t0 += SA[idx++]*r[i];
-    a += rj*(d*rj + 2.0*t0);
-  }
-  return factor1(a, x0, kf);
-}
-__device__ inline double feature2(const double* SA, const double* ra, int NS, int N, double x0, double x1, double kf)
-{
-  const double* rb = ra + NS;
-  double a00 = 0.0, a01 = 0.0, a11 = 0.0;
-  int idx = 0;
-  for(int j = 0; j < N; j++)
-  {
-    const double aj = ra[j], bj = rb[j], d = SA[idx++];
-    double t0 = 0.0, t1 = 0.0;
-    for(int i = j + 1; i < N; i++) { const double s = SA[idx++]; t0 += s*ra[i]; t1 += s*rb[i]; }
-    a00 += aj*(d*aj + 2.0*t0); a01 += aj*(d*bj + t1) + bj*t0; a11 += bj*(d*bj + 2.0*t1);
-  }
-  return factor2(a00, a01, a11, x0, x1, kf);
-}
-
-// the front half of a problem of the uncertainty and of the query kernel, one text for both: the sweep (or the products) into
-// SA, the finiteness test, the lambda loop on chol_packed in SL and, where that stands, X = L^-1 in place.  Between the two,
-// report(ok, lambda, norm2(x)) is the caller's: what it writes back of the factorisation and, for a problem that failed, the
-// NaN of its outputs.  Returns whether the factorisation stands.
-template <int NMAX, int FORM, class Report>
-__device__ __forceinline__ bool factor_and_invert(const UncDev& A, int b, int lane, double* SA, double* SL, Report report)
-{
-  const int N = A.N, M = A.M, NP = A.NP;
-  double gacc, n2x;
-  bool ok;
-  if constexpr(FORM == FORM_J)
-  {
-    n2x = sweep_point<NMAX>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc);
-    const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
-    ok = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
-  }
-  else
-    n2x = load_products<NMAX>(A.P, b, N, NP, lane, SA, gacc, ok);
-
-  // ---- the factorisation at lambda[b]; a pivot <= 0 moves lambda as the solve does (dogleg.c:634-820) ----
-  double lam = A.lam[b];
-  if(!(lam >= 0.0)) ok = false;        // a negative or NaN lambda[b]: FAILED, written back as it came
-  while(ok)
-  {
-    wsync();
-    for(int e = lane; e < NP; e += 64) SL[e] = SA[e];
-    wsync();
-    if(lam > 0.0 && lane < N) SL[col_off(lane, N)] += lam;
-    wsync();
-    if(chol_packed(SL, N, lane)) break;
-    lam = lam == 0.0 ? LAMBDA_INITIAL : lam*10.0;
-    if(!isfinite(lam)) ok = false;
-  }
-  report(ok, lam, n2x);
-  if(!ok) return false;
-
-  // ---- X = L^-1 in place, from the last column to the first (DTRTI2 'L'): column j of X is -X[j+1:, j+1:] L[j+1:, j] / L[j][j],
-  // lane l takes row j + 1 + l ----
-  for(int j = N - 1; j >= 0; j--)
-  {
-    const int jj = col_off(j, N), i = j + 1 + lane;
-    const double d = 1.0/SL[jj];
-    double s = 0.0;
-    if(i < N)
-    {
-      for(int k = j + 1; k <= i; k++) s += SL[col_off(k, N) + i - k]*SL[jj + k - j];
-      s *= -d;
-    }
-    wsync();
-    if(lane == 0) SL[jj] = d;
-    if(i < N) SL[jj + 1 + lane] = s;
-    wsync();
-  }
-  return true;
-}
-
-template <int NMAX, int FORM>
-__device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
-{
-  using C = BatchCfg<NMAX>;
-  const int N = A.N, M = A.M, NP = A.NP;
-  double* SA = S;                      // JtJ, then Sigma
-  double* SL = S + C::NP;              // the row tile of the sweeps; between them the factor and its inverse
-  const double* Jb = nullptr; const double* xb = nullptr;
-  if constexpr(FORM == FORM_J)
-  {
-    Jb = A.J + (size_t)b*M*N;
-    xb = A.x + (size_t)b*M;
-  }
-
-  double scale = 0.0;
-  const bool stands = factor_and_invert<NMAX, FORM>(A, b, lane, SA, SL, [&](bool ok, double lam, double n2x)
-  {
-    if(A.fac)
-    {
-      scale = A.scale[b];
-      if(!(scale > 0.0))
-      {
-        // NoutlierFeatures = 0 (api_extensions.cpp: outlier_scale); NaN for a problem that failed on a non-finite x
-        scale = (double)M/(4.0*((double)(N + 1)*n2x/(double)(M - N - 1)));
-        if(lane == 0) A.scale[b] = scale;
-      }
-    }
-    if(lane == 0) { A.lam[b] = lam; A.status[b] = ok ? DOGLEG_AMD_BATCH_UNC_OK : DOGLEG_AMD_BATCH_UNC_FAILED; }
-    if(!ok)
-    {
-      const double nan = __builtin_nan("");
-      if(A.var && lane < N) A.var[(size_t)b*N + lane] = nan;
-      if(A.cov) for(int e = lane; e < N*N; e += 64) A.cov[(size_t)b*N*N + e] = nan;
-      if(A.fac) for(int f = lane; f < A.NF; f += 64) A.fac[(size_t)b*A.NF + f] = nan;
-    }
-  });
-  if(!stands) return;
-
-  // ---- Sigma = X' X, one lane per entry: Sigma[i][j] = sum over r >= i of X[r][i] X[r][j] (i >= j) ----
-  {
-    int ei[C::NE], ej[C::NE];
-    packed_entries<NMAX>(N, NP, lane, ei, ej);
-#pragma unroll
-    for(int k = 0; k < C::NE; k++)
-      if(lane + 64*k < NP)
-      {
-        const double* ci = SL + col_off(ei[k], N); const double* cj = SL + col_off(ej[k], N) + ei[k] - ej[k];
-        double s = 0.0;
-        for(int r = 0; r < N - ei[k]; r++) s += ci[r]*cj[r];
-        SA[lane + 64*k] = s;
-      }
-  }
-  wsync();
-  if(A.var && lane < N) A.var[(size_t)b*N + lane] = SA[col_off(lane, N)];
-  if(A.cov)
-    for(int e = lane; e < N*N; e += 64)
-    {
-      const int i = e/N;
-      A.cov[(size_t)b*N*N + e] = sym_at(SA, i, e - i*N, N);
-    }
-  if(FORM != FORM_J || !A.fac) return;
-
-  // ---- the second sweep over J: tiles of T rows, row stride N | 1 in LDS (lanes read different rows: an odd stride keeps
-  // them on different banks), lane t takes feature t of the tile: a = J_f Sigma J_f' against Sigma in LDS ----
-  const int fs = A.fs, NF = A.NF, NS = N | 1, Mc = NF*fs;
-  if constexpr(NMAX > 32)
-  {
-    const double kf = scale/8.0;
-    double* tile = SL;
-    // the classes above 32 variables: the first sweep's tile would hold 4 to 7 rows, so 4 to 7 lanes of 64 would work.  The
-    // tile is the whole region the factor lay in, NP doubles: T = min(64, NP / (N | 1)) rows (24 .. 35 at <48>, 32 .. 42 at
-    // <64>), copied from global memory as it lies (coalesced) with no registers held across the features' loops
-    int T = min(64, C::SCR/NS);
-    if(fs == 2) T &= ~1;
-    for(int r0 = 0; r0 < Mc; r0 += T)
-    {
-      const int tc = min(T, Mc - r0), cnt = tc*N;
-      const double* Jt = Jb + (size_t)r0*N;
-      wsync();
-      for(int e = lane, r = lane/N, c = lane - r*N; e < cnt; e += 64)
-      {
-        tile[r*NS + c] = Jt[e];
-        c += 64;
-        while(c >= N) { c -= N; r++; }
-      }
-      wsync();
-      if(lane*fs < tc)
-      {
-        const size_t f = (size_t)(r0/fs + lane);
-        if(fs == 1) A.fac[(size_t)b*NF + f] = feature1(SA, tile + lane*NS, N, xb[r0 + lane], kf);
-        else        A.fac[(size_t)b*NF + f] = feature2(SA, tile + 2*lane*NS, NS, N, xb[r0 + 2*lane], xb[r0 + 2*lane + 1], kf);
-      }
-    }
-    return;
-  }
-  int T = min(min(64, BATCH_TILE/N), (BATCH_TILE + 64)/NS);
-  if(fs == 2) T &= ~1;
-  constexpr int NL = BATCH_TILE/64;
-  int po[NL];
-#pragma unroll
-  for(int u = 0; u < NL; u++) { const int e = lane + 64*u, r = e/N; po[u] = r*NS + e - r*N; }
-  const double kf = scale/8.0;
-  double* tile = SL;
-  double v[NL];
-  {
-    const int cnt = min(T, Mc)*N;
-#pragma unroll
-    for(int u = 0; u < NL; u++) v[u] = lane + 64*u < cnt ? Jb[lane + 64*u] : 0.0;
-  }
-  for(int r0 = 0; r0 < Mc; r0 += T)
-  {
-    const int tc = min(T, Mc - r0);
-    wsync();
-#pragma unroll
-    for(int u = 0; u < NL; u++) if(lane + 64*u < T*N) tile[po[u]] = v[u];
-    wsync();
-    if(r0 + T < Mc)
-    {
-      const int r1 = r0 + T, cnt = min(T, Mc - r1)*N;
-      const double* Jn = Jb + (size_t)r1*N;
-#pragma unroll
-      for(int u = 0; u < NL; u++) v[u] = lane + 64*u < cnt ? Jn[lane + 64*u] : 0.0;
-    }
-    if(lane*fs < tc)
-    {
-      const size_t f = (size_t)(r0/fs + lane);
-      if(fs == 1)
-      {
-        const double* r = tile + lane*NS;
-        double a = 0.0;
-        int idx = 0;
-        for(int j = 0; j < N; j++)
-        {
-          const double rj = r[j], d = SA[idx++];
-          double t0 = 0.0;
-          for(int i = j + 1; i < N; i++) t0 += SA[idx++]*r[i];
-          a += rj*(d*rj + 2.0*t0);
-        }
-        A.fac[(size_t)b*NF + f] = factor1(a, xb[r0 + lane], kf);
-      }
-      else
-      {
-        const double* ra = tile + 2*lane*NS; const double* rb = ra + NS;
-        double a00 = 0.0, a01 = 0.0, a11 = 0.0;
-        int idx = 0;
-        for(int j = 0; j < N; j++)
-        {
-          const double aj = ra[j], bj = rb[j], d = SA[idx++];
-          double t0 = 0.0, t1 = 0.0;
-          for(int i = j + 1; i < N; i++) { const double s = SA[idx++]; t0 += s*ra[i]; t1 += s*rb[i]; }
-          a00 += aj*(d*aj + 2.0*t0); a01 += aj*(d*bj + t1) + bj*t0; a11 += bj*(d*bj + 2.0*t1);
-        }
-        A.fac[(size_t)b*NF + f] = factor2(a00, a01, a11, xb[r0 + 2*lane], xb[r0 + 2*lane + 1], kf);
-      }
-    }
-  }
-}
-
-template <int NMAX, int FORM>
-__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_uncertainty(UncDev A)
-{
-  constexpr int LDSW = BatchCfg<NMAX>::NP + FormCfg<NMAX, FORM>::SCR, WPB = BatchCfg<NMAX>::WPB;
-  __shared__ double lds[WPB*LDSW];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int b = blockIdx.x*WPB + w;
-  if(b >= A.B) return;
-  // the mask: b is the wave's, so the whole wave leaves together
-  if(A.active && !A.active[b])
-  {
-    if(lane == 0) A.status[b] = DOGLEG_AMD_BATCH_UNC_SKIPPED;
-    return;
-  }
-  unc_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
-}
-
-// a . b over the wave, every lane ending with the same bits: the products are rounded before the butterfly.  (An FMA that took
-// its lane's product into the first level's sum would round differently in the two lanes of a pair.)
-__device__ inline double wave_dot(double a, double b)
-{
-#pragma clang fp contract(off)
-  double v = a*b;
-  for(int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// ---- dogleg_amd_dense_batch_query_covariance: Var(q) = Jq Sigma_b Jq' of Nq caller-supplied query Jacobians of Q rows per
-// problem, ONE launch behind one call of the batch callback.  Per wave: factor_and_invert, then per query row c the forward
-// product z_c = X Jq_c' (lane i holds element i), and out[c][d] = z_c . z_d by the wave's butterfly sum: Sigma is never formed.
-// The observations-only (sandwich) form Jq Sigma J_obs' J_obs Sigma Jq' (J form, nobs >= 0): G = J_obs' J_obs by a sweep of its
-// own over the first nobs rows, Y_c = X' z_c (= Sigma Jq_c'), out[c][d] = Y_c' G Y_d.
-struct QueryDev
-{
-  UncDev U;                    // B, N, M, NP, x, J, P, lam, status, active; cov, var, fac, scale: nullptr
-  const double* Jq;            // [B][Nq][Q][N]
-  double* out;                 // [B][Nq][Q][Q]
-  int Nq, Q, nobs;             // nobs < 0: the plain form
-};
-
-// LDS of a wavefront of the query kernel: JtJ | the row tile, then the factor and X | an N-vector | G (J form) | the Q vectors
-// z (or Y) of one query.  The last lie in the region of JtJ, which nobody reads once the factorisation stands, where that
-// holds DOGLEG_AMD_BATCH_QUERY_MAX_ROWS rows (from <32> on), and in a region of their own below
-template <int NMAX, int FORM> struct QueryCfg
-{
-  using C = BatchCfg<NMAX>;
-  static constexpr int SCR = FormCfg<NMAX, FORM>::SCR;
-  static constexpr int GB = FORM == FORM_J ? C::NP : 0;
-  static constexpr int ZROWS = DOGLEG_AMD_BATCH_QUERY_MAX_ROWS*NMAX;
-  static constexpr int ZOWN = C::NP >= ZROWS ? 0 : ZROWS;
-  static constexpr int LDSW = C::NP + SCR + NMAX + GB + ZOWN;
-  static_assert(sizeof(double)*C::WPB*LDSW <= 65536, "k_batch_query: the wavefronts of a workgroup need more than 64 KB of LDS");
-};
-
-template <int NMAX, int FORM>
-__device__ void query_problem(const QueryDev& A, int b, int lane, double* S)
-{
-  using C = BatchCfg<NMAX>;
-  using QC = QueryCfg<NMAX, FORM>;
-  const UncDev& U = A.U;
-  const int N = U.N, Q = A.Q;
-  double* SA = S;                      // JtJ
-  double* SL = SA + C::NP;             // the row tile of the sweeps, then the factor and X = L^-1
-  double* SV = SL + QC::SCR;           // an N-vector, read at wave-uniform addresses
-  double* SG = SV + NMAX;              // G, packed as JtJ
-  double* SZ = QC::ZOWN ? SG + QC::GB : SA;       // z_c (sandwich form: Y_c), row c at c N
-  const size_t rows = (size_t)A.Nq*Q;
-  const double* Jqb = A.Jq + (size_t)b*rows*N;
-  double* ob = A.out + (size_t)b*rows*Q;
-
-  bool sandwich = false;
-  if constexpr(FORM == FORM_J)
-  {
-    sandwich = A.nobs >= 0;
-    if(sandwich)
-    {
-      // sweep_point over the first nobs rows: its JtJ is G (nobs = 0: no row is read, G is exactly 0)
-      double g;
-      (void)sweep_point<NMAX>(U.J + (size_t)b*U.M*N, U.x + (size_t)b*U.M, N, A.nobs, U.NP, lane, SG, SL, g);
-    }
-  }
-  const bool stands = factor_and_invert<NMAX, FORM>(U, b, lane, SA, SL, [&](bool ok, double lam, double)
-  {
-    if(lane == 0) { U.lam[b] = lam; U.status[b] = ok ? DOGLEG_AMD_BATCH_UNC_OK : DOGLEG_AMD_BATCH_UNC_FAILED; }
-    if(!ok)
-    {
-      const double nan = __builtin_nan("");
-      for(size_t e = lane; e < rows*Q; e += 64) ob[e] = nan;
-    }
-  });
-  if(!stands) return;
-
-  // the rows of Jq as they lie, lane i element i of a row (coalesced); the next row's load is in flight under the current
-  // row's product
-  double qn = lane < N ? Jqb[lane] : 0.0;
-  for(int q = 0; q < A.Nq; q++)
-  {
-    for(int c = 0; c < Q; c++)
-    {
-      const size_t r = (size_t)q*Q + c;
-      const double qv = qn;
-      if(r + 1 < rows) qn = lane < N ? Jqb[(r + 1)*N + lane] : 0.0;
-      wsync();
-      if(lane < N) SV[lane] = qv;
-      wsync();
-      // z = X Jq_c': lane i sums along row i of X (consecutive lanes read consecutive doubles of a column)
-      double z = 0.0;
-      if(lane < N)
-        for(int j = 0; j <= lane; j++) z += SL[col_off(j, N) + lane - j]*SV[j];
-      if(sandwich)
-      {
-        // Y = X' z: lane i sums along column i of X
-        wsync();
-        if(lane < N) SV[lane] = z;
-        wsync();
-        double y = 0.0;
-        if(lane < N)
-        {
-          const double* col = SL + col_off(lane, N) - lane;
-          for(int k = lane; k < N; k++) y += col[k]*SV[k];
-        }
-        z = y;
-      }
-      if(lane < N) SZ[c*N + lane] = z;
-    }
-    wsync();
-    // the triangle of the block, every entry once: the butterfly leaves the same bits in every lane, the lanes that own
-    // [c][d] and [d][c] store them -- a bitwise symmetric block whose diagonal (plain form) is a sum of squares
-    double* oq = ob + (size_t)q*Q*Q;
-    for(int d = 0; d < Q; d++)
-    {
-      double w = lane < N ? SZ[d*N + lane] : 0.0;
-      if(sandwich)
-      {
-        // w = G Y_d
-        wsync();
-        if(lane < N) SV[lane] = w;
-        wsync();
-        double t = 0.0;
-        if(lane < N)
-          for(int j = 0; j < N; j++) t += sym_at(SG, lane, j, N)*SV[j];
-        w = t;
-      }
-      for(int c = 0; c <= d; c++)
-      {
-        const double zc = lane < N ? SZ[c*N + lane] : 0.0;
-        const double s = wave_dot(zc, w);
-        const int e = c*Q + d, f = d*Q + c;
-        if(lane == (e & 63)) oq[e] = s;
-        if(c != d && lane == (f & 63)) oq[f] = s;
-      }
-    }
-    wsync();
-  }
-}
-
-template <int NMAX, int FORM>
-__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_query(QueryDev A)
-{
-  constexpr int LDSW = QueryCfg<NMAX, FORM>::LDSW, WPB = BatchCfg<NMAX>::WPB;
-  __shared__ double lds[WPB*LDSW];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int b = blockIdx.x*WPB + w;
-  if(b >= A.U.B) return;
-  // the mask, as in k_batch_uncertainty
-  if(A.U.active && !A.U.active[b])
-  {
-    if(lane == 0) A.U.status[b] = DOGLEG_AMD_BATCH_UNC_SKIPPED;
-    return;
-  }
-  query_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
-}
-
-// active: [B] or nullptr (all); a problem with active[b] == 0 starts, and stays, not live
-__global__ void __launch_bounds__(256) k_batch_init(BatchDev A, const unsigned char* active)
-{
-  const int b = blockIdx.x*256 + threadIdx.x;
-  if(b >= A.B) return;
-  double* sc = A.sc + (size_t)SC_COUNT*b; int* st = A.st + (size_t)ST_COUNT*b;
-  for(int k = 0; k < SC_COUNT; k++) sc[k] = 0.0;
-  sc[SC_TR] = A.trustregion0;
-  for(int k = 0; k < ST_COUNT; k++) st[k] = 0;
-  A.live[b] = active ? (active[b] ? 1 : 0) : 1;
-}
-
-// the start of a bounded solve, behind k_batch_init: the start point of every live problem clamped into its box.  A problem with
-// a NaN bound or lo > hi is FAILED here, alone: never live, no evaluation, its p not touched
-__global__ void __launch_bounds__(256) k_batch_clamp(BatchDev A)
-{
-  const int b = blockIdx.x*256 + threadIdx.x;
-  if(b >= A.B || !A.live[b]) return;
-  const size_t bN = (size_t)b*A.N;
-  bool ok = true;
-  for(int i = 0; i < A.N; i++)
-  {
-    const double lo = A.lo ? A.lo[bN + i] : -INFINITY, hi = A.hi ? A.hi[bN + i] : INFINITY;
-    if(!(lo <= hi)) ok = false;
-  }
-  if(!ok)
-  {
-    A.st[(size_t)ST_COUNT*b + ST_STATUS] = DOGLEG_AMD_BATCH_FAILED;
-    A.live[b] = 0;
-    return;
-  }
-  for(int i = 0; i < A.N; i++)
-  {
-    double p = A.p_trial[bN + i];
-    if(A.lo && p < A.lo[bN + i]) p = A.lo[bN + i];
-    if(A.hi && p > A.hi[bN + i]) p = A.hi[bN + i];
-    A.p_trial[bN + i] = p;
-  }
-}
-// 0 free, 1 held at lower, 2 held at upper: the held set at a point with the g of that point (held_mask, per element)
-__host__ __device__ inline unsigned char held_code(double p, double g, double lo, double hi)
-{
-  return p == lo && g > 0.0 ? 1 : p == hi && g < 0.0 ? 2 : 0;
-}
-
-// the end of a device-resident solve: the state of every problem into the caller's arrays (what run_locked does on the
-// host for the host-pointer entry points).  Thread t takes element t of p, [B][N] (coalesced stores; a problem that FAILED
-// or was not run keeps its input), and, for t < B, the record and the lambda of problem t.  A status of 0 after the last
-// round is a problem that never was live: every live problem leaves its last round with a status.
-// The robust form (weights != nullptr; the grid covers [B][NF] too): thread t takes element t of the weights, NaN for a problem
-// that FAILED.
-// The bounded form (A.held != nullptr): the held set at the returned point, from p, g and the bounds as the round kernel forms
-// it; all 0 for a problem that FAILED.
-__global__ void __launch_bounds__(256) k_batch_finish(BatchDev A, double* p, dogleg_amd_batch_result_t* results, double* lambda,
-                                                      double* weights)
-{
-  const size_t t = (size_t)blockIdx.x*256 + threadIdx.x;
-  if(t < (size_t)A.B*A.N)
-  {
-    const int status = A.st[(size_t)ST_COUNT*(t/A.N) + ST_STATUS];
-    if(status != DOGLEG_AMD_BATCH_NOT_RUN && status != DOGLEG_AMD_BATCH_FAILED) p[t] = A.p_before[t];
-    if(A.held && status != DOGLEG_AMD_BATCH_NOT_RUN)
-      A.held[t] = status == DOGLEG_AMD_BATCH_FAILED ? 0 :
-                  held_code(A.p_before[t], A.g[t], A.lo ? A.lo[t] : -INFINITY, A.hi ? A.hi[t] : INFINITY);
-  }
-  if(weights && t < (size_t)A.B*A.NF)
-  {
-    const int status = A.st[(size_t)ST_COUNT*(t/A.NF) + ST_STATUS];
-    if(status == DOGLEG_AMD_BATCH_FAILED) weights[t] = __builtin_nan("");
-    else if(status != DOGLEG_AMD_BATCH_NOT_RUN) weights[t] = A.wts[t];
-  }
-  if(t >= (size_t)A.B) return;
-  const int* st = A.st + (size_t)ST_COUNT*t; const double* sc = A.sc + (size_t)SC_COUNT*t;
-  const int status = st[ST_STATUS];
-  const bool run = status != DOGLEG_AMD_BATCH_NOT_RUN;
-  dogleg_amd_batch_result_t& R = results[t];
-  const double lam = run ? sc[SC_LAMBDA] : 0.0;
-  R.norm2_x = !run || status == DOGLEG_AMD_BATCH_FAILED ? -1.0 : sc[SC_N2X];
-  R.trustregion = run ? sc[SC_TR] : 0.0; R.lambda = lam;
-  R.iterations = st[ST_ITER]; R.evaluations = st[ST_EVAL]; R.status = status;
-  if(lambda) lambda[t] = lam;
-}
 
 // ---- what is kept between calls ----
 struct BatchCache
@@ -1243,6 +50,14 @@ void release_locked()
     if(sw) (void)hipSetDevice(cur);
   }
   K = BatchCache();
+}
+// a public call: under the lock, and without a cache where the environment says so
+template <class Fn> int locked_call(Fn fn)
+{
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int rc = fn();
+  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
+  return rc;
 }
 
 #define BHIP(call) \
@@ -1312,7 +127,14 @@ bool stage_ensure(const char* who, unsigned int B, unsigned int N, unsigned int 
   K.stage_bytes = io_bytes;
   return true;
 }
+// segments of a buffer, each aligned to 256 bytes: off = add(bytes)
+struct Segments
+{
+  size_t bytes = 0;
+  size_t add(size_t n) { const size_t off = bytes; bytes += align256(n); return off; }
+};
 
+// ---- what every call path shares ----
 // the callback of a call and what it writes: the J form (fJ: x, J of Nmeas = M rows) or the products form (fP: norm2x,
 // xtJ, JtJ; M is 0 there)
 struct BatchForm
@@ -1323,109 +145,134 @@ struct BatchForm
   bool products() const { return fP != nullptr; }
   unsigned int S(unsigned int N) const { return unpacked ? N*N : N*(N + 1)/2; }
 };
-// where the products callback's three outputs lie in the evaluation buffer
-struct ProductsLayout { size_t n2_bytes, g_bytes, G_bytes; };
-ProductsLayout products_layout(const BatchForm& F, unsigned int B, unsigned int N)
+// the evaluation buffer of a call, what the callback writes for B problems: x | J, or norm2x | xtJ | JtJ
+struct EvalBuffer
 {
-  return { align256(sizeof(double)*(size_t)B), align256(sizeof(double)*(size_t)B*N), align256(sizeof(double)*(size_t)B*F.S(N)) };
+  double doubles;              // its size in doubles: B * M * (N + 1) can pass 2^64 bytes, so a call is refused on this
+  size_t bytes;
+  size_t second, third;        // where J, or xtJ and JtJ, begin
+};
+EvalBuffer eval_buffer(const BatchForm& F, unsigned int B, unsigned int N, unsigned int M)
+{
+  EvalBuffer E;
+  Segments S;
+  if(F.products())
+  {
+    E.doubles = (double)B*(1.0 + N + F.S(N));
+    S.add(sizeof(double)*(size_t)B); E.second = S.add(sizeof(double)*(size_t)B*N); E.third = S.add(sizeof(double)*(size_t)B*F.S(N));
+  }
+  else
+  {
+    E.doubles = (double)B*(double)M*((double)N + 1.0);
+    S.add(sizeof(double)*(size_t)B*M); E.second = S.add(sizeof(double)*(size_t)B*M*N); E.third = 0;
+  }
+  E.bytes = S.bytes;
+  return E;
 }
-ProductsDev products_dev(const BatchForm& F, const ProductsLayout& L, void* d_eval)
+// x / J / P of a kernel's argument (BatchDev, UncDev), the buffer at d_eval.  P stays empty in the J form (the launchers tell the
+// forms apart by it); x and J are not read in the products form
+template <class Dev> void point_at_eval(Dev& A, const BatchForm& F, const EvalBuffer& E, void* d_eval)
 {
-  ProductsDev P;
   char* q = (char*)d_eval;
-  P.n2x = (double*)q; q += L.n2_bytes; P.xtJ = (double*)q; q += L.g_bytes; P.JtJ = (double*)q;
-  P.unpacked = F.unpacked ? 1 : 0;
-  return P;
+  A.x = (double*)q; A.J = (double*)(q + (F.products() ? 0 : E.second));
+  A.P = ProductsDev{nullptr, nullptr, nullptr, 0};
+  if(F.products()) A.P = ProductsDev{(double*)q, (double*)(q + E.second), (double*)(q + E.third), F.unpacked ? 1 : 0};
 }
+// the caller's callback at the points p of the problems whose live byte is set, into the buffer A points at, on st
+template <class Dev> void invoke_callback(const BatchForm& F, const double* p, const Dev& A, const unsigned char* live,
+                                          unsigned int B, hipStream_t st, void* cookie)
+{
+  if(F.products())
+    F.fP(p, const_cast<double*>(A.P.n2x), const_cast<double*>(A.P.xtJ), const_cast<double*>(A.P.JtJ), live, B, (void*)st, cookie);
+  else
+    F.fJ(p, const_cast<double*>(A.x), const_cast<double*>(A.J), live, B, (void*)st, cookie);
+}
+// whether a call fits, from the arithmetic alone: the evaluation buffer, state_d doubles of state and, for a query call, q's Jq
+// and out
+bool fits(const char* who, const BatchForm& F, unsigned int B, unsigned int N, unsigned int M, const EvalBuffer& E, double state_d,
+          const DlgBatchQuery* q = nullptr)
+{
+  const double rows_d = q ? (double)B*(double)q->Nq*(double)q->Qrows : 0.0;
+  const double Jq_d = rows_d*N*8.0, out_d = q ? rows_d*q->Qrows*8.0 : 0.0;
+  const double need = (E.doubles + state_d)*8.0 + Jq_d + out_d;
+  if(!(need > 1.0e15)) return true;
+  dlg_set_error("%s: %.3g bytes of device memory", who, need);
+  if(q)                 BMSG("%s: B = %u problems of %u variables with %u queries of %u rows need %.3g bytes of device memory (%.3g of "
+                             "them for Jq, %.3g for out)", who, B, N, q->Nq, q->Qrows, need, Jq_d, out_d);
+  else if(F.products()) BMSG("%s: B = %u problems of %u variables need %.3g bytes of device memory", who, B, N, need);
+  else                  BMSG("%s: B = %u problems of %u x %u need %.3g bytes of device memory", who, B, M, N, need);
+  return false;
+}
+// DOGLEG_AMD_BATCH_TIMING: the time of the callback and of the library's launch behind it, between three marks on the stream
+struct BatchTimer
+{
+  bool on = false;
+  double ms_callback = 0.0, ms_library = 0.0;
+  int start(const char* who)
+  {
+    on = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
+    if(on) for(hipEvent_t& e : g_cache.ev) if(!e) BHIP(hipEventCreate(&e));
+    return 0;
+  }
+  int mark(const char* who, int k, hipStream_t st)
+  {
+    if(on) BHIP(hipEventRecord(g_cache.ev[k], st));
+    return 0;
+  }
+  // behind a synchronisation: adds what lies between the marks
+  int read(const char* who)
+  {
+    if(!on) return 0;
+    float a = 0.f, c = 0.f;
+    BHIP(hipEventElapsedTime(&a, g_cache.ev[0], g_cache.ev[1])); BHIP(hipEventElapsedTime(&c, g_cache.ev[1], g_cache.ev[2]));
+    ms_callback += a; ms_library += c;
+    return 0;
+  }
+};
 
-// the grid and the block follow the size class: BatchCfg<NMAX>::WPB problems per workgroup
-template <int NMAX, int FORM, bool ROBUST, bool BOUNDED> void launch_round_class(hipStream_t st, const BatchDev& A)
+// ---- the solve ----
+const char* solve_who(const DlgBatchSolve& a)
 {
-  constexpr int WPB = BatchCfg<NMAX>::WPB;
-  hipLaunchKernelGGL((k_batch_round<NMAX, FORM, ROBUST, BOUNDED>), dim3((A.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
+  static const char* const names[4][2] = {
+    {"dogleg_amd_optimize_dense_products_batch", "dogleg_amd_optimize_dense_products_batch_device"},
+    {"dogleg_amd_optimize_dense_batch_bounded", "dogleg_amd_optimize_dense_batch_bounded_device"},
+    {"dogleg_amd_optimize_dense_batch_robust", "dogleg_amd_optimize_dense_batch_robust_device"},
+    {"dogleg_amd_optimize_dense_batch", "dogleg_amd_optimize_dense_batch_device"}};
+  return names[a.fP ? 0 : a.bounds ? 1 : a.loss ? 2 : 3][a.device ? 1 : 0];
 }
-template <int NMAX, int FORM> void launch_uncertainty_class(hipStream_t st, const UncDev& A)
+// the cache opened and grown for the solve a, and the kernels' argument pointing into it.  The host route keeps the bounds it is
+// given behind the state (A.lo, A.hi); the device route reads the caller's arrays
+int batch_setup(const char* who, const DlgBatchSolve& a, const BatchForm& F, BatchDev& A)
 {
-  constexpr int WPB = BatchCfg<NMAX>::WPB;
-  hipLaunchKernelGGL((k_batch_uncertainty<NMAX, FORM>), dim3((A.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
-}
-template <int NMAX, int FORM> void launch_query_class(hipStream_t st, const QueryDev& A)
-{
-  constexpr int WPB = BatchCfg<NMAX>::WPB;
-  hipLaunchKernelGGL((k_batch_query<NMAX, FORM>), dim3((A.U.B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
-}
-template <int FORM> void launch_query(unsigned int N, hipStream_t st, const QueryDev& A)
-{
-  if(N <= 8)       launch_query_class<8, FORM>(st, A);
-  else if(N <= 16) launch_query_class<16, FORM>(st, A);
-  else if(N <= 24) launch_query_class<24, FORM>(st, A);
-  else if(N <= 32) launch_query_class<32, FORM>(st, A);
-  else if(N <= 48) launch_query_class<48, FORM>(st, A);
-  else             launch_query_class<64, FORM>(st, A);
-}
-template <int FORM, bool ROBUST = false, bool BOUNDED = false> void launch_round(unsigned int N, hipStream_t st, const BatchDev& A)
-{
-  if(N <= 8)       launch_round_class<8, FORM, ROBUST, BOUNDED>(st, A);
-  else if(N <= 16) launch_round_class<16, FORM, ROBUST, BOUNDED>(st, A);
-  else if(N <= 24) launch_round_class<24, FORM, ROBUST, BOUNDED>(st, A);
-  else if(N <= 32) launch_round_class<32, FORM, ROBUST, BOUNDED>(st, A);
-  else if(N <= 48) launch_round_class<48, FORM, ROBUST, BOUNDED>(st, A);
-  else             launch_round_class<64, FORM, ROBUST, BOUNDED>(st, A);
-}
-template <int FORM> void launch_uncertainty(unsigned int N, hipStream_t st, const UncDev& A)
-{
-  if(N <= 8)       launch_uncertainty_class<8, FORM>(st, A);
-  else if(N <= 16) launch_uncertainty_class<16, FORM>(st, A);
-  else if(N <= 24) launch_uncertainty_class<24, FORM>(st, A);
-  else if(N <= 32) launch_uncertainty_class<32, FORM>(st, A);
-  else if(N <= 48) launch_uncertainty_class<48, FORM>(st, A);
-  else             launch_uncertainty_class<64, FORM>(st, A);
-}
-
-// the cache opened and grown for B problems of N variables (M measurements; 0: the products form), and the kernels'
-// argument pointing into it.  loss: the robust form (checked by the caller), or nullptr
-// nbounds: the bounded host-pointer form keeps that many arrays [B][N] of bounds (0 .. 2) behind the state; they come back in
-// A.lo (the first) and A.hi (the second) and the caller says which is which
-int batch_setup(const char* who, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F,
-                const dogleg_parameters2_t* prm, const dogleg_amd_batch_loss_t* loss, BatchDev& A, int nbounds = 0)
-{
+  const unsigned int B = a.B, N = a.N, M = a.M;
+  const dogleg_amd_batch_loss_t* loss = a.loss;
+  const dogleg_parameters2_t* prm = a.prm;
+  const bool room_lo = !a.device && a.bounds && a.bounds->lower, room_hi = !a.device && a.bounds && a.bounds->upper;
+  const int nbounds = (room_lo ? 1 : 0) + (room_hi ? 1 : 0);
   const unsigned int fs = loss ? (loss->featureSize <= 1 ? 1u : (unsigned int)loss->featureSize) : 1u;
   const unsigned int NF = loss ? M/fs : 0;
   if(cache_open(who)) return -1;
   BatchCache& K = g_cache;
   const int NP = (int)(N*(N + 1)/2);
-  // sizes in doubles first: B * M * (N + 1) can pass 2^64 bytes
-  const double eval_d = F.products() ? (double)B*(1.0 + N + F.S(N)) : (double)B*(double)M*((double)N + 1.0);
-  const double state_d = (double)B*(5.0*N + NP + SC_COUNT + 1.0 + NF + (double)nbounds*N);
-  if((eval_d + state_d)*8.0 > 1.0e15)
-  {
-    dlg_set_error("%s: %.3g bytes of device memory", who, (eval_d + state_d)*8.0);
-    if(F.products()) BMSG("%s: B = %u problems of %u variables need %.3g bytes of device memory", who, B, N, (eval_d + state_d)*8.0);
-    else             BMSG("%s: B = %u problems of %u x %u need %.3g bytes of device memory", who, B, M, N, (eval_d + state_d)*8.0);
-    return -1;
-  }
-  const size_t x_bytes = align256(sizeof(double)*(size_t)B*M), J_bytes = align256(sizeof(double)*(size_t)B*M*N);
-  const size_t vec_bytes = align256(sizeof(double)*(size_t)B*N), G_bytes = align256(sizeof(double)*(size_t)B*NP);
-  const size_t sc_bytes = align256(sizeof(double)*(size_t)B*SC_COUNT), st_bytes = align256(sizeof(int)*(size_t)B*ST_COUNT);
-  const size_t live_bytes = align256(B);
-  const ProductsLayout PL = products_layout(F, B, N);
-  const size_t eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : x_bytes + J_bytes;
-  const size_t wts_bytes = align256(sizeof(double)*(size_t)B*NF);
-  const size_t state_bytes = 5*vec_bytes + G_bytes + sc_bytes + st_bytes + live_bytes + 256 + wts_bytes + (size_t)nbounds*vec_bytes;
-  if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes)) return -1;
+  const EvalBuffer E = eval_buffer(F, B, N, M);
+  if(!fits(who, F, B, N, M, E, (double)B*(5.0*N + NP + SC_COUNT + 1.0 + NF + (double)nbounds*N))) return -1;
+  const size_t vec_bytes = sizeof(double)*(size_t)B*N;
+  Segments S;
+  const size_t o_before = S.add(vec_bytes), o_trial = S.add(vec_bytes), o_g = S.add(vec_bytes), o_cauchy = S.add(vec_bytes);
+  const size_t o_gn = S.add(vec_bytes), o_JtJ = S.add(sizeof(double)*(size_t)B*NP), o_sc = S.add(sizeof(double)*(size_t)B*SC_COUNT);
+  const size_t o_st = S.add(sizeof(int)*(size_t)B*ST_COUNT), o_live = S.add(B), o_counter = S.add(256);
+  const size_t o_wts = S.add(sizeof(double)*(size_t)B*NF);
+  const size_t o_lo = S.add(room_lo ? vec_bytes : 0), o_hi = S.add(room_hi ? vec_bytes : 0);
+  if(!cache_ensure(who, B, N, M, E.bytes, S.bytes)) return -1;
 
   A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = NP;
-  char* q = (char*)K.d_eval;
-  A.x = (double*)q; q += x_bytes; A.J = (double*)q;
-  A.P = products_dev(F, PL, K.d_eval);
-  q = (char*)K.d_state;
-  A.p_before = (double*)q; q += vec_bytes; A.p_trial = (double*)q; q += vec_bytes; A.g = (double*)q; q += vec_bytes;
-  A.cauchy = (double*)q; q += vec_bytes; A.gn = (double*)q; q += vec_bytes; A.JtJ = (double*)q; q += G_bytes;
-  A.sc = (double*)q; q += sc_bytes; A.st = (int*)q; q += st_bytes; A.live = (unsigned char*)q; q += live_bytes;
-  A.counter = (int*)q; q += 256;
-  A.wts = loss ? (double*)q : nullptr; A.NF = (int)NF; A.robust = loss ? 1 : 0;
-  q += wts_bytes;
-  A.lo = nbounds > 0 ? (const double*)q : nullptr; A.hi = nbounds > 1 ? (const double*)(q + vec_bytes) : nullptr;
+  point_at_eval(A, F, E, K.d_eval);
+  char* q = (char*)K.d_state;
+  A.p_before = (double*)(q + o_before); A.p_trial = (double*)(q + o_trial); A.g = (double*)(q + o_g);
+  A.cauchy = (double*)(q + o_cauchy); A.gn = (double*)(q + o_gn); A.JtJ = (double*)(q + o_JtJ);
+  A.sc = (double*)(q + o_sc); A.st = (int*)(q + o_st); A.live = (unsigned char*)(q + o_live); A.counter = (int*)(q + o_counter);
+  A.wts = loss ? (double*)(q + o_wts) : nullptr; A.NF = (int)NF; A.robust = loss ? 1 : 0;
+  A.lo = room_lo ? (const double*)(q + o_lo) : nullptr; A.hi = room_hi ? (const double*)(q + o_hi) : nullptr;
   A.held = nullptr; A.bounded = 0;
   A.L.kind = loss ? loss->kind : DOGLEG_AMD_LOSS_TRIVIAL; A.L.fs = (int)fs;
   A.L.a = loss && loss->kind != DOGLEG_AMD_LOSS_TRIVIAL ? loss->scale : 1.0; A.L.c = A.L.a*A.L.a;
@@ -1441,15 +288,13 @@ int batch_setup(const char* who, unsigned int B, unsigned int N, unsigned int M,
 int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* cookie, hipStream_t st)
 {
   BatchCache& K = g_cache;
-  const unsigned int B = (unsigned int)A.B, N = (unsigned int)A.N;
-  const bool timing = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
-  if(timing) for(hipEvent_t& e : K.ev) if(!e) BHIP(hipEventCreate(&e));
+  BatchTimer T;
+  if(T.start(who)) return -1;
   // a problem leaves a round finished or with a new trial point; rejected trials shrink the trust region until the
   // threshold stops them, so the rounds are bounded wherever the reference's own loop is.  The cap only keeps a
   // parameter set under which the reference would never return (a decrease factor >= 1) from holding the device.
   const long max_rounds = 1000000;
   long rounds = 0;
-  double ms_cb = 0.0, ms_lib = 0.0;
   while(true)
   {
     if(rounds >= max_rounds)
@@ -1458,62 +303,56 @@ int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* c
       return -1;
     }
     BHIP(hipMemsetAsync(A.counter, 0, sizeof(int), st));
-    if(timing) BHIP(hipEventRecord(K.ev[0], st));
-    if(F.products())
-      F.fP(A.p_trial, const_cast<double*>(A.P.n2x), const_cast<double*>(A.P.xtJ), const_cast<double*>(A.P.JtJ), A.live, B,
-           (void*)st, cookie);
-    else
-      F.fJ(A.p_trial, const_cast<double*>(A.x), const_cast<double*>(A.J), A.live, B, (void*)st, cookie);
-    if(timing) BHIP(hipEventRecord(K.ev[1], st));
-    if(F.products())   launch_round<FORM_PRODUCTS>(N, st, A);
-    else if(A.bounded) { if(A.robust) launch_round<FORM_J, true, true>(N, st, A); else launch_round<FORM_J, false, true>(N, st, A); }
-    else if(A.robust)  launch_round<FORM_J, true>(N, st, A);
-    else               launch_round<FORM_J>(N, st, A);
+    if(T.mark(who, 0, st)) return -1;
+    invoke_callback(F, A.p_trial, A, A.live, (unsigned int)A.B, st, cookie);
+    if(T.mark(who, 1, st)) return -1;
+    launch_batch_round(st, A);
     BHIP(hipGetLastError());
-    if(timing) BHIP(hipEventRecord(K.ev[2], st));
+    if(T.mark(who, 2, st)) return -1;
     BHIP(hipMemcpyAsync(K.h_counter, A.counter, sizeof(int), hipMemcpyDeviceToHost, st));
     BHIP(hipStreamSynchronize(st));
     rounds++;
-    if(timing)
-    {
-      float a = 0.f, c = 0.f;
-      BHIP(hipEventElapsedTime(&a, K.ev[0], K.ev[1])); BHIP(hipEventElapsedTime(&c, K.ev[1], K.ev[2]));
-      ms_cb += a; ms_lib += c;
-    }
+    if(T.read(who)) return -1;
     if(*K.h_counter == 0) break;
   }
-  t_stats[0] = (double)rounds; t_stats[1] = ms_cb; t_stats[2] = ms_lib;
+  t_stats[0] = (double)rounds; t_stats[1] = T.ms_callback; t_stats[2] = T.ms_library;
   return 0;
 }
 
-// loss, weights: the robust form (weights: [B][NF] or nullptr), or both nullptr.  bounds: the bounded form (host pointers; the
-// bounds that are given are uploaded behind the state), or nullptr
-int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F, void* cookie,
-               const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results,
-               const dogleg_amd_batch_loss_t* loss = nullptr, double* weights = nullptr,
-               const dogleg_amd_batch_bounds_t* bounds = nullptr)
+// Both routes: the initial p into the cache (from the host, or by a copy within the device), the live bytes (the mask of the
+// device route), the start points clamped into the bounds, the rounds.  Then the host route downloads the state and forms the
+// caller's arrays in a loop here; the device route ends in k_batch_finish, which writes them where the caller has them.
+// Everything on the caller's stream if one is given.
+int solve_locked(const DlgBatchSolve& a)
 {
-  const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch" :
-                    bounds ? "dogleg_amd_optimize_dense_batch_bounded" :
-                    loss ? "dogleg_amd_optimize_dense_batch_robust" : "dogleg_amd_optimize_dense_batch";
+  const BatchForm F{a.fJ, a.fP, a.unpacked};
+  const char* who = solve_who(a);
+  const unsigned int B = a.B, N = a.N;
+  const dogleg_amd_batch_bounds_t* bounds = a.bounds;
+  double* const weights = a.loss ? a.weights : nullptr;
   BatchDev A;
-  const int nbounds = bounds ? (bounds->lower ? 1 : 0) + (bounds->upper ? 1 : 0) : 0;
-  if(batch_setup(who, B, N, M, F, prm, loss, A, nbounds)) return -1;
-  hipStream_t st = g_cache.stream;
-  BHIP(hipMemcpyAsync(A.p_trial, p, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_batch_init, dim3((B + 255)/256), dim3(256), 0, st, A, (const unsigned char*)nullptr);
+  if(batch_setup(who, a, F, A)) return -1;
+  hipStream_t st = a.stream ? (hipStream_t)a.stream : g_cache.stream;
+  BHIP(hipMemcpyAsync(A.p_trial, a.p, sizeof(double)*(size_t)B*N, a.device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  launch_batch_init(st, A, a.active);
   BHIP(hipGetLastError());
   if(bounds)
   {
-    // batch_setup left the first array in A.lo and the second in A.hi
     A.bounded = 1;
-    if(bounds->upper && !bounds->lower) { A.hi = A.lo; A.lo = nullptr; }
-    if(A.lo) BHIP(hipMemcpyAsync(const_cast<double*>(A.lo), bounds->lower, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
-    if(A.hi) BHIP(hipMemcpyAsync(const_cast<double*>(A.hi), bounds->upper, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_batch_clamp, dim3((B + 255)/256), dim3(256), 0, st, A);
+    if(a.device) { A.lo = bounds->lower; A.hi = bounds->upper; A.held = bounds->held; }      // the caller's arrays, where they lie
+    if(!a.device && A.lo) BHIP(hipMemcpyAsync(const_cast<double*>(A.lo), bounds->lower, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
+    if(!a.device && A.hi) BHIP(hipMemcpyAsync(const_cast<double*>(A.hi), bounds->upper, sizeof(double)*(size_t)B*N, hipMemcpyHostToDevice, st));
+    launch_batch_clamp(st, A);
     BHIP(hipGetLastError());
   }
-  if(batch_rounds(who, F, A, cookie, st)) return -1;
+  if(batch_rounds(who, F, A, a.cookie, st)) return -1;
+  if(a.device)
+  {
+    launch_batch_finish(st, A, a.p, a.results, a.lambda, weights);
+    BHIP(hipGetLastError());
+    BHIP(hipStreamSynchronize(st));
+    return 0;
+  }
   std::vector<double> sc((size_t)B*SC_COUNT), pb((size_t)B*N);
   std::vector<double> gb(bounds && bounds->held ? (size_t)B*N : 0);
   if(!gb.empty()) BHIP(hipMemcpyAsync(gb.data(), A.g, sizeof(double)*gb.size(), hipMemcpyDeviceToHost, st));
@@ -1527,13 +366,13 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
   BHIP(hipStreamSynchronize(st));
   for(size_t b = 0; b < B; b++)
   {
-    dogleg_amd_batch_result_t& R = results[b];
+    dogleg_amd_batch_result_t& R = a.results[b];
     const int status = sti[b*ST_COUNT + ST_STATUS];
     const bool failed = status == DOGLEG_AMD_BATCH_FAILED;
     R.norm2_x = failed ? -1.0 : sc[b*SC_COUNT + SC_N2X];
     R.trustregion = sc[b*SC_COUNT + SC_TR]; R.lambda = sc[b*SC_COUNT + SC_LAMBDA];
     R.iterations = sti[b*ST_COUNT + ST_ITER]; R.evaluations = sti[b*ST_COUNT + ST_EVAL]; R.status = status;
-    if(!failed) memcpy(p + b*N, pb.data() + b*N, sizeof(double)*N);
+    if(!failed) memcpy(a.p + b*N, pb.data() + b*N, sizeof(double)*N);
     if(weights)
     {
       if(failed) for(size_t f = 0; f < NF; f++) weights[b*NF + f] = std::nan("");
@@ -1547,414 +386,158 @@ int run_locked(double* p, unsigned int B, unsigned int N, unsigned int M, const 
   return 0;
 }
 
-// the device-resident solve: the initial p by a copy within the device, the mask as the initial live bytes, the rounds,
-// then k_batch_finish in place of the three downloads and the host's loop.  Everything on the caller's stream if given.
-int run_device_locked(const DlgBatchDeviceSolve& a)
+// ---- the evaluation calls: the uncertainty and the query calls, each by host arrays or by the caller's device arrays.  One
+// callback and ONE launch at given points.  What the four share is here; a kind says where its arrays lie and what it launches.
+struct EvalCall
 {
-  const BatchForm F{a.fJ, a.fP, a.unpacked};
-  const char* who = F.products() ? "dogleg_amd_optimize_dense_products_batch_device" :
-                    a.bounds ? "dogleg_amd_optimize_dense_batch_bounded_device" :
-                    a.loss ? "dogleg_amd_optimize_dense_batch_robust_device" : "dogleg_amd_optimize_dense_batch_device";
-  const unsigned int B = a.B, N = a.N;
-  BatchDev A;
-  if(batch_setup(who, B, N, a.M, F, a.prm, a.loss, A)) return -1;
-  hipStream_t st = a.stream ? (hipStream_t)a.stream : g_cache.stream;
-  BHIP(hipMemcpyAsync(A.p_trial, a.p, sizeof(double)*(size_t)B*N, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(k_batch_init, dim3((B + 255)/256), dim3(256), 0, st, A, a.active);
-  BHIP(hipGetLastError());
-  if(a.bounds)
-  {
-    // the caller's arrays, where they lie
-    A.bounded = 1; A.lo = a.bounds->lower; A.hi = a.bounds->upper; A.held = a.bounds->held;
-    hipLaunchKernelGGL(k_batch_clamp, dim3((B + 255)/256), dim3(256), 0, st, A);
-    BHIP(hipGetLastError());
-  }
-  if(batch_rounds(who, F, A, a.cookie, st)) return -1;
-  const size_t nw = a.loss && a.weights ? (size_t)B*A.NF : 0, n = (size_t)B*N > nw ? (size_t)B*N : nw;
-  hipLaunchKernelGGL(k_batch_finish, dim3((unsigned int)((n + 255)/256)), dim3(256), 0, st, A, a.p, a.results, a.lambda,
-                     a.loss ? a.weights : nullptr);
-  BHIP(hipGetLastError());
-  BHIP(hipStreamSynchronize(st));
-  return 0;
+  const char* who; BatchForm F; unsigned int B, N, M; void* cookie;
+  const double* p; double* lambda; int* status; const unsigned char* active; void* stream; bool device;
+  // the host route.  stage: the segments of the state buffer and of its page-locked mirror: p first, lambda at o_lam, the status
+  // at o_st and whatever the kind adds, inputs before o_st and outputs behind it, so that up: p .. o_st and down: o_lam .. end
+  // are one copy each; the live bytes lie behind them.  state_d: their doubles, for the refusal
+  Segments stage; size_t o_lam, o_st; double state_d;
+  const DlgBatchQuery* query;  // a query call (for the refusal), or nullptr
+};
+template <class Req> EvalCall eval_call(const char* who, const Req& a)
+{
+  EvalCall c{};
+  c.who = who; c.F = BatchForm{a.fJ, a.fP, a.unpacked}; c.B = a.B; c.N = a.N; c.M = a.M; c.cookie = a.cookie;
+  c.p = a.p; c.lambda = a.lambda; c.status = a.status; c.active = a.active; c.stream = a.stream; c.device = a.device;
+  return c;
 }
-
-int unc_locked(const double* p, unsigned int B, unsigned int N, unsigned int M, const BatchForm& F, void* cookie,
-               double* lambda, double* covariance, double* variances, double* factors, double* scale, int fs, int* status)
+// where an array of a kind lies for the kernel: nowhere if the caller has none, at off of the state buffer d on the host route,
+// where the caller has it on the device route (d == nullptr)
+template <class T> T* placed(char* d, size_t off, T* callers)
 {
-  const char* who = F.products() ? "dogleg_amd_dense_products_batch_uncertainty" : "dogleg_amd_dense_batch_uncertainty";
-  double* const ts = t_unc_stats;              // kernel launches, synchronisations, copies + fills: counted where they happen
-  for(int k = 0; k < 5; k++) ts[k] = 0.0;
-  const unsigned int NF = M/(unsigned int)fs;
-  const double eval_d = F.products() ? (double)B*(1.0 + N + F.S(N)) : (double)B*(double)M*((double)N + 1.0);
-  const double state_d = (double)B*((double)N + 3.0 + (variances ? N : 0.0) + (covariance ? (double)N*N : 0.0) + (factors ? NF : 0.0));
-  if((eval_d + state_d)*8.0 > 1.0e15)
-  {
-    dlg_set_error("%s: %.3g bytes of device memory", who, (eval_d + state_d)*8.0);
-    if(F.products()) BMSG("%s: B = %u problems of %u variables need %.3g bytes of device memory", who, B, N, (eval_d + state_d)*8.0);
-    else             BMSG("%s: B = %u problems of %u x %u need %.3g bytes of device memory", who, B, M, N, (eval_d + state_d)*8.0);
-    return -1;
-  }
-  // (the arithmetic above needs no device: a call that cannot fit is refused before any device work)
-  if(cache_open(who)) return -1;
-  BatchCache& K = g_cache;
-  // device (and staging) layout: p | lambda | scale | status | variances | covariance | factors, then the live bytes;
-  // up: p .. scale, down: lambda .. factors, one copy each
-  const size_t x_bytes = align256(sizeof(double)*(size_t)B*M), J_bytes = align256(sizeof(double)*(size_t)B*M*N);
-  const size_t p_bytes = align256(sizeof(double)*(size_t)B*N), b_bytes = align256(sizeof(double)*(size_t)B);
-  const size_t st_bytes = align256(sizeof(int)*(size_t)B);
-  const size_t var_bytes = variances ? p_bytes : 0, cov_bytes = covariance ? align256(sizeof(double)*(size_t)B*N*N) : 0;
-  const size_t fac_bytes = factors ? align256(sizeof(double)*(size_t)B*NF) : 0;
-  const size_t o_lam = p_bytes, o_scale = o_lam + b_bytes, o_st = o_scale + b_bytes, o_var = o_st + st_bytes;
-  const size_t o_cov = o_var + var_bytes, o_fac = o_cov + cov_bytes, io_bytes = o_fac + fac_bytes;
-  const ProductsLayout PL = products_layout(F, B, N);
-  const size_t eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : x_bytes + J_bytes;
-  const size_t state_bytes = io_bytes + align256(B);
-  if(!cache_ensure(who, B, N, M, eval_bytes, state_bytes) || !stage_ensure(who, B, N, M, io_bytes)) return -1;
-  char* d = (char*)K.d_state; char* h = (char*)K.h_stage;
-  UncDev A;
-  A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = (int)(N*(N + 1)/2); A.fs = fs; A.NF = (int)NF;
-  A.x = (double*)K.d_eval; A.J = (double*)((char*)K.d_eval + x_bytes);
-  A.P = products_dev(F, PL, K.d_eval);
-  double* d_p = (double*)d;
-  A.lam = (double*)(d + o_lam); A.scale = factors ? (double*)(d + o_scale) : nullptr; A.status = (int*)(d + o_st);
-  A.var = variances ? (double*)(d + o_var) : nullptr; A.cov = covariance ? (double*)(d + o_cov) : nullptr;
-  A.fac = factors ? (double*)(d + o_fac) : nullptr;
-  A.active = nullptr;
-  unsigned char* d_live = (unsigned char*)(d + io_bytes);
-
-  memcpy(h, p, sizeof(double)*(size_t)B*N);
-  if(lambda) memcpy(h + o_lam, lambda, sizeof(double)*B); else memset(h + o_lam, 0, sizeof(double)*B);
-  if(factors) memcpy(h + o_scale, scale, sizeof(double)*B);
-
-  const bool timing = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
-  if(timing) for(hipEvent_t& e : K.ev) if(!e) BHIP(hipEventCreate(&e));
-  hipStream_t st = K.stream;
-  BHIP(hipMemcpyAsync(d, h, o_st, hipMemcpyHostToDevice, st)); ts[2] += 1.0;
-  BHIP(hipMemsetAsync(d_live, 1, B, st)); ts[2] += 1.0;
-  if(timing) BHIP(hipEventRecord(K.ev[0], st));
-  if(F.products())
-    F.fP(d_p, const_cast<double*>(A.P.n2x), const_cast<double*>(A.P.xtJ), const_cast<double*>(A.P.JtJ), d_live, B, (void*)st,
-         cookie);
-  else
-    F.fJ(d_p, const_cast<double*>(A.x), const_cast<double*>(A.J), d_live, B, (void*)st, cookie);
-  if(timing) BHIP(hipEventRecord(K.ev[1], st));
-  if(F.products()) launch_uncertainty<FORM_PRODUCTS>(N, st, A);
-  else             launch_uncertainty<FORM_J>(N, st, A);
-  BHIP(hipGetLastError()); ts[0] += 1.0;
-  if(timing) BHIP(hipEventRecord(K.ev[2], st));
-  BHIP(hipMemcpyAsync(h + o_lam, d + o_lam, io_bytes - o_lam, hipMemcpyDeviceToHost, st)); ts[2] += 1.0;
-  BHIP(hipStreamSynchronize(st)); ts[1] += 1.0;
-  double ms_cb = 0.0, ms_lib = 0.0;
-  if(timing)
-  {
-    float a = 0.f, c = 0.f;
-    BHIP(hipEventElapsedTime(&a, K.ev[0], K.ev[1])); BHIP(hipEventElapsedTime(&c, K.ev[1], K.ev[2]));
-    ms_cb = a; ms_lib = c;
-  }
-  if(lambda) memcpy(lambda, h + o_lam, sizeof(double)*B);
-  if(factors) { memcpy(scale, h + o_scale, sizeof(double)*B); memcpy(factors, h + o_fac, sizeof(double)*(size_t)B*NF); }
-  memcpy(status, h + o_st, sizeof(int)*B);
-  if(variances) memcpy(variances, h + o_var, sizeof(double)*(size_t)B*N);
-  if(covariance) memcpy(covariance, h + o_cov, sizeof(double)*(size_t)B*N*N);
-  ts[3] = ms_cb; ts[4] = ms_lib;
-  return 0;
+  return !callers ? nullptr : d ? (T*)(d + off) : callers;
 }
-
-// the device-resident uncertainty call: the kernel reads p, lambda and scale and writes every output where the caller has
-// them.  The cache holds x, J (or the products) and at most two small arrays: the live bytes, all 1, where no mask is given
-// (the mask itself is the callback's live_dev otherwise) and a zeroed lambda where the caller gives none.
-int unc_device_locked(const DlgBatchDeviceUnc& a)
+// U: the kernel's argument (of a query: its front half), its shape filled in.  bind(d): the kind's own pointers into the
+// kernel's argument (placed); gather(h): its inputs into the staging buffer h; launch(st); scatter(h): its outputs from h into the
+// caller's arrays.  gather and scatter: the host route only.  Counted into t_unc_stats where they happen: kernel launches,
+// synchronisations, copies + fills.
+// The device route keeps of the cache x / J (or the products) and at most two small arrays: a zeroed lambda where the caller
+// gives none and the live bytes, all 1, where no mask is given (the mask itself is the callback's live_dev otherwise)
+template <class Bind, class Gather, class Launch, class Scatter>
+int evaluate_at(const EvalCall& c, UncDev& U, Bind bind, Gather gather, Launch launch, Scatter scatter)
 {
-  const BatchForm F{a.fJ, a.fP, a.unpacked};
-  const char* who = F.products() ? "dogleg_amd_dense_products_batch_uncertainty_device" : "dogleg_amd_dense_batch_uncertainty_device";
-  const unsigned int B = a.B, N = a.N, M = a.M;
+  const char* who = c.who;
+  const unsigned int B = c.B, N = c.N, M = c.M;
   double* const ts = t_unc_stats;
   for(int k = 0; k < 5; k++) ts[k] = 0.0;
-  const unsigned int NF = M/(unsigned int)a.fs;
-  const double eval_d = F.products() ? (double)B*(1.0 + N + F.S(N)) : (double)B*(double)M*((double)N + 1.0);
-  if((eval_d + 2.0*B)*8.0 > 1.0e15)
-  {
-    dlg_set_error("%s: %.3g bytes of device memory", who, (eval_d + 2.0*B)*8.0);
-    if(F.products()) BMSG("%s: B = %u problems of %u variables need %.3g bytes of device memory", who, B, N, (eval_d + 2.0*B)*8.0);
-    else             BMSG("%s: B = %u problems of %u x %u need %.3g bytes of device memory", who, B, M, N, (eval_d + 2.0*B)*8.0);
-    return -1;
-  }
+  const EvalBuffer E = eval_buffer(c.F, B, N, M);
+  // (the arithmetic needs no device: a call that cannot fit is refused before any device work)
+  if(!fits(who, c.F, B, N, M, E, c.device ? 2.0*B : c.state_d, c.query)) return -1;
   if(cache_open(who)) return -1;
   BatchCache& K = g_cache;
-  const size_t x_bytes = align256(sizeof(double)*(size_t)B*M), J_bytes = align256(sizeof(double)*(size_t)B*M*N);
-  const size_t b_bytes = align256(sizeof(double)*(size_t)B);
-  const ProductsLayout PL = products_layout(F, B, N);
-  const size_t eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : x_bytes + J_bytes;
-  if(!cache_ensure(who, B, N, M, eval_bytes, b_bytes + align256(B))) return -1;
-  char* d = (char*)K.d_state;
-  UncDev A;
-  A.B = (int)B; A.N = (int)N; A.M = (int)M; A.NP = (int)(N*(N + 1)/2); A.fs = a.fs; A.NF = (int)NF;
-  A.x = (double*)K.d_eval; A.J = (double*)((char*)K.d_eval + x_bytes);
-  A.P = products_dev(F, PL, K.d_eval);
-  A.lam = a.lambda ? a.lambda : (double*)d;
-  A.scale = a.factors ? a.scale : nullptr; A.status = a.status;
-  A.var = a.variances; A.cov = a.covariance; A.fac = a.factors;
-  A.active = a.active;
-  const unsigned char* d_live = a.active ? a.active : (const unsigned char*)(d + b_bytes);
-
-  const bool timing = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
-  if(timing) for(hipEvent_t& e : K.ev) if(!e) BHIP(hipEventCreate(&e));
-  hipStream_t st = a.stream ? (hipStream_t)a.stream : K.stream;
-  if(!a.lambda) { BHIP(hipMemsetAsync(d, 0, sizeof(double)*(size_t)B, st)); ts[2] += 1.0; }
-  if(!a.active) { BHIP(hipMemsetAsync(d + b_bytes, 1, B, st)); ts[2] += 1.0; }
-  if(timing) BHIP(hipEventRecord(K.ev[0], st));
-  if(F.products())
-    F.fP(a.p, const_cast<double*>(A.P.n2x), const_cast<double*>(A.P.xtJ), const_cast<double*>(A.P.JtJ), d_live, B, (void*)st,
-         a.cookie);
+  const size_t b_bytes = align256(sizeof(double)*(size_t)B), io_bytes = c.device ? b_bytes : c.stage.bytes;
+  if(!cache_ensure(who, B, N, M, E.bytes, io_bytes + align256(B)) || (!c.device && !stage_ensure(who, B, N, M, io_bytes))) return -1;
+  char* d = (char*)K.d_state; char* h = (char*)K.h_stage;
+  unsigned char* own_live = (unsigned char*)(d + io_bytes);
+  point_at_eval(U, c.F, E, K.d_eval);
+  bind(c.device ? nullptr : d);
+  U.lam = c.device ? (c.lambda ? c.lambda : (double*)d) : (double*)(d + c.o_lam);
+  U.status = c.device ? c.status : (int*)(d + c.o_st);
+  U.active = c.active;
+  const double* d_p = c.device ? c.p : (const double*)d;
+  const unsigned char* d_live = c.active ? c.active : own_live;
+  BatchTimer T;
+  if(T.start(who)) return -1;
+  hipStream_t st = c.stream ? (hipStream_t)c.stream : K.stream;
+  if(c.device)
+  {
+    if(!c.lambda) { BHIP(hipMemsetAsync(d, 0, sizeof(double)*(size_t)B, st)); ts[2] += 1.0; }
+  }
   else
-    F.fJ(a.p, const_cast<double*>(A.x), const_cast<double*>(A.J), d_live, B, (void*)st, a.cookie);
-  if(timing) BHIP(hipEventRecord(K.ev[1], st));
-  if(F.products()) launch_uncertainty<FORM_PRODUCTS>(N, st, A);
-  else             launch_uncertainty<FORM_J>(N, st, A);
+  {
+    memcpy(h, c.p, sizeof(double)*(size_t)B*N);
+    if(c.lambda) memcpy(h + c.o_lam, c.lambda, sizeof(double)*B); else memset(h + c.o_lam, 0, sizeof(double)*B);
+    gather(h);
+    BHIP(hipMemcpyAsync(d, h, c.o_st, hipMemcpyHostToDevice, st)); ts[2] += 1.0;
+  }
+  if(!c.active) { BHIP(hipMemsetAsync(own_live, 1, B, st)); ts[2] += 1.0; }
+  if(T.mark(who, 0, st)) return -1;
+  invoke_callback(c.F, d_p, U, d_live, B, st, c.cookie);
+  if(T.mark(who, 1, st)) return -1;
+  launch(st);
   BHIP(hipGetLastError()); ts[0] += 1.0;
-  if(timing) BHIP(hipEventRecord(K.ev[2], st));
+  if(T.mark(who, 2, st)) return -1;
+  if(!c.device) { BHIP(hipMemcpyAsync(h + c.o_lam, d + c.o_lam, io_bytes - c.o_lam, hipMemcpyDeviceToHost, st)); ts[2] += 1.0; }
   BHIP(hipStreamSynchronize(st)); ts[1] += 1.0;
-  if(timing)
-  {
-    float ta = 0.f, tc = 0.f;
-    BHIP(hipEventElapsedTime(&ta, K.ev[0], K.ev[1])); BHIP(hipEventElapsedTime(&tc, K.ev[1], K.ev[2]));
-    ts[3] = ta; ts[4] = tc;
-  }
+  if(T.read(who)) return -1;
+  ts[3] = T.ms_callback; ts[4] = T.ms_library;
+  if(c.device) return 0;
+  if(c.lambda) memcpy(c.lambda, h + c.o_lam, sizeof(double)*B);
+  memcpy(c.status, h + c.o_st, sizeof(int)*B);
+  scatter(h);
   return 0;
 }
 
-// ---- the query calls.  What both routes share: the sizes, the cache's x / J (or products) buffer and the kernel's argument
-// but for the pointers of the caller's arrays
-struct QuerySizes { size_t x_bytes, eval_bytes, Jq_bytes, out_bytes; };
-const char* query_who(const DlgBatchQuery& a, bool device)
+// host layout: p | lambda | scale | status | variances | covariance | factors
+int unc_locked(const DlgBatchUnc& a)
 {
-  if(a.fP) return device ? "dogleg_amd_dense_products_batch_query_covariance_device" : "dogleg_amd_dense_products_batch_query_covariance";
-  return device ? "dogleg_amd_dense_batch_query_covariance_device" : "dogleg_amd_dense_batch_query_covariance";
-}
-// refused from the arithmetic alone, before the device is opened (extra_d: doubles of state beside x / J and the callback's output)
-bool query_sizes(const char* who, const DlgBatchQuery& a, const BatchForm& F, double extra_d, QuerySizes& S)
-{
-  const unsigned int B = a.B, N = a.N, M = a.M;
-  const double eval_d = F.products() ? (double)B*(1.0 + N + F.S(N)) : (double)B*(double)M*((double)N + 1.0);
-  const double rows_d = (double)B*(double)a.Nq*(double)a.Qrows;
-  const double need = (eval_d + extra_d)*8.0, Jq_d = rows_d*N*8.0, out_d = rows_d*a.Qrows*8.0;
-  if(need + Jq_d + out_d > 1.0e15)
-  {
-    dlg_set_error("%s: %.3g bytes of device memory", who, need + Jq_d + out_d);
-    BMSG("%s: B = %u problems of %u variables with %u queries of %u rows need %.3g bytes of device memory (%.3g of them for Jq, "
-         "%.3g for out)", who, B, N, a.Nq, a.Qrows, need + Jq_d + out_d, Jq_d, out_d);
-    return false;
-  }
-  const size_t rows = (size_t)B*a.Nq*a.Qrows;
-  const ProductsLayout PL = products_layout(F, B, N);
-  S.x_bytes = align256(sizeof(double)*(size_t)B*M);
-  S.eval_bytes = F.products() ? PL.n2_bytes + PL.g_bytes + PL.G_bytes : S.x_bytes + align256(sizeof(double)*(size_t)B*M*N);
-  S.Jq_bytes = align256(sizeof(double)*rows*N); S.out_bytes = align256(sizeof(double)*rows*a.Qrows);
-  return true;
-}
-QueryDev query_dev(const DlgBatchQuery& a, const BatchForm& F, const QuerySizes& S)
-{
-  BatchCache& K = g_cache;
-  QueryDev A;
-  UncDev& U = A.U;
-  U.B = (int)a.B; U.N = (int)a.N; U.M = (int)a.M; U.NP = (int)(a.N*(a.N + 1)/2); U.fs = 1; U.NF = 0;
-  U.x = (double*)K.d_eval; U.J = (double*)((char*)K.d_eval + S.x_bytes);
-  U.P = products_dev(F, products_layout(F, a.B, a.N), K.d_eval);
-  U.lam = nullptr; U.scale = nullptr; U.cov = nullptr; U.var = nullptr; U.fac = nullptr; U.status = nullptr; U.active = nullptr;
-  A.Jq = nullptr; A.out = nullptr;
-  A.Nq = (int)a.Nq; A.Q = (int)a.Qrows; A.nobs = F.products() ? -1 : a.Nobservations;
-  return A;
-}
-// the callback at d_p with the live bytes d_live, then the ONE launch, on st
-int query_enqueue(const char* who, const BatchForm& F, const QueryDev& A, const double* d_p, const unsigned char* d_live,
-                  void* cookie, hipStream_t st, bool timing)
-{
-  BatchCache& K = g_cache;
-  const UncDev& U = A.U;
-  const unsigned int B = (unsigned int)U.B;
-  if(timing) BHIP(hipEventRecord(K.ev[0], st));
-  if(F.products())
-    F.fP(d_p, const_cast<double*>(U.P.n2x), const_cast<double*>(U.P.xtJ), const_cast<double*>(U.P.JtJ), d_live, B, (void*)st, cookie);
-  else
-    F.fJ(d_p, const_cast<double*>(U.x), const_cast<double*>(U.J), d_live, B, (void*)st, cookie);
-  if(timing) BHIP(hipEventRecord(K.ev[1], st));
-  if(F.products()) launch_query<FORM_PRODUCTS>((unsigned int)U.N, st, A);
-  else             launch_query<FORM_J>((unsigned int)U.N, st, A);
-  BHIP(hipGetLastError()); t_unc_stats[0] += 1.0;
-  if(timing) BHIP(hipEventRecord(K.ev[2], st));
-  return 0;
-}
-int query_times(const char* who)
-{
-  BatchCache& K = g_cache;
-  float ta = 0.f, tc = 0.f;
-  BHIP(hipEventElapsedTime(&ta, K.ev[0], K.ev[1])); BHIP(hipEventElapsedTime(&tc, K.ev[1], K.ev[2]));
-  t_unc_stats[3] = ta; t_unc_stats[4] = tc;
-  return 0;
+  static const char* const names[2][2] = {
+    {"dogleg_amd_dense_batch_uncertainty", "dogleg_amd_dense_batch_uncertainty_device"},
+    {"dogleg_amd_dense_products_batch_uncertainty", "dogleg_amd_dense_products_batch_uncertainty_device"}};
+  EvalCall c = eval_call(names[a.fP ? 1 : 0][a.device ? 1 : 0], a);
+  const unsigned int B = a.B, N = a.N, NF = a.M/(unsigned int)a.fs;
+  const size_t vec_bytes = sizeof(double)*(size_t)B*N, fac_bytes = sizeof(double)*(size_t)B*NF;
+  c.stage.add(vec_bytes);
+  c.o_lam = c.stage.add(sizeof(double)*(size_t)B);
+  const size_t o_scale = c.stage.add(sizeof(double)*(size_t)B);
+  c.o_st = c.stage.add(sizeof(int)*(size_t)B);
+  const size_t o_var = c.stage.add(a.variances ? vec_bytes : 0), o_cov = c.stage.add(a.covariance ? vec_bytes*N : 0);
+  const size_t o_fac = c.stage.add(a.factors ? fac_bytes : 0);
+  c.state_d = (double)B*((double)N + 3.0 + (a.variances ? N : 0.0) + (a.covariance ? (double)N*N : 0.0) + (a.factors ? NF : 0.0));
+  UncDev A;
+  A.B = (int)B; A.N = (int)N; A.M = (int)a.M; A.NP = (int)(N*(N + 1)/2); A.fs = a.fs; A.NF = (int)NF;
+  return evaluate_at(c, A,
+    [&](char* d) {
+      A.scale = a.factors ? placed(d, o_scale, a.scale) : nullptr;
+      A.var = placed(d, o_var, a.variances); A.cov = placed(d, o_cov, a.covariance); A.fac = placed(d, o_fac, a.factors);
+    },
+    [&](char* h) { if(a.factors) memcpy(h + o_scale, a.scale, sizeof(double)*B); },
+    [&](hipStream_t st) { launch_batch_uncertainty(st, A); },
+    [&](const char* h) {
+      if(a.factors) { memcpy(a.scale, h + o_scale, sizeof(double)*B); memcpy(a.factors, h + o_fac, fac_bytes); }
+      if(a.variances) memcpy(a.variances, h + o_var, vec_bytes);
+      if(a.covariance) memcpy(a.covariance, h + o_cov, vec_bytes*N);
+    });
 }
 
-// host pointers.  Device (and staging) layout: p | Jq | lambda | status | out, then the live bytes; up: p .. lambda, down:
-// lambda .. out, one copy each
+// host layout: p | Jq | lambda | status | out
 int query_locked(const DlgBatchQuery& a)
 {
-  const BatchForm F{a.fJ, a.fP, a.unpacked};
-  const char* who = query_who(a, false);
+  static const char* const names[2][2] = {
+    {"dogleg_amd_dense_batch_query_covariance", "dogleg_amd_dense_batch_query_covariance_device"},
+    {"dogleg_amd_dense_products_batch_query_covariance", "dogleg_amd_dense_products_batch_query_covariance_device"}};
+  EvalCall c = eval_call(names[a.fP ? 1 : 0][a.device ? 1 : 0], a);
   const unsigned int B = a.B, N = a.N;
-  double* const ts = t_unc_stats;
-  for(int k = 0; k < 5; k++) ts[k] = 0.0;
-  QuerySizes S;
-  if(!query_sizes(who, a, F, (double)B*((double)N + 3.0), S)) return -1;
-  if(cache_open(who)) return -1;
-  BatchCache& K = g_cache;
-  const size_t p_bytes = align256(sizeof(double)*(size_t)B*N), b_bytes = align256(sizeof(double)*(size_t)B);
-  const size_t st_bytes = align256(sizeof(int)*(size_t)B);
-  const size_t o_Jq = p_bytes, o_lam = o_Jq + S.Jq_bytes, o_st = o_lam + b_bytes, o_out = o_st + st_bytes;
-  const size_t io_bytes = o_out + S.out_bytes;
-  if(!cache_ensure(who, B, N, a.M, S.eval_bytes, io_bytes + align256(B)) || !stage_ensure(who, B, N, a.M, io_bytes)) return -1;
-  char* d = (char*)K.d_state; char* h = (char*)K.h_stage;
-  QueryDev A = query_dev(a, F, S);
-  A.U.lam = (double*)(d + o_lam); A.U.status = (int*)(d + o_st);
-  A.Jq = (const double*)(d + o_Jq); A.out = (double*)(d + o_out);
-  unsigned char* d_live = (unsigned char*)(d + io_bytes);
-  const size_t rows = (size_t)B*a.Nq*a.Qrows;
-
-  memcpy(h, a.p, sizeof(double)*(size_t)B*N);
-  memcpy(h + o_Jq, a.Jq, sizeof(double)*rows*N);
-  if(a.lambda) memcpy(h + o_lam, a.lambda, sizeof(double)*B); else memset(h + o_lam, 0, sizeof(double)*B);
-
-  const bool timing = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
-  if(timing) for(hipEvent_t& e : K.ev) if(!e) BHIP(hipEventCreate(&e));
-  hipStream_t st = K.stream;
-  BHIP(hipMemcpyAsync(d, h, o_st, hipMemcpyHostToDevice, st)); ts[2] += 1.0;
-  BHIP(hipMemsetAsync(d_live, 1, B, st)); ts[2] += 1.0;
-  if(query_enqueue(who, F, A, (const double*)d, d_live, a.cookie, st, timing)) return -1;
-  BHIP(hipMemcpyAsync(h + o_lam, d + o_lam, io_bytes - o_lam, hipMemcpyDeviceToHost, st)); ts[2] += 1.0;
-  BHIP(hipStreamSynchronize(st)); ts[1] += 1.0;
-  if(timing && query_times(who)) return -1;
-  if(a.lambda) memcpy(a.lambda, h + o_lam, sizeof(double)*B);
-  memcpy(a.status, h + o_st, sizeof(int)*B);
-  memcpy(a.out, h + o_out, sizeof(double)*rows*a.Qrows);
-  return 0;
-}
-
-// device pointers: the kernel reads p, lambda and Jq and writes lambda, status and out where the caller has them.  Of the
-// cache: x / J (or the products), the live bytes where no mask is given and a zeroed lambda where the caller gives none
-int query_device_locked(const DlgBatchQuery& a)
-{
-  const BatchForm F{a.fJ, a.fP, a.unpacked};
-  const char* who = query_who(a, true);
-  const unsigned int B = a.B, N = a.N;
-  double* const ts = t_unc_stats;
-  for(int k = 0; k < 5; k++) ts[k] = 0.0;
-  QuerySizes S;
-  if(!query_sizes(who, a, F, 2.0*B, S)) return -1;
-  if(cache_open(who)) return -1;
-  BatchCache& K = g_cache;
-  const size_t b_bytes = align256(sizeof(double)*(size_t)B);
-  if(!cache_ensure(who, B, N, a.M, S.eval_bytes, b_bytes + align256(B))) return -1;
-  char* d = (char*)K.d_state;
-  QueryDev A = query_dev(a, F, S);
-  A.U.lam = a.lambda ? a.lambda : (double*)d;
-  A.U.status = a.status; A.U.active = a.active;
-  A.Jq = a.Jq; A.out = a.out;
-  const unsigned char* d_live = a.active ? a.active : (const unsigned char*)(d + b_bytes);
-
-  const bool timing = getenv("DOGLEG_AMD_BATCH_TIMING") != nullptr;
-  if(timing) for(hipEvent_t& e : K.ev) if(!e) BHIP(hipEventCreate(&e));
-  hipStream_t st = a.stream ? (hipStream_t)a.stream : K.stream;
-  if(!a.lambda) { BHIP(hipMemsetAsync(d, 0, sizeof(double)*(size_t)B, st)); ts[2] += 1.0; }
-  if(!a.active) { BHIP(hipMemsetAsync(d + b_bytes, 1, B, st)); ts[2] += 1.0; }
-  if(query_enqueue(who, F, A, a.p, d_live, a.cookie, st, timing)) return -1;
-  BHIP(hipStreamSynchronize(st)); ts[1] += 1.0;
-  if(timing && query_times(who)) return -1;
-  return 0;
+  const size_t rows = (size_t)B*a.Nq*a.Qrows, Jq_bytes = sizeof(double)*rows*N, out_bytes = sizeof(double)*rows*a.Qrows;
+  c.stage.add(sizeof(double)*(size_t)B*N);
+  const size_t o_Jq = c.stage.add(Jq_bytes);
+  c.o_lam = c.stage.add(sizeof(double)*(size_t)B);
+  c.o_st = c.stage.add(sizeof(int)*(size_t)B);
+  const size_t o_out = c.stage.add(out_bytes);
+  c.state_d = (double)B*((double)N + 3.0);
+  c.query = &a;
+  QueryDev A;
+  UncDev& U = A.U;
+  U.B = (int)B; U.N = (int)N; U.M = (int)a.M; U.NP = (int)(N*(N + 1)/2); U.fs = 1; U.NF = 0;
+  U.scale = nullptr; U.cov = nullptr; U.var = nullptr; U.fac = nullptr;
+  A.Nq = (int)a.Nq; A.Q = (int)a.Qrows; A.nobs = a.fP ? -1 : a.Nobservations;
+  return evaluate_at(c, U,
+    [&](char* d) { A.Jq = placed(d, o_Jq, a.Jq); A.out = placed(d, o_out, a.out); },
+    [&](char* h) { memcpy(h + o_Jq, a.Jq, Jq_bytes); },
+    [&](hipStream_t st) { launch_batch_query(st, A); },
+    [&](const char* h) { memcpy(a.out, h + o_out, out_bytes); });
 }
 
 } // namespace
 
-int dlg_dense_batch_query_run(const DlgBatchQuery& a)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = query_locked(a);
-  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
-  return rc;
-}
-int dlg_dense_batch_query_device_run(const DlgBatchQuery& a)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = query_device_locked(a);
-  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
-  return rc;
-}
+int dlg_dense_batch_solve(const DlgBatchSolve& a) { return locked_call([&] { return solve_locked(a); }); }
+int dlg_dense_batch_uncertainty(const DlgBatchUnc& a) { return locked_call([&] { return unc_locked(a); }); }
+int dlg_dense_batch_query(const DlgBatchQuery& a) { return locked_call([&] { return query_locked(a); }); }
 
-int dlg_dense_batch_run(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f,
-                        void* cookie, const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = run_locked(p, B, N, M, BatchForm{f, nullptr, false}, cookie, prm, results);
-  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
-  return rc;
-}
-int dlg_dense_batch_robust_run(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f,
-                               void* cookie, const dogleg_parameters2_t* prm, const dogleg_amd_batch_loss_t* loss,
-                               dogleg_amd_batch_result_t* results, double* weights)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = run_locked(p, B, N, M, BatchForm{f, nullptr, false}, cookie, prm, results, loss, weights);
-  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
-  return rc;
-}
-int dlg_dense_products_batch_run(double* p, unsigned int B, unsigned int N, dogleg_callback_device_batch_products_t* f,
-                                 void* cookie, const dogleg_parameters2_t* prm, dogleg_amd_batch_result_t* results)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = run_locked(p, B, N, 0, BatchForm{nullptr, f, !prm->JtJ_packed}, cookie, prm, results);
-  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
-  return rc;
-}
-int dlg_dense_batch_uncertainty_run(const double* p, unsigned int B, unsigned int N, unsigned int M,
-                                     dogleg_callback_device_batch_t* f, void* cookie, double* lambda, double* covariance,
-                                     double* variances, double* factors, double* scale, int fs, int* status)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = unc_locked(p, B, N, M, BatchForm{f, nullptr, false}, cookie, lambda, covariance, variances, factors, scale, fs,
-                            status);
-  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
-  return rc;
-}
-int dlg_dense_products_batch_uncertainty_run(const double* p, unsigned int B, unsigned int N,
-                                             dogleg_callback_device_batch_products_t* f, void* cookie, bool unpacked,
-                                             double* lambda, double* covariance, double* variances, int* status)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = unc_locked(p, B, N, 0, BatchForm{nullptr, f, unpacked}, cookie, lambda, covariance, variances, nullptr, nullptr, 1,
-                            status);
-  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
-  return rc;
-}
-int dlg_dense_batch_bounded_run(double* p, unsigned int B, unsigned int N, unsigned int M, dogleg_callback_device_batch_t* f,
-                                void* cookie, const dogleg_parameters2_t* prm, const dogleg_amd_batch_loss_t* loss,
-                                const dogleg_amd_batch_bounds_t* bounds, dogleg_amd_batch_result_t* results, double* weights)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = run_locked(p, B, N, M, BatchForm{f, nullptr, false}, cookie, prm, results, loss, weights, bounds);
-  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
-  return rc;
-}
-int dlg_dense_batch_device_run(const DlgBatchDeviceSolve& a)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = run_device_locked(a);
-  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
-  return rc;
-}
-int dlg_dense_batch_uncertainty_device_run(const DlgBatchDeviceUnc& a)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  const int rc = unc_device_locked(a);
-  if(getenv("DOGLEG_AMD_NO_BACKEND_CACHE")) release_locked();
-  return rc;
-}
 extern "C" int dlg_batch_device_span_ok(const void* ptr, size_t bytes)
 {
   if(!ptr) return 0;

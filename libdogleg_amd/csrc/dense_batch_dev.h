@@ -1,0 +1,76 @@
+// dense_batch_dev.h -- what the host code of the batch solver (dense_batch.hip) and its kernels (dense_batch_kernels.hip)
+// share: the kernels' argument structs, the indices of the per-problem state and the launchers (internal, not installed).
+#pragma once
+#include <hip/hip_runtime.h>
+#include "../../include/dogleg.h"
+
+// per-problem state: sc [B][SC_COUNT] doubles, st [B][ST_COUNT] ints
+enum { SC_N2X, SC_TR, SC_LAMBDA, SC_N2C, SC_N2GN, SC_EI, SC_COUNT = 8 };
+enum { ST_FLAGS, ST_ITER, ST_EVAL, ST_STATUS, ST_COUNT = 4 };
+
+// what a products callback wrote: norm2(x) [B], Jt x [B][N], JtJ [B][S]; unpacked: S = N^2 row-major, of which the
+// entries [i][j], j >= i, are read; otherwise S = NP, row-major packed upper = the kernels' packed lower column-major.
+// All nullptr in the J form: that is how the launchers tell the forms apart
+struct ProductsDev
+{
+  const double* n2x; const double* xtJ; const double* JtJ;
+  int unpacked;
+};
+
+// the loss of a robust solve: c = a^2, fs rows a feature
+struct LossDev { int kind, fs; double a, c; };
+
+struct BatchDev
+{
+  int B, N, M, NP;
+  const double* x; const double* J;
+  double *p_before, *p_trial, *g, *cauchy, *gn, *JtJ, *sc;
+  int* st; unsigned char* live; int* counter;
+  int max_iterations;
+  double trustregion0, dec_factor, dec_thr, inc_factor, inc_thr, jtx_thr, upd_thr, tr_thr;
+  ProductsDev P;               // FORM_PRODUCTS (x, J, M unused there)
+  LossDev L; int NF; double* wts;      // the robust form: NF = M / L.fs features, rho' at the point stepped from [B][NF]
+  int robust;                  // (host side: which kernel is launched)
+  // the bounded form (behind everything above: the other kernels read their arguments where they did): lo, hi [B][N] or nullptr
+  // (no bound on that side), held [B][N] out or nullptr
+  const double *lo, *hi; unsigned char* held;
+  int bounded;                 // (host side: which kernel is launched)
+};
+
+struct UncDev
+{
+  int B, N, M, NP, fs, NF;
+  const double* x; const double* J;
+  double *lam, *scale, *cov, *var, *fac;     // cov, var, fac (and scale with fac): nullptr where not asked for
+  int* status;
+  ProductsDev P;               // FORM_PRODUCTS (x, J, M, fs, NF unused there; fac and scale nullptr: they need J)
+  const unsigned char* active; // [B] or nullptr (all): 0: problem b is skipped, only its status is written
+};
+
+struct QueryDev
+{
+  UncDev U;                    // B, N, M, NP, x, J, P, lam, status, active; cov, var, fac, scale: nullptr
+  const double* Jq;            // [B][Nq][Q][N]
+  double* out;                 // [B][Nq][Q][Q]
+  int Nq, Q, nobs;             // nobs < 0: the plain form
+};
+
+// 0 free, 1 held at lower, 2 held at upper: the held set at a point with the g of that point (held_mask, per element)
+__host__ __device__ inline unsigned char held_code(double p, double g, double lo, double hi)
+{
+  return p == lo && g > 0.0 ? 1 : p == hi && g < 0.0 ? 2 : 0;
+}
+
+// ---- the launchers (dense_batch_kernels.hip): one launch each on st, the instantiation chosen from what the record says (the
+// size class of N, the form, robust, bounded).  The caller asks hipGetLastError
+#pragma GCC visibility push(hidden)
+void launch_batch_round(hipStream_t st, const BatchDev& A);
+void launch_batch_uncertainty(hipStream_t st, const UncDev& A);
+void launch_batch_query(hipStream_t st, const QueryDev& A);
+// active: [B] or nullptr (all): the initial live bytes
+void launch_batch_init(hipStream_t st, const BatchDev& A, const unsigned char* active);
+void launch_batch_clamp(hipStream_t st, const BatchDev& A);
+// the end of a device-resident solve, into the caller's device arrays (lambda, weights: or nullptr)
+void launch_batch_finish(hipStream_t st, const BatchDev& A, double* p, dogleg_amd_batch_result_t* results, double* lambda,
+                         double* weights);
+#pragma GCC visibility pop

@@ -17,7 +17,7 @@ BATCH_TILE = 256                        # doubles of J staged per tile (64 of x 
 
 
 def size_class(N):
-    """NMAX of the k_batch_round / k_batch_uncertainty instantiation that run_locked / unc_locked launch"""
+    """NMAX of the k_batch_round / k_batch_uncertainty instantiation that launch_batch_round / launch_batch_uncertainty pick"""
     return 8 if N <= 8 else 16 if N <= 16 else 24 if N <= 24 else 32
 
 
