@@ -642,6 +642,53 @@ int dogleg_amd_optimize_dense_batch_robust_device(double* p_dev, unsigned int B,
                                                   dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
                                                   double* weights_dev, const unsigned char* active_dev, void* hip_stream);
 
+/* ---- robust loss functions in dogleg_optimize_device2: the sparse (NJnnz > 0) and the dense (NJnnz == 0) device solve
+ * minimise F = sum_f rho(s_f) in place of norm2(x), with the losses, the struct and the first-order treatment written above:
+ * F replaces norm2(x) in the gain ratio and in the return value, g = sum_f w_f J_f^T x_f replaces Jt x and H = sum_f w_f J_f^T J_f
+ * replaces JtJ everywhere else, w_f = rho'(s_f); features are featureSize consecutive measurement rows counted from row 0.
+ * Every argument but loss and weights, the callback's contract, the trust-region loop, the lambda schedule and the ways to stop
+ * are those of dogleg_optimize_device2.
+ *
+ * How: directly behind every invocation of the callback, on the same stream, the library computes s_f from the rows of x (summed
+ * in row order), writes w_f, sums rho(s_f) in a fixed order (no floating-point atomics: F has the same bits on every run) and
+ * multiplies row r of x and of J, in place, by sqrt(w_{r / featureSize}).  Everything behind that -- Jt x, the assembly of JtJ,
+ * the factorisation, both steps, the expected improvement -- is the plain solve's code on the weighted rows; only the gain
+ * ratio, the trace / vnlog records and the return value take F (one 8-byte copy an evaluation) where they took norm2(x).  The
+ * sparse pass finds the row of an entry from THIS call's Jt_colptr, of which the solve keeps a device copy of its own.
+ *   loss        kind DOGLEG_AMD_LOSS_*, scale a > 0 (ignored by TRIVIAL), featureSize 1 .. 4 (<= 1 means 1).
+ *   weights     host, [Nmeas / featureSize], or NULL: rho'(s_f) at the returned p, in (0, 1].
+ * Returns F at the returned p.  A solve that fails returns -1.0 and leaves p and weights untouched.
+ * With DOGLEG_AMD_LOSS_TRIVIAL every weight is exactly 1, x and J keep their bits and the iterates are those of
+ * dogleg_optimize_device2; F is summed in another order than norm2(x), so its last bits may differ.
+ *
+ * A returned context holds the WEIGHTED point:
+ *   beforeStep->norm2_x is F (NOT norm2 of the x it holds);
+ *   beforeStep->x and the device-resident J (dlg_point_download, DLG_VEC_J) are the callback's rows times sqrt(w_f);
+ *   Jt_x is g, and the factor held is that of H + lambda I.
+ * dogleg_getOutliernessFactors, dogleg_amd_covariance_blocks, dogleg_amd_marginal_variances, dogleg_amd_covariance_entries and
+ * dogleg_amd_query_covariance, called on that context, are therefore those of the reweighted problem (JtWJ + lambda I)^-1.
+ *
+ * Refused with a message and -1.0 before any device work, p and weights untouched: everything dogleg_optimize_device2 refuses, a
+ * Jt_colptr that decreases somewhere, a NULL loss, an unknown kind, a scale that is not finite and > 0 (unless TRIVIAL),
+ * featureSize above 4, Nmeas not a multiple of featureSize, and more than one rank, whether by dogleg_amd_set_communicator,
+ * dogleg_amd_set_allreduce or the environment contract.
+ * Device memory beyond the plain solve's: 2 Nmeas / featureSize doubles of weights, Nmeas + 1 ints of pattern (sparse), and
+ * about Nmeas / (256 featureSize) doubles of partial sums.
+ * Not provided: robust solves on several GPUs; a loss for the host-callback entry points (dogleg_optimize2 / _dense2) and for
+ * the products form (it has no per-feature x); per-feature scales (normalise x in the callback); losses that are not concave
+ * in s; Triggs' curvature term. */
+double dogleg_amd_optimize_device2_robust(double* p, unsigned int Nstate, unsigned int Nmeas, unsigned int NJnnz,
+                                          const int* Jt_colptr, const int* Jt_rowidx,
+                                          dogleg_callback_device_t* f, void* cookie,
+                                          const dogleg_amd_batch_loss_t* loss,
+                                          double* weights,      /* host, [Nmeas / featureSize], or NULL */
+                                          const dogleg_parameters2_t* parameters,
+                                          dogleg_solverContext_t** returnContext);
+/* measurement: the calling thread's last robust device solve: out[0] = evaluations the prelude ran behind, out[1] = kernel
+ * launches of the prelude per evaluation, and, if DOGLEG_AMD_TIMING=1 was set for the solve (two events an evaluation on the
+ * stream), out[2] = ms in the prelude's kernels over the solve.  Returns the number of entries written (at most n, at most 3). */
+int dogleg_amd_robust_last_stats(double* out, int n);
+
 /* ---- box bounds in the batch solve: every problem minimises norm2(x) (or, with a loss, F) subject to lower[b] <= p[b] <=
  * upper[b], by an active-set dog-leg loop: variables on a bound whose gradient pushes outwards are held, the two steps are
  * those of the free variables, the step chosen is clipped into the box, and a clipped step that the model does not like

@@ -74,6 +74,7 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_dense_batch_query_covariance_device", "dogleg_amd_dense_products_batch_query_covariance_device",
     "dogleg_amd_jacobian_colouring", "dogleg_amd_check_jacobian_device", "dogleg_amd_check_jacobian_device_batch",
     "dogleg_amd_testGradient_device", "dogleg_amd_check_jacobian_last_stats",
+    "dogleg_amd_optimize_device2_robust", "dogleg_amd_robust_last_stats",
 ]
 
 _lib = None
@@ -265,6 +266,10 @@ def lib():
         L.dogleg_amd_testGradient_device.argtypes = [C.c_uint, D, C.c_uint, C.c_uint, C.c_uint, I, I, V, V]
         L.dogleg_amd_testGradient_device.restype = None
         L.dogleg_amd_check_jacobian_last_stats.argtypes = [D, C.c_int]
+    if hasattr(L, "dogleg_amd_optimize_device2_robust"):
+        L.dogleg_amd_optimize_device2_robust.restype = C.c_double
+        L.dogleg_amd_optimize_device2_robust.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, I, I, V, V, C.POINTER(BatchLoss), D, PP, V]
+        L.dogleg_amd_robust_last_stats.argtypes = [D, C.c_int]
     L.dogleg_amd_last_solve_timing.argtypes = [D, I]
     L.dlg_point_gather_device.argtypes = [V, C.c_int, V, V, I]
     L.dogleg_setMaxIterations.argtypes = [C.c_int]
@@ -327,6 +332,38 @@ def optimize_device(p0, N, M, nnz, Jp, Ji, cb, cookie, params=None, capacity=256
     finally:
         L.dlg_set_trace(None)
     return r, p, tr
+
+
+def optimize_device_robust(p0, N, M, nnz, Jp, Ji, cb, cookie, loss, params=None, capacity=256, trace=True, want_weights=True,
+                           ctx=None):
+    """dogleg_amd_optimize_device2_robust: the arguments of optimize_device with loss a BatchLoss (None: NULL).  Returns what
+    optimize_device returns and the weights: (F, p_final, TraceBuffer, weights (M // max(featureSize, 1),) prefilled with -1, or
+    None if not asked for).  ctx: a ctypes.c_void_p that receives the returnContext (release it with dogleg_freeContext)."""
+    L = lib()
+    p = np.array(p0, dtype=np.float64, copy=True)
+    tr = TraceBuffer(N, capacity) if trace else None
+    fs = max(loss.featureSize, 1) if loss is not None else 1
+    w = np.full(M // fs, -1.0) if want_weights else None
+    if nnz > 0:
+        Jp = np.ascontiguousarray(Jp, dtype=np.int32)
+        Ji = np.ascontiguousarray(Ji, dtype=np.int32)
+    L.dlg_set_trace(C.cast(tr.byref(), C.c_void_p) if trace else None)
+    try:
+        r = L.dogleg_amd_optimize_device2_robust(dptr(p), N, M, nnz, iptr(Jp) if nnz > 0 else None, iptr(Ji) if nnz > 0 else None,
+                                                 cb, cookie, C.byref(loss) if loss is not None else None,
+                                                 dptr(w) if w is not None else None,
+                                                 C.byref(params) if params is not None else None,
+                                                 C.byref(ctx) if ctx is not None else None)
+    finally:
+        L.dlg_set_trace(None)
+    return r, p, tr, w
+
+
+def robust_last_stats():
+    """dogleg_amd_robust_last_stats as a dict: evaluations, launches per evaluation, ms in the prelude (DOGLEG_AMD_TIMING=1)"""
+    out = np.zeros(3)
+    n = lib().dogleg_amd_robust_last_stats(dptr(out), 3)
+    return dict(zip(("evaluations", "launches_per_evaluation", "prelude_ms"), out[:n]))
 
 
 def optimize_dense_batch(p0s, N, M, cb, cookie, params=None):

@@ -251,10 +251,13 @@ DevicePoint device_point(Driver* d, int s)
   return { (const double*)dlg_point_device_ptr(d->be, s, DLG_VEC_P), (double*)dlg_point_device_ptr(d->be, s, DLG_VEC_X_OWN),
            (double*)dlg_point_device_ptr(d->be, s, DLG_VEC_J_OWN) };
 }
-void device_callback(Driver* d, const double* p, double* x, double* J)
+// (a solve with a loss: the prelude -- weights, F, x and J times sqrt(w) -- goes onto the stream directly behind the callback's
+// kernels, in front of whatever reads x and J of slot s; robust_prelude.hip)
+void device_callback(Driver* d, int s, const double* p, double* x, double* J)
 {
   Tick tk(d, TM_CALLBACK);
   (*d->f_device)(p, x, J, dlg_backend_get_stream(d->be), d->pub.cookie);
+  if(d->robust) robust_enqueue(d, s, x, J);
 }
 // the backend takes the slot's own buffers as they are (dense on a rank: its rows, a contiguous slice of them)
 bool bind_and_evaluate(Driver* d, int s, const DevicePoint& v, double* norm2x, double* absmax, int* rc_eval)
@@ -274,7 +277,7 @@ bool feed_device_rank_rows(Driver* d, int s, const DevicePoint& v)
     d->J_full_dev = (double*)dlg_mem_alloc(sizeof(double)*(size_t)d->nnz);
     if(!d->x_full_dev || !d->J_full_dev) { MSG("out of device memory"); return false; }
   }
-  device_callback(d, v.p, d->x_full_dev, d->J_full_dev);
+  device_callback(d, s, v.p, d->x_full_dev, d->J_full_dev);
   Tick tu(d, TM_UPLOAD);
   return be_ok(dlg_point_gather_device(d->be, s, d->x_full_dev, d->J_full_dev, d->dev_cp), "gather of the rank's rows");
 }
@@ -292,7 +295,7 @@ bool eval_device(Driver* d, int s, double* norm2x, double* absmax, int* rc_eval)
   // that was made again behind it moved the point: then it runs again)
   const bool early_cb = d->early_slot == s && !dlg_backend_between_redone(d->be);
   d->early_slot = -1;
-  if(!early_cb) device_callback(d, v.p, v.x, v.J);
+  if(!early_cb) device_callback(d, s, v.p, v.x, v.J);
   if(!bind_and_evaluate(d, s, v, norm2x, absmax, rc_eval)) return false;
   if(d->pat_check && !finish_pattern_check(d))
   {
@@ -366,6 +369,8 @@ bool eval_point(bool* converged, dogleg_operatingPoint_t* pt, Driver* d)
   pt->have_Jtx = true;
   if(products) pt->have_JtJ = true;                 // (norm2_x is the callback's)
   else { pt->norm2_x = norm2x; pt->have_x = pt->have_J = true; }
+  // (a loss: the backend summed the squares of the weighted x; the gain ratio, the records and the return value take F)
+  if(d->robust && !robust_F(d, s, &pt->norm2_x)) return false;
   // dogleg.c:1073-1082: converged unless some |Jt_x[i]| exceeds the threshold
   *converged = !(absmax > ctx->parameters->Jt_x_threshold);
   if(*converged) VERBOSE(d, "gradient below threshold everywhere: done");
@@ -476,7 +481,7 @@ void driver_between(void* c)
   Driver* d = a->d;
   const int s = a->slot;
   const DevicePoint v = device_point(d, s);
-  device_callback(d, v.p, v.x, v.J);
+  device_callback(d, s, v.p, v.x, v.J);
   d->early_slot = s;
   if(d->pub.solve_type == DOGLEG_SPARSE)
   {
@@ -720,6 +725,7 @@ void destroy(Driver* d)
   if(!d) return;
   if(d->pat_check) { (void)d->pat_check->get(); delete d->pat_check; d->pat_check = nullptr; }      // (it reads the backend's pattern)
   free_point(d, 0); free_point(d, 1);
+  robust_destroy(d);
   if(d->pub.solve_type != DOGLEG_SPARSE) free(d->pub.factorization_dense);
   if(d->x_full_dev) dlg_mem_free(d->x_full_dev);
   if(d->J_full_dev) dlg_mem_free(d->J_full_dev);
@@ -826,13 +832,14 @@ bool set_up(Driver* d, const Callbacks& cb, const double* p, Laps& lap)
   Comm cm;
   if(!solve_communicator(&cm) || !obtain_backend(d, cm, lap) || !attach_communicator(d, cm)) return false;
   if(d->sharded) lap("communicator");
+  if(d->robust && !robust_set_up(d)) return false;
   if(!allocate_points(d, p)) return false;
   lap("operating points (pinned host)");
   memcpy(ctx->beforeStep->p, p, sizeof(double)*(size_t)ctx->Nstate);
   return be_ok(dlg_point_set_p(d->be, 0, ctx->beforeStep->p), "upload of p");
 }
 
-bool run(Driver* d, double* p, Laps& lap)
+bool run(Driver* d, double* p, double* weights, Laps& lap)
 {
   dogleg_solverContext_t* ctx = &d->pub;
   trace_begin(ctx->Nstate);
@@ -842,6 +849,7 @@ bool run(Driver* d, double* p, Laps& lap)
   lap("run_optimizer (incl. symbolic phase)");
   trace_end(d);
   if(numsteps < 0) { MSG("the solve failed"); d->failed = true; return false; }
+  if(d->robust && !robust_weights(d, slot_of(d, ctx->beforeStep), weights)) { d->failed = true; return false; }
   memcpy(p, ctx->beforeStep->p, sizeof(double)*(size_t)ctx->Nstate);        // dogleg.c:1745
   VERBOSE(d, "success: %d iterations", numsteps);
   return true;
@@ -860,10 +868,12 @@ bool hand_back(Driver* d)
 
 // dogleg.c:1633-1753
 double optimize(double* p, unsigned int Nstate, unsigned int Nmeas, unsigned int NJnnz, const Callbacks& cb, void* cookie,
-                const dogleg_parameters2_t* parameters, dogleg_solverContext_t** returnContext)
+                const dogleg_parameters2_t* parameters, dogleg_solverContext_t** returnContext,
+                const dogleg_amd_batch_loss_t* loss = nullptr, double* weights = nullptr)
 {
   Driver* d = (Driver*)calloc(1, sizeof(Driver));
   if(!d) { MSG("out of memory"); return -1.0; }
+  if(loss && !(d->robust = robust_create(loss))) { MSG("out of memory"); free(d); return -1.0; }
   d->early_slot = -1; d->no_between = getenv("DOGLEG_AMD_NO_BETWEEN") != nullptr;
   dogleg_solverContext_t* ctx = &d->pub;
   ctx->cookie = cookie;
@@ -876,7 +886,7 @@ double optimize(double* p, unsigned int Nstate, unsigned int Nmeas, unsigned int
   d->check_pattern = chk && chk[0] == '1';
 
   Laps lap{getenv("DOGLEG_AMD_TIMING") != nullptr, {}};
-  const bool ok = set_up(d, cb, p, lap) && run(d, p, lap) && (!returnContext || hand_back(d));
+  const bool ok = set_up(d, cb, p, lap) && run(d, p, weights, lap) && (!returnContext || hand_back(d));
   const double norm2_x = ok ? ctx->beforeStep->norm2_x : -1.0;
   if(ok && returnContext) *returnContext = ctx;
   else destroy(d);                                     // the one exit of every failure, and of a solve whose context nobody wants
@@ -949,6 +959,20 @@ double dogleg_optimize_device2(double* p, unsigned int Nstate, unsigned int Nmea
 {
   if(!f) { MSG("dogleg_optimize_device2 needs a device callback"); return -1.0; }
   return optimize(p, Nstate, Nmeas, NJnnz, Callbacks{nullptr, nullptr, nullptr, f, Jt_colptr, Jt_rowidx}, cookie, parameters, returnContext);
+}
+// dogleg.h, "robust loss functions in dogleg_optimize_device2": refused here, before any device work, is what needs no device
+double dogleg_amd_optimize_device2_robust(double* p, unsigned int Nstate, unsigned int Nmeas, unsigned int NJnnz,
+                                          const int* Jt_colptr, const int* Jt_rowidx,
+                                          dogleg_callback_device_t* f, void* cookie,
+                                          const dogleg_amd_batch_loss_t* loss, double* weights,
+                                          const dogleg_parameters2_t* parameters,
+                                          dogleg_solverContext_t** returnContext)
+{
+  if(!f) { MSG("dogleg_amd_optimize_device2_robust needs a device callback"); return -1.0; }
+  if(!p || Nstate == 0) { MSG("dogleg_amd_optimize_device2_robust: a NULL p or no variables"); return -1.0; }
+  if(!robust_loss_ok(loss, Nmeas, NJnnz, Jt_colptr) || !one_rank_only("dogleg_amd_optimize_device2_robust")) return -1.0;
+  return optimize(p, Nstate, Nmeas, NJnnz, Callbacks{nullptr, nullptr, nullptr, f, Jt_colptr, Jt_rowidx}, cookie, parameters, returnContext,
+                  loss, weights);
 }
 double dogleg_optimize_dense_products(double* p, unsigned int Nstate,
                                       dogleg_callback_dense_products_t* f, void* cookie,

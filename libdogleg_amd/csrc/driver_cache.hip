@@ -103,4 +103,5 @@ extern "C" void dogleg_amd_release_cache(void)
   if(be) dlg_backend_destroy(be);
   for(const PinnedBuf& b : pool) (void)hipHostFree(b.p);
   dlg_dense_batch_release();
+  robust_release_cache();
 }

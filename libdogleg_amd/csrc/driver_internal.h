@@ -6,6 +6,7 @@
 //   driver_records.cpp  vnlog and trace records, the timing report
 //   api_extensions.hip  entry points that check their arguments and forward (outliers, covariance, batch, gradcheck)
 //   id_file.cpp         the id-file rendezvous of the environment contract
+//   robust_prelude.hip  a loss on a device solve: weights, F = sum rho and the sqrt(w) scaling of x and J behind the callback
 // Everything declared here is hidden: the library exports dogleg.h, dlg_backend.h and dlg_trace.h, nothing of this.
 #pragma once
 #include <cstdio>
@@ -32,6 +33,8 @@ struct Comm
   dlg_allreduce_fn fn = nullptr; void* cookie = nullptr;
   bool set = false;
 };
+
+struct Robust;                                 // robust_prelude.hip
 
 enum { TM_PATTERN, TM_CALLBACK, TM_UPLOAD, TM_EVAL, TM_STEP, TM_TRACE, TM_COUNT };
 
@@ -72,6 +75,7 @@ struct Driver
   // device-side evaluation (dogleg_optimize_device2): the model runs on the GPU, x / J never cross PCIe
   dogleg_callback_device_t* f_device;
   const int *dev_cp, *dev_ri;                  // the caller's pattern (host), valid during the call
+  Robust* robust;                              // dogleg_amd_optimize_device2_robust: the loss and its device arrays; NULL: least squares, nothing of it runs
   // DOGLEG_AMD_TIMING=1: where the wall time of run_optimizer goes (host clock around the driver's own calls)
   bool timing;
   double tm_ms[8]; int tm_n[8];
@@ -120,5 +124,19 @@ void trace_begin(int Nstate);
 void trace_end(const Driver* d);
 // DOGLEG_AMD_TIMING: run_optimizer's wall time by TM_* on stderr, kept for dogleg_amd_last_solve_timing
 void timing_report(const Driver* d, double run_ms);
+
+// ---- robust_prelude.hip: a loss on a device solve.  One rank, device callback only.
+// the checks of the entry point that need no device; false: a message was printed
+bool robust_loss_ok(const dogleg_amd_batch_loss_t* loss, unsigned int Nmeas, unsigned int NJnnz, const int* Jt_colptr);
+// the record of a solve (host only; the device arrays come with robust_set_up, behind the backend)
+Robust* robust_create(const dogleg_amd_batch_loss_t* loss);
+bool robust_set_up(Driver* d);
+// behind the callback that wrote x and J of slot s, on the backend's stream: weights, F, x and J times sqrt(w)
+void robust_enqueue(Driver* d, int s, double* x, double* J);
+// F of the last prelude of slot s, once the host has it (waits for the 8-byte copy behind that prelude)
+bool robust_F(Driver* d, int s, double* F);
+bool robust_weights(Driver* d, int s, double* weights_host);
+void robust_destroy(Driver* d);
+void robust_release_cache();                   // dogleg_amd_release_cache: the device block kept between robust solves
 
 #pragma GCC visibility pop
