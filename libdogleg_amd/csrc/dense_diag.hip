@@ -710,8 +710,7 @@ __global__ void __launch_bounds__(TPB) k_trsv_tiles(const double* __restrict__ A
 } // namespace
 
 // the dynamic-LDS limit of a kernel, set once per device (a failure is left for the launch to report)
-constexpr int DLG_MAX_DEV = 64;
-static void dlg_func_lds_once(bool (&done)[DLG_MAX_DEV], const void* fn, int bytes)
+void dlg_func_lds_once(bool (&done)[DLG_MAX_DEV], const void* fn, int bytes)
 {
   int dev = 0;
   if(hipGetDevice(&dev) != hipSuccess) return;

@@ -370,6 +370,10 @@ void dense_launch_trsv_tiles(hipStream_t st, const double* A, int lda, int n, co
 void dense_trsv_arm(hipStream_t st, double* Yh, double* Xh, size_t n_each);
 void dense_launch_potrf_diag_trsm(hipStream_t st, double* A, int lda, int kb, int nb, int n, int* info_dev, double* Linv,
                                   int* flag, int epoch, const DlgHandoff& ho);
+// dense_diag.hip: the dynamic-LDS limit of a kernel, set once per device -- a function attribute is a property of
+// (function, device); `done`: one array per kernel (per instantiation of a template)
+constexpr int DLG_MAX_DEV = 64;
+void dlg_func_lds_once(bool (&done)[DLG_MAX_DEV], const void* fn, int bytes);
 void dense_destroy(dlg_backend* b);
 int dense_eval(dlg_backend* b, int slot);                       // K1
 int dense_norm2_Jv(dlg_backend* b, int slot, const double* v, double* out_dev, StepLaunch& L); // K3/K8

@@ -771,13 +771,8 @@ int launch_syrk(hipStream_t st, double* C, int ldc, const double* A, int lda, in
   const int T = dlg_cdiv(n, BT);
   const int ntiles = T*(T+1)/2;
   const size_t lds = (size_t)4*KC*(BT + 16)*sizeof(double);
-  static bool attr_set = false;            // per instantiation
-  if(!attr_set)
-  {
-    DLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_syrk_lower<WT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  static bool attr[DLG_MAX_DEV] = {};       // per instantiation: a function attribute is a property of (function, device)
+  dlg_func_lds_once(attr, reinterpret_cast<const void*>(&k_syrk_lower<WT>), (int)lds);
   if(!overwrite)
   {
     const int kper = dlg_cdiv(K, KC)*KC;

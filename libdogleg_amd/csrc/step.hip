@@ -470,6 +470,9 @@ extern "C" int dlg_factorize(dlg_backend_t* b, int s, double lambda, int* ok)
   DLG_CHECK(dlg_step_unprepare(b));
   DlgSlot& S = b->slot[s];
   if(!S.have_inputs) { dlg_set_error("dlg_factorize: slot %d has no J/JtJ", s); return DLG_ERR_STATE; }
+  // (a Gauss-Newton step this slot still holds came from another factor -- another lambda, perhaps: dlg_solve_gn and
+  // dlg_gauss_newton would hand it out again as the cached one)
+  S.have_gn = false; S.ident_ok = false;
   int good = 0;
   switch(b->type)
   {
