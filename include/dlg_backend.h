@@ -106,7 +106,8 @@ int  dlg_point_gather_device(dlg_backend_t* b, int slot, const double* x_full_de
                              const int* colptr_host);
 /* stats[] = {cut level, supernodes above the cut, supernodes of this rank, rows of this rank,
  * doubles summed per factorisation (panels above the cut + update matrices crossing it),
- * doubles of the whole panel buffer, non-zeros of this rank} */
+ * doubles of the whole panel buffer, non-zeros of this rank,
+ * 64-bit FNV-1a hash over every field of the symbolic analysis as it stands} */
 int  dlg_partition_stats(dlg_backend_t* b, long* stats, int nstats);
 /* host-only (no GPU): the partition of a pattern over nranks ranks as rank `rank` sees it.
  * row_owner[M] (may be NULL) receives 1 for the rows of this rank, 0 otherwise; stats as above */
@@ -177,8 +178,9 @@ int  dlg_sparse_leaf_rows_stats(dlg_backend_t* b, long* stats, int nstats);
 /* host-only symbolic phase on a pattern (no GPU): stats[] = {var-blocks,
  * supernodes, levels, nnz(tril JtJ), nnz(L), panel doubles, factor flops, max
  * panel, assembly tasks, update items, relpos entries, output blocks,
- * contributions, update sub-tasks, solve scratch, Jt*x tasks}; perm_out[N] may
- * be NULL */
+ * contributions, update sub-tasks, solve scratch, Jt*x tasks, MFMA assembly
+ * tasks, k-groups, shapes, 64-bit FNV-1a hash over every field of the analysis};
+ * perm_out[N] may be NULL */
 int  dlg_sparse_symbolic_probe(int N, int M, const int* colptr, const int* rowidx, int row0,
                                int row1, long* stats, int nstats, int* perm_out);
 

@@ -676,7 +676,7 @@ def check_jacobian_last_stats():
 SYM_STAT_NAMES = ["var_blocks", "supernodes", "levels", "nnz_JtJ_lower", "nnz_L", "panel_doubles",
                   "factor_flops", "max_panel", "asm_tasks", "update_items", "relpos", "out_blocks",
                   "contribs", "update_subtasks", "solve_scratch", "jtx_tasks", "asm_mfma_tasks",
-                  "asm_kgroups", "asm_shapes"]
+                  "asm_kgroups", "asm_shapes", "sym_hash"]
 
 
 def covariance_plan_probe(N, M, Jp, Ji, r0, nr, c0, nc):
@@ -728,12 +728,12 @@ def symbolic_probe(N, M, Jp, Ji, row0=0, row1=None, want_perm=False):
     _ck(L.dlg_sparse_symbolic_probe(N, M, iptr(Jp), iptr(Ji), row0, M if row1 is None else row1,
                                     st, len(SYM_STAT_NAMES), iptr(perm) if want_perm else None),
         "symbolic probe")
-    d = {k: st[i] for i, k in enumerate(SYM_STAT_NAMES)}
+    d = {k: (st[i] & (2**64 - 1) if k.endswith("_hash") else st[i]) for i, k in enumerate(SYM_STAT_NAMES)}
     return (d, perm) if want_perm else d
 
 
 PART_STAT_NAMES = ["cut_level", "supernodes_above_cut", "supernodes_mine", "rows_mine", "reduced_doubles",
-                   "panel_doubles", "nnz_mine"]
+                   "panel_doubles", "nnz_mine", "sym_hash"]
 
 
 def partition_probe(N, M, Jp, Ji, rank, nranks):
@@ -746,7 +746,7 @@ def partition_probe(N, M, Jp, Ji, rank, nranks):
     own = np.zeros(M, dtype=np.uint8)
     _ck(L.dlg_sparse_partition_probe(N, M, iptr(Jp), iptr(Ji), rank, nranks, st, len(PART_STAT_NAMES),
                                      own.ctypes.data_as(C.c_char_p)), "partition probe")
-    return {k: st[i] for i, k in enumerate(PART_STAT_NAMES)}, own.astype(bool)
+    return {k: (st[i] & (2**64 - 1) if k.endswith("_hash") else st[i]) for i, k in enumerate(PART_STAT_NAMES)}, own.astype(bool)
 
 
 REGION_STAT_NAMES = ["level0", "supernodes", "workgroups", "lds_bytes", "sliced_workgroups", "hbm_update_matrices",

@@ -487,7 +487,7 @@ static void partition_stats(const SymHost& H, long* stats, int nstats)
     }
   }
   long nnz_loc = 0;
-  const long v[] = { (long)H.cut_level, ntop, nmine, (long)H.part_rows.size(), red, (long)H.lx_size, nnz_loc };
+  const long v[] = { (long)H.cut_level, ntop, nmine, (long)H.part_rows.size(), red, (long)H.lx_size, nnz_loc, (long)sym_hash(H) };
   for(int i = 0; i < nstats && i < (int)(sizeof(v)/sizeof(v[0])); i++) stats[i] = v[i];
 }
 extern "C" int dlg_partition_stats(dlg_backend_t* b, long* stats, int nstats)
@@ -700,7 +700,7 @@ extern "C" int dlg_sparse_symbolic_probe(int N, int M, const int* colptr, const 
                      (long)H.ui_t.size(), (long)H.relpos.size(), (long)H.oblk.size(),
                      (long)H.contrib.size(), (long)H.usub.size(), (long)H.scr_size,
                      (long)H.jtx_task.size(), (long)H.asm_mtask.size(), (long)H.asm_kg.size(),
-                     (long)H.asm_shape.size() };
+                     (long)H.asm_shape.size(), (long)sym_hash(H) };
   if(getenv("DOGLEG_AMD_SYM_DEBUG"))
     for(int l = 0; l + 1 < (int)H.uw_lvl_ptr.size(); l++)
     {

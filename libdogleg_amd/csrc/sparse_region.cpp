@@ -1,5 +1,6 @@
 // sparse_region.cpp -- see sparse_region.h.  Pure host code (no HIP).
 #include "sparse_region.h"
+#include "fnv.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -70,13 +71,6 @@ int write_children(const SymHost& H, const FwItem& it, long jA, long jB, long dr
   }
   return ch0_new;
 }
-
-struct Fnv
-{
-  uint64_t h = 1469598103934665603ull;
-  template <class... T> void add(T... x)
-  { for(int64_t v : {(int64_t)x...}) for(int k = 0; k < 8; k++) { h ^= ((uint64_t)v >> (8*k)) & 0xff; h *= 1099511628211ull; } }
-};
 
 } // namespace
 

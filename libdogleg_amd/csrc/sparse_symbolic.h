@@ -60,7 +60,7 @@ struct SymSub
 };
 static_assert(sizeof(SymSub) == 24, "SymSub layout");
 
-// ---- JtJ assembly schedule (column-block centric, see sparse_symbolic.cpp 9b)
+// ---- JtJ assembly schedule (column-block centric, see sparse_symbolic_asm.cpp)
 struct AsmRho                // one row-block inside a task
 {
   int32_t  base;             // first value of the row-block in the (rank-local) value array
@@ -308,3 +308,5 @@ struct SymHost
 // row0 / row1 are ignored.
 int sym_analyze(SymHost& S, int N, int M, const int* colptr, const int* rowidx, int row0, int row1,
                 char* err, int errlen, int part_rank = 0, int part_nranks = 1);
+// 64-bit FNV-1a over every field of S, records field by field (sparse_symbolic_hash.cpp): what pins the analysis bit for bit
+uint64_t sym_hash(const SymHost& S);

@@ -1,5 +1,5 @@
 // region_plan_main.cpp -- the factorisation's host-only planner as a stand-alone program, so that it can be built
-// with -fsanitize=address,undefined (tests/test_library_cpu.py).  Links sparse_symbolic.cpp and sparse_region.cpp
+// with -fsanitize=address,undefined (tests/test_library_cpu.py).  Links the sparse_symbolic*.cpp files and sparse_region.cpp
 // only: no HIP, no GPU.
 //   region_plan_main PATTERN NCU
 // PATTERN: int32 words N, M, colptr[M+1], rowidx[colptr[M]] (the pattern of Jt, CSC).  The knobs come from the

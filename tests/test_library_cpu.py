@@ -2,6 +2,7 @@
 declared symbol, struct layouts, the symbolic phase, error behaviour without a GPU,
 and the row-sharding arithmetic under a 2-rank gloo group."""
 import ctypes as C
+import functools
 import os
 import re
 import subprocess
@@ -10,7 +11,7 @@ import pytest
 
 from libdogleg_amd import capi
 from libdogleg_amd.ctypes_defs import Parameters2, dptr, iptr
-from tests import oracle_api as oa
+from tests import factor_user_zoo as zoo, oracle_api as oa, sparse_patterns
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -456,14 +457,14 @@ def test_one_launch_region_schedule_is_pinned(monkeypatch):
     assert sliced > 0 and hbm > 0 and hbm_replicas > 0
 
 
-def _sanitizing_compiler(tmp):
-    """the first of g++ / clang++ / ROCm's clang++ that links and runs a sanitized program"""
+def _sanitizing_compiler(tmp, flags=None):
+    """the first of g++ / clang++ / ROCm's clang++ that links and runs a program sanitized with `flags` (_SAN_FLAGS)"""
     from libdogleg_amd import build as B
     hello = tmp / "hello.cpp"
     hello.write_text("#include <vector>\nint main(){std::vector<int> v(3); return v[2];}\n")
     for cc in ("g++", "clang++", os.path.join(os.path.dirname(B.HIPCC), "amdclang++")):
         try:
-            subprocess.run([cc] + _SAN_FLAGS + [str(hello), "-o", str(tmp / "hello")], check=True, capture_output=True)
+            subprocess.run([cc] + (flags or _SAN_FLAGS) + [str(hello), "-o", str(tmp / "hello")], check=True, capture_output=True)
             subprocess.run([str(tmp / "hello")], check=True, capture_output=True)
             return cc
         except (OSError, subprocess.CalledProcessError):
@@ -472,6 +473,20 @@ def _sanitizing_compiler(tmp):
 
 
 _SAN_FLAGS = ["-std=c++17", "-O0", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread"]
+_TSAN_FLAGS = ["-std=c++17", "-O1", "-fsanitize=thread", "-pthread"]
+
+
+def _symbolic_objects(cc, flags, tmp):
+    """(csrc, the host sources of the symbolic phase compiled with `flags` into tmp): what a stand-alone program that
+    calls sym_analyze links"""
+    csrc = os.path.join(ROOT, "libdogleg_amd", "csrc")
+    names = sorted(f for f in os.listdir(csrc) if f.startswith("sparse_symbolic") and f.endswith(".cpp"))
+    subprocess.run([cc] + flags + ["-I", csrc, "-c"] + [os.path.join(csrc, f) for f in names], check=True, cwd=tmp)
+    return csrc, [str(tmp / (f[:-4] + ".o")) for f in names]
+
+
+def _write_pattern(path, N, M, Jp, Ji):
+    np.concatenate([[N, M], Jp, Ji]).astype(np.int32).tofile(path)
 
 
 def test_region_planner_is_clean_under_sanitizers(tmp_path, monkeypatch):
@@ -481,15 +496,23 @@ def test_region_planner_is_clean_under_sanitizers(tmp_path, monkeypatch):
     cc = _sanitizing_compiler(tmp_path)
     if cc is None:
         pytest.skip("no compiler here links a program with -fsanitize=address,undefined")
-    csrc = os.path.join(ROOT, "libdogleg_amd", "csrc")
-    exe = str(tmp_path / "region_plan_main")
-    subprocess.run([cc] + _SAN_FLAGS + ["-I", csrc, os.path.join(ROOT, "tests", "c", "region_plan_main.cpp"),
-                                        os.path.join(csrc, "sparse_symbolic.cpp"), os.path.join(csrc, "sparse_region.cpp"),
-                                        "-o", exe], check=True)
+    csrc, sym_objs = _symbolic_objects(cc, _SAN_FLAGS, tmp_path)
+    exe, sym_exe = str(tmp_path / "region_plan_main"), str(tmp_path / "symbolic_main")
+    subprocess.run([cc] + _SAN_FLAGS + ["-I", csrc, os.path.join(ROOT, "tests", "c", "region_plan_main.cpp")] + sym_objs +
+                   [os.path.join(csrc, "sparse_region.cpp"), "-o", exe], check=True)
+    subprocess.run([cc] + _SAN_FLAGS + ["-I", csrc, os.path.join(ROOT, "tests", "c", "symbolic_main.cpp")] + sym_objs + ["-o", sym_exe],
+                   check=True)
     for shape in list(_REGION_HASHES)[:3]:
         N, M, Jp, Ji = _region_pattern(shape)
         pat = tmp_path / "pattern.bin"
-        np.concatenate([[N, M], Jp, Ji]).astype(np.int32).tofile(pat)
+        _write_pattern(pat, N, M, Jp, Ji)
+        _set_knob(monkeypatch, None)
+        # the symbolic phase alone: the whole pattern, a row shard, one rank of a partition -- the library's sym_hash
+        for args, want in (([], capi.symbolic_probe(N, M, Jp, Ji)), (["rows", "150", "401"], capi.symbolic_probe(N, M, Jp, Ji, row0=150, row1=401)),
+                           (["part", "1", "2"], capi.partition_probe(N, M, Jp, Ji, 1, 2)[0])):
+            r = subprocess.run([sym_exe, str(pat)] + args, capture_output=True, text=True)
+            assert r.returncode == 0 and r.stderr == "", (shape, args, r.returncode, r.stderr[-2000:])
+            assert int(r.stdout, 16) == want["sym_hash"], (shape, args)
         for ncu in (256, 64):
             for knob in _REGION_KNOBS:
                 _set_knob(monkeypatch, knob)
@@ -497,6 +520,32 @@ def test_region_planner_is_clean_under_sanitizers(tmp_path, monkeypatch):
                 assert r.returncode == 0 and r.stderr == "", (shape, ncu, knob, r.returncode, r.stderr[-2000:])
                 st = capi.region_probe(N, M, Jp, Ji, ncu)
                 assert [int(h, 16) for h in r.stdout.split()] == [st["schedule_hash"], st["level_params_hash"]], (shape, ncu, knob)
+
+
+def test_symbolic_schedule_threads_are_clean_under_thread_sanitizer(tmp_path, monkeypatch):
+    """The four schedules of the symbolic phase (factor updates, Jt*x lists, assembly, solve gather lists) run on four
+    threads that share the analysis so far read-only and fill a record each: tests/c/symbolic_main.cpp under
+    ThreadSanitizer reports nothing, exits 0 and prints the library's hash, on three bundle adjustments and on one rank of
+    a partition."""
+    cc = _sanitizing_compiler(tmp_path, _TSAN_FLAGS)
+    if cc is None:
+        pytest.skip("no compiler here links a program with -fsanitize=thread")
+    csrc, sym_objs = _symbolic_objects(cc, _TSAN_FLAGS, tmp_path)
+    exe = str(tmp_path / "symbolic_main")
+    subprocess.run([cc] + _TSAN_FLAGS + ["-I", csrc, os.path.join(ROOT, "tests", "c", "symbolic_main.cpp")] + sym_objs + ["-o", exe], check=True)
+    for k in _SYM_KNOB_NAMES:
+        monkeypatch.delenv(k, raising=False)
+    for shape in _SYM_BA:
+        N, M, Jp, Ji = _region_pattern(shape)
+        pat = tmp_path / "pattern.bin"
+        _write_pattern(pat, N, M, Jp, Ji)
+        runs = [([], capi.symbolic_probe(N, M, Jp, Ji))]
+        if shape == _SYM_BA[1]:
+            runs.append((["part", "7", "8"], capi.partition_probe(N, M, Jp, Ji, 7, 8)[0]))
+        for args, want in runs:
+            r = subprocess.run([exe, str(pat)] + args, capture_output=True, text=True)
+            assert r.returncode == 0 and r.stderr == "", (shape, args, r.returncode, r.stderr[-3000:])
+            assert int(r.stdout, 16) == want["sym_hash"], (shape, args)
 
 
 def test_id_file_rendezvous_is_clean_under_sanitizers(tmp_path):
@@ -667,3 +716,170 @@ def test_symbolic_debug_output_changes_nothing(monkeypatch, capfd):
     err = capfd.readouterr().err
     assert a == b
     assert "sym_analyze" in err or "ms" in err
+
+
+# ---- the symbolic analysis pinned bit for bit: sym_hash (64-bit FNV-1a over every field of SymHost, records field by
+# field) of every case below.  The literals were produced by sym_analyze as it stood while it was one function: that
+# tree with the same sym_hash and probe entry added and nothing else (profiles/symbolic_refactor.md).
+_SYM_KNOB_NAMES = ("DOGLEG_AMD_SLICE_CAP", "DOGLEG_AMD_ND_LEAF", "DOGLEG_AMD_LDS_SPLIT", "DOGLEG_AMD_MF_LEVEL",
+                   "DOGLEG_AMD_SYRK_MIN", "DOGLEG_AMD_ASM_MFMA", "DOGLEG_AMD_RIDER_MIN", "DOGLEG_AMD_SYM_DEBUG")
+_SYM_KNOBS = (("DOGLEG_AMD_SLICE_CAP", "3000"), ("DOGLEG_AMD_ND_LEAF", "50"), ("DOGLEG_AMD_LDS_SPLIT", "0"),
+              ("DOGLEG_AMD_MF_LEVEL", "-1"), ("DOGLEG_AMD_SYRK_MIN", "1"), ("DOGLEG_AMD_ASM_MFMA", "0"),
+              ("DOGLEG_AMD_ASM_MFMA", "2"), ("DOGLEG_AMD_RIDER_MIN", "64"))
+_SYM_BA = ((49, 900, 10000), (99, 1800, 20000), (199, 3000, 30000))
+
+
+@functools.lru_cache(maxsize=None)
+def _sym_pattern(key):
+    """(N, M, Jp, Ji) of ("zoo", name), ("ba", Ncam, Npt, Nobs) (seed 11, _REGION_KW), ("ba-small",), ("structured",
+    seed, scale), ("ragged", seed)"""
+    if key[0] == "zoo":
+        return zoo.case(key[1])[:4]
+    if key[0] == "ba":
+        return _region_pattern(key[1:])
+    if key[0] == "ba-small":
+        prob = oa.BAProblem(9, 60, 300, seed=3)                # (test_symbolic_shards_partition_the_contributions)
+        return (prob.N, prob.M) + tuple(prob.pattern())
+    rng = np.random.default_rng(key[1])
+    if key[0] == "structured":
+        N, rows, _ = sparse_patterns.random_structured_pattern(rng, scale=key[2])
+    else:
+        N, _, rows = sparse_patterns.ragged_rows(rng, key[1])
+    return (N, len(rows)) + sparse_patterns.rows_to_csc(rows, N)
+
+
+def _sym_cases():
+    """(id, pattern key, ("rows", row0, row1 or None) / ("part", rank, nranks), ((knob, value), ...))"""
+    cases = [("zoo:" + n, ("zoo", n), ("rows", 0, None), ()) for n in zoo.NAMES]
+    ba = [("ba", *s) for s in _SYM_BA]
+    cases += [("ba:%d-%d-%d" % k[1:], k, ("rows", 0, None), ()) for k in ba + [("ba", 833, 15000, 250000)]]
+    cases += [("structured:%d" % s, ("structured", s, 1), ("rows", 0, None), ()) for s in (1000, 1001, 1002, 1007)]
+    # (the dense block with many row layouts reaches the riders' left-over rows with this threshold only)
+    cases += [("structured-x20:9026", ("structured", 9026, 20), ("rows", 0, None), (("DOGLEG_AMD_RIDER_MIN", "8"),)),
+              ("ragged:21", ("ragged", 21), ("rows", 0, None), ())]
+    cuts = [0, 150, 151, 400, None]
+    cases += [("shard:%d" % a, ("ba-small",), ("rows", a, b), ()) for a, b in zip(cuts[:-1], cuts[1:])]
+    cases += [("part:%d-%d-%d:%d/%d" % (k[1:] + (r, n)), k, ("part", r, n), ()) for k in ba for n in (2, 8) for r in (0, n - 1)]
+    for knob in _SYM_KNOBS:
+        cases += [("%s=%s:%s" % (knob[0][11:], knob[1], "-".join(str(x) for x in k[1:])), k, ("rows", 0, None), (knob,))
+                  for k in ba + [("zoo", "arrow-9x40+128"), ("zoo", "wide-children")]]
+    # (RIDER_MIN=64 leaves the riders of the cases above as they are: a threshold under which a structured pattern gets
+    # riders and one over which the bundle adjustment loses them)
+    cases += [("%s=%s:%s" % (knob[11:], val, "-".join(str(x) for x in k[1:])), k, ("rows", 0, None), ((knob, val),))
+              for knob, val, k in (("DOGLEG_AMD_RIDER_MIN", "16", ("structured", 1000, 1)), ("DOGLEG_AMD_RIDER_MIN", "100000", ba[0]))]
+    return cases
+
+
+_SYM_CASES = _sym_cases()
+_SYM_HASHES = {
+    "zoo:dense-16": 0xe56393d9dd65ddfa,
+    "zoo:dense-17": 0x10c58f1d2d9c104,
+    "zoo:dense-64": 0x90dbc6204da1479a,
+    "zoo:dense-65": 0x684a008f18e4c5e7,
+    "zoo:dense-127": 0x91c03db4a99cc3fc,
+    "zoo:dense-128": 0x69497d787ac655d,
+    "zoo:dense-129": 0xa97e4dfc8d9f96aa,
+    "zoo:scattered": 0x4c5a067246a9c3fe,
+    "zoo:banded": 0xe9cf819581db143c,
+    "zoo:holes": 0x659912a2d92ae390,
+    "zoo:arrow-3x60+70": 0xf28406672058e945,
+    "zoo:arrow-1x300+5": 0x7accb3803507705,
+    "zoo:arrow-3x200+17": 0xc7c72686a1935c40,
+    "zoo:arrow-9x40+128": 0xfaecc8b5d56d9d02,
+    "zoo:wide-children": 0xebcd5d7e607528f2,
+    "zoo:wide-root": 0xcbcfb61f57d80aae,
+    "zoo:ba-tiny": 0x5435f4623e3607e9,
+    "ba:49-900-10000": 0x83612db5b6142cde,
+    "ba:99-1800-20000": 0xcc244183a9f443d2,
+    "ba:199-3000-30000": 0xf27ea9f74f442cff,
+    "ba:833-15000-250000": 0x95c8da4316ff3745,
+    "structured:1000": 0x7f2a1d4fdcac2db6,
+    "structured:1001": 0x657e030b42a4b960,
+    "structured:1002": 0xb3149f9043d23bf5,
+    "structured:1007": 0x5e5bc182363ec093,
+    "structured-x20:9026": 0xda38389bdf9a0377,
+    "ragged:21": 0x8d4f6f30d6870cf,
+    "shard:0": 0x6f4c1aad988225e4,
+    "shard:150": 0x5806c1dc82b82d1a,
+    "shard:151": 0x13d4edc4a573eeb8,
+    "shard:400": 0x4f11c4d79c5dcff1,
+    "part:49-900-10000:0/2": 0x15fb1d7a8239ffb3,
+    "part:49-900-10000:1/2": 0x4699987c353e6ae9,
+    "part:49-900-10000:0/8": 0xf1602fe5731be79e,
+    "part:49-900-10000:7/8": 0xde28613c94c121c4,
+    "part:99-1800-20000:0/2": 0xfec566a1771fd082,
+    "part:99-1800-20000:1/2": 0x408508e1171ce739,
+    "part:99-1800-20000:0/8": 0x28f5ad1f27444d8c,
+    "part:99-1800-20000:7/8": 0x559177d72e5b2b9d,
+    "part:199-3000-30000:0/2": 0x55e4b77fe1c76385,
+    "part:199-3000-30000:1/2": 0xfa9fe7930b0dcca7,
+    "part:199-3000-30000:0/8": 0x6aebac4eed6d8999,
+    "part:199-3000-30000:7/8": 0xf60b25542d5a7e7b,
+    "SLICE_CAP=3000:49-900-10000": 0x533156d4e1d7a9b2,
+    "SLICE_CAP=3000:99-1800-20000": 0x8e677ce7c76f28bd,
+    "SLICE_CAP=3000:199-3000-30000": 0xafc0f55268b17702,
+    "SLICE_CAP=3000:arrow-9x40+128": 0xea9f69c2140e94b8,
+    "SLICE_CAP=3000:wide-children": 0xd0b6204e85b22de7,
+    "ND_LEAF=50:49-900-10000": 0x83612db5b6142cde,
+    "ND_LEAF=50:99-1800-20000": 0xc276ec144467c51,
+    "ND_LEAF=50:199-3000-30000": 0xf27ea9f74f442cff,
+    "ND_LEAF=50:arrow-9x40+128": 0xfaecc8b5d56d9d02,
+    "ND_LEAF=50:wide-children": 0xebcd5d7e607528f2,
+    "LDS_SPLIT=0:49-900-10000": 0x766d86f3f6caf53b,
+    "LDS_SPLIT=0:99-1800-20000": 0x561827911d20b81a,
+    "LDS_SPLIT=0:199-3000-30000": 0x5e69443655abd2c3,
+    "LDS_SPLIT=0:arrow-9x40+128": 0xfaecc8b5d56d9d02,
+    "LDS_SPLIT=0:wide-children": 0xebcd5d7e607528f2,
+    "MF_LEVEL=-1:49-900-10000": 0x16d63d0e95029ac8,
+    "MF_LEVEL=-1:99-1800-20000": 0xbe7de81c06224b53,
+    "MF_LEVEL=-1:199-3000-30000": 0x474ef0662d5a9509,
+    "MF_LEVEL=-1:arrow-9x40+128": 0x8fd1760aa6bb0b00,
+    "MF_LEVEL=-1:wide-children": 0x769b1cefa5ae990,
+    "SYRK_MIN=1:49-900-10000": 0xbef88fcc3160bfd8,
+    "SYRK_MIN=1:99-1800-20000": 0xcc244183a9f443d2,
+    "SYRK_MIN=1:199-3000-30000": 0xf27ea9f74f442cff,
+    "SYRK_MIN=1:arrow-9x40+128": 0xfaecc8b5d56d9d02,
+    "SYRK_MIN=1:wide-children": 0xebcd5d7e607528f2,
+    "ASM_MFMA=0:49-900-10000": 0x753ebbf8f3c47235,
+    "ASM_MFMA=0:99-1800-20000": 0xec28a9ea27c24325,
+    "ASM_MFMA=0:199-3000-30000": 0xcd6d4bb0fb02ad9a,
+    "ASM_MFMA=0:arrow-9x40+128": 0xebcc7ae66c05c67c,
+    "ASM_MFMA=0:wide-children": 0x355bed998c5bef0b,
+    "ASM_MFMA=2:49-900-10000": 0x83eeb1e6314637ab,
+    "ASM_MFMA=2:99-1800-20000": 0x76ab8b07d8c6d15f,
+    "ASM_MFMA=2:199-3000-30000": 0x3d5c15e0c490c452,
+    "ASM_MFMA=2:arrow-9x40+128": 0xbd1ec51cd880a4c3,
+    "ASM_MFMA=2:wide-children": 0xbd99a1d8b76fdf8f,
+    "RIDER_MIN=64:49-900-10000": 0x83612db5b6142cde,
+    "RIDER_MIN=64:99-1800-20000": 0xcc244183a9f443d2,
+    "RIDER_MIN=64:199-3000-30000": 0xf27ea9f74f442cff,
+    "RIDER_MIN=64:arrow-9x40+128": 0xfaecc8b5d56d9d02,
+    "RIDER_MIN=64:wide-children": 0xebcd5d7e607528f2,
+    "RIDER_MIN=16:1000-1": 0xa1c7321c8d511cc1,
+    "RIDER_MIN=100000:49-900-10000": 0xb3af2d8be9a8c73,
+}
+
+
+def _sym_case_hash(key, mode):
+    N, M, Jp, Ji = _sym_pattern(key)
+    if mode[0] == "part":
+        return capi.partition_probe(N, M, Jp, Ji, mode[1], mode[2])[0]["sym_hash"]
+    return capi.symbolic_probe(N, M, Jp, Ji, row0=mode[1], row1=mode[2])["sym_hash"]
+
+
+@pytest.mark.parametrize("case", _SYM_CASES, ids=[c[0] for c in _SYM_CASES])
+def test_symbolic_analysis_is_pinned(case, monkeypatch):
+    """Every array and scalar the symbolic phase hands the kernels, hashed and compared with what sym_analyze produced
+    before it was split into phases: every pattern of the factor-user zoo, four bundle adjustments (one with scaled and
+    zero columns), random structured patterns, the dense block with many row layouts, ragged rows; the row shards of
+    test_symbolic_shards_partition_the_contributions; subtree partitions over 2 and 8 ranks as the first and the last
+    rank see them; every knob of the phase at a non-default value.  Between them the cases reach MFMA and scalar
+    assembly tasks, riders, partial-sum stages with intermediates, k-groups with and without inline destinations,
+    sliced supernodes, two-phase levels, empty and non-empty multifrontal regions, update units with partial slabs,
+    chunked Jt*x lists and a partition cut (the list per case: profiles/symbolic_refactor.md)."""
+    cid, key, mode, env = case
+    for k in _SYM_KNOB_NAMES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env:
+        monkeypatch.setenv(k, v)
+    assert hex(_sym_case_hash(key, mode)) == hex(_SYM_HASHES[cid])

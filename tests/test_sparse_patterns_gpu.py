@@ -8,6 +8,7 @@ import pytest
 from libdogleg_amd import capi
 from libdogleg_amd.ctypes_defs import dptr, iptr
 from tests import oracle_api as oa
+from tests.sparse_patterns import ragged_rows, random_structured_pattern, rows_to_csc
 
 pytestmark = pytest.mark.gpu
 
@@ -47,21 +48,11 @@ def _check_pattern(N, M, Jp, Ji, Jx, x, lam=0.0, tol=1e-9):
     return st
 
 
-def _rows_to_csc(rows, N):
-    Jp = [0]
-    Ji = []
-    for r in rows:
-        r = sorted(set(int(i) for i in r))
-        Ji.extend(r)
-        Jp.append(len(Ji))
-    return np.array(Jp, dtype=np.int32), np.array(Ji, dtype=np.int32)
-
-
 def test_random_sparse_pattern(gpu):
     rng = np.random.default_rng(3)
     N, M = 400, 2500
     rows = [rng.choice(N, size=rng.integers(2, 7), replace=False) for _ in range(M)]
-    Jp, Ji = _rows_to_csc(rows, N)
+    Jp, Ji = rows_to_csc(rows, N)
     Jx = rng.standard_normal(Jp[-1])
     x = rng.standard_normal(M)
     st = _check_pattern(N, M, Jp, Ji, Jx, x)
@@ -87,7 +78,7 @@ def test_banded_chain_pattern(gpu):
     rng = np.random.default_rng(5)
     N = 3000
     rows = [[i, i + 1, i + 2] for i in range(N - 2)] + [[i] for i in range(0, N, 7)]
-    Jp, Ji = _rows_to_csc(rows, N)
+    Jp, Ji = rows_to_csc(rows, N)
     M = len(rows)
     Jx = rng.standard_normal(Jp[-1]) + 2.0
     x = rng.standard_normal(M)
@@ -107,7 +98,7 @@ def test_empty_rows_and_untouched_variables(gpu):
             rows.append([])
         else:
             rows.append(rng.choice(np.arange(0, N - 5), size=4, replace=False))   # last 5 vars untouched
-    Jp, Ji = _rows_to_csc(rows, N)
+    Jp, Ji = rows_to_csc(rows, N)
     Jx = rng.standard_normal(Jp[-1])
     x = rng.standard_normal(M)
     _check_pattern(N, M, Jp, Ji, Jx, x, lam=0.0)          # both sides must report "singular"
@@ -127,7 +118,7 @@ def test_block_sizes_around_the_limits(gpu):
         idx = np.concatenate([np.arange(starts[b], starts[b + 1]) for b in pick])
         for _ in range(int(rng.integers(1, 13))):
             rows.append(idx)
-    Jp, Ji = _rows_to_csc(rows, N)
+    Jp, Ji = rows_to_csc(rows, N)
     M = len(rows)
     Jx = rng.standard_normal(Jp[-1])
     x = rng.standard_normal(M)
@@ -150,37 +141,6 @@ def test_wide_dense_tail(gpu):
     print("wide dense tail:", st)
 
 
-def _random_structured_pattern(rng, scale=1):
-    """variable blocks of random widths, a few of them 'dense' (touched by every row), rows drawn
-    from a small set of templates and repeated 1..10 times (row-blocks), random values"""
-    nblk = int(rng.integers(6, 40))*scale
-    widths = rng.integers(1, 10, size=nblk)
-    starts = np.concatenate([[0], np.cumsum(widths)])
-    N = int(starts[-1])
-    ndense = int(rng.integers(0, 3))
-    dense_blocks = list(rng.choice(nblk, size=ndense, replace=False)) if ndense else []
-    templates = []
-    for _ in range(int(rng.integers(3, 60))*scale):
-        k = int(rng.integers(1, min(5, nblk) + 1))
-        blks = set(rng.choice(nblk, size=k, replace=False).tolist()) | set(dense_blocks)
-        templates.append(sorted(blks))
-    rows = []
-    target = int(rng.integers(N + 20, 6 * N + 200))
-    while len(rows) < target:
-        t = templates[int(rng.integers(0, len(templates)))]
-        idx = np.concatenate([np.arange(starts[b], starts[b + 1]) for b in t])
-        for _ in range(int(rng.integers(1, 11))):
-            rows.append(idx)
-    # every block gets as many rows of its own as it is wide, so that J has full column rank
-    # (the values of these rows are boosted by the caller)
-    ntail = 0
-    for b in range(nblk):
-        for _ in range(int(widths[b])):
-            rows.append(np.arange(starts[b], starts[b + 1]))
-            ntail += int(widths[b])
-    return N, rows, ntail
-
-
 @pytest.mark.parametrize("seed", range(24))
 def test_random_structured_patterns(gpu, seed, monkeypatch):
     """stress of the symbolic phase and the schedules (layout classes, riders with a low threshold,
@@ -192,8 +152,8 @@ def test_random_structured_patterns(gpu, seed, monkeypatch):
         monkeypatch.setenv("DOGLEG_AMD_SYRK_MIN", "2")         # two-phase updates at small levels
     if seed % 5 == 2:
         monkeypatch.setenv("DOGLEG_AMD_SLICE_CAP", "3000")     # sliced panels
-    N, rows, ntail = _random_structured_pattern(rng)
-    Jp, Ji = _rows_to_csc(rows, N)
+    N, rows, ntail = random_structured_pattern(rng)
+    Jp, Ji = rows_to_csc(rows, N)
     M = len(rows)
     Jx = rng.standard_normal(Jp[-1])
     tail = Jp[-1] - ntail
@@ -208,8 +168,8 @@ def test_dense_block_with_many_row_layouts(gpu, seed, monkeypatch):
     left-over rows come in more than 64 different layouts used to have no assembly schedule"""
     monkeypatch.setenv("DOGLEG_AMD_RIDER_MIN", "8")
     rng = np.random.default_rng(seed)
-    N, rows, ntail = _random_structured_pattern(rng, scale=20)
-    Jp, Ji = _rows_to_csc(rows, N)
+    N, rows, ntail = random_structured_pattern(rng, scale=20)
+    Jp, Ji = rows_to_csc(rows, N)
     M = len(rows)
     Jx = rng.standard_normal(Jp[-1])
     Jx[Jp[-1] - ntail:] *= 4.0
@@ -223,11 +183,8 @@ def test_ragged_rows_with_every_alignment_of_the_value_runs(gpu, seed):
     rows of 1..9 entries put the runs of the workgroups at every offset, the total count at every
     remainder (the last thread goes element by element past the end of the arrays)"""
     rng = np.random.default_rng(seed)
-    N = 120
-    M = 3000 + seed          # several runs of <= 2048 values
-    rows = [rng.choice(N, size=rng.integers(1, 10), replace=False) for _ in range(M)]
-    rows[-1] = rows[-1][:1 + seed % 3]
-    Jp, Ji = _rows_to_csc(rows, N)
+    N, M, rows = ragged_rows(rng, seed)
+    Jp, Ji = rows_to_csc(rows, N)
     Jx = rng.standard_normal(Jp[-1])
     x = rng.standard_normal(M)
     _check_pattern(N, M, Jp, Ji, Jx, x)
