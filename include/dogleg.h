@@ -618,9 +618,9 @@ int dogleg_amd_dense_products_batch_uncertainty_device(const double* p_dev, unsi
  * communicator; the device twin also refuses weights_dev as it refuses the other pointers.  Device memory: the plain solve's,
  * plus B * Nmeas / featureSize doubles.
  * Not provided: the products form with a loss (it has no per-feature x); per-problem scales (normalise x in the callback);
- * losses that are not concave in s (Tukey's biweight): H would need the curvature term; uncertainty and query calls that take a
- * loss -- the recipe: call dogleg_amd_dense_batch_uncertainty / _query_covariance at the returned p with a callback that
- * multiplies row r of x and J by sqrt(weights[b][r / featureSize]). */
+ * losses that are not concave in s (Tukey's biweight): H would need the curvature term.  The uncertainty and the query
+ * covariances of the reweighted problem at the returned p: dogleg_amd_dense_batch_uncertainty_fit / _query_covariance_fit below,
+ * with this loss and these weights in their fit record. */
 #define DOGLEG_AMD_LOSS_TRIVIAL 0
 #define DOGLEG_AMD_LOSS_HUBER   1
 #define DOGLEG_AMD_LOSS_SOFT_L1 2
@@ -729,9 +729,9 @@ int dogleg_amd_robust_last_stats(double* out, int n);
  * a NULL bounds, weights without a loss; the device twin also refuses lower, upper and held as it refuses the other pointers.
  * Device memory: the plain or robust solve's; the host-pointer form adds B Nstate doubles for each of lower and upper that
  * is given (held is formed on the host from the returned point's p and g).
- * Not provided: bounds in the products form; bounds in the uncertainty and query calls -- the recipe: call them at the returned
- * p with a callback that zeroes the columns of J of the held variables and adds a unit row for each, using held; general
- * linear constraints. */
+ * Not provided: bounds in the products form; general linear constraints.  The uncertainty and the query covariances of the free
+ * variables at the returned p: dogleg_amd_dense_batch_uncertainty_fit / _query_covariance_fit below, with held (and, with a loss,
+ * the loss and the weights) in their fit record. */
 typedef struct
 {
   const double*  lower;   /* [B][Nstate] or NULL: no lower bounds; -INFINITY entries allowed */
@@ -800,6 +800,101 @@ int dogleg_amd_dense_products_batch_query_covariance_device(const double* p_dev,
                                                             const double* Jq_dev, unsigned int Nq, unsigned int Qrows,
                                                             double* out_dev, int* status_dev,
                                                             const unsigned char* active_dev, void* hip_stream);
+
+/* ---- uncertainty and query calls at the optimum of a robust or bounded fit: the eight calls above (uncertainty and query
+ * covariance, J and products form, host and _device) with one more argument, a record that says how the fit was made.  Without
+ * it the eight compute (JtJ + lambda I)^-1 of the unweighted, unconstrained problem, which at an optimum whose outliers were
+ * down-weighted, or whose variables sit on a bound, is the covariance of another problem.  The weights are applied while a row
+ * is staged and the held set is a mask on the matrix that is factorised: J is read as often as in the plain call and nothing
+ * is written back into it.
+ *   fit->loss     NULL: unweighted.  Otherwise its featureSize (1 .. 4, <= 1: 1; called lfs below) says how many consecutive rows
+ *                 share a weight; kind and scale are read only if weights is NULL.  lfs is independent of the featureSize
+ *                 argument of the outlierness factors, which stays 1 or 2.
+ *   fit->weights  [B][Nmeas / lfs] or NULL.  Given (what the robust or bounded solve wrote): used as they come; 0 is allowed and
+ *                 drops the feature; a weight that is negative or not finite makes that problem DOGLEG_AMD_BATCH_UNC_FAILED alone
+ *                 (so a problem whose solve FAILED, with its NaN weights, fails here too).  NULL with a loss: w_f = rho'(s_f) is
+ *                 computed from the callback's x at p[b], the bits the robust solve returns at that p.
+ *   fit->held     [B][Nstate] or NULL: nonzero = variable held (what the bounded solve wrote).
+ * For problem b, with row r in weight feature r / lfs:
+ *   1. x~_r = sqrt(w_f) x_r and J~_r = sqrt(w_f) J_r, every product rounded once, as a callback that scales the rows would write
+ *      them.  H = J~^T J~.
+ *   2. After lambda is added, every held row and column of the matrix to be factorised gets zero off-diagonals and a diagonal of 1
+ *      (step 4 of the bounded solve); the lambda schedule (0 -> 1e-10 -> x10) runs on that matrix.  With every variable held the
+ *      factorisation succeeds at the lambda that came in.
+ *   3. covariance: (H_FF + lambda I)^-1 on the free variables; every entry in a held row or column is exactly +0.0 (a variable on
+ *      its bound is not estimated).  variances: that diagonal.
+ *   4. factors: the leverage block is J~_f Sigma J~_f^T with x~_f; a computed scale is Nmeas / (4 (N_F + 1) |x~|^2 / (Nmeas - N_F - 1))
+ *      with N_F the number of free variables and |x~|^2 the sum of the squares of the weighted x (NOT the robust cost).  The
+ *      refusal of a scale to be computed while Nmeas <= Nstate + 1 is unchanged.
+ *   5. query: Jq Sigma Jq^T; the observations-only form takes J_obs = the first Nobservations rows of J~, and with a loss
+ *      Nobservations must be a multiple of lfs.
+ *   6. the products form has no rows: it takes held only.
+ * fit == NULL, or all three members NULL: the call without _fit, bit for bit.  With DOGLEG_AMD_LOSS_TRIVIAL of size 1 and no held
+ * variable, and with weights that are all 1.0, Sigma, the variances and the query blocks have the bits of the call without _fit
+ * too; at other lfs the rows of x are summed in tiles of another height, so a computed scale and the factors may differ in their
+ * last bits, as they may from a callback that scales the rows.
+ * Everything else is the contract of the call without _fit: one callback, one launch, one synchronisation
+ * (dogleg_amd_batch_uncertainty_last_stats covers these calls), the active mask, the stream rule, the status codes, NaN in every
+ * output of a FAILED problem, and problem b's bits independent of B, of its position and of its neighbours.
+ * The host-pointer forms stage weights and held through the page-locked buffer of the uncertainty calls, 8 B Nmeas / lfs bytes
+ * and B Nstate bytes more, and keep as many in device memory; the _device forms read them where they lie (fit itself is host
+ * memory) and copy nothing.
+ * Refused with a message and -1 before any device work, outputs untouched: what the call without _fit refuses; weights without
+ * loss; an unknown kind, or a scale that is not finite and > 0 (unless TRIVIAL), while weights is NULL; featureSize above 4 or not
+ * dividing Nmeas; with a loss, an Nobservations >= 0 that is not a multiple of lfs; a loss or weights in the products form; the
+ * _device forms also refuse weights and held as they refuse their other pointers, over [B][Nmeas / lfs] doubles and [B][Nstate]
+ * bytes.
+ * Not provided: a loss in the products form (it has no rows) and bounds in the products-form solve; per-problem loss scales;
+ * losses that are not concave in s; weights that differ between J and x; marking outliers on a batch. */
+typedef struct
+{
+  const dogleg_amd_batch_loss_t* loss;     /* NULL: unweighted.  Gives featureSize (1..4) of the weights; kind / scale are read only if weights is NULL */
+  const double*                  weights;  /* [B][Nmeas / loss->featureSize] in, or NULL: w_f = rho'(s_f) is computed from x at p[b] with *loss */
+  const unsigned char*           held;     /* [B][Nstate] in, or NULL: nonzero = variable held (what the bounded solve wrote) */
+} dogleg_amd_batch_fit_t;
+int dogleg_amd_dense_batch_uncertainty_fit(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                           dogleg_callback_device_batch_t* f, void* cookie,
+                                           double* lambda, double* covariance, double* variances, double* factors,
+                                           double* scale, int featureSize, int* status, const dogleg_amd_batch_fit_t* fit);
+int dogleg_amd_dense_products_batch_uncertainty_fit(const double* p, unsigned int B, unsigned int Nstate,
+                                                    dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                    const dogleg_parameters2_t* parameters,
+                                                    double* lambda, double* covariance, double* variances, int* status,
+                                                    const dogleg_amd_batch_fit_t* fit);
+int dogleg_amd_dense_batch_uncertainty_fit_device(const double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                  dogleg_callback_device_batch_t* f, void* cookie,
+                                                  double* lambda_dev, double* covariance_dev, double* variances_dev,
+                                                  double* factors_dev, double* scale_dev, int featureSize, int* status_dev,
+                                                  const unsigned char* active_dev, void* hip_stream,
+                                                  const dogleg_amd_batch_fit_t* fit);
+int dogleg_amd_dense_products_batch_uncertainty_fit_device(const double* p_dev, unsigned int B, unsigned int Nstate,
+                                                           dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                           const dogleg_parameters2_t* parameters,
+                                                           double* lambda_dev, double* covariance_dev, double* variances_dev,
+                                                           int* status_dev, const unsigned char* active_dev, void* hip_stream,
+                                                           const dogleg_amd_batch_fit_t* fit);
+int dogleg_amd_dense_batch_query_covariance_fit(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                dogleg_callback_device_batch_t* f, void* cookie, double* lambda,
+                                                const double* Jq, unsigned int Nq, unsigned int Qrows, int Nobservations,
+                                                double* out, int* status, const dogleg_amd_batch_fit_t* fit);
+int dogleg_amd_dense_products_batch_query_covariance_fit(const double* p, unsigned int B, unsigned int Nstate,
+                                                         dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                         const dogleg_parameters2_t* parameters, double* lambda,
+                                                         const double* Jq, unsigned int Nq, unsigned int Qrows,
+                                                         double* out, int* status, const dogleg_amd_batch_fit_t* fit);
+int dogleg_amd_dense_batch_query_covariance_fit_device(const double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                       dogleg_callback_device_batch_t* f, void* cookie, double* lambda_dev,
+                                                       const double* Jq_dev, unsigned int Nq, unsigned int Qrows,
+                                                       int Nobservations, double* out_dev, int* status_dev,
+                                                       const unsigned char* active_dev, void* hip_stream,
+                                                       const dogleg_amd_batch_fit_t* fit);
+int dogleg_amd_dense_products_batch_query_covariance_fit_device(const double* p_dev, unsigned int B, unsigned int Nstate,
+                                                                dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                                const dogleg_parameters2_t* parameters, double* lambda_dev,
+                                                                const double* Jq_dev, unsigned int Nq, unsigned int Qrows,
+                                                                double* out_dev, int* status_dev,
+                                                                const unsigned char* active_dev, void* hip_stream,
+                                                                const dogleg_amd_batch_fit_t* fit);
 
 /* ---- extension (not in the reference): the Jacobian of a DEVICE callback checked against central differences, on the
  * device.  dogleg_testGradient* above take host callbacks, one variable a call.  Here the whole Jacobian is compared, and

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, BatchLoss, BatchBounds, JacobianReport, JacobianEntry,
+from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, BatchLoss, BatchBounds, BatchFit, JacobianReport, JacobianEntry,
                           CB_SPARSE, CB_DENSE, CB_PRODUCTS, dptr, iptr)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -72,6 +72,10 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_optimize_dense_batch_bounded", "dogleg_amd_optimize_dense_batch_bounded_device",
     "dogleg_amd_dense_batch_query_covariance", "dogleg_amd_dense_products_batch_query_covariance",
     "dogleg_amd_dense_batch_query_covariance_device", "dogleg_amd_dense_products_batch_query_covariance_device",
+    "dogleg_amd_dense_batch_uncertainty_fit", "dogleg_amd_dense_products_batch_uncertainty_fit",
+    "dogleg_amd_dense_batch_uncertainty_fit_device", "dogleg_amd_dense_products_batch_uncertainty_fit_device",
+    "dogleg_amd_dense_batch_query_covariance_fit", "dogleg_amd_dense_products_batch_query_covariance_fit",
+    "dogleg_amd_dense_batch_query_covariance_fit_device", "dogleg_amd_dense_products_batch_query_covariance_fit_device",
     "dogleg_amd_jacobian_colouring", "dogleg_amd_check_jacobian_device", "dogleg_amd_check_jacobian_device_batch",
     "dogleg_amd_testGradient_device", "dogleg_amd_check_jacobian_last_stats",
     "dogleg_amd_optimize_device2_robust", "dogleg_amd_robust_last_stats",
@@ -256,6 +260,13 @@ def lib():
         L.dogleg_amd_dense_products_batch_query_covariance.argtypes = [D, U, U, V, V, PP, D, D, U, U, D, I]
         L.dogleg_amd_dense_batch_query_covariance_device.argtypes = [V, U, U, U, V, V, V, V, U, U, C.c_int, V, V, V, V]
         L.dogleg_amd_dense_products_batch_query_covariance_device.argtypes = [V, U, U, V, V, PP, V, V, U, U, V, V, V, V]
+    if hasattr(L, "dogleg_amd_dense_batch_uncertainty_fit"):
+        # the argument lists of the eight calls without _fit, then the fit record
+        FP = C.POINTER(BatchFit)
+        for name in DOGLEG_SYMBOLS:
+            if "_fit" in name:
+                twin = name.replace("_fit", "")
+                getattr(L, name).argtypes = list(getattr(L, twin).argtypes) + [FP]
     if hasattr(L, "dogleg_amd_check_jacobian_device"):
         JR, JE = C.POINTER(JacobianReport), C.POINTER(JacobianEntry)
         L.dogleg_amd_jacobian_colouring.argtypes = [C.c_uint, C.c_uint, I, I, I]
@@ -399,7 +410,7 @@ def optimize_dense_products_batch(p0s, N, cb, cookie, params=None):
     return rc, p, _batch_results(res, B)
 
 
-def dense_products_batch_uncertainty(p, N, cb, cookie, params=None, lam=None, want=("cov", "var")):
+def dense_products_batch_uncertainty(p, N, cb, cookie, params=None, lam=None, want=("cov", "var"), fit=None):
     """dogleg_amd_dense_products_batch_uncertainty at the points p (B, N).  lam: (B,) or None (NULL: start at 0); want: which
     of "cov", "var" to ask for.  Returns dict(rc, status, lam (None if lam was None), cov (B, N, N) / var (B, N) as asked)."""
     L = lib()
@@ -412,7 +423,7 @@ def dense_products_batch_uncertainty(p, N, cb, cookie, params=None, lam=None, wa
     if "var" in want:
         out["var"] = np.zeros((B, N))
     opt = lambda k: dptr(out[k]) if out.get(k) is not None else None
-    out["rc"] = L.dogleg_amd_dense_products_batch_uncertainty(dptr(p), B, N, cb, cookie,
+    out["rc"] = _call_fit("dogleg_amd_dense_products_batch_uncertainty", fit, dptr(p), B, N, cb, cookie,
                                                               C.byref(params) if params is not None else None,
                                                               opt("lam"), opt("cov"), opt("var"), iptr(out["status"]))
     return out
@@ -425,10 +436,11 @@ def batch_last_stats():
     return dict(rounds=int(out[0]), ms_callback=out[1], ms_library=out[2])
 
 
-def dense_batch_uncertainty(p, N, M, cb, cookie, lam=None, want=("cov", "var", "factors"), fs=1, scale=None):
+def dense_batch_uncertainty(p, N, M, cb, cookie, lam=None, want=("cov", "var", "factors"), fs=1, scale=None, fit=None):
     """dogleg_amd_dense_batch_uncertainty at the points p (B, N).  lam: (B,) or None (NULL: start at 0); want: which of
     "cov", "var", "factors" to ask for; scale: (B,) or a number for all, None: computed (<= 0).  Returns dict(rc, status,
-    lam (None if lam was None), and cov (B, N, N) / var (B, N) / factors (B, M // max(fs, 1)) + scale (B,) as asked)."""
+    lam (None if lam was None), and cov (B, N, N) / var (B, N) / factors (B, M // max(fs, 1)) + scale (B,) as asked).
+    fit: None, or batch_fit(...) / NULL_FIT for dogleg_amd_dense_batch_uncertainty_fit; so in the seven wrappers below."""
     L = lib()
     p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, N)
     B = p.shape[0]
@@ -442,9 +454,42 @@ def dense_batch_uncertainty(p, N, M, cb, cookie, lam=None, want=("cov", "var", "
         out["factors"] = np.zeros((B, M // max(fs, 1)))
         out["scale"] = np.full(B, -1.0) if scale is None else np.array(np.broadcast_to(scale, (B,)), dtype=np.float64)
     opt = lambda k: dptr(out[k]) if out.get(k) is not None else None
-    out["rc"] = L.dogleg_amd_dense_batch_uncertainty(dptr(p), B, N, M, cb, cookie, opt("lam"), opt("cov"), opt("var"),
+    out["rc"] = _call_fit("dogleg_amd_dense_batch_uncertainty", fit, dptr(p), B, N, M, cb, cookie, opt("lam"), opt("cov"), opt("var"),
                                                      opt("factors"), opt("scale"), fs, iptr(out["status"]))
     return out
+
+
+NULL_FIT = object()          # fit=NULL_FIT: the ..._fit entry point with fit == NULL
+
+
+def batch_fit(loss=None, weights=None, held=None):
+    """the fit argument of the eight uncertainty / query wrappers (dogleg_amd_batch_fit_t): loss a BatchLoss, weights (B, M //
+    featureSize) doubles and held (B, N) bytes -- numpy arrays (taken by their host address), DeviceArrays or raw addresses --
+    each or None (NULL).  fit=None calls the entry point without _fit."""
+    return dict(loss=loss, weights=weights, held=held)
+
+
+def _call_fit(name, fit, *args):
+    """the entry point `name`, or with a fit its ..._fit form: the same arguments, then the record"""
+    L = lib()
+    if fit is None:
+        return getattr(L, name)(*args)
+    name = name[:-len("_device")] + "_fit_device" if name.endswith("_device") else name + "_fit"
+    if fit is NULL_FIT:
+        return getattr(L, name)(*args, None)
+    keep = []
+
+    def addr(a, dtype):
+        if a is None:
+            return None
+        if isinstance(a, np.ndarray):
+            keep.append(np.ascontiguousarray(a, dtype=dtype))
+            return keep[-1].ctypes.data
+        return _dev(a).value
+
+    loss = fit["loss"]
+    rec = BatchFit(C.pointer(loss) if loss is not None else None, addr(fit["weights"], np.float64), addr(fit["held"], np.uint8))
+    return getattr(L, name)(*args, C.byref(rec))
 
 
 def batch_uncertainty_last_stats():
@@ -556,17 +601,17 @@ def batch_results_from_device(results_dev, B):
 
 
 def dense_batch_uncertainty_device(p_dev, B, N, M, cb, cookie, status_dev, lambda_dev=None, cov_dev=None, var_dev=None,
-                                   factors_dev=None, scale_dev=None, fs=1, active_dev=None, stream=None):
+                                   factors_dev=None, scale_dev=None, fs=1, active_dev=None, stream=None, fit=None):
     """dogleg_amd_dense_batch_uncertainty_device: every array a DeviceArray or a raw device address (None: NULL).  Returns rc."""
-    return lib().dogleg_amd_dense_batch_uncertainty_device(_dev(p_dev), B, N, M, cb, cookie, _dev(lambda_dev), _dev(cov_dev),
+    return _call_fit("dogleg_amd_dense_batch_uncertainty_device", fit, _dev(p_dev), B, N, M, cb, cookie, _dev(lambda_dev), _dev(cov_dev),
                                                            _dev(var_dev), _dev(factors_dev), _dev(scale_dev), fs,
                                                            _dev(status_dev), _dev(active_dev), _dev(stream))
 
 
 def dense_products_batch_uncertainty_device(p_dev, B, N, cb, cookie, params, status_dev, lambda_dev=None, cov_dev=None,
-                                            var_dev=None, active_dev=None, stream=None):
+                                            var_dev=None, active_dev=None, stream=None, fit=None):
     """dogleg_amd_dense_products_batch_uncertainty_device, as dense_batch_uncertainty_device.  Returns rc."""
-    return lib().dogleg_amd_dense_products_batch_uncertainty_device(_dev(p_dev), B, N, cb, cookie,
+    return _call_fit("dogleg_amd_dense_products_batch_uncertainty_device", fit, _dev(p_dev), B, N, cb, cookie,
                                                                     C.byref(params) if params is not None else None,
                                                                     _dev(lambda_dev), _dev(cov_dev), _dev(var_dev),
                                                                     _dev(status_dev), _dev(active_dev), _dev(stream))
@@ -583,22 +628,22 @@ def _query_arrays(p, N, Jq, lam):
     return p, Jq, out
 
 
-def dense_batch_query_covariance(p, N, M, cb, cookie, Jq, lam=None, nobs=-1):
+def dense_batch_query_covariance(p, N, M, cb, cookie, Jq, lam=None, nobs=-1, fit=None):
     """dogleg_amd_dense_batch_query_covariance at the points p (B, N): Jq (B, Nq, Qrows, N); lam: (B,) or None (NULL: start at
     0); nobs < 0: Jq Sigma Jq^T, otherwise the observations-only form over the first nobs measurements.  Returns dict(rc,
     status, lam (None if lam was None), out (B, Nq, Qrows, Qrows))."""
     p, Jq, out = _query_arrays(p, N, Jq, lam)
-    out["rc"] = lib().dogleg_amd_dense_batch_query_covariance(dptr(p), p.shape[0], N, M, cb, cookie,
+    out["rc"] = _call_fit("dogleg_amd_dense_batch_query_covariance", fit, dptr(p), p.shape[0], N, M, cb, cookie,
                                                               dptr(out["lam"]) if lam is not None else None, dptr(Jq),
                                                               Jq.shape[1], Jq.shape[2], nobs, dptr(out["out"]), iptr(out["status"]))
     return out
 
 
-def dense_products_batch_query_covariance(p, N, cb, cookie, Jq, params=None, lam=None):
+def dense_products_batch_query_covariance(p, N, cb, cookie, Jq, params=None, lam=None, fit=None):
     """dogleg_amd_dense_products_batch_query_covariance, as dense_batch_query_covariance (the plain form only); the layout of
     JtJ is params.JtJ_packed / JtJ_upper."""
     p, Jq, out = _query_arrays(p, N, Jq, lam)
-    out["rc"] = lib().dogleg_amd_dense_products_batch_query_covariance(dptr(p), p.shape[0], N, cb, cookie,
+    out["rc"] = _call_fit("dogleg_amd_dense_products_batch_query_covariance", fit, dptr(p), p.shape[0], N, cb, cookie,
                                                                        C.byref(params) if params is not None else None,
                                                                        dptr(out["lam"]) if lam is not None else None, dptr(Jq),
                                                                        Jq.shape[1], Jq.shape[2], dptr(out["out"]),
@@ -607,18 +652,18 @@ def dense_products_batch_query_covariance(p, N, cb, cookie, Jq, params=None, lam
 
 
 def dense_batch_query_covariance_device(p_dev, B, N, M, cb, cookie, Jq_dev, Nq, Q, out_dev, status_dev, nobs=-1, lambda_dev=None,
-                                        active_dev=None, stream=None):
+                                        active_dev=None, stream=None, fit=None):
     """dogleg_amd_dense_batch_query_covariance_device: every array a DeviceArray or a raw device address (None: NULL).
     Returns rc."""
-    return lib().dogleg_amd_dense_batch_query_covariance_device(_dev(p_dev), B, N, M, cb, cookie, _dev(lambda_dev), _dev(Jq_dev),
+    return _call_fit("dogleg_amd_dense_batch_query_covariance_device", fit, _dev(p_dev), B, N, M, cb, cookie, _dev(lambda_dev), _dev(Jq_dev),
                                                                 Nq, Q, nobs, _dev(out_dev), _dev(status_dev), _dev(active_dev),
                                                                 _dev(stream))
 
 
 def dense_products_batch_query_covariance_device(p_dev, B, N, cb, cookie, params, Jq_dev, Nq, Q, out_dev, status_dev,
-                                                 lambda_dev=None, active_dev=None, stream=None):
+                                                 lambda_dev=None, active_dev=None, stream=None, fit=None):
     """dogleg_amd_dense_products_batch_query_covariance_device, as dense_batch_query_covariance_device.  Returns rc."""
-    return lib().dogleg_amd_dense_products_batch_query_covariance_device(_dev(p_dev), B, N, cb, cookie,
+    return _call_fit("dogleg_amd_dense_products_batch_query_covariance_device", fit, _dev(p_dev), B, N, cb, cookie,
                                                                          C.byref(params) if params is not None else None,
                                                                          _dev(lambda_dev), _dev(Jq_dev), Nq, Q, _dev(out_dev),
                                                                          _dev(status_dev), _dev(active_dev), _dev(stream))

@@ -115,6 +115,35 @@ bool batch_bounds_ok(const char* who, const dogleg_amd_batch_bounds_t* bounds, c
   return true;
 }
 
+// the fit of the ..._fit uncertainty and query calls, as it lies in a request record (all three NULL: nothing to check).  The
+// products form has no rows, so it takes held only; with weights given, loss says only how many rows share one, and kind and
+// scale are not read.  Nobservations: of a query call (the first rows must be whole features), < 0 otherwise
+bool batch_fit_ok(const char* who, bool products, const dogleg_amd_batch_loss_t* loss, const double* weights, unsigned int Nmeas,
+                  int Nobservations)
+{
+  if(products && (loss || weights))
+  { MSG("%s: the products form has no rows to weight: fit->loss and fit->weights must be NULL there (fit->held is taken)", who); return false; }
+  if(weights && !loss) { MSG("%s: fit->weights without fit->loss, which says how many rows share a weight", who); return false; }
+  if(!loss) return true;
+  if(weights)
+  {
+    // (featureSize alone: batch_loss_ok's two last checks)
+    const dogleg_amd_batch_loss_t shape = {DOGLEG_AMD_LOSS_TRIVIAL, 1.0, loss->featureSize};
+    if(!batch_loss_ok(who, &shape, Nmeas)) return false;
+  }
+  else if(!batch_loss_ok(who, loss, Nmeas)) return false;
+  const int fs = loss->featureSize <= 1 ? 1 : loss->featureSize;
+  if(Nobservations >= 0 && Nobservations % fs)
+  { MSG("%s: Nobservations = %d is not a multiple of fit->loss->featureSize = %d", who, Nobservations, fs); return false; }
+  return true;
+}
+// a fit into the last three members of a request record (dense_batch.h); fit == NULL: none
+template <class Req> Req with_fit(Req a, const dogleg_amd_batch_fit_t* fit)
+{
+  if(fit) { a.loss = fit->loss; a.weights = fit->weights; a.held = fit->held; }
+  return a;
+}
+
 // a *_dev argument of the device-resident batch entry points: memory a kernel of the current device may touch over `bytes`
 bool device_span_ok(const char* who, const char* name, const void* ptr, size_t bytes)
 {
@@ -196,6 +225,7 @@ int batch_unc_entry(const char* who, DlgBatchUnc a, const dogleg_parameters2_t* 
         return -1;
       }
   }
+  if(!batch_fit_ok(who, a.fP != nullptr, a.loss, a.weights, a.M, -1)) return -1;
   if(!one_rank_only(who)) return -1;
   const size_t B = a.B, BN = B*a.N;
   if(a.device &&
@@ -205,7 +235,9 @@ int batch_unc_entry(const char* who, DlgBatchUnc a, const dogleg_parameters2_t* 
        device_span_ok_or_null(who, "variances_dev", a.variances, sizeof(double)*BN) &&
        (!a.factors || (device_span_ok(who, "factors_dev", a.factors, sizeof(double)*B*NF) &&
                        device_span_ok(who, "scale_dev", a.scale, sizeof(double)*B))) &&
-       device_span_ok_or_null(who, "active_dev", a.active, B))) return -1;
+       device_span_ok_or_null(who, "active_dev", a.active, B) &&
+       device_span_ok_or_null(who, "fit->weights", a.weights, sizeof(double)*B*loss_features(a.loss, a.M)) &&
+       device_span_ok_or_null(who, "fit->held", a.held, BN))) return -1;
   return dlg_dense_batch_uncertainty(a);
 }
 // Nq queries of Qrows rows per problem, Nobservations of the J form's Nmeas
@@ -228,13 +260,16 @@ int batch_query_entry(const char* who, DlgBatchQuery a, const dogleg_parameters2
   { MSG("%s: B = %u problems of %u queries of %u rows: beyond the index range of the batch kernels", who, a.B, a.Nq, a.Qrows); return -1; }
   if(a.Nobservations >= 0 && (unsigned int)a.Nobservations > a.M)
   { MSG("%s: Nobservations = %d exceeds Nmeas = %u (< 0 selects the plain form)", who, a.Nobservations, a.M); return -1; }
+  if(!batch_fit_ok(who, a.fP != nullptr, a.loss, a.weights, a.M, a.fP ? -1 : a.Nobservations)) return -1;
   if(!one_rank_only(who)) return -1;
   const size_t B = a.B, rows = B*a.Nq*a.Qrows;
   if(a.device &&
      !(device_span_ok(who, "p_dev", a.p, sizeof(double)*B*a.N) && device_span_ok(who, "status_dev", a.status, sizeof(int)*B) &&
        device_span_ok_or_null(who, "lambda_dev", a.lambda, sizeof(double)*B) &&
        device_span_ok(who, "Jq_dev", a.Jq, sizeof(double)*rows*a.N) && device_span_ok(who, "out_dev", a.out, sizeof(double)*rows*a.Qrows) &&
-       device_span_ok_or_null(who, "active_dev", a.active, B))) return -1;
+       device_span_ok_or_null(who, "active_dev", a.active, B) &&
+       device_span_ok_or_null(who, "fit->weights", a.weights, sizeof(double)*B*loss_features(a.loss, a.M)) &&
+       device_span_ok_or_null(who, "fit->held", a.held, B*a.N))) return -1;
   return dlg_dense_batch_query(a);
 }
 
@@ -564,6 +599,88 @@ int dogleg_amd_dense_products_batch_query_covariance_device(const double* p_dev,
 {
   return batch_query_entry(__func__, DlgBatchQuery{p_dev, B, Nstate, 0, nullptr, f, cookie, false, lambda_dev, Jq_dev, Nq, Qrows, -1,
                                                    out_dev, status_dev, active_dev, hip_stream, true}, parameters);
+}
+
+// ---- the eight uncertainty and query calls at the optimum of a robust or bounded fit: the records of the eight above with the
+// fit in their last three members
+int dogleg_amd_dense_batch_uncertainty_fit(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                           dogleg_callback_device_batch_t* f, void* cookie,
+                                           double* lambda, double* covariance, double* variances, double* factors,
+                                           double* scale, int featureSize, int* status, const dogleg_amd_batch_fit_t* fit)
+{
+  return batch_unc_entry(__func__, with_fit(DlgBatchUnc{p, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda, covariance, variances,
+                                                        factors, scale, 0, status}, fit), nullptr, featureSize);
+}
+int dogleg_amd_dense_products_batch_uncertainty_fit(const double* p, unsigned int B, unsigned int Nstate,
+                                                    dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                    const dogleg_parameters2_t* parameters,
+                                                    double* lambda, double* covariance, double* variances, int* status,
+                                                    const dogleg_amd_batch_fit_t* fit)
+{
+  return batch_unc_entry(__func__, with_fit(DlgBatchUnc{p, B, Nstate, 0, nullptr, f, cookie, false, lambda, covariance, variances,
+                                                        nullptr, nullptr, 0, status}, fit), parameters, 1);
+}
+int dogleg_amd_dense_batch_uncertainty_fit_device(const double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                  dogleg_callback_device_batch_t* f, void* cookie,
+                                                  double* lambda_dev, double* covariance_dev, double* variances_dev,
+                                                  double* factors_dev, double* scale_dev, int featureSize, int* status_dev,
+                                                  const unsigned char* active_dev, void* hip_stream,
+                                                  const dogleg_amd_batch_fit_t* fit)
+{
+  return batch_unc_entry(__func__, with_fit(DlgBatchUnc{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda_dev,
+                                                        covariance_dev, variances_dev, factors_dev, scale_dev, 0, status_dev,
+                                                        active_dev, hip_stream, true}, fit), nullptr, featureSize);
+}
+int dogleg_amd_dense_products_batch_uncertainty_fit_device(const double* p_dev, unsigned int B, unsigned int Nstate,
+                                                           dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                           const dogleg_parameters2_t* parameters,
+                                                           double* lambda_dev, double* covariance_dev, double* variances_dev,
+                                                           int* status_dev, const unsigned char* active_dev, void* hip_stream,
+                                                           const dogleg_amd_batch_fit_t* fit)
+{
+  return batch_unc_entry(__func__, with_fit(DlgBatchUnc{p_dev, B, Nstate, 0, nullptr, f, cookie, false, lambda_dev, covariance_dev,
+                                                        variances_dev, nullptr, nullptr, 0, status_dev, active_dev, hip_stream,
+                                                        true}, fit), parameters, 1);
+}
+int dogleg_amd_dense_batch_query_covariance_fit(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                dogleg_callback_device_batch_t* f, void* cookie, double* lambda,
+                                                const double* Jq, unsigned int Nq, unsigned int Qrows, int Nobservations,
+                                                double* out, int* status, const dogleg_amd_batch_fit_t* fit)
+{
+  return batch_query_entry(__func__, with_fit(DlgBatchQuery{p, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda, Jq, Nq, Qrows,
+                                                            Nobservations, out, status}, fit), nullptr);
+}
+int dogleg_amd_dense_products_batch_query_covariance_fit(const double* p, unsigned int B, unsigned int Nstate,
+                                                         dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                         const dogleg_parameters2_t* parameters, double* lambda,
+                                                         const double* Jq, unsigned int Nq, unsigned int Qrows,
+                                                         double* out, int* status, const dogleg_amd_batch_fit_t* fit)
+{
+  return batch_query_entry(__func__, with_fit(DlgBatchQuery{p, B, Nstate, 0, nullptr, f, cookie, false, lambda, Jq, Nq, Qrows, -1,
+                                                            out, status}, fit), parameters);
+}
+int dogleg_amd_dense_batch_query_covariance_fit_device(const double* p_dev, unsigned int B, unsigned int Nstate, unsigned int Nmeas,
+                                                       dogleg_callback_device_batch_t* f, void* cookie, double* lambda_dev,
+                                                       const double* Jq_dev, unsigned int Nq, unsigned int Qrows,
+                                                       int Nobservations, double* out_dev, int* status_dev,
+                                                       const unsigned char* active_dev, void* hip_stream,
+                                                       const dogleg_amd_batch_fit_t* fit)
+{
+  return batch_query_entry(__func__, with_fit(DlgBatchQuery{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, lambda_dev, Jq_dev,
+                                                            Nq, Qrows, Nobservations, out_dev, status_dev, active_dev, hip_stream,
+                                                            true}, fit), nullptr);
+}
+int dogleg_amd_dense_products_batch_query_covariance_fit_device(const double* p_dev, unsigned int B, unsigned int Nstate,
+                                                                dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                                const dogleg_parameters2_t* parameters, double* lambda_dev,
+                                                                const double* Jq_dev, unsigned int Nq, unsigned int Qrows,
+                                                                double* out_dev, int* status_dev,
+                                                                const unsigned char* active_dev, void* hip_stream,
+                                                                const dogleg_amd_batch_fit_t* fit)
+{
+  return batch_query_entry(__func__, with_fit(DlgBatchQuery{p_dev, B, Nstate, 0, nullptr, f, cookie, false, lambda_dev, Jq_dev, Nq,
+                                                            Qrows, -1, out_dev, status_dev, active_dev, hip_stream, true}, fit),
+                           parameters);
 }
 
 // ---- extension (not in the reference): the Jacobian of a device callback against central differences (gradcheck.hip)

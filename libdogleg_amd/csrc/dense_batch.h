@@ -24,7 +24,10 @@ struct DlgBatchSolve
   bool device;
 };
 int  dlg_dense_batch_solve(const DlgBatchSolve& a);
-// dogleg_amd_dense[_products]_batch_uncertainty[_device]; fs is 1 or 2 here
+// the fit of the ..._fit entry points (dogleg_amd_batch_fit_t, checked by the caller), the last three members of the two records
+// below: loss (a featureSize <= 4 that divides M; kind and scale checked where weights is NULL), weights [B][M / featureSize],
+// held [B][N]; all NULL: the call without _fit.  Host or device arrays as the record's other arrays
+// dogleg_amd_dense[_products]_batch_uncertainty[_fit][_device]; fs is 1 or 2 here
 struct DlgBatchUnc
 {
   const double* p; unsigned int B, N, M;
@@ -32,9 +35,10 @@ struct DlgBatchUnc
   double *lambda, *covariance, *variances, *factors, *scale; int fs; int* status;
   const unsigned char* active; void* stream;
   bool device;
+  const dogleg_amd_batch_loss_t* loss; const double* weights; const unsigned char* held;
 };
 int  dlg_dense_batch_uncertainty(const DlgBatchUnc& a);
-// dogleg_amd_dense[_products]_batch_query_covariance[_device]; the products form has no Nobservations (< 0: the plain form)
+// dogleg_amd_dense[_products]_batch_query_covariance[_fit][_device]; the products form has no Nobservations (< 0: the plain form)
 struct DlgBatchQuery
 {
   const double* p; unsigned int B, N, M;
@@ -42,6 +46,7 @@ struct DlgBatchQuery
   double* lambda; const double* Jq; unsigned int Nq, Qrows; int Nobservations; double* out; int* status;
   const unsigned char* active; void* stream;
   bool device;
+  const dogleg_amd_batch_loss_t* loss; const double* weights; const unsigned char* held;
 };
 int  dlg_dense_batch_query(const DlgBatchQuery& a);
 #pragma GCC visibility pop

@@ -1,6 +1,7 @@
 // dense_batch.hip -- the host side of the batch solver: what is kept between calls (the cache), and one call path per kind of
 // request of dense_batch.h -- the solve (solve_locked: the rounds), and the uncertainty and query calls (evaluate_at: one
-// callback and ONE launch).  Each path serves the J and the products form, host arrays and the caller's device arrays.  The
+// callback and ONE launch; with the fit of the ..._fit entry points, whose weights and held set travel with the inputs).  Each
+// path serves the J and the products form, host arrays and the caller's device arrays.  The
 // kernels and what they compute: dense_batch_kernels.hip; their arguments and launchers: dense_batch_dev.h.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -397,13 +398,33 @@ struct EvalCall
   // are one copy each; the live bytes lie behind them.  state_d: their doubles, for the refusal
   Segments stage; size_t o_lam, o_st; double state_d;
   const DlgBatchQuery* query;  // a query call (for the refusal), or nullptr
+  // the fit of the ..._fit forms (dense_batch.h), all nullptr without one; the host route stages weights and held at o_wts and
+  // o_held (stage_fit), among the inputs in front of o_lam, so that they go up with p and do not come down again
+  const dogleg_amd_batch_loss_t* loss; const double* weights; const unsigned char* held;
+  size_t o_wts, o_held, wts_bytes, held_bytes;
+  bool fit() const { return loss || weights || held; }
 };
 template <class Req> EvalCall eval_call(const char* who, const Req& a)
 {
   EvalCall c{};
   c.who = who; c.F = BatchForm{a.fJ, a.fP, a.unpacked}; c.B = a.B; c.N = a.N; c.M = a.M; c.cookie = a.cookie;
   c.p = a.p; c.lambda = a.lambda; c.status = a.status; c.active = a.active; c.stream = a.stream; c.device = a.device;
+  c.loss = a.loss; c.weights = a.weights; c.held = a.held;
   return c;
+}
+// rows a weight feature of a (checked) loss; 1 without one
+unsigned int loss_fs(const dogleg_amd_batch_loss_t* loss)
+{
+  return loss && loss->featureSize > 1 ? (unsigned int)loss->featureSize : 1u;
+}
+// the segments of weights and held in the staging buffer: behind the inputs added so far, in front of lambda.  Returns their
+// doubles, for the refusal
+double stage_fit(EvalCall& c)
+{
+  c.wts_bytes = c.weights ? sizeof(double)*(size_t)c.B*(c.M/loss_fs(c.loss)) : 0;
+  c.held_bytes = c.held ? (size_t)c.B*c.N : 0;
+  c.o_wts = c.stage.add(c.wts_bytes); c.o_held = c.stage.add(c.held_bytes);
+  return (double)(c.wts_bytes + c.held_bytes)/8.0;
 }
 // where an array of a kind lies for the kernel: nowhere if the caller has none, at off of the state buffer d on the host route,
 // where the caller has it on the device route (d == nullptr)
@@ -411,9 +432,21 @@ template <class T> T* placed(char* d, size_t off, T* callers)
 {
   return !callers ? nullptr : d ? (T*)(d + off) : callers;
 }
+// the kernels' argument of a call's fit
+FitDev fit_dev(const EvalCall& c, char* d)
+{
+  FitDev F;
+  // (with weights given, kind and scale are not read)
+  const bool eval = c.loss && !c.weights && c.loss->kind != DOGLEG_AMD_LOSS_TRIVIAL;
+  F.L.kind = eval ? c.loss->kind : DOGLEG_AMD_LOSS_TRIVIAL; F.L.fs = (int)loss_fs(c.loss);
+  F.L.a = eval ? c.loss->scale : 1.0; F.L.c = F.L.a*F.L.a;
+  F.wts = placed(d, c.o_wts, c.weights); F.held = placed(d, c.o_held, c.held);
+  F.fit = c.fit() ? 1 : 0;
+  return F;
+}
 // U: the kernel's argument (of a query: its front half), its shape filled in.  bind(d): the kind's own pointers into the
-// kernel's argument (placed); gather(h): its inputs into the staging buffer h; launch(st); scatter(h): its outputs from h into the
-// caller's arrays.  gather and scatter: the host route only.  Counted into t_unc_stats where they happen: kernel launches,
+// kernel's argument (placed); gather(h): its inputs into the staging buffer h; launch(st, fit): with the call's fit as the kernels
+// take it (weights and held are staged and placed here, for both kinds); scatter(h): its outputs from h into the caller's arrays.  gather and scatter: the host route only.  Counted into t_unc_stats where they happen: kernel launches,
 // synchronisations, copies + fills.
 // The device route keeps of the cache x / J (or the products) and at most two small arrays: a zeroed lambda where the caller
 // gives none and the live bytes, all 1, where no mask is given (the mask itself is the callback's live_dev otherwise)
@@ -435,6 +468,7 @@ int evaluate_at(const EvalCall& c, UncDev& U, Bind bind, Gather gather, Launch l
   unsigned char* own_live = (unsigned char*)(d + io_bytes);
   point_at_eval(U, c.F, E, K.d_eval);
   bind(c.device ? nullptr : d);
+  const FitDev fit = fit_dev(c, c.device ? nullptr : d);
   U.lam = c.device ? (c.lambda ? c.lambda : (double*)d) : (double*)(d + c.o_lam);
   U.status = c.device ? c.status : (int*)(d + c.o_st);
   U.active = c.active;
@@ -452,13 +486,15 @@ int evaluate_at(const EvalCall& c, UncDev& U, Bind bind, Gather gather, Launch l
     memcpy(h, c.p, sizeof(double)*(size_t)B*N);
     if(c.lambda) memcpy(h + c.o_lam, c.lambda, sizeof(double)*B); else memset(h + c.o_lam, 0, sizeof(double)*B);
     gather(h);
+    if(c.weights) memcpy(h + c.o_wts, c.weights, c.wts_bytes);
+    if(c.held) memcpy(h + c.o_held, c.held, c.held_bytes);
     BHIP(hipMemcpyAsync(d, h, c.o_st, hipMemcpyHostToDevice, st)); ts[2] += 1.0;
   }
   if(!c.active) { BHIP(hipMemsetAsync(own_live, 1, B, st)); ts[2] += 1.0; }
   if(T.mark(who, 0, st)) return -1;
   invoke_callback(c.F, d_p, U, d_live, B, st, c.cookie);
   if(T.mark(who, 1, st)) return -1;
-  launch(st);
+  launch(st, fit);
   BHIP(hipGetLastError()); ts[0] += 1.0;
   if(T.mark(who, 2, st)) return -1;
   if(!c.device) { BHIP(hipMemcpyAsync(h + c.o_lam, d + c.o_lam, io_bytes - c.o_lam, hipMemcpyDeviceToHost, st)); ts[2] += 1.0; }
@@ -472,22 +508,25 @@ int evaluate_at(const EvalCall& c, UncDev& U, Bind bind, Gather gather, Launch l
   return 0;
 }
 
-// host layout: p | lambda | scale | status | variances | covariance | factors
+// host layout: p | weights | held | lambda | scale | status | variances | covariance | factors
 int unc_locked(const DlgBatchUnc& a)
 {
-  static const char* const names[2][2] = {
-    {"dogleg_amd_dense_batch_uncertainty", "dogleg_amd_dense_batch_uncertainty_device"},
-    {"dogleg_amd_dense_products_batch_uncertainty", "dogleg_amd_dense_products_batch_uncertainty_device"}};
-  EvalCall c = eval_call(names[a.fP ? 1 : 0][a.device ? 1 : 0], a);
+  static const char* const names[2][2][2] = {
+    {{"dogleg_amd_dense_batch_uncertainty", "dogleg_amd_dense_batch_uncertainty_device"},
+     {"dogleg_amd_dense_products_batch_uncertainty", "dogleg_amd_dense_products_batch_uncertainty_device"}},
+    {{"dogleg_amd_dense_batch_uncertainty_fit", "dogleg_amd_dense_batch_uncertainty_fit_device"},
+     {"dogleg_amd_dense_products_batch_uncertainty_fit", "dogleg_amd_dense_products_batch_uncertainty_fit_device"}}};
+  EvalCall c = eval_call(names[a.loss || a.weights || a.held ? 1 : 0][a.fP ? 1 : 0][a.device ? 1 : 0], a);
   const unsigned int B = a.B, N = a.N, NF = a.M/(unsigned int)a.fs;
   const size_t vec_bytes = sizeof(double)*(size_t)B*N, fac_bytes = sizeof(double)*(size_t)B*NF;
   c.stage.add(vec_bytes);
+  const double fit_d = stage_fit(c);
   c.o_lam = c.stage.add(sizeof(double)*(size_t)B);
   const size_t o_scale = c.stage.add(sizeof(double)*(size_t)B);
   c.o_st = c.stage.add(sizeof(int)*(size_t)B);
   const size_t o_var = c.stage.add(a.variances ? vec_bytes : 0), o_cov = c.stage.add(a.covariance ? vec_bytes*N : 0);
   const size_t o_fac = c.stage.add(a.factors ? fac_bytes : 0);
-  c.state_d = (double)B*((double)N + 3.0 + (a.variances ? N : 0.0) + (a.covariance ? (double)N*N : 0.0) + (a.factors ? NF : 0.0));
+  c.state_d = (double)B*((double)N + 3.0 + (a.variances ? N : 0.0) + (a.covariance ? (double)N*N : 0.0) + (a.factors ? NF : 0.0)) + fit_d;
   UncDev A;
   A.B = (int)B; A.N = (int)N; A.M = (int)a.M; A.NP = (int)(N*(N + 1)/2); A.fs = a.fs; A.NF = (int)NF;
   return evaluate_at(c, A,
@@ -496,7 +535,7 @@ int unc_locked(const DlgBatchUnc& a)
       A.var = placed(d, o_var, a.variances); A.cov = placed(d, o_cov, a.covariance); A.fac = placed(d, o_fac, a.factors);
     },
     [&](char* h) { if(a.factors) memcpy(h + o_scale, a.scale, sizeof(double)*B); },
-    [&](hipStream_t st) { launch_batch_uncertainty(st, A); },
+    [&](hipStream_t st, const FitDev& fit) { launch_batch_uncertainty(st, A, fit); },
     [&](const char* h) {
       if(a.factors) { memcpy(a.scale, h + o_scale, sizeof(double)*B); memcpy(a.factors, h + o_fac, fac_bytes); }
       if(a.variances) memcpy(a.variances, h + o_var, vec_bytes);
@@ -504,21 +543,24 @@ int unc_locked(const DlgBatchUnc& a)
     });
 }
 
-// host layout: p | Jq | lambda | status | out
+// host layout: p | Jq | weights | held | lambda | status | out
 int query_locked(const DlgBatchQuery& a)
 {
-  static const char* const names[2][2] = {
-    {"dogleg_amd_dense_batch_query_covariance", "dogleg_amd_dense_batch_query_covariance_device"},
-    {"dogleg_amd_dense_products_batch_query_covariance", "dogleg_amd_dense_products_batch_query_covariance_device"}};
-  EvalCall c = eval_call(names[a.fP ? 1 : 0][a.device ? 1 : 0], a);
+  static const char* const names[2][2][2] = {
+    {{"dogleg_amd_dense_batch_query_covariance", "dogleg_amd_dense_batch_query_covariance_device"},
+     {"dogleg_amd_dense_products_batch_query_covariance", "dogleg_amd_dense_products_batch_query_covariance_device"}},
+    {{"dogleg_amd_dense_batch_query_covariance_fit", "dogleg_amd_dense_batch_query_covariance_fit_device"},
+     {"dogleg_amd_dense_products_batch_query_covariance_fit", "dogleg_amd_dense_products_batch_query_covariance_fit_device"}}};
+  EvalCall c = eval_call(names[a.loss || a.weights || a.held ? 1 : 0][a.fP ? 1 : 0][a.device ? 1 : 0], a);
   const unsigned int B = a.B, N = a.N;
   const size_t rows = (size_t)B*a.Nq*a.Qrows, Jq_bytes = sizeof(double)*rows*N, out_bytes = sizeof(double)*rows*a.Qrows;
   c.stage.add(sizeof(double)*(size_t)B*N);
   const size_t o_Jq = c.stage.add(Jq_bytes);
+  const double fit_d = stage_fit(c);
   c.o_lam = c.stage.add(sizeof(double)*(size_t)B);
   c.o_st = c.stage.add(sizeof(int)*(size_t)B);
   const size_t o_out = c.stage.add(out_bytes);
-  c.state_d = (double)B*((double)N + 3.0);
+  c.state_d = (double)B*((double)N + 3.0) + fit_d;
   c.query = &a;
   QueryDev A;
   UncDev& U = A.U;
@@ -528,7 +570,7 @@ int query_locked(const DlgBatchQuery& a)
   return evaluate_at(c, U,
     [&](char* d) { A.Jq = placed(d, o_Jq, a.Jq); A.out = placed(d, o_out, a.out); },
     [&](char* h) { memcpy(h + o_Jq, a.Jq, Jq_bytes); },
-    [&](hipStream_t st) { launch_batch_query(st, A); },
+    [&](hipStream_t st, const FitDev& fit) { launch_batch_query(st, A, fit); },
     [&](const char* h) { memcpy(a.out, h + o_out, out_bytes); });
 }
 

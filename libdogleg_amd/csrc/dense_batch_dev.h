@@ -46,6 +46,14 @@ struct UncDev
   ProductsDev P;               // FORM_PRODUCTS (x, J, M, fs, NF unused there; fac and scale nullptr: they need J)
   const unsigned char* active; // [B] or nullptr (all): 0: problem b is skipped, only its status is written
 };
+// the fit of the ..._fit forms of the uncertainty and query calls (dogleg.h: dogleg_amd_batch_fit_t), a kernel argument of its own
+// behind UncDev / QueryDev, so that the kernels without a fit read their arguments where they did.  L.fs rows a weight feature;
+// wts [B][M / L.fs] or nullptr: w_f = rho'(s_f) from L at the callback's x (L.kind TRIVIAL: 1); held [B][N] or nullptr
+struct FitDev
+{
+  LossDev L; const double* wts; const unsigned char* held;
+  int fit;                     // (host side: which kernel is launched)
+};
 
 struct QueryDev
 {
@@ -62,11 +70,11 @@ __host__ __device__ inline unsigned char held_code(double p, double g, double lo
 }
 
 // ---- the launchers (dense_batch_kernels.hip): one launch each on st, the instantiation chosen from what the record says (the
-// size class of N, the form, robust, bounded).  The caller asks hipGetLastError
+// size class of N, the form, robust, bounded, fit).  The caller asks hipGetLastError
 #pragma GCC visibility push(hidden)
 void launch_batch_round(hipStream_t st, const BatchDev& A);
-void launch_batch_uncertainty(hipStream_t st, const UncDev& A);
-void launch_batch_query(hipStream_t st, const QueryDev& A);
+void launch_batch_uncertainty(hipStream_t st, const UncDev& A, const FitDev& F);
+void launch_batch_query(hipStream_t st, const QueryDev& A, const FitDev& F);
 // active: [B] or nullptr (all): the initial live bytes
 void launch_batch_init(hipStream_t st, const BatchDev& A, const unsigned char* active);
 void launch_batch_clamp(hipStream_t st, const BatchDev& A);

@@ -39,6 +39,13 @@
 // the eight steps above the prototype in dogleg.h.  BOUNDED is a template flag of batch_problem and k_batch_round beside ROBUST
 // (J form only); everything it adds lies behind the sweep, on the on-chip JtJ, g and the two cached steps, and needs no LDS of
 // its own.  k_batch_clamp (behind k_batch_init) clamps the start points; k_batch_finish, or solve_locked (dense_batch.hip) on the host, forms held.
+//
+// The fit forms (dogleg_amd_dense[_products]_batch_uncertainty_fit, _query_covariance_fit and their _device twins): the two
+// kernels above at the optimum of a robust or bounded solve.  FIT is a template flag of factor_and_invert, unc_problem,
+// query_problem and the two kernels: the rows of x and J are multiplied by sqrt(w) of their feature while they are staged
+// (SWEEP_FIT of sweep_point; the second sweep and the sweep for G do the same), the held rows and columns of the matrix that is
+// factorised are those of the identity, and the held diagonal entries of X = L^-1 are cleared, so that everything behind X has
+// exact zeros there.  The held set is one 64-bit value a wave; no LDS is added.  The instantiations without FIT keep their text.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cfloat>
@@ -231,10 +238,19 @@ __device__ __forceinline__ double feature_s(const double* xf, int fs)
 // gets s of its feature by shuffles, evaluates rho and rho' and stages sqrt(w) x; every staged element of J is multiplied
 // by the sqrt(w) of its row (the element -> row map is the same for every tile).  The loop over the tile's rows is the plain
 // one.  Returns F.
-template <int NMAX, bool ROBUST = false>
+//
+// SWEEP_FIT: the sweep of the weighted problem at a point that is given (the fit forms of the uncertainty and query calls): the
+// tile height, the element -> row map and the staging are those of SWEEP_ROBUST; w of a row's feature comes from wb ([M / L.fs],
+// loaded with the tile's x, so one tile ahead) or, with wb == nullptr, from the loss as above.  Every product sqrt(w) x and
+// sqrt(w) J is rounded once, as a callback that scales the rows would write it.  Returns the sum of the squares of the WEIGHTED
+// x, not F: with L TRIVIAL of size 1 and no wb, SWEEP_PLAIN's bits.  bad: a weight of wb that is negative or not finite.
+enum { SWEEP_PLAIN = 0, SWEEP_ROBUST = 1, SWEEP_FIT = 2 };
+template <int NMAX, int MODE = SWEEP_PLAIN>
 __device__ __forceinline__ double sweep_point(const double* Jb, const double* xb, int N, int M, int NP, int lane,
-                                              double* SA, double* tile, double& gacc_out, const LossDev& L = LossDev())
+                                              double* SA, double* tile, double& gacc_out, const LossDev& L = LossDev(),
+                                              const double* wb = nullptr, bool* bad = nullptr)
 {
+  constexpr bool ROBUST = MODE == SWEEP_ROBUST, FIT = MODE == SWEEP_FIT;
   using C = BatchCfg<NMAX>;
   double* xt = tile + BATCH_TILE;
   int ei[C::NE], ej[C::NE];
@@ -246,23 +262,57 @@ __device__ __forceinline__ double sweep_point(const double* Jb, const double* xb
   constexpr int NL = BATCH_TILE/64;
   double v[NL], xv;
   int rowof[NL], t0 = 0;       // ROBUST: the row of the tile element lane + 64 u; the first row of this lane's feature
-  if constexpr(ROBUST)
+  if constexpr(ROBUST || FIT)
   {
     T -= T % L.fs;
     t0 = lane - lane % L.fs;
 #pragma unroll
     for(int u = 0; u < NL; u++) rowof[u] = min((lane + 64*u)/N, 63);     // (elements behind the tile's rows hold 0)
   }
+  [[maybe_unused]] double wv = 1.0;             // FIT with wb: w of this lane's row (1 behind the tile's rows)
+  [[maybe_unused]] bool wbad = false;
   {
     const int tc = min(T, M), cnt = tc*N;
 #pragma unroll
     for(int u = 0; u < NL; u++) v[u] = lane + 64*u < cnt ? Jb[lane + 64*u] : 0.0;
     xv = lane < tc ? xb[lane] : 0.0;
+    if constexpr(FIT) { if(wb && lane < tc) wv = wb[lane/L.fs]; }
   }
   for(int r0 = 0; r0 < M; r0 += T)
   {
     const int tc = min(T, M - r0);
-    if constexpr(ROBUST)
+    if constexpr(FIT)
+    {
+      double sw = 1.0;
+      if(wb)
+      {
+        // (rows behind the tile's hold w = 1)
+        wbad = wbad || !(wv >= 0.0) || !isfinite(wv);
+        sw = sqrt(wv);
+      }
+      else if(L.kind != DOGLEG_AMD_LOSS_TRIVIAL)
+      {
+        // s of the feature as SWEEP_ROBUST forms it: the bits of feature_s, so w has the bits the robust solve returns
+        const double x2 = xv*xv;
+        double s = x2;
+        if(L.fs > 1)
+        {
+          s = __shfl(x2, t0, 64);
+          for(int k = 1; k < L.fs; k++) s += __shfl(x2, t0 + k, 64);
+        }
+        double rho, w;
+        loss_eval(L, s, rho, w);
+        if(lane < tc) sw = sqrt(w);
+      }
+      const double xs = sw*xv;
+      wsync();
+#pragma unroll
+      for(int u = 0; u < NL; u++) tile[lane + 64*u] = v[u]*__shfl(sw, rowof[u], 64);
+      xt[lane] = xs;
+      wsync();
+      n2 = __builtin_fma(xs, xs, n2);
+    }
+    else if constexpr(ROBUST)
     {
       // sqrt(w) of this lane's row (1 behind the tile's rows) and the feature's rho, once a feature
       double sw = 1.0;
@@ -309,6 +359,7 @@ __device__ __forceinline__ double sweep_point(const double* Jb, const double* xb
 #pragma unroll
       for(int u = 0; u < NL; u++) v[u] = lane + 64*u < cnt ? Jn[lane + 64*u] : 0.0;
       xv = lane < tn ? xb[r1 + lane] : 0.0;
+      if constexpr(FIT) { if(wb) wv = lane < tn ? wb[(r1 + lane)/L.fs] : 1.0; }
     }
     for(int t = 0; t < tc; t++)
     {
@@ -324,6 +375,7 @@ __device__ __forceinline__ double sweep_point(const double* Jb, const double* xb
   for(int k = 0; k < C::NE; k++) if(lane + 64*k < NP) SA[lane + 64*k] = acc[k];
   wsync();
   gacc_out = gacc;
+  if constexpr(FIT) { if(bad) *bad = __any(wbad); }
   return n2x;
 }
 
@@ -698,20 +750,35 @@ __device__ inline double feature2(const double* SA, const double* ra, int NS, in
 // SA, the finiteness test, the lambda loop on chol_packed in SL and, where that stands, X = L^-1 in place.  Between the two,
 // report(ok, lambda, norm2(x)) is the caller's: what it writes back of the factorisation and, for a problem that failed, the
 // NaN of its outputs.  Returns whether the factorisation stands.
-template <int NMAX, int FORM, class Report>
-__device__ __forceinline__ bool factor_and_invert(const UncDev& A, int b, int lane, double* SA, double* SL, Report report)
+//
+// FIT (dogleg.h: dogleg_amd_batch_fit_t): the sweep is that of the weighted rows (SWEEP_FIT; report gets the sum of their
+// squares, NaN with a bad weight); hm gets the held set, bit i for variable i, the same in every lane; the held rows and columns of
+// the matrix that is factorised are the identity's, as in the bounded solve, so the factor and X have unit vectors there; and the
+// held diagonal entries of X are cleared: X' X, X q and X' z then have exact zeros in the held places and the inverse of the free
+// block in the others.  hm stays 0 otherwise.
+template <int NMAX, int FORM, bool FIT, class Report>
+__device__ __forceinline__ bool factor_and_invert(const UncDev& A, const FitDev& F, int b, int lane, double* SA, double* SL,
+                                                  unsigned long long& hm, Report report)
 {
   const int N = A.N, M = A.M, NP = A.NP;
   double gacc, n2x;
   bool ok;
   if constexpr(FORM == FORM_J)
   {
-    n2x = sweep_point<NMAX>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc);
+    if constexpr(FIT)
+    {
+      bool bad;
+      n2x = sweep_point<NMAX, SWEEP_FIT>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc, F.L,
+                                         F.wts ? F.wts + (size_t)b*(M/F.L.fs) : nullptr, &bad);
+      if(bad) n2x = __builtin_nan("");
+    }
+    else n2x = sweep_point<NMAX>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc);
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     ok = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
   }
   else
     n2x = load_products<NMAX>(A.P, b, N, NP, lane, SA, gacc, ok);
+  if constexpr(FIT) { if(F.held) hm = __ballot(lane < N && F.held[(size_t)b*N + lane] != 0); }
 
   // ---- the factorisation at lambda[b]; a pivot <= 0 moves lambda as the solve does (dogleg.c:634-820) ----
   double lam = A.lam[b];
@@ -723,6 +790,20 @@ __device__ __forceinline__ bool factor_and_invert(const UncDev& A, int b, int la
     wsync();
     if(lam > 0.0 && lane < N) SL[col_off(lane, N)] += lam;
     wsync();
+    if constexpr(FIT)
+    {
+      if(hm)
+      {
+        int c = 0;
+        for(int e = lane; e < NP; e += 64)
+        {
+          while(e >= col_off(c + 1, N)) c++;
+          const int i = c + e - col_off(c, N);
+          if(((hm >> c) | (hm >> i)) & 1) SL[e] = i == c ? 1.0 : 0.0;
+        }
+        wsync();
+      }
+    }
     if(chol_packed(SL, N, lane)) break;
     lam = lam == 0.0 ? LAMBDA_INITIAL : lam*10.0;
     if(!isfinite(lam)) ok = false;
@@ -747,25 +828,50 @@ __device__ __forceinline__ bool factor_and_invert(const UncDev& A, int b, int la
     if(i < N) SL[jj + 1 + lane] = s;
     wsync();
   }
+  if constexpr(FIT)
+  {
+    if(hm)
+    {
+      if((hm >> lane) & 1) SL[col_off(lane, N)] = 0.0;
+      wsync();
+    }
+  }
   return true;
 }
 
-template <int NMAX, int FORM>
-__device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
+// sqrt(w) of row r of a problem under the fit F, outside the first sweep: from its weights wb ([M / F.L.fs] or nullptr)
+// or from the loss at the callback's x (xb: [M]), the bits the first sweep multiplied that row by
+__device__ __forceinline__ double fit_sqrt_w(const FitDev& F, const double* wb, const double* xb, int r)
+{
+  const int f = r/F.L.fs;
+  if(wb) return sqrt(wb[f]);
+  if(F.L.kind == DOGLEG_AMD_LOSS_TRIVIAL) return 1.0;
+  double rho, w;
+  loss_eval(F.L, feature_s(xb + (size_t)f*F.L.fs, F.L.fs), rho, w);
+  return sqrt(w);
+}
+
+// FIT: the leverage blocks and x of the second sweep are those of the weighted rows, against a Sigma with zero held rows and
+// columns; a computed scale counts the free variables only
+template <int NMAX, int FORM, bool FIT>
+__device__ void unc_problem(const UncDev& A, const FitDev& F, int b, int lane, double* S)
 {
   using C = BatchCfg<NMAX>;
   const int N = A.N, M = A.M, NP = A.NP;
   double* SA = S;                      // JtJ, then Sigma
   double* SL = S + C::NP;              // the row tile of the sweeps; between them the factor and its inverse
   const double* Jb = nullptr; const double* xb = nullptr;
+  [[maybe_unused]] const double* wb = nullptr;
   if constexpr(FORM == FORM_J)
   {
     Jb = A.J + (size_t)b*M*N;
     xb = A.x + (size_t)b*M;
+    if constexpr(FIT) { if(F.wts) wb = F.wts + (size_t)b*(M/F.L.fs); }
   }
 
   double scale = 0.0;
-  const bool stands = factor_and_invert<NMAX, FORM>(A, b, lane, SA, SL, [&](bool ok, double lam, double n2x)
+  unsigned long long hm = 0;
+  const bool stands = factor_and_invert<NMAX, FORM, FIT>(A, F, b, lane, SA, SL, hm, [&](bool ok, double lam, double n2x)
   {
     if(A.fac)
     {
@@ -773,7 +879,12 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
       if(!(scale > 0.0))
       {
         // NoutlierFeatures = 0 (api_extensions.cpp: outlier_scale); NaN for a problem that failed on a non-finite x
-        scale = (double)M/(4.0*((double)(N + 1)*n2x/(double)(M - N - 1)));
+        if constexpr(FIT)
+        {
+          const int NFree = N - __popcll(hm);
+          scale = (double)M/(4.0*((double)(NFree + 1)*n2x/(double)(M - NFree - 1)));
+        }
+        else scale = (double)M/(4.0*((double)(N + 1)*n2x/(double)(M - N - 1)));
         if(lane == 0) A.scale[b] = scale;
       }
     }
@@ -829,18 +940,38 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
       const int tc = min(T, Mc - r0), cnt = tc*N;
       const double* Jt = Jb + (size_t)r0*N;
       wsync();
-      for(int e = lane, r = lane/N, c = lane - r*N; e < cnt; e += 64)
+      if constexpr(FIT)
       {
-        tile[r*NS + c] = Jt[e];
-        c += 64;
-        while(c >= N) { c -= N; r++; }
+        // lane t holds sqrt(w) of row t of the tile; every lane makes every trip, so that the shuffle finds its source
+        const double sw = lane < tc ? fit_sqrt_w(F, wb, xb, r0 + lane) : 1.0;
+        for(int e = lane, r = lane/N, c = lane - r*N; e - lane < cnt; e += 64)
+        {
+          const double m = __shfl(sw, r & 63, 64);
+          if(e < cnt) tile[r*NS + c] = Jt[e]*m;
+          c += 64;
+          while(c >= N) { c -= N; r++; }
+        }
       }
+      else
+        for(int e = lane, r = lane/N, c = lane - r*N; e < cnt; e += 64)
+        {
+          tile[r*NS + c] = Jt[e];
+          c += 64;
+          while(c >= N) { c -= N; r++; }
+        }
       wsync();
       if(lane*fs < tc)
       {
         const size_t f = (size_t)(r0/fs + lane);
-        if(fs == 1) A.fac[(size_t)b*NF + f] = feature1(SA, tile + lane*NS, N, xb[r0 + lane], kf);
-        else        A.fac[(size_t)b*NF + f] = feature2(SA, tile + 2*lane*NS, NS, N, xb[r0 + 2*lane], xb[r0 + 2*lane + 1], kf);
+        if constexpr(FIT)
+        {
+          const int r = r0 + fs*lane;
+          const double x0 = fit_sqrt_w(F, wb, xb, r)*xb[r];
+          if(fs == 1) A.fac[(size_t)b*NF + f] = feature1(SA, tile + lane*NS, N, x0, kf);
+          else        A.fac[(size_t)b*NF + f] = feature2(SA, tile + 2*lane*NS, NS, N, x0, fit_sqrt_w(F, wb, xb, r + 1)*xb[r + 1], kf);
+        }
+        else if(fs == 1) A.fac[(size_t)b*NF + f] = feature1(SA, tile + lane*NS, N, xb[r0 + lane], kf);
+        else             A.fac[(size_t)b*NF + f] = feature2(SA, tile + 2*lane*NS, NS, N, xb[r0 + 2*lane], xb[r0 + 2*lane + 1], kf);
       }
     }
     return;
@@ -863,8 +994,22 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
   {
     const int tc = min(T, Mc - r0);
     wsync();
+    if constexpr(FIT)
+    {
+      // lane t holds sqrt(w) of row t of the tile (the rows behind the tile's hold 0)
+      const double sw = lane < tc ? fit_sqrt_w(F, wb, xb, r0 + lane) : 1.0;
 #pragma unroll
-    for(int u = 0; u < NL; u++) if(lane + 64*u < T*N) tile[po[u]] = v[u];
+      for(int u = 0; u < NL; u++)
+      {
+        const double m = __shfl(sw, min((lane + 64*u)/N, 63), 64);
+        if(lane + 64*u < T*N) tile[po[u]] = v[u]*m;
+      }
+    }
+    else
+    {
+#pragma unroll
+      for(int u = 0; u < NL; u++) if(lane + 64*u < T*N) tile[po[u]] = v[u];
+    }
     wsync();
     if(r0 + T < Mc)
     {
@@ -888,7 +1033,8 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
           for(int i = j + 1; i < N; i++) t0 += SA[idx++]*r[i];
           a += rj*(d*rj + 2.0*t0);
         }
-        A.fac[(size_t)b*NF + f] = factor1(a, xb[r0 + lane], kf);
+        if constexpr(FIT) A.fac[(size_t)b*NF + f] = factor1(a, fit_sqrt_w(F, wb, xb, r0 + lane)*xb[r0 + lane], kf);
+        else              A.fac[(size_t)b*NF + f] = factor1(a, xb[r0 + lane], kf);
       }
       else
       {
@@ -902,14 +1048,19 @@ __device__ void unc_problem(const UncDev& A, int b, int lane, double* S)
           for(int i = j + 1; i < N; i++) { const double s = SA[idx++]; t0 += s*ra[i]; t1 += s*rb[i]; }
           a00 += aj*(d*aj + 2.0*t0); a01 += aj*(d*bj + t1) + bj*t0; a11 += bj*(d*bj + 2.0*t1);
         }
-        A.fac[(size_t)b*NF + f] = factor2(a00, a01, a11, xb[r0 + 2*lane], xb[r0 + 2*lane + 1], kf);
+        if constexpr(FIT)
+        {
+          const int r = r0 + 2*lane;
+          A.fac[(size_t)b*NF + f] = factor2(a00, a01, a11, fit_sqrt_w(F, wb, xb, r)*xb[r], fit_sqrt_w(F, wb, xb, r + 1)*xb[r + 1], kf);
+        }
+        else A.fac[(size_t)b*NF + f] = factor2(a00, a01, a11, xb[r0 + 2*lane], xb[r0 + 2*lane + 1], kf);
       }
     }
   }
 }
 
-template <int NMAX, int FORM>
-__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_uncertainty(UncDev A)
+template <int NMAX, int FORM, bool FIT>
+__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_uncertainty(UncDev A, FitDev F)
 {
   constexpr int LDSW = BatchCfg<NMAX>::NP + FormCfg<NMAX, FORM>::SCR, WPB = BatchCfg<NMAX>::WPB;
   __shared__ double lds[WPB*LDSW];
@@ -922,7 +1073,7 @@ __global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_uncertainty(Un
     if(lane == 0) A.status[b] = DOGLEG_AMD_BATCH_UNC_SKIPPED;
     return;
   }
-  unc_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
+  unc_problem<NMAX, FORM, FIT>(A, F, b, lane, lds + w*LDSW);
 }
 
 // a . b over the wave, every lane ending with the same bits: the products are rounded before the butterfly.  (An FMA that took
@@ -954,8 +1105,9 @@ template <int NMAX, int FORM> struct QueryCfg
   static_assert(sizeof(double)*C::WPB*LDSW <= 65536, "k_batch_query: the wavefronts of a workgroup need more than 64 KB of LDS");
 };
 
-template <int NMAX, int FORM>
-__device__ void query_problem(const QueryDev& A, int b, int lane, double* S)
+// FIT: G is that of the weighted rows, X that of the free block (factor_and_invert); everything behind them is the same text
+template <int NMAX, int FORM, bool FIT>
+__device__ void query_problem(const QueryDev& A, const FitDev& F, int b, int lane, double* S)
 {
   using C = BatchCfg<NMAX>;
   using QC = QueryCfg<NMAX, FORM>;
@@ -978,10 +1130,15 @@ __device__ void query_problem(const QueryDev& A, int b, int lane, double* S)
     {
       // sweep_point over the first nobs rows: its JtJ is G (nobs = 0: no row is read, G is exactly 0)
       double g;
-      (void)sweep_point<NMAX>(U.J + (size_t)b*U.M*N, U.x + (size_t)b*U.M, N, A.nobs, U.NP, lane, SG, SL, g);
+      if constexpr(FIT)
+        (void)sweep_point<NMAX, SWEEP_FIT>(U.J + (size_t)b*U.M*N, U.x + (size_t)b*U.M, N, A.nobs, U.NP, lane, SG, SL, g, F.L,
+                                           F.wts ? F.wts + (size_t)b*(U.M/F.L.fs) : nullptr);
+      else
+        (void)sweep_point<NMAX>(U.J + (size_t)b*U.M*N, U.x + (size_t)b*U.M, N, A.nobs, U.NP, lane, SG, SL, g);
     }
   }
-  const bool stands = factor_and_invert<NMAX, FORM>(U, b, lane, SA, SL, [&](bool ok, double lam, double)
+  unsigned long long hm = 0;
+  const bool stands = factor_and_invert<NMAX, FORM, FIT>(U, F, b, lane, SA, SL, hm, [&](bool ok, double lam, double)
   {
     if(lane == 0) { U.lam[b] = lam; U.status[b] = ok ? DOGLEG_AMD_BATCH_UNC_OK : DOGLEG_AMD_BATCH_UNC_FAILED; }
     if(!ok)
@@ -1056,8 +1213,8 @@ __device__ void query_problem(const QueryDev& A, int b, int lane, double* S)
   }
 }
 
-template <int NMAX, int FORM>
-__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_query(QueryDev A)
+template <int NMAX, int FORM, bool FIT>
+__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_query(QueryDev A, FitDev F)
 {
   constexpr int LDSW = QueryCfg<NMAX, FORM>::LDSW, WPB = BatchCfg<NMAX>::WPB;
   __shared__ double lds[WPB*LDSW];
@@ -1070,7 +1227,7 @@ __global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_query(QueryDev
     if(lane == 0) A.U.status[b] = DOGLEG_AMD_BATCH_UNC_SKIPPED;
     return;
   }
-  query_problem<NMAX, FORM>(A, b, lane, lds + w*LDSW);
+  query_problem<NMAX, FORM, FIT>(A, F, b, lane, lds + w*LDSW);
 }
 
 // active: [B] or nullptr (all); a problem with active[b] == 0 starts, and stays, not live
@@ -1162,10 +1319,10 @@ template <class Fn> void for_size_class(int N, Fn fn)
   else             fn(std::integral_constant<int, 64>{});
 }
 // the grid and the block follow the size class: BatchCfg<NMAX>::WPB problems per workgroup
-template <int NMAX, class Arg> void launch_class(void (*kernel)(Arg), hipStream_t st, int B, const Arg& A)
+template <int NMAX, class... Args> void launch_class(void (*kernel)(Args...), hipStream_t st, int B, const Args&... A)
 {
   constexpr int WPB = BatchCfg<NMAX>::WPB;
-  hipLaunchKernelGGL(kernel, dim3((B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A);
+  hipLaunchKernelGGL(kernel, dim3((B + WPB - 1)/WPB), dim3(64*WPB), 0, st, A...);
 }
 dim3 grid256(size_t n) { return dim3((unsigned int)((n + 255)/256)); }
 
@@ -1185,20 +1342,30 @@ void launch_batch_round(hipStream_t st, const BatchDev& A)
     else                     launch_class<NMAX>(k_batch_round<NMAX, FORM_J, false, false>, st, A.B, A);
   });
 }
-void launch_batch_uncertainty(hipStream_t st, const UncDev& A)
+void launch_batch_uncertainty(hipStream_t st, const UncDev& A, const FitDev& F)
 {
   for_size_class(A.N, [&](auto c) {
     constexpr int NMAX = decltype(c)::value;
-    if(A.P.n2x) launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_PRODUCTS>, st, A.B, A);
-    else        launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_J>, st, A.B, A);
+    if(F.fit)
+    {
+      if(A.P.n2x) launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_PRODUCTS, true>, st, A.B, A, F);
+      else        launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_J, true>, st, A.B, A, F);
+    }
+    else if(A.P.n2x) launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_PRODUCTS, false>, st, A.B, A, F);
+    else             launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_J, false>, st, A.B, A, F);
   });
 }
-void launch_batch_query(hipStream_t st, const QueryDev& A)
+void launch_batch_query(hipStream_t st, const QueryDev& A, const FitDev& F)
 {
   for_size_class(A.U.N, [&](auto c) {
     constexpr int NMAX = decltype(c)::value;
-    if(A.U.P.n2x) launch_class<NMAX>(k_batch_query<NMAX, FORM_PRODUCTS>, st, A.U.B, A);
-    else          launch_class<NMAX>(k_batch_query<NMAX, FORM_J>, st, A.U.B, A);
+    if(F.fit)
+    {
+      if(A.U.P.n2x) launch_class<NMAX>(k_batch_query<NMAX, FORM_PRODUCTS, true>, st, A.U.B, A, F);
+      else          launch_class<NMAX>(k_batch_query<NMAX, FORM_J, true>, st, A.U.B, A, F);
+    }
+    else if(A.U.P.n2x) launch_class<NMAX>(k_batch_query<NMAX, FORM_PRODUCTS, false>, st, A.U.B, A, F);
+    else               launch_class<NMAX>(k_batch_query<NMAX, FORM_J, false>, st, A.U.B, A, F);
   });
 }
 void launch_batch_init(hipStream_t st, const BatchDev& A, const unsigned char* active)

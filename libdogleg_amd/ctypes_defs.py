@@ -140,6 +140,11 @@ class BatchBounds(C.Structure):
     _fields_ = [("lower", C.c_void_p), ("upper", C.c_void_p), ("held", C.c_void_p)]
 
 
+class BatchFit(C.Structure):
+    """dogleg_amd_batch_fit_t (include/dogleg.h): a BatchLoss* and two addresses, each 0 for NULL."""
+    _fields_ = [("loss", C.POINTER(BatchLoss)), ("weights", C.c_void_p), ("held", C.c_void_p)]
+
+
 class JacobianReport(C.Structure):
     """dogleg_amd_jacobian_report_t (include/dogleg.h)."""
     _fields_ = [
