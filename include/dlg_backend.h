@@ -196,6 +196,15 @@ int  dlg_point_upload_products(dlg_backend_t* b, int slot, double norm2x,
 int  dlg_point_bind_device(dlg_backend_t* b, int slot, const double* x_dev,
                            const double* J_dev);
 int  dlg_point_eval(dlg_backend_t* b, int slot, double* norm2_x, double* Jtx_absmax);
+/* Held variables of a slot (the bounded device solve, dogleg.h: dogleg_amd_optimize_device2_bounded).  held_dev: Nstate bytes on
+ * the device, not 0 = held; the caller has, behind dlg_point_eval and on the backend's stream, set the slot's Jt_x to 0 in the
+ * held entries and the held columns of the slot's J to 0, and passes |Jt_x|^2 of what is left (the Cauchy step divides by the
+ * value dlg_point_eval kept otherwise).  From then on every matrix assembled for the slot -- dlg_factorize, dlg_gauss_newton,
+ * whatever lambda -- gets a diagonal of exactly 1.0 in the held rows after lambda is added, so the factor is that of the free
+ * block and the identity, and a solve returns exactly 0 where held.  The bytes are read when a factorisation runs and must
+ * stay valid until then.  held_dev == NULL unbinds (norm2_Jtx is ignored); dlg_backend_reset unbinds both slots.  One rank,
+ * sparse and dense. */
+int  dlg_point_bind_held(dlg_backend_t* b, int slot, const unsigned char* held_dev, double norm2_Jtx);
 /* Assembly at evaluation time (sparse): while it is on, every dlg_point_eval also assembles the
  * slot's JtJ into a second panel buffer -- in the SAME pass over J that forms Jt*x where the
  * assembly schedule allows (the assembly kernel's B operand times x; DOGLEG_AMD_NO_FUSED_EVAL or

@@ -750,6 +750,65 @@ int dogleg_amd_optimize_dense_batch_bounded_device(double* p_dev, unsigned int B
                                                    dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
                                                    double* weights_dev, const unsigned char* active_dev, void* hip_stream);
 
+/* ---- box bounds in dogleg_optimize_device2: the sparse (NJnnz > 0) and the dense (NJnnz == 0) device solve minimise norm2(x)
+ * (with a loss: F, as dogleg_amd_optimize_device2_robust defines H, g and F) subject to lower <= p <= upper.  The algorithm is
+ * steps 1 to 8 written above dogleg_amd_optimize_dense_batch_bounded, word for word, placed in the loop of
+ * dogleg_optimize_device2: the start clamp on the host before p is uploaded; the held set and g_F at every evaluated point; the
+ * Jt_x_threshold test on |g_F|_inf; the factor of H + lambda I with the held rows and columns made the identity's; the chosen
+ * step clipped and its expected improvement formed again when something was clamped; the Cauchy fallback; update_threshold on
+ * the step that is applied; held at the returned p.  What follows from there being one problem: a failing fallback (step 6)
+ * fails the solve; a NaN bound or lower_i > upper_i is refused before any device work; the ways to stop, the trace and the vnlog
+ * records are those of dogleg_optimize_device2, and a fallback step is recorded as a Cauchy step; in the fallback the component
+ * that sets alpha ends on its bound's bits whichever way p + alpha d rounds (one ulp short of the bound the variable would be
+ * neither held nor free to move, and the next fallback would be cut at alpha ~ 1e-16).
+ *
+ * How: directly behind every evaluation the library forms the held bytes of that invocation of the callback (per operating
+ * point: a rejected trial steps again from the bytes of the point it returns to), writes g_F over Jt x and zeros over the held
+ * columns of J, in place, and sums |g_F|_inf, |g_F|^2 and the number of held variables in a fixed order (no floating-point
+ * atomics: the same bits on every run; one 24-byte read-back an evaluation).  Everything behind that -- the Cauchy step, the
+ * assembly, the factorisation, the Gauss-Newton solve, the expected improvement of an unclipped step -- is the plain solve's
+ * code on J_F and g_F; the assembled matrix gets a diagonal of exactly 1 in the held rows after lambda is added.  With a loss the
+ * rows are scaled first, then evaluated, then held and masked; F is not affected by the mask.  The sparse mask finds the
+ * variable of an entry from THIS call's Jt_rowidx, of which the solve keeps a device copy of its own.  A bounded solve does
+ * without the fused step, the assembly at evaluation time and the work the plain solve puts between a step and its wait.
+ *   loss        NULL: least squares.  weights: as in dogleg_amd_optimize_device2_robust; NULL unless a loss is given.
+ *   bounds      the batch struct with B = 1: lower, upper and held are host arrays of Nstate; lower or upper may be NULL, entries
+ *               may be -INFINITY / +INFINITY; held (out, or NULL): 0 free, 1 held at lower, 2 held at upper, at the returned p.
+ * Returns norm2(x) (with a loss: F) at the returned p.  A solve that fails returns -1.0 and leaves p, weights and held untouched.
+ * With bounds that clamp nothing the iterates are those of dogleg_optimize_device2 (with a loss: of _robust) to rounding: Jt x is
+ * summed in another fixed order than the one-pass evaluation of the plain solve sums it; held is all 0.
+ *
+ * A returned context holds the MASKED point:
+ *   Jt_x is g_F (exact zeros in the held entries);
+ *   the device-resident J (dlg_point_download, DLG_VEC_J) has exact zeros in the held columns, every other entry keeps its bits
+ *   (with a loss: the weighted rows');
+ *   the factor held is that of the matrix of step 4: H + lambda I with the held rows and columns made the identity's.
+ * dogleg_getOutliernessFactors, dogleg_amd_covariance_blocks, dogleg_amd_marginal_variances, dogleg_amd_covariance_entries and
+ * dogleg_amd_query_covariance, called on that context, therefore give the free problem's values on the free variables, and in a
+ * held row or column the identity's entries: 1.0 on the diagonal, 0 elsewhere.
+ *
+ * Refused with a message and -1.0 before any device work, p, weights and held untouched: everything dogleg_optimize_device2
+ * refuses; with a loss everything dogleg_amd_optimize_device2_robust refuses; a NULL bounds; weights without a loss; a NaN bound
+ * or lower_i > upper_i; more than one rank, whether by dogleg_amd_set_communicator, dogleg_amd_set_allreduce or the
+ * environment contract.
+ * Device memory beyond the plain (robust) solve's: 2 Nstate doubles of bounds, 2 Nstate bytes of held sets, NJnnz ints of pattern
+ * (sparse) and about Nstate / 64 doubles of partial results.
+ * Not provided: bounds on several GPUs; bounds for the host-callback entry points (dogleg_optimize2 / _dense2) and in the
+ * products form; general linear constraints; a fused or overlapped bounded step. */
+double dogleg_amd_optimize_device2_bounded(double* p, unsigned int Nstate, unsigned int Nmeas, unsigned int NJnnz,
+                                           const int* Jt_colptr, const int* Jt_rowidx,
+                                           dogleg_callback_device_t* f, void* cookie,
+                                           const dogleg_amd_batch_loss_t* loss,     /* NULL: least squares */
+                                           double* weights,                         /* as in _robust; NULL unless loss */
+                                           const dogleg_amd_batch_bounds_t* bounds, /* the batch struct with B = 1 */
+                                           const dogleg_parameters2_t* parameters,
+                                           dogleg_solverContext_t** returnContext);
+/* measurement: the calling thread's last bounded device solve: out[0] = evaluations, out[1] = steps with a clamped component,
+ * out[2] = fallbacks (step 6), out[3] = steps taken with a held variable, and, if DOGLEG_AMD_TIMING=1 was set for the solve
+ * (two events a launch group on the stream), out[4] = ms in the feature's own kernels over the solve and out[5] = the part of
+ * that in the mask passes over J.  Returns the number of entries written (at most n, at most 6). */
+int dogleg_amd_bounded_last_stats(double* out, int n);
+
 /* ---- covariance of per-problem query Jacobians of a batch: Var(q) = Jq Sigma_b Jq^T with Sigma_b = (JtJ + lambda I)^-1 of
  * problem b at p[b], the batch twin of dogleg_amd_query_covariance.  Sigma_b is neither formed nor written: per problem the
  * answer is Nq blocks of Qrows x Qrows.  Four entry points, mirroring the four uncertainty entry points above: the same

@@ -26,7 +26,7 @@ BACKEND_SYMBOLS = [
     "dlg_last_error", "dlg_device_count", "dlg_backend_create", "dlg_backend_destroy",
     "dlg_backend_set_stream", "dlg_backend_get_stream", "dlg_backend_set_shard",
     "dlg_sparse_set_pattern", "dlg_sparse_stats", "dlg_sparse_schedule", "dlg_sparse_leaf_rows_stats", "dlg_point_set_p", "dlg_point_upload",
-    "dlg_point_upload_products", "dlg_point_bind_device", "dlg_point_eval", "dlg_cauchy",
+    "dlg_point_upload_products", "dlg_point_bind_device", "dlg_point_eval", "dlg_point_bind_held", "dlg_cauchy",
     "dlg_factorize", "dlg_solve_gn", "dlg_gauss_newton", "dlg_cauchy_gauss_newton", "dlg_make_step",
     "dlg_expected_improvement", "dlg_step", "dlg_take_step", "dlg_solve_with_factor",
     "dlg_point_download", "dlg_factor_download_dense", "dlg_point_device_ptr",
@@ -79,6 +79,7 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_jacobian_colouring", "dogleg_amd_check_jacobian_device", "dogleg_amd_check_jacobian_device_batch",
     "dogleg_amd_testGradient_device", "dogleg_amd_check_jacobian_last_stats",
     "dogleg_amd_optimize_device2_robust", "dogleg_amd_robust_last_stats",
+    "dogleg_amd_optimize_device2_bounded", "dogleg_amd_bounded_last_stats",
 ]
 
 _lib = None
@@ -281,6 +282,12 @@ def lib():
         L.dogleg_amd_optimize_device2_robust.restype = C.c_double
         L.dogleg_amd_optimize_device2_robust.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, I, I, V, V, C.POINTER(BatchLoss), D, PP, V]
         L.dogleg_amd_robust_last_stats.argtypes = [D, C.c_int]
+    if hasattr(L, "dogleg_amd_optimize_device2_bounded"):
+        L.dogleg_amd_optimize_device2_bounded.restype = C.c_double
+        L.dogleg_amd_optimize_device2_bounded.argtypes = [D, C.c_uint, C.c_uint, C.c_uint, I, I, V, V, C.POINTER(BatchLoss), D,
+                                                          C.POINTER(BatchBounds), PP, V]
+        L.dogleg_amd_bounded_last_stats.argtypes = [D, C.c_int]
+        L.dlg_point_bind_held.argtypes = [V, C.c_int, V, C.c_double]
     L.dogleg_amd_last_solve_timing.argtypes = [D, I]
     L.dlg_point_gather_device.argtypes = [V, C.c_int, V, V, I]
     L.dogleg_setMaxIterations.argtypes = [C.c_int]
@@ -368,6 +375,53 @@ def optimize_device_robust(p0, N, M, nnz, Jp, Ji, cb, cookie, loss, params=None,
     finally:
         L.dlg_set_trace(None)
     return r, p, tr, w
+
+
+def optimize_device_bounded(p0, N, M, nnz, Jp, Ji, cb, cookie, lower=None, upper=None, loss=None, params=None, capacity=256,
+                            trace=True, want_weights=None, want_held=True, ctx=None, null_bounds=False):
+    """dogleg_amd_optimize_device2_bounded: the arguments of optimize_device_robust with lower / upper (N,) arrays or None
+    (NULL: no bounds on that side); loss None: least squares.  Returns (norm2x or F, p_final, TraceBuffer, weights or None,
+    held (N,) uint8 prefilled with 255 or None).  weights are asked for by default iff a loss is given (want_weights=True
+    without one passes an array all the same: the call is refused).  null_bounds: pass NULL for the struct itself."""
+    L = lib()
+    p = np.array(p0, dtype=np.float64, copy=True)
+    tr = TraceBuffer(N, capacity) if trace else None
+    fs = max(loss.featureSize, 1) if loss is not None else 1
+    if want_weights is None:
+        want_weights = loss is not None
+    w = np.full(M // fs, -1.0) if want_weights else None
+    held = np.full(N, 255, dtype=np.uint8) if want_held else None
+    lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64)
+    hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
+    assert all(a is None or a.shape == (N,) for a in (lo, hi))
+    addr = lambda a: a.ctypes.data if a is not None else None
+    bounds = BatchBounds(addr(lo), addr(hi), addr(held))
+    if nnz > 0:
+        Jp = np.ascontiguousarray(Jp, dtype=np.int32)
+        Ji = np.ascontiguousarray(Ji, dtype=np.int32)
+    L.dlg_set_trace(C.cast(tr.byref(), C.c_void_p) if trace else None)
+    try:
+        r = L.dogleg_amd_optimize_device2_bounded(dptr(p), N, M, nnz, iptr(Jp) if nnz > 0 else None, iptr(Ji) if nnz > 0 else None,
+                                                  cb, cookie, C.byref(loss) if loss is not None else None,
+                                                  dptr(w) if w is not None else None,
+                                                  None if null_bounds else C.byref(bounds),
+                                                  C.byref(params) if params is not None else None,
+                                                  C.byref(ctx) if ctx is not None else None)
+    finally:
+        L.dlg_set_trace(None)
+    return r, p, tr, w, held
+
+
+BOUNDED_STATS = ("evaluations", "clipped", "fallbacks", "held_steps", "kernels_ms", "mask_ms")
+
+
+def bounded_last_stats():
+    """dogleg_amd_bounded_last_stats as a dict: evaluations, steps with a clamped component, fallbacks, steps taken with a held
+    variable (the oracle's evaluations, clipped, fallbacks, held_steps), ms in the feature's kernels and, of those, in the mask
+    passes (DOGLEG_AMD_TIMING=1)"""
+    out = np.zeros(6)
+    n = lib().dogleg_amd_bounded_last_stats(dptr(out), 6)
+    return dict(zip(BOUNDED_STATS, out[:n]))
 
 
 def robust_last_stats():

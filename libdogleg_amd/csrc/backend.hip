@@ -335,7 +335,7 @@ extern "C" int dlg_backend_reset(dlg_backend_t* b)
   for(int s = 0; s < 2; s++)
   {
     DlgSlot& S = b->slot[s];
-    S.x_bound = S.J_bound = nullptr;
+    S.x_bound = S.J_bound = nullptr; S.held = nullptr;
     S.have_inputs = S.have_Jtx = S.have_cauchy = S.have_gn = false;
     S.norm2_x = S.norm2_cauchy = S.norm2_gn = S.norm2_jtx = 0;
     // (step_to_here of the first point of a solve is read by nobody, but a returned context downloads it)
@@ -402,6 +402,23 @@ extern "C" int dlg_backend_set_defer_tail(dlg_backend_t* b, int on)
 {
   if(!b) return DLG_ERR_ARG;
   b->defer_tail = on != 0;
+  return DLG_OK;
+}
+// the held variables of a slot: the assembly's hooks (sparse_assemble.hip: k_held_diag_sparse; kernels_dense.hip: k_held_diag_dense) read the bytes
+extern "C" int dlg_point_bind_held(dlg_backend_t* b, int s, const unsigned char* held_dev, double norm2_Jtx)
+{
+  DLG_CHECK(dlg_check_slot(b, s));
+  if(held_dev && (b->type == DLG_DENSE_PRODUCTS || b->sharded() || b->part_nranks > 1))
+  { dlg_set_error("dlg_point_bind_held: one rank, sparse or dense only"); return DLG_ERR_STATE; }
+  DlgSlot& S = b->slot[s];
+  S.held = held_dev;
+  if(!held_dev) return DLG_OK;
+  if(!S.have_Jtx) { dlg_set_error("dlg_point_bind_held: slot %d has not been evaluated", s); return DLG_ERR_STATE; }
+  S.norm2_jtx = norm2_Jtx;
+  // (whatever was formed from the unmasked point is not this point's)
+  S.have_cauchy = S.have_gn = false; S.ident_ok = false;
+  if(b->factor_slot == s) b->factor_slot = -1;
+  if(b->type == DLG_SPARSE) sparse_spec_invalidate(b, s);
   return DLG_OK;
 }
 extern "C" int dlg_backend_set_between(dlg_backend_t* b, dlg_between_fn fn, void* cookie)

@@ -50,6 +50,9 @@ struct DlgSlot
   // and whether the factor the Gauss-Newton step came from allows it (pivot ratio)
   double  Jg2 = 0, g_dot_gn = 0, a_dot_gn = 0, ident_lam = 0; bool ident_ok = false;      // (ident_norm2_Jstep: <Jt x, gn>, <cauchy, gn>, the lambda gn was solved at)
   bool    have_inputs = false, have_Jtx = false, have_cauchy = false, have_gn = false;
+  // a bounded solve (dlg_point_bind_held): a byte a variable, not 0 = held -- J has zeros in those columns and Jt_x in those
+  // entries, and the matrix that is factorised gets a diagonal of exactly 1 there; NULL: nothing of it runs
+  const unsigned char* held = nullptr;
   const double* xin() const { return x_bound ? x_bound : x; }
   const double* Jin() const { return J_bound ? J_bound : J; }
 };

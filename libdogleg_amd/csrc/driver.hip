@@ -167,7 +167,8 @@ bool set_pattern(Driver* d, const int* cp, const int* ri)
 // binds a row slice and keeps the step's tail in line, which the second call would have to repeat exactly.
 bool start_pattern_check(Driver* d)
 {
-  if(d->sharded || !d->be_reused || d->check_pattern || getenv("DOGLEG_AMD_NO_PATTERN_OVERLAP") != nullptr) return false;
+  // (a bounded solve masks J behind the first evaluation: that evaluation must be THE evaluation, the comparison comes first)
+  if(d->sharded || !d->be_reused || d->check_pattern || d->bounds || getenv("DOGLEG_AMD_NO_PATTERN_OVERLAP") != nullptr) return false;
   dlg_backend_t* be = d->be; const int* cp = d->dev_cp; const int* ri = d->dev_ri;
   // (a thread that cannot be started throws: then the comparison is made in line, as without the overlap)
   try { d->pat_check = new std::future<int>(std::async(std::launch::async, [be, cp, ri] { return dlg_sparse_pattern_matches(be, cp, ri); })); }
@@ -234,11 +235,13 @@ int evaluate_fed(Driver* d, int s, double* norm2x, double* absmax)
   const dogleg_solve_type_t type = d->pub.solve_type;
   // once steps need the Gauss-Newton step an accepted point is factorised next: its JtJ is assembled
   // beside Jt*x (an unused assembly -- a rejected point -- is simply dropped; no number changes)
-  if(type == DOGLEG_SPARSE) dlg_backend_set_speculation(d->be, d->expect_gn);
+  // (a bounded solve: never -- an assembly at evaluation time would be one of the unmasked J)
+  if(type == DOGLEG_SPARSE) dlg_backend_set_speculation(d->be, d->expect_gn && !d->bounds);
   // the model lives on the device: nothing on the host waits for p_new, and the expected improvement of a step is needed as
   // rho's denominator behind the evaluation of its trial point (dogleg.c:1410-1427; the `< 0` stop of 1403-1408 is made
   // there too, run_optimizer) -- its pass over J, if it needs one, runs beside this evaluation
-  if(d->f_device && type != DOGLEG_DENSE_PRODUCTS && !d->sharded) dlg_backend_set_defer_tail(d->be, 1);
+  // (a bounded solve clips the step behind it and forms the value again: nothing is deferred)
+  if(d->f_device && type != DOGLEG_DENSE_PRODUCTS && !d->sharded && !d->bounds) dlg_backend_set_defer_tail(d->be, 1);
   Tick te(d, TM_EVAL);
   return dlg_point_eval(d->be, s, norm2x, absmax);
 }
@@ -371,6 +374,14 @@ bool eval_point(bool* converged, dogleg_operatingPoint_t* pt, Driver* d)
   else { pt->norm2_x = norm2x; pt->have_x = pt->have_J = true; }
   // (a loss: the backend summed the squares of the weighted x; the gain ratio, the records and the return value take F)
   if(d->robust && !robust_F(d, s, &pt->norm2_x)) return false;
+  // (bounds: the held set of this invocation of the callback, g_F for Jt x, zeros in the held columns of J; the test below is on |g_F|_inf)
+  // (a gradient that is not finite stops the solve as it stops the plain one: the unmasked value stands)
+  if(d->bounds)
+  {
+    double absmax_F = 0;
+    if(!bounds_hold_mask(d, s, &absmax_F)) return false;
+    if(std::isfinite(absmax)) absmax = absmax_F;
+  }
   // dogleg.c:1073-1082: converged unless some |Jt_x[i]| exceeds the threshold
   *converged = !(absmax > ctx->parameters->Jt_x_threshold);
   if(*converged) VERBOSE(d, "gradient below threshold everywhere: done");
@@ -492,7 +503,7 @@ void driver_between(void* c)
 }
 bool between_ok(const Driver* d)
 {
-  return d->f_device && !d->sharded && !d->no_between && !d->pat_check &&
+  return d->f_device && !d->sharded && !d->no_between && !d->bounds && !d->pat_check &&
          (d->pub.solve_type == DOGLEG_DENSE || (d->pub.solve_type == DOGLEG_SPARSE && d->pattern_set));
 }
 
@@ -523,6 +534,35 @@ bool fetch_deferred_improvement(double* expectedImprovement, Driver* d)
   return true;
 }
 
+// Steps 5 and 6 of the bounded solve (dogleg.h, above dogleg_amd_optimize_dense_batch_bounded) behind the step dlg_step made:
+// clip it into the box and, if something was clamped, form the expected improvement again with the pass over J (the value from
+// the solved system holds for combinations of the Cauchy and the Gauss-Newton step only); a clipped step the model does not
+// like, or one below update_threshold, gives way to the Cauchy step cut at the first bound, which is recorded as a Cauchy step.
+bool bounded_step(double* expectedImprovement, double* n2, double* k, double* amax, dogleg_operatingPoint_t* to, dogleg_operatingPoint_t* from,
+                  double trustregion, Driver* d)
+{
+  const int sf = slot_of(d, from), st = slot_of(d, to);
+  bounds_note_step(d, sf);
+  double clamped = 0, smax = 0, s2 = 0;
+  if(!bounds_clip(d, sf, st, &clamped, &smax, &s2)) return false;
+  if(!(clamped > 0.0)) return true;                 // (nothing differs from the plain solve)
+  VERBOSE(d, "%g components of the step clamped at their bounds", clamped);
+  if(!be_ok(dlg_expected_improvement(d->be, sf, st, expectedImprovement), "expected improvement of the clipped step")) return false;
+  if(*expectedImprovement <= 0.0 || smax <= d->pub.parameters->update_threshold)
+  {
+    const double t0 = fmin(1.0, trustregion/sqrt(from->norm2_updateCauchy));
+    if(!bounds_fallback(d, sf, st, t0, &smax, &s2)) return false;
+    if(!be_ok(dlg_expected_improvement(d->be, sf, st, expectedImprovement), "expected improvement of the fallback step")) return false;
+    if(!(*expectedImprovement > 0.0) || !std::isfinite(*expectedImprovement))
+    { MSG("the Cauchy step cut at the first bound has expected improvement %g", *expectedImprovement); return false; }
+    VERBOSE(d, "fallback: the Cauchy step cut at the first bound");
+    d->cur.step_type = DLG_STEP_CAUCHY; *k = NAN;
+    from->didStepToEdgeOfTrustRegion = from->norm2_updateCauchy >= trustregion*trustregion;
+  }
+  *n2 = s2; *amax = smax;
+  return be_ok(dlg_point_download(d->be, st, DLG_VEC_P, to->p, (size_t)d->pub.Nstate), "download of the clipped p");
+}
+
 // dogleg.c:1172-1297.  The step vector stays on the device (slot `to`); p_new
 // comes back because the user callback needs it.
 bool take_step(double* expectedImprovement, dogleg_operatingPoint_t* to,
@@ -544,7 +584,8 @@ bool take_step(double* expectedImprovement, dogleg_operatingPoint_t* to,
   // Otherwise the step, its expected improvement and p_new are one backend op behind the steps it is made of.
   int kind = -1;
   double n2 = 0, k = NAN, amax = 0, o[7];
-  const bool fused = d->expect_gn && !from->have_updateCauchy && !from->have_updateGN && !from->have_factorization;
+  // (a bounded solve: the fused step acts on the unclipped p_new and takes its expected improvement from the solved system -- never)
+  const bool fused = !d->bounds && d->expect_gn && !from->have_updateCauchy && !from->have_updateGN && !from->have_factorization;
   if(fused) { if(!need_Jtx(from, "Cauchy step") || !need_J(from, ctx)) return false; }
   else
   {
@@ -573,6 +614,7 @@ bool take_step(double* expectedImprovement, dogleg_operatingPoint_t* to,
     }
     record_kind(kind, from, d);
   }
+  if(d->bounds && !bounded_step(expectedImprovement, &n2, &k, &amax, to, from, trustregion, d)) return false;
   to->norm2_step_to_here = n2;
   d->cur.norm2_step = n2;
   d->cur.k_cauchy_to_gn = k;
@@ -726,6 +768,7 @@ void destroy(Driver* d)
   if(d->pat_check) { (void)d->pat_check->get(); delete d->pat_check; d->pat_check = nullptr; }      // (it reads the backend's pattern)
   free_point(d, 0); free_point(d, 1);
   robust_destroy(d);
+  bounds_destroy(d);
   if(d->pub.solve_type != DOGLEG_SPARSE) free(d->pub.factorization_dense);
   if(d->x_full_dev) dlg_mem_free(d->x_full_dev);
   if(d->J_full_dev) dlg_mem_free(d->J_full_dev);
@@ -833,9 +876,11 @@ bool set_up(Driver* d, const Callbacks& cb, const double* p, Laps& lap)
   if(!solve_communicator(&cm) || !obtain_backend(d, cm, lap) || !attach_communicator(d, cm)) return false;
   if(d->sharded) lap("communicator");
   if(d->robust && !robust_set_up(d)) return false;
+  if(d->bounds && !bounds_set_up(d)) return false;
   if(!allocate_points(d, p)) return false;
   lap("operating points (pinned host)");
   memcpy(ctx->beforeStep->p, p, sizeof(double)*(size_t)ctx->Nstate);
+  if(d->bounds) bounds_clamp_start(d, ctx->beforeStep->p);
   return be_ok(dlg_point_set_p(d->be, 0, ctx->beforeStep->p), "upload of p");
 }
 
@@ -849,6 +894,8 @@ bool run(Driver* d, double* p, double* weights, Laps& lap)
   lap("run_optimizer (incl. symbolic phase)");
   trace_end(d);
   if(numsteps < 0) { MSG("the solve failed"); d->failed = true; return false; }
+  // (the held set first: a download that fails leaves the weights alone too)
+  if(d->bounds && !bounds_finish(d, slot_of(d, ctx->beforeStep))) { d->failed = true; return false; }
   if(d->robust && !robust_weights(d, slot_of(d, ctx->beforeStep), weights)) { d->failed = true; return false; }
   memcpy(p, ctx->beforeStep->p, sizeof(double)*(size_t)ctx->Nstate);        // dogleg.c:1745
   VERBOSE(d, "success: %d iterations", numsteps);
@@ -869,11 +916,13 @@ bool hand_back(Driver* d)
 // dogleg.c:1633-1753
 double optimize(double* p, unsigned int Nstate, unsigned int Nmeas, unsigned int NJnnz, const Callbacks& cb, void* cookie,
                 const dogleg_parameters2_t* parameters, dogleg_solverContext_t** returnContext,
-                const dogleg_amd_batch_loss_t* loss = nullptr, double* weights = nullptr)
+                const dogleg_amd_batch_loss_t* loss = nullptr, double* weights = nullptr,
+                const dogleg_amd_batch_bounds_t* bounds = nullptr)
 {
   Driver* d = (Driver*)calloc(1, sizeof(Driver));
   if(!d) { MSG("out of memory"); return -1.0; }
   if(loss && !(d->robust = robust_create(loss))) { MSG("out of memory"); free(d); return -1.0; }
+  if(bounds && !(d->bounds = bounds_create(bounds))) { MSG("out of memory"); robust_destroy(d); free(d); return -1.0; }
   d->early_slot = -1; d->no_between = getenv("DOGLEG_AMD_NO_BETWEEN") != nullptr;
   dogleg_solverContext_t* ctx = &d->pub;
   ctx->cookie = cookie;
@@ -973,6 +1022,23 @@ double dogleg_amd_optimize_device2_robust(double* p, unsigned int Nstate, unsign
   if(!robust_loss_ok(loss, Nmeas, NJnnz, Jt_colptr) || !one_rank_only("dogleg_amd_optimize_device2_robust")) return -1.0;
   return optimize(p, Nstate, Nmeas, NJnnz, Callbacks{nullptr, nullptr, nullptr, f, Jt_colptr, Jt_rowidx}, cookie, parameters, returnContext,
                   loss, weights);
+}
+// dogleg.h, "box bounds in dogleg_optimize_device2": refused here, before any device work, is what needs no device
+double dogleg_amd_optimize_device2_bounded(double* p, unsigned int Nstate, unsigned int Nmeas, unsigned int NJnnz,
+                                           const int* Jt_colptr, const int* Jt_rowidx,
+                                           dogleg_callback_device_t* f, void* cookie,
+                                           const dogleg_amd_batch_loss_t* loss, double* weights,
+                                           const dogleg_amd_batch_bounds_t* bounds,
+                                           const dogleg_parameters2_t* parameters,
+                                           dogleg_solverContext_t** returnContext)
+{
+  const char* who = "dogleg_amd_optimize_device2_bounded";
+  if(!f) { MSG("%s needs a device callback", who); return -1.0; }
+  if(!bounds_args_ok(bounds, loss, weights, p, Nstate)) return -1.0;
+  if(loss && !robust_loss_ok(loss, Nmeas, NJnnz, Jt_colptr)) return -1.0;
+  if(!one_rank_only(who)) return -1.0;
+  return optimize(p, Nstate, Nmeas, NJnnz, Callbacks{nullptr, nullptr, nullptr, f, Jt_colptr, Jt_rowidx}, cookie, parameters, returnContext,
+                  loss, weights, bounds);
 }
 double dogleg_optimize_dense_products(double* p, unsigned int Nstate,
                                       dogleg_callback_dense_products_t* f, void* cookie,

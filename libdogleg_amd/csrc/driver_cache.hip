@@ -104,4 +104,5 @@ extern "C" void dogleg_amd_release_cache(void)
   for(const PinnedBuf& b : pool) (void)hipHostFree(b.p);
   dlg_dense_batch_release();
   robust_release_cache();
+  bounds_release_cache();
 }

@@ -7,6 +7,7 @@
 //   api_extensions.hip  entry points that check their arguments and forward (outliers, covariance, batch, gradcheck)
 //   id_file.cpp         the id-file rendezvous of the environment contract
 //   robust_prelude.hip  a loss on a device solve: weights, F = sum rho and the sqrt(w) scaling of x and J behind the callback
+//   bounds_device.hip   box bounds on a device solve: the held set, g_F and the masked J behind an evaluation, the clipped step
 // Everything declared here is hidden: the library exports dogleg.h, dlg_backend.h and dlg_trace.h, nothing of this.
 #pragma once
 #include <cstdio>
@@ -35,6 +36,7 @@ struct Comm
 };
 
 struct Robust;                                 // robust_prelude.hip
+struct Bounds;                                 // bounds_device.hip
 
 enum { TM_PATTERN, TM_CALLBACK, TM_UPLOAD, TM_EVAL, TM_STEP, TM_TRACE, TM_COUNT };
 
@@ -76,6 +78,7 @@ struct Driver
   dogleg_callback_device_t* f_device;
   const int *dev_cp, *dev_ri;                  // the caller's pattern (host), valid during the call
   Robust* robust;                              // dogleg_amd_optimize_device2_robust: the loss and its device arrays; NULL: least squares, nothing of it runs
+  Bounds* bounds;                              // dogleg_amd_optimize_device2_bounded: the box and its device arrays; NULL: no bounds, nothing of it runs
   // DOGLEG_AMD_TIMING=1: where the wall time of run_optimizer goes (host clock around the driver's own calls)
   bool timing;
   double tm_ms[8]; int tm_n[8];
@@ -138,5 +141,23 @@ bool robust_F(Driver* d, int s, double* F);
 bool robust_weights(Driver* d, int s, double* weights_host);
 void robust_destroy(Driver* d);
 void robust_release_cache();                   // dogleg_amd_release_cache: the device block kept between robust solves
+
+// ---- bounds_device.hip: box bounds on a device solve.  One rank, device callback only.
+// the checks of the entry point that need no device (a NULL bounds, weights without a loss, a NaN bound, lower > upper); false: a message was printed
+bool bounds_args_ok(const dogleg_amd_batch_bounds_t* bounds, const dogleg_amd_batch_loss_t* loss, const double* weights, const double* p,
+                    unsigned int Nstate);
+Bounds* bounds_create(const dogleg_amd_batch_bounds_t* bounds);
+void bounds_clamp_start(const Driver* d, double* p);      // step 1, on the host
+bool bounds_set_up(Driver* d);
+// behind dlg_point_eval of slot s: held bytes, g_F in place, the held columns of J zeroed, the backend told; *absmax = |g_F|_inf
+bool bounds_hold_mask(Driver* d, int s, double* absmax);
+void bounds_note_step(Driver* d, int from);               // a step is taken from slot `from` (counts the ones with a held variable)
+// behind a step into slot `to`: clamp p and the step in place; clamped components, max |s'|, |s'|^2
+bool bounds_clip(Driver* d, int from, int to, double* clamped, double* smax, double* n2);
+// the Cauchy step of `from` times t0, cut at the first bound, into slot `to`
+bool bounds_fallback(Driver* d, int from, int to, double t0, double* smax, double* n2);
+bool bounds_finish(Driver* d, int s);                     // held of slot s to the caller, the stats record
+void bounds_destroy(Driver* d);
+void bounds_release_cache();                   // dogleg_amd_release_cache: the device block kept between bounded solves
 
 #pragma GCC visibility pop

@@ -181,6 +181,13 @@ __global__ void __launch_bounds__(TPB) k_add_diag(double* __restrict__ G, int N,
   const int i = blockIdx.x*TPB + threadIdx.x;
   if(i < N) G[(size_t)i*N + i] += lambda;
 }
+// a bounded solve (DlgSlot::held): the diagonal entry of a held variable becomes exactly 1.0, behind lambda (a store: its row
+// and column hold zeros, the held columns of J are zero)
+__global__ void __launch_bounds__(TPB) k_held_diag_dense(double* __restrict__ G, int N, const unsigned char* __restrict__ held)
+{
+  const int i = blockIdx.x*TPB + threadIdx.x;
+  if(i < N && held[i] != 0) G[(size_t)i*N + i] = 1.0;
+}
 // packed (as dpptrf('L') leaves it) <- G
 __global__ void __launch_bounds__(TPB) k_pack_from_G(const double* __restrict__ G, int N,
                                                      double* __restrict__ P)
@@ -990,6 +997,12 @@ int dense_factorize(dlg_backend* b, int s, double lambda, int* ok)
     DLG_CHECK(dlg_allreduce_dev(b, b->G, (size_t)b->N*b->N));
     if(lambda != 0.0)
       hipLaunchKernelGGL(k_add_diag, dim3(dlg_cdiv(b->N, TPB)), dim3(TPB), 0, b->stream, b->G, b->N, lambda);
+  }
+  // (behind the syrk's epilogue and k_add_diag, the two places that put lambda on the diagonal)
+  if(S.held)
+  {
+    hipLaunchKernelGGL(k_held_diag_dense, dim3(dlg_cdiv(b->N, TPB)), dim3(TPB), 0, b->stream, b->G, b->N, S.held);
+    DLG_LAUNCH_CHECK();
   }
   // K5: independent work may run beside it from here on (the one-launch form raises a word for the second stream
   // itself: no event between the SYRK's reduce and the factorisation; the chain of small kernels: an event)

@@ -893,6 +893,18 @@ __global__ void __launch_bounds__(TPB) k_add_lambda(double* __restrict__ Lx,
   const int i = blockIdx.x*TPB + threadIdx.x;
   if(i < n && phase_has(sn_owner, col_sn[i], phase)) Lx[diagpos[i]] += lambda;
 }
+// a bounded solve (DlgSlot::held): the diagonal entry of a held variable becomes exactly 1.0 -- a store, behind every launch
+// above: its row and column hold zeros (the held columns of J are zero), lambda was added, and the matrix that is factorised
+// is the free block's beside the identity's.  Column i of the panels is variable perm[i]; held: [n] bytes by variable.
+__global__ void __launch_bounds__(TPB) k_held_diag_sparse(double* __restrict__ Lx, const int64_t* __restrict__ diagpos, int n,
+                                                   const int* __restrict__ perm, const unsigned char* __restrict__ held,
+                                                   const int* __restrict__ col_sn, const int* __restrict__ sn_owner, int phase)
+{
+  const int i = blockIdx.x*TPB + threadIdx.x;
+  if(i >= n || !phase_has(sn_owner, col_sn[i], phase)) return;
+  const int v = perm[i];
+  if((unsigned)v < (unsigned)n && held[v] != 0) Lx[diagpos[i]] = 1.0;
+}
 
 // augmented row: panel(last row, column k) += rhs[perm[k]]   (the row is zero after the assembly;
 // above the cut of a subtree partition it already carries the updates from below).  augpos[k] = the
@@ -1486,6 +1498,19 @@ static int allreduce_panels(dlg_backend* b, bool* again)
   return DLG_OK;
 }
 
+// behind every place that puts lambda on the diagonal, whatever lambda is: the held variables' diagonal entries (no-op unless
+// the slot has held bytes bound, dlg_point_bind_held)
+static int held_diag(dlg_backend* b, int s, int phase)
+{
+  SparseSym* Y = b->sym;
+  if(s < 0 || s > 1 || !b->slot[s].held) return DLG_OK;
+  DLG_CHECK(sparse_fin_side_gate(b));
+  hipLaunchKernelGGL(k_held_diag_sparse, dim3(dlg_cdiv(Y->H.N, TPB)), dim3(TPB), 0, b->stream, Y->Lx, Y->diagpos, Y->H.N,
+                     (const int*)Y->perm, b->slot[s].held, Y->col_sn, Y->sn_owner, phase);
+  DLG_LAUNCH_CHECK();
+  return DLG_OK;
+}
+
 // K4: JtJ straight into the supernode panels, summed over the ranks, + lambda, + augmented row
 int sparse_assemble(dlg_backend* b, int s, double lambda)
 {
@@ -1515,6 +1540,7 @@ int sparse_assemble(dlg_backend* b, int s, double lambda)
                          dl, Y->col_sn, Y->sn_owner, -1);
       DLG_LAUNCH_CHECK();
     }
+    DLG_CHECK(held_diag(b, s, -1));   // (the difference of the lambdas went onto the held entries too)
     Y->info_armed = false;            // (sparse_factorize arms the pivot word with a copy)
     return DLG_OK;
   }
@@ -1552,6 +1578,7 @@ int sparse_assemble(dlg_backend* b, int s, double lambda)
   if(lambda != 0.0)
     hipLaunchKernelGGL(k_add_lambda, dim3(dlg_cdiv(H.N, TPB)), dim3(TPB), 0, st, Y->Lx, Y->diagpos, H.N,
                        lambda, Y->col_sn, Y->sn_owner, phase);
+  DLG_CHECK(held_diag(b, s, phase));
   // the right-hand side rides along as the last row of every panel: y = L^-1 P Jt_x falls out
   Y->aug_rhs = nullptr;
   Y->info_armed = false;
@@ -1625,6 +1652,7 @@ int sparse_partition_reduce(dlg_backend* b)
   if(Y->cur_lambda != 0.0)
     hipLaunchKernelGGL(k_add_lambda, dim3(dlg_cdiv(H.N, TPB)), dim3(TPB), 0, st, Y->Lx, Y->diagpos, H.N,
                        Y->cur_lambda, Y->col_sn, Y->sn_owner, 1);
+  DLG_CHECK(held_diag(b, Y->fac_slot, 1));
   if(Y->aug_rhs)
     hipLaunchKernelGGL(k_set_aug_row, dim3(dlg_cdiv(H.N, TPB)), dim3(TPB), 0, st, Y->Lx, Y->col_sn, Y->augpos,
                        Y->perm, Y->aug_rhs, H.N, Y->d_info, Y->sn_owner, 1);
