@@ -1024,6 +1024,78 @@ void dogleg_amd_testGradient_device(unsigned var, const double* p0, unsigned Nst
  * written (at most n, at most 6). */
 int dogleg_amd_check_jacobian_last_stats(double* out, int n);  /* callback calls, library launches, syncs, copies */
 
+/* ---- extension (not in the reference): numeric Jacobians for a batch whose model comes as VALUES ONLY.  An adapter, not a
+ * solver: dogleg_amd_batch_numeric_callback is a dogleg_callback_device_batch_t that evaluates the caller's values-only model
+ * at p and at perturbed copies of p and writes the difference quotients into the J it is handed, [B][Nmeas][Nstate].  Passed
+ * as f with cookie = the handle it serves EVERY J-form batch entry point above -- the plain, robust and bounded solves, the
+ * uncertainty, query and _fit calls, all their _device twins and dogleg_amd_check_jacobian_device_batch -- and none of them
+ * knows.  Not covered: the products form, the sparse and the single-problem solvers.
+ *
+ * The values callback evaluates x at `copies` points per problem.  All pointers are device memory.
+ *   p_dev    in : [copies][B][Nstate]
+ *   x_dev    out: [copies][B][Nmeas]
+ *   live_dev in : [B] bytes; problem b is evaluated in every copy or in none (what is written for a dead one is ignored)
+ *   hip_stream  : enqueue here, do not synchronise
+ *
+ * The step rule (include/dogleg_numeric_step.h, one function for host and device; dogleg_amd_numeric_step below is that
+ * function).  With p = p[b][j], lo / hi = lower / upper[b][j] (-inf / +inf without) and h = delta_rel |p| + delta_abs:
+ *   forward: tp = p + h, and where tp > hi: tp = max(p - h, lo).  d = tp - p,  J[r][j] = (x(tp)[r] - x(p)[r]) / d
+ *   central: tp = min(p + h, hi), tm = max(p - h, lo).            d = tp - tm, J[r][j] = (x(tp)[r] - x(tm)[r]) / d
+ * (central: one-sided by itself when p lies on a bound).  d == 0, a variable with lo == hi, gives a column of exact zeros (its
+ * gradient entry is then exactly 0, so the bounded solve reports held = 0 for it: it stays put because its box is a point).
+ * delta_rel and delta_abs both <= 0: 2^-26 for both (forward), 2^-17 for both (central).  The quotient is one IEEE division.
+ * With the bounds of dogleg_amd_optimize_dense_batch_bounded no point outside the box is ever evaluated: the solve keeps p
+ * inside, and the rule keeps the perturbed points inside.  The copies: copy 0 is p, copy 1 + j the plus point of variable j,
+ * and for central differences copy 1 + Nstate + j its minus point; x_dev handed back is copy 0's x.
+ *
+ * One invocation of the adapter is ONE launch that writes the copies, ONE call of f and ONE launch that forms J, whatever B
+ * is, all on the stream it is handed and without a synchronisation.  Dead problems' x and J are not touched.  Non-finite
+ * values propagate by the arithmetic alone, so a problem whose model fails fails alone.
+ *
+ * dogleg_amd_batch_numeric_create allocates, on the current device, the copies: K B (Nstate + Nmeas) + B Nstate doubles with
+ * K = Nstate + 1 (forward) or 2 Nstate + 1 (central) -- about 2 GB for B = 131 072 problems of 96 x 16 with forward
+ * differences -- plus 2 B Nstate doubles for host bounds, which it copies; bounds_on_device != 0: lower / upper are device
+ * arrays that are read where they lie at every invocation (they are the caller's to keep alive, and are not checked).  NULL and
+ * a message: B, Nstate or Nmeas 0, Nstate above DOGLEG_AMD_BATCH_MAX_NSTATE, a NULL f, an unknown scheme, a negative or NaN
+ * delta, host bounds with lower[b][j] > upper[b][j] or a NaN, a size that does not fit (the message names it), no device.  The
+ * arguments are checked before any device is touched.  A handle serves calls of its B or fewer problems of its shape, one at a
+ * time.  The adapter can return nothing: invoked with a B above the handle's it writes NaN into x of every live problem -- each
+ * then fails alone with FAILED --, calls nothing and prints one message. */
+typedef void (dogleg_callback_device_batch_values_t)(const double* p_dev, double* x_dev, const unsigned char* live_dev,
+                                                     unsigned int B, unsigned int copies, void* hip_stream, void* cookie);
+#define DOGLEG_AMD_NUMERIC_FORWARD 0
+#define DOGLEG_AMD_NUMERIC_CENTRAL 1
+typedef struct
+{
+  int scheme;                     /* DOGLEG_AMD_NUMERIC_FORWARD or _CENTRAL                                     */
+  double delta_rel, delta_abs;    /* both <= 0: the scheme's default                                            */
+  const double* lower;            /* [B][Nstate] or NULL; entries may be -inf                                   */
+  const double* upper;            /* [B][Nstate] or NULL; entries may be +inf                                   */
+  int bounds_on_device;           /* lower / upper are device memory                                            */
+} dogleg_amd_numeric_options_t;
+struct dogleg_amd_batch_numeric;  /* opaque */
+/* opt == NULL: forward differences, default deltas, no bounds */
+struct dogleg_amd_batch_numeric* dogleg_amd_batch_numeric_create(unsigned B, unsigned Nstate, unsigned Nmeas,
+                                                                 dogleg_callback_device_batch_values_t* f, void* cookie,
+                                                                 const dogleg_amd_numeric_options_t* opt);
+void dogleg_amd_batch_numeric_destroy(struct dogleg_amd_batch_numeric* h);
+/* a dogleg_callback_device_batch_t: pass it as f, with cookie = h, to any J-form batch entry point */
+void dogleg_amd_batch_numeric_callback(const double* p_dev, double* x_dev, double* J_dev, const unsigned char* live_dev,
+                                       unsigned int B, void* hip_stream, void* cookie);
+/* measurement, since the handle was made: out[0] = invocations of the adapter, out[1] = invocations of f, out[2] =
+ * problem-copies requested of f (copies x B, summed), out[3] = kernel launches of the library, and, if DOGLEG_AMD_BATCH_TIMING=1
+ * was set when an invocation ran (four events an invocation on its stream, read here: this call waits for the last of them),
+ * out[4] = ms in f's kernels, out[5] = ms in the library's.  Returns the number of entries written (at most n, at most 6). */
+int dogleg_amd_batch_numeric_stats(struct dogleg_amd_batch_numeric* h, double* out, int n);
+/* tests and debugging: the device buffers of the handle as the last invocation left them: p_copies [K][B'][Nstate], x_copies
+ * [K][B'][Nmeas], divisor [B'][Nstate] with B' the B of that invocation.  Returns K, or -1 on a NULL handle. */
+int dogleg_amd_batch_numeric_buffers(struct dogleg_amd_batch_numeric* h, const double** p_copies_dev,
+                                     const double** x_copies_dev, const double** divisor_dev);
+/* the step rule on the host: the plus point, the minus point (forward: p) and the divisor of one variable, with the deltas as
+ * given (no defaults are substituted here) */
+void dogleg_amd_numeric_step(int scheme, double p, double lo, double hi, double delta_rel, double delta_abs,
+                             double* tp, double* tm, double* d);
+
 #ifdef __cplusplus
 }
 #endif

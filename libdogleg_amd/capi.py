@@ -8,6 +8,7 @@ import os
 import numpy as np
 
 from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, BatchLoss, BatchBounds, BatchFit, JacobianReport, JacobianEntry,
+                          NumericOptions, NUMERIC_FORWARD, NUMERIC_CENTRAL,
                           CB_SPARSE, CB_DENSE, CB_PRODUCTS, dptr, iptr)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -80,6 +81,8 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_testGradient_device", "dogleg_amd_check_jacobian_last_stats",
     "dogleg_amd_optimize_device2_robust", "dogleg_amd_robust_last_stats",
     "dogleg_amd_optimize_device2_bounded", "dogleg_amd_bounded_last_stats",
+    "dogleg_amd_batch_numeric_create", "dogleg_amd_batch_numeric_destroy", "dogleg_amd_batch_numeric_callback",
+    "dogleg_amd_batch_numeric_stats", "dogleg_amd_batch_numeric_buffers", "dogleg_amd_numeric_step",
 ]
 
 _lib = None
@@ -288,6 +291,17 @@ def lib():
                                                           C.POINTER(BatchBounds), PP, V]
         L.dogleg_amd_bounded_last_stats.argtypes = [D, C.c_int]
         L.dlg_point_bind_held.argtypes = [V, C.c_int, V, C.c_double]
+    if hasattr(L, "dogleg_amd_batch_numeric_create"):
+        L.dogleg_amd_batch_numeric_create.restype = V
+        L.dogleg_amd_batch_numeric_create.argtypes = [C.c_uint, C.c_uint, C.c_uint, V, V, C.POINTER(NumericOptions)]
+        L.dogleg_amd_batch_numeric_destroy.argtypes = [V]
+        L.dogleg_amd_batch_numeric_destroy.restype = None
+        L.dogleg_amd_batch_numeric_callback.argtypes = [V, V, V, V, C.c_uint, V, V]
+        L.dogleg_amd_batch_numeric_callback.restype = None
+        L.dogleg_amd_batch_numeric_stats.argtypes = [V, D, C.c_int]
+        L.dogleg_amd_batch_numeric_buffers.argtypes = [V, C.POINTER(V), C.POINTER(V), C.POINTER(V)]
+        L.dogleg_amd_numeric_step.argtypes = [C.c_int] + [C.c_double] * 5 + [D, D, D]
+        L.dogleg_amd_numeric_step.restype = None
     L.dogleg_amd_last_solve_timing.argtypes = [D, I]
     L.dlg_point_gather_device.argtypes = [V, C.c_int, V, V, I]
     L.dogleg_setMaxIterations.argtypes = [C.c_int]
@@ -1300,6 +1314,86 @@ class Backend:
         out = np.zeros(n)
         _ck(self.L.dlg_factor_download_dense(self.h, dptr(out), n), "factor download")
         return out
+
+
+def numeric_step(scheme, p, lo, hi, delta_rel, delta_abs):
+    """dogleg_amd_numeric_step: (plus point, minus point, divisor) of one variable"""
+    tp, tm, d = C.c_double(), C.c_double(), C.c_double()
+    lib().dogleg_amd_numeric_step(scheme, p, lo, hi, delta_rel, delta_abs, C.byref(tp), C.byref(tm), C.byref(d))
+    return tp.value, tm.value, d.value
+
+
+def numeric_options(scheme=NUMERIC_FORWARD, delta_rel=0.0, delta_abs=0.0, lower=None, upper=None, bounds_on_device=False):
+    """(a NumericOptions, what it points at): lower / upper numpy arrays (B, N), or with bounds_on_device DeviceArrays / raw
+    device addresses, or None"""
+    keep = []
+
+    def addr(a):
+        if a is None:
+            return None
+        if bounds_on_device:
+            return a.ptr if isinstance(a, DeviceArray) else int(a)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        keep.append(a)
+        return a.ctypes.data
+
+    return NumericOptions(scheme, delta_rel, delta_abs, addr(lower), addr(upper), 1 if bounds_on_device else 0), keep
+
+
+class BatchNumeric:
+    """dogleg_amd_batch_numeric_create: the numeric-Jacobian adapter over a values-only batch callback (values_cb: the address
+    of a dogleg_callback_device_batch_values_t).  .cb / .cookie go to any J-form batch entry point.  Creation that the library
+    refuses raises DlgError with its message."""
+
+    def __init__(self, B, N, M, values_cb, values_cookie, scheme=None, delta_rel=0.0, delta_abs=0.0, lower=None, upper=None,
+                 bounds_on_device=False):
+        L = lib()
+        self.B, self.N, self.M = B, N, M
+        opt = None
+        if scheme is not None:
+            opt, self._keep = numeric_options(scheme, delta_rel, delta_abs, lower, upper, bounds_on_device)
+        self.scheme = NUMERIC_FORWARD if scheme is None else scheme
+        self.K = (2 * N + 1) if self.scheme == NUMERIC_CENTRAL else N + 1
+        self.h = L.dogleg_amd_batch_numeric_create(B, N, M, values_cb, values_cookie, C.byref(opt) if opt is not None else None)
+        if not self.h:
+            raise DlgError((L.dlg_last_error() or b"").decode())
+        self.cb = C.cast(L.dogleg_amd_batch_numeric_callback, C.c_void_p)
+        self.cookie = C.c_void_p(self.h)
+
+    def invoke(self, p_dev, x_dev, J_dev, live_dev, B=None, stream=None):
+        """the adapter itself, as a batch entry point would call it (asynchronous: dlg_device_sync or a download follows)"""
+        lib().dogleg_amd_batch_numeric_callback(_dev(p_dev), _dev(x_dev), _dev(J_dev), _dev(live_dev), self.B if B is None else B,
+                                                _dev(stream), self.h)
+
+    def stats(self):
+        """{invocations, f_calls, copies, launches, ms_f, ms_library} since the handle was made"""
+        out = (C.c_double * 6)()
+        lib().dogleg_amd_batch_numeric_stats(self.h, out, 6)
+        return dict(zip(("invocations", "f_calls", "copies", "launches", "ms_f", "ms_library"), (float(v) for v in out)))
+
+    def buffers(self, B=None):
+        """(p_copies (K, B, N), x_copies (K, B, M), divisor (B, N)) downloaded, as the last invocation (of B problems) left them"""
+        B = self.B if B is None else B
+        a, b, d = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        K = lib().dogleg_amd_batch_numeric_buffers(self.h, C.byref(a), C.byref(b), C.byref(d))
+        assert K == self.K
+        out = []
+        for ptr, shape in ((a, (K, B, self.N)), (b, (K, B, self.M)), (d, (B, self.N))):
+            arr = np.zeros(shape)
+            _ck(lib().dlg_mem_download(arr.ctypes.data, ptr, arr.nbytes), "download")
+            out.append(arr)
+        return tuple(out)
+
+    def close(self):
+        if self.h:
+            lib().dogleg_amd_batch_numeric_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def last_solve_timing():

@@ -168,11 +168,25 @@ class JacobianEntry(C.Structure):
 
 JACOBIAN_ONE_AT_A_TIME = 1
 
+NUMERIC_FORWARD, NUMERIC_CENTRAL = 0, 1          # dogleg_amd_numeric_options_t.scheme
+NUMERIC_DELTA_DEFAULT = {NUMERIC_FORWARD: 2.0 ** -26, NUMERIC_CENTRAL: 2.0 ** -17}     # of delta_rel and of delta_abs
+NUMERIC_TILE_ROWS = 32                           # rows of J per tile of k_numeric_jacobian (csrc/batch_numeric.hip: NUM_TR)
+
+
+class NumericOptions(C.Structure):
+    """dogleg_amd_numeric_options_t (include/dogleg.h): lower / upper are addresses, each 0 for NULL."""
+    _fields_ = [("scheme", C.c_int), ("delta_rel", C.c_double), ("delta_abs", C.c_double),
+                ("lower", C.c_void_p), ("upper", C.c_void_p), ("bounds_on_device", C.c_int)]
+
+
 # dogleg_callback_device_batch_t
 CB_DEVICE_BATCH = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p)
 # dogleg_callback_device_batch_products_t
 CB_DEVICE_BATCH_PRODUCTS = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p,
                                        C.c_void_p)
+
+# dogleg_callback_device_batch_values_t
+CB_DEVICE_BATCH_VALUES = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p)
 
 CB_SPARSE = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double),
                         C.POINTER(CholmodSparse), C.c_void_p)
