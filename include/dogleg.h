@@ -1096,6 +1096,64 @@ int dogleg_amd_batch_numeric_buffers(struct dogleg_amd_batch_numeric* h, const d
 void dogleg_amd_numeric_step(int scheme, double p, double lo, double hi, double delta_rel, double delta_abs,
                              double* tp, double* tm, double* d);
 
+/* ---- extension (not in the reference): numeric Jacobians for ONE problem whose model comes as VALUES ONLY, sparse or dense.
+ * An adapter, not a solver: dogleg_amd_numeric_callback is a dogleg_callback_device_t that evaluates the caller's values-only
+ * model at p and at perturbed copies of p and writes x and the difference quotients into the buffers it is handed.  Passed as f
+ * with cookie = the handle it serves dogleg_optimize_device2, dogleg_amd_optimize_device2_robust, _bounded,
+ * dogleg_amd_check_jacobian_device, dogleg_amd_testGradient_device and the held-factor users of a returned context, and none
+ * of them knows.  Not covered: the products form, the host-callback solvers, several GPUs.
+ *
+ * The pattern is the one dogleg_optimize_device2 takes: Jt in CSC, rows ascending within a column, and J_dev receives the values
+ * of Jt in pattern order.  NJnnz == 0 (the pattern pointers are then not read) is the dense solve: J[Nmeas][Nstate] row-major.
+ * Variables that share no measurement row are perturbed TOGETHER: the colouring is exactly dogleg_amd_jacobian_colouring's
+ * (first fit, natural order, a variable in no row gets colour 0), so the adapter and the Jacobian check agree on the groups.
+ * With C colours the model is evaluated at K = C + 1 (forward) or 2 C + 1 (central) points per invocation -- 16 or 31 on a
+ * block-arrowhead pattern of 15 entries a row whatever Nstate is.  A dense problem has every variable as its own colour, C =
+ * Nstate.  One row that holds R variables forces R colours; dogleg_amd_numeric_plan tells C, K and the memory without a device.
+ *
+ * The copies: copy 0 is p; copy 1 + c has every variable of colour c at its plus point; copy 1 + C + c (central) has them at
+ * their minus points; x_dev handed back is copy 0's x.  For entry t of Jt in row r with variable v = Jt_rowidx[t] of colour c:
+ *   J[t] = d[v] == 0 ? 0 : (x[1 + c][r] - xm[r]) / d[v],   xm = copy 1 + C + c (central) or copy 0 (forward)
+ * one subtraction and one IEEE division.  The step rule, its defaults and the options are those of the batch adapter above
+ * (dogleg_numeric_step, dogleg_amd_numeric_options_t), with lower / upper [Nstate] here, host arrays that are copied or, with
+ * bounds_on_device, device arrays read where they lie.  With the bounds of dogleg_amd_optimize_device2_bounded in the options
+ * no point outside the box is ever evaluated, and a variable with lower == upper has exact zeros in all its entries.
+ *
+ * One invocation is ONE launch that writes the copies and divisors, ONE call of f and ONE launch that forms x and J, whatever
+ * Nstate, Nmeas and C are, on the stream it is handed, with no synchronisation, allocation or copy.  Non-finite values
+ * propagate by the arithmetic alone.  The handle owns K (Nstate + Nmeas) + Nstate doubles and, for a sparse problem, Nstate +
+ * Nmeas + 1 + 2 NJnnz ints (plus Nstate doubles per copied host bound), on the device that is current at creation.
+ *
+ * dogleg_amd_numeric_create returns NULL with a message, before any device is touched, for: Nstate or Nmeas 0, a NULL f, a
+ * pattern that is not a valid Jt or disagrees with NJnnz, an unknown scheme, a negative or NaN delta, host bounds with lower[j] >
+ * upper[j] or a NaN, a size that does not fit (the message names C, K, the bytes and the longest row); then for no device.  A
+ * handle serves one call at a time. */
+typedef void (dogleg_callback_device_values_t)(const double* p_dev /* [copies][Nstate] */,
+                                               double* x_dev       /* [copies][Nmeas]  */,
+                                               unsigned int copies, void* hip_stream, void* cookie);
+struct dogleg_amd_numeric;  /* opaque */
+/* host only, touches no device: the colouring (colour[Nstate], or NULL), the copies K (or NULL) and the device bytes the handle
+ * would own without copied bounds (or NULL) for scheme DOGLEG_AMD_NUMERIC_FORWARD or _CENTRAL.  Returns C, or -1 with a message. */
+int dogleg_amd_numeric_plan(unsigned Nstate, unsigned Nmeas, unsigned NJnnz, const int* Jt_colptr, const int* Jt_rowidx,
+                            int scheme, int* colour, int* copies, double* device_bytes);
+/* opt == NULL: forward differences, default deltas, no bounds */
+struct dogleg_amd_numeric* dogleg_amd_numeric_create(unsigned Nstate, unsigned Nmeas, unsigned NJnnz,
+                                                     const int* Jt_colptr, const int* Jt_rowidx,
+                                                     dogleg_callback_device_values_t* f, void* cookie,
+                                                     const dogleg_amd_numeric_options_t* opt);
+void dogleg_amd_numeric_destroy(struct dogleg_amd_numeric* h);
+/* a dogleg_callback_device_t: pass it as f, with cookie = h */
+void dogleg_amd_numeric_callback(const double* p_dev, double* x_dev, double* J_dev, void* hip_stream, void* cookie);
+/* measurement, since the handle was made: out[0] = invocations of the adapter, out[1] = invocations of f, out[2] = copies
+ * requested of f (summed), out[3] = kernel launches of the library, and, if DOGLEG_AMD_NUMERIC_TIMING=1 was set when an invocation
+ * ran (four events an invocation on its stream, read here: this call waits for the last of them), out[4] = ms in f's kernels,
+ * out[5] = ms in the library's.  Returns the number of entries written (at most n, at most 6). */
+int dogleg_amd_numeric_stats(struct dogleg_amd_numeric* h, double* out, int n);
+/* tests and debugging: the device buffers of the handle as the last invocation left them: p_copies [K][Nstate], x_copies
+ * [K][Nmeas], divisor [Nstate].  Returns K, or -1 on a NULL handle. */
+int dogleg_amd_numeric_buffers(struct dogleg_amd_numeric* h, const double** p_copies_dev, const double** x_copies_dev,
+                               const double** divisor_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,9 +38,9 @@ def headers():
 # default heuristic the compiler parks them in AGPRs and copies all of them to VGPRs and back in
 # every loop iteration, the VGPR form of the instruction avoids that.
 _VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
-# batch_numeric.hip: its step rule is restated bit for bit by the tests, so no multiply-add of it may be fused
+# batch_numeric.hip, numeric_device.hip: their step rule is restated bit for bit by the tests, so no multiply-add of it may be fused
 EXTRA = {"sparse_assemble.hip": _VGPR_MFMA, "sparse_factor.hip": _VGPR_MFMA, "dense_diag.hip": _VGPR_MFMA,
-         "batch_numeric.hip": ["-ffp-contract=off"]}
+         "batch_numeric.hip": ["-ffp-contract=off"], "numeric_device.hip": ["-ffp-contract=off"]}
 
 
 def _compile(src, newest_hdr, verbose):

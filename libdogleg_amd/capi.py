@@ -83,6 +83,8 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_optimize_device2_bounded", "dogleg_amd_bounded_last_stats",
     "dogleg_amd_batch_numeric_create", "dogleg_amd_batch_numeric_destroy", "dogleg_amd_batch_numeric_callback",
     "dogleg_amd_batch_numeric_stats", "dogleg_amd_batch_numeric_buffers", "dogleg_amd_numeric_step",
+    "dogleg_amd_numeric_plan", "dogleg_amd_numeric_create", "dogleg_amd_numeric_destroy", "dogleg_amd_numeric_callback",
+    "dogleg_amd_numeric_stats", "dogleg_amd_numeric_buffers",
 ]
 
 _lib = None
@@ -302,6 +304,16 @@ def lib():
         L.dogleg_amd_batch_numeric_buffers.argtypes = [V, C.POINTER(V), C.POINTER(V), C.POINTER(V)]
         L.dogleg_amd_numeric_step.argtypes = [C.c_int] + [C.c_double] * 5 + [D, D, D]
         L.dogleg_amd_numeric_step.restype = None
+    if hasattr(L, "dogleg_amd_numeric_create"):
+        L.dogleg_amd_numeric_plan.argtypes = [C.c_uint, C.c_uint, C.c_uint, I, I, C.c_int, I, I, D]
+        L.dogleg_amd_numeric_create.restype = V
+        L.dogleg_amd_numeric_create.argtypes = [C.c_uint, C.c_uint, C.c_uint, I, I, V, V, C.POINTER(NumericOptions)]
+        L.dogleg_amd_numeric_destroy.argtypes = [V]
+        L.dogleg_amd_numeric_destroy.restype = None
+        L.dogleg_amd_numeric_callback.argtypes = [V, V, V, V, V]
+        L.dogleg_amd_numeric_callback.restype = None
+        L.dogleg_amd_numeric_stats.argtypes = [V, D, C.c_int]
+        L.dogleg_amd_numeric_buffers.argtypes = [V, C.POINTER(V), C.POINTER(V), C.POINTER(V)]
     L.dogleg_amd_last_solve_timing.argtypes = [D, I]
     L.dlg_point_gather_device.argtypes = [V, C.c_int, V, V, I]
     L.dogleg_setMaxIterations.argtypes = [C.c_int]
@@ -1387,6 +1399,77 @@ class BatchNumeric:
     def close(self):
         if self.h:
             lib().dogleg_amd_batch_numeric_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def numeric_plan(N, M, nnz, Jp, Ji, scheme=NUMERIC_FORWARD):
+    """dogleg_amd_numeric_plan (host only): (C or -1, colour[N], K, device bytes).  nnz == 0: dense (Jp, Ji ignored)"""
+    if nnz > 0:
+        Jp = np.ascontiguousarray(Jp, dtype=np.int32)
+        Ji = np.ascontiguousarray(Ji, dtype=np.int32)
+    colour = np.full(max(N, 1), -1, dtype=np.int32)
+    K, nbytes = C.c_int(-1), C.c_double(-1.0)
+    ncol = lib().dogleg_amd_numeric_plan(N, M, nnz, iptr(Jp) if nnz > 0 else None, iptr(Ji) if nnz > 0 else None, scheme,
+                                         iptr(colour), C.byref(K), C.byref(nbytes))
+    return ncol, colour[:N], K.value, nbytes.value
+
+
+class DeviceNumeric:
+    """dogleg_amd_numeric_create: the numeric-Jacobian adapter over a values-only single-problem callback (values_cb: the
+    address of a dogleg_callback_device_values_t) on the pattern (Jp, Ji) of Jt; nnz == 0: dense.  .cb / .cookie go to
+    optimize_device and its kin.  lower / upper: (N,) arrays.  Creation that the library refuses raises DlgError with its
+    message."""
+
+    def __init__(self, N, M, nnz, Jp, Ji, values_cb, values_cookie, scheme=None, delta_rel=0.0, delta_abs=0.0, lower=None,
+                 upper=None, bounds_on_device=False):
+        L = lib()
+        self.N, self.M, self.nnz = N, M, nnz
+        opt = None
+        if scheme is not None:
+            opt, self._keep = numeric_options(scheme, delta_rel, delta_abs, lower, upper, bounds_on_device)
+        self.scheme = NUMERIC_FORWARD if scheme is None else scheme
+        if nnz > 0:
+            Jp = np.ascontiguousarray(Jp, dtype=np.int32)
+            Ji = np.ascontiguousarray(Ji, dtype=np.int32)
+        self.h = L.dogleg_amd_numeric_create(N, M, nnz, iptr(Jp) if nnz > 0 else None, iptr(Ji) if nnz > 0 else None, values_cb,
+                                             values_cookie, C.byref(opt) if opt is not None else None)
+        if not self.h:
+            raise DlgError((L.dlg_last_error() or b"").decode())
+        self.K = L.dogleg_amd_numeric_buffers(self.h, None, None, None)
+        self.C = (self.K - 1) // (2 if self.scheme == NUMERIC_CENTRAL else 1)
+        self.cb = C.cast(L.dogleg_amd_numeric_callback, C.c_void_p)
+        self.cookie = C.c_void_p(self.h)
+
+    def invoke(self, p_dev, x_dev, J_dev, stream=None):
+        """the adapter itself, as a solver would call it (asynchronous: dlg_device_sync or a download follows)"""
+        lib().dogleg_amd_numeric_callback(_dev(p_dev), _dev(x_dev), _dev(J_dev), _dev(stream), self.h)
+
+    def stats(self):
+        """{invocations, f_calls, copies, launches, ms_f, ms_library} since the handle was made"""
+        out = (C.c_double * 6)()
+        lib().dogleg_amd_numeric_stats(self.h, out, 6)
+        return dict(zip(("invocations", "f_calls", "copies", "launches", "ms_f", "ms_library"), (float(v) for v in out)))
+
+    def buffers(self):
+        """(p_copies (K, N), x_copies (K, M), divisor (N,)) downloaded, as the last invocation left them"""
+        a, b, d = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        K = lib().dogleg_amd_numeric_buffers(self.h, C.byref(a), C.byref(b), C.byref(d))
+        out = []
+        for ptr, shape in ((a, (K, self.N)), (b, (K, self.M)), (d, (self.N,))):
+            arr = np.zeros(shape)
+            _ck(lib().dlg_mem_download(arr.ctypes.data, ptr, arr.nbytes), "download")
+            out.append(arr)
+        return tuple(out)
+
+    def close(self):
+        if self.h:
+            lib().dogleg_amd_numeric_destroy(self.h)
             self.h = None
 
     def __del__(self):

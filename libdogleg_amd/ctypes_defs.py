@@ -188,6 +188,12 @@ CB_DEVICE_BATCH_PRODUCTS = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p,
 # dogleg_callback_device_batch_values_t
 CB_DEVICE_BATCH_VALUES = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p)
 
+# dogleg_callback_device_values_t
+CB_DEVICE_VALUES = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p)
+# csrc/numeric_device.hip: rows of a tile of k_numeric_jacobian_sparse (ND_TR), the copies one LDS chunk stages at most
+# (ND_SLOTS: copy 0 and the chunk's plus and minus copies), the lanes of a workgroup (ND_THREADS), and the dense tile's edge
+NUMERIC_DEVICE_TILE_ROWS, NUMERIC_DEVICE_LDS_SLOTS, NUMERIC_DEVICE_THREADS, NUMERIC_DEVICE_DENSE_TILE = 64, 63, 256, 32
+
 CB_SPARSE = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double),
                         C.POINTER(CholmodSparse), C.c_void_p)
 CB_DENSE = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double),
