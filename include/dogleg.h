@@ -729,8 +729,8 @@ int dogleg_amd_robust_last_stats(double* out, int n);
  * a NULL bounds, weights without a loss; the device twin also refuses lower, upper and held as it refuses the other pointers.
  * Device memory: the plain or robust solve's; the host-pointer form adds B Nstate doubles for each of lower and upper that
  * is given (held is formed on the host from the returned point's p and g).
- * Not provided: bounds in the products form; general linear constraints.  The uncertainty and the query covariances of the free
- * variables at the returned p: dogleg_amd_dense_batch_uncertainty_fit / _query_covariance_fit below, with held (and, with a loss,
+ * Not provided: general linear constraints.  The products form: dogleg_amd_optimize_dense_products_batch_bounded below.  The
+ * uncertainty and the query covariances of the free variables at the returned p: dogleg_amd_dense_batch_uncertainty_fit / _query_covariance_fit below, with held (and, with a loss,
  * the loss and the weights) in their fit record. */
 typedef struct
 {
@@ -749,6 +749,39 @@ int dogleg_amd_optimize_dense_batch_bounded_device(double* p_dev, unsigned int B
                                                    const dogleg_amd_batch_bounds_t* bounds,
                                                    dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
                                                    double* weights_dev, const unsigned char* active_dev, void* hip_stream);
+
+/* ---- box bounds in the products form of the batch solve: the bounded solve above for a callback that hands back norm2(x),
+ * Jt x and JtJ per problem (dogleg_callback_device_batch_products_t), so for ragged batches -- every problem with its own number
+ * of measurements -- and for problems whose x and J would not fit.  Steps 1 to 8 written above
+ * dogleg_amd_optimize_dense_batch_bounded apply word for word; JtJ, Jt x and norm2(x) are what the callback returned.  Everything
+ * the bounds add lies behind the load of the products, on the on-chip JtJ, g and the two cached steps, as it lies behind the sweep
+ * in the J form.  There is no loss and there are no weights: the products form has no rows.
+ * Step 6 here: the J form's JtJ is a sum of squares, so positive semidefinite, and the fallback's expected improvement is > 0 up
+ * to rounding.  Here the callback answers for that: with a JtJ that is not positive semidefinite along the fallback step the
+ * improvement may be <= 0, and one that is <= 0 or not finite stays DOGLEG_AMD_BATCH_FAILED for that problem alone.
+ * held[b] is what dogleg_amd_dense_products_batch_uncertainty_fit / _query_covariance_fit take in their fit record, unchanged.
+ * With bounds that clamp nothing (lower = upper = NULL, infinite entries, a box that is never met) every result has the bits of
+ * dogleg_amd_optimize_dense_products_batch, and held is all 0.
+ * Everything else is the contract of dogleg_amd_optimize_dense_products_batch and its _device twin: the three layouts of JtJ
+ * (packed upper, unpacked with either triangle read as the parameters say; packed lower refused), the finiteness vote over
+ * everything read, the live bytes, one callback, one launch and one 4-byte read-back per round, the result struct and the status
+ * codes (none is new), dogleg_amd_batch_last_stats; and for the twin the pointer checks (lower, upper and held inside *bounds,
+ * which itself is host memory, included), the stream rule and the mask (held of a problem that is not run is not written).
+ * Refused with a message and -1 before any device work, outputs untouched: what the plain products twin refuses, and a NULL
+ * bounds; the device twin also refuses lower, upper and held as it refuses the other pointers.
+ * Device memory: the plain products solve's; the host-pointer form adds B Nstate doubles for each of lower and upper that is
+ * given (held is formed on the host from the returned point's p and g).
+ * Not provided: a loss (no rows); general linear constraints; bounds for the host-callback dogleg_optimize_dense_products. */
+int dogleg_amd_optimize_dense_products_batch_bounded(double* p, unsigned int B, unsigned int Nstate,
+                                                     dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                     const dogleg_parameters2_t* parameters,
+                                                     const dogleg_amd_batch_bounds_t* bounds, dogleg_amd_batch_result_t* results);
+int dogleg_amd_optimize_dense_products_batch_bounded_device(double* p_dev, unsigned int B, unsigned int Nstate,
+                                                            dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                            const dogleg_parameters2_t* parameters,
+                                                            const dogleg_amd_batch_bounds_t* bounds,
+                                                            dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                            const unsigned char* active_dev, void* hip_stream);
 
 /* ---- box bounds in dogleg_optimize_device2: the sparse (NJnnz > 0) and the dense (NJnnz == 0) device solve minimise norm2(x)
  * (with a loss: F, as dogleg_amd_optimize_device2_robust defines H, g and F) subject to lower <= p <= upper.  The algorithm is
@@ -903,7 +936,7 @@ int dogleg_amd_dense_products_batch_query_covariance_device(const double* p_dev,
  * dividing Nmeas; with a loss, an Nobservations >= 0 that is not a multiple of lfs; a loss or weights in the products form; the
  * _device forms also refuse weights and held as they refuse their other pointers, over [B][Nmeas / lfs] doubles and [B][Nstate]
  * bytes.
- * Not provided: a loss in the products form (it has no rows) and bounds in the products-form solve; per-problem loss scales;
+ * Not provided: a loss in the products form (it has no rows); per-problem loss scales;
  * losses that are not concave in s; weights that differ between J and x; marking outliers on a batch. */
 typedef struct
 {

@@ -71,6 +71,7 @@ DOGLEG_SYMBOLS = [
     "dlg_batch_device_span_ok",          # (csrc/dense_batch.h: the pointer check of the four above, exported for the tests)
     "dogleg_amd_optimize_dense_batch_robust", "dogleg_amd_optimize_dense_batch_robust_device",
     "dogleg_amd_optimize_dense_batch_bounded", "dogleg_amd_optimize_dense_batch_bounded_device",
+    "dogleg_amd_optimize_dense_products_batch_bounded", "dogleg_amd_optimize_dense_products_batch_bounded_device",
     "dogleg_amd_dense_batch_query_covariance", "dogleg_amd_dense_products_batch_query_covariance",
     "dogleg_amd_dense_batch_query_covariance_device", "dogleg_amd_dense_products_batch_query_covariance_device",
     "dogleg_amd_dense_batch_uncertainty_fit", "dogleg_amd_dense_products_batch_uncertainty_fit",
@@ -260,6 +261,10 @@ def lib():
                                                               C.POINTER(BatchResult), D]
         L.dogleg_amd_optimize_dense_batch_bounded_device.argtypes = [V, C.c_uint, C.c_uint, C.c_uint, V, V, PP, LP, BP, V, V, V,
                                                                      V, V]
+    if hasattr(L, "dogleg_amd_optimize_dense_products_batch_bounded"):
+        BP = C.POINTER(BatchBounds)
+        L.dogleg_amd_optimize_dense_products_batch_bounded.argtypes = [D, C.c_uint, C.c_uint, V, V, PP, BP, C.POINTER(BatchResult)]
+        L.dogleg_amd_optimize_dense_products_batch_bounded_device.argtypes = [V, C.c_uint, C.c_uint, V, V, PP, BP, V, V, V, V]
     if hasattr(L, "dogleg_amd_dense_batch_query_covariance"):
         U = C.c_uint
         L.dogleg_amd_dense_batch_query_covariance.argtypes = [D, U, U, U, V, V, D, D, U, U, C.c_int, D, I]
@@ -672,6 +677,35 @@ def optimize_dense_batch_bounded_device(p_dev, B, N, M, cb, cookie, params, loss
                                                                 C.byref(loss) if loss is not None else None, C.byref(bounds),
                                                                 _dev(results_dev), _dev(lambda_dev), _dev(weights_dev),
                                                                 _dev(active_dev), _dev(stream))
+
+
+def optimize_dense_products_batch_bounded(p0s, N, cb, cookie, lower, upper, params=None, want_held=True):
+    """dogleg_amd_optimize_dense_products_batch_bounded: as optimize_dense_products_batch with lower, upper (B, N) arrays or None
+    (NULL).  Returns (rc, p (B, N), results, held (B, N) uint8 prefilled with 255 or None)."""
+    L = lib()
+    p = np.array(p0s, dtype=np.float64, copy=True).reshape(-1, N)
+    B = p.shape[0]
+    res = (BatchResult * max(B, 1))()
+    lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).reshape(B, N)
+    hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).reshape(B, N)
+    held = np.full((B, N), 255, dtype=np.uint8) if want_held else None
+    addr = lambda a: None if a is None else a.ctypes.data
+    bounds = BatchBounds(addr(lo), addr(hi), addr(held))
+    rc = L.dogleg_amd_optimize_dense_products_batch_bounded(dptr(p), B, N, cb, cookie,
+                                                            C.byref(params) if params is not None else None, C.byref(bounds), res)
+    return rc, p, _batch_results(res, B), held
+
+
+def optimize_dense_products_batch_bounded_device(p_dev, B, N, cb, cookie, params, lower_dev, upper_dev, held_dev, results_dev,
+                                                 lambda_dev=None, active_dev=None, stream=None):
+    """dogleg_amd_optimize_dense_products_batch_bounded_device, the arguments as optimize_dense_products_batch_device; lower_dev,
+    upper_dev (B, N) doubles and held_dev (B, N) bytes: DeviceArrays, raw addresses or None.  Returns rc."""
+    raw = lambda a: None if a is None else _dev(a).value
+    bounds = BatchBounds(raw(lower_dev), raw(upper_dev), raw(held_dev))
+    return lib().dogleg_amd_optimize_dense_products_batch_bounded_device(_dev(p_dev), B, N, cb, cookie,
+                                                                         C.byref(params) if params is not None else None,
+                                                                         C.byref(bounds), _dev(results_dev), _dev(lambda_dev),
+                                                                         _dev(active_dev), _dev(stream))
 
 
 def batch_results_from_device(results_dev, B):

@@ -106,10 +106,13 @@ size_t loss_features(const dogleg_amd_batch_loss_t* loss, unsigned int Nmeas)
   return loss ? Nmeas/(loss->featureSize <= 1 ? 1u : (unsigned int)loss->featureSize) : 0;
 }
 
-// the bounds of the bounded batch solve: the struct must be given (its pointers may be NULL), weights belong to a loss
-bool batch_bounds_ok(const char* who, const dogleg_amd_batch_bounds_t* bounds, const dogleg_amd_batch_loss_t* loss,
+// the bounds of the bounded batch solve: the struct must be given (its pointers may be NULL), weights belong to a loss, and the
+// products form has no rows for either
+bool batch_bounds_ok(const char* who, bool products, const dogleg_amd_batch_bounds_t* bounds, const dogleg_amd_batch_loss_t* loss,
                      const double* weights)
 {
+  if(products && (loss || weights))
+  { MSG("%s: the products form has no rows: it takes neither a loss nor weights", who); return false; }
   if(!bounds) { MSG("%s: bounds must be given (no bounds at all: lower = upper = NULL inside it, or the entry point without _bounded)", who); return false; }
   if(weights && !loss) { MSG("%s: weights are those of a loss, and loss is NULL", who); return false; }
   return true;
@@ -170,7 +173,7 @@ int batch_solve_entry(const char* who, SolveKind kind, DlgBatchSolve a)
   a.unpacked = a.fP && !a.prm->JtJ_packed;
   if(!request_shape_ok(who, a, a.prm, "a loop over dogleg_optimize_dense2")) return -1;
   if((kind == SOLVE_ROBUST || a.loss) && !batch_loss_ok(who, a.loss, a.M)) return -1;
-  if(kind == SOLVE_BOUNDED && !batch_bounds_ok(who, a.bounds, a.loss, a.weights)) return -1;
+  if(kind == SOLVE_BOUNDED && !batch_bounds_ok(who, a.fP != nullptr, a.bounds, a.loss, a.weights)) return -1;
   if(!one_rank_only(who)) return -1;
   const size_t B = a.B, BN = B*a.N;
   const dogleg_amd_batch_bounds_t none = {nullptr, nullptr, nullptr}, &bounds = a.bounds ? *a.bounds : none;
@@ -530,6 +533,26 @@ int dogleg_amd_optimize_dense_batch_bounded_device(double* p_dev, unsigned int B
 {
   return batch_solve_entry(__func__, SOLVE_BOUNDED, DlgBatchSolve{p_dev, B, Nstate, Nmeas, f, nullptr, cookie, false, parameters,
                                                                   results_dev, lambda_dev, active_dev, hip_stream, loss, weights_dev,
+                                                                  bounds, true});
+}
+// ---- the bounded products form and its device twin (no loss, no weights: the form has no rows)
+int dogleg_amd_optimize_dense_products_batch_bounded(double* p, unsigned int B, unsigned int Nstate,
+                                                     dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                     const dogleg_parameters2_t* parameters,
+                                                     const dogleg_amd_batch_bounds_t* bounds, dogleg_amd_batch_result_t* results)
+{
+  return batch_solve_entry(__func__, SOLVE_BOUNDED, DlgBatchSolve{p, B, Nstate, 0, nullptr, f, cookie, false, parameters, results,
+                                                                  nullptr, nullptr, nullptr, nullptr, nullptr, bounds});
+}
+int dogleg_amd_optimize_dense_products_batch_bounded_device(double* p_dev, unsigned int B, unsigned int Nstate,
+                                                            dogleg_callback_device_batch_products_t* f, void* cookie,
+                                                            const dogleg_parameters2_t* parameters,
+                                                            const dogleg_amd_batch_bounds_t* bounds,
+                                                            dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                            const unsigned char* active_dev, void* hip_stream)
+{
+  return batch_solve_entry(__func__, SOLVE_BOUNDED, DlgBatchSolve{p_dev, B, Nstate, 0, nullptr, f, cookie, false, parameters,
+                                                                  results_dev, lambda_dev, active_dev, hip_stream, nullptr, nullptr,
                                                                   bounds, true});
 }
 int dogleg_amd_optimize_dense_products_batch_device(double* p_dev, unsigned int B, unsigned int Nstate,

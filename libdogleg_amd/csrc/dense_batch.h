@@ -20,7 +20,7 @@ struct DlgBatchSolve
   // the robust form (J form only; kind, scale and a featureSize <= 4 that divides M checked by the caller; weights: [B][M /
   // featureSize] or NULL), or both NULL
   const dogleg_amd_batch_loss_t* loss; double* weights;
-  const dogleg_amd_batch_bounds_t* bounds;                     // the bounded form (J form only; lower / upper / held may be NULL), or NULL
+  const dogleg_amd_batch_bounds_t* bounds;                     // the bounded form (either form; lower / upper / held may be NULL), or NULL
   bool device;
 };
 int  dlg_dense_batch_solve(const DlgBatchSolve& a);

@@ -234,12 +234,13 @@ struct BatchTimer
 // ---- the solve ----
 const char* solve_who(const DlgBatchSolve& a)
 {
-  static const char* const names[4][2] = {
+  static const char* const names[5][2] = {
+    {"dogleg_amd_optimize_dense_products_batch_bounded", "dogleg_amd_optimize_dense_products_batch_bounded_device"},
     {"dogleg_amd_optimize_dense_products_batch", "dogleg_amd_optimize_dense_products_batch_device"},
     {"dogleg_amd_optimize_dense_batch_bounded", "dogleg_amd_optimize_dense_batch_bounded_device"},
     {"dogleg_amd_optimize_dense_batch_robust", "dogleg_amd_optimize_dense_batch_robust_device"},
     {"dogleg_amd_optimize_dense_batch", "dogleg_amd_optimize_dense_batch_device"}};
-  return names[a.fP ? 0 : a.bounds ? 1 : a.loss ? 2 : 3][a.device ? 1 : 0];
+  return names[a.fP ? (a.bounds ? 0 : 1) : a.bounds ? 2 : a.loss ? 3 : 4][a.device ? 1 : 0];
 }
 // the cache opened and grown for the solve a, and the kernels' argument pointing into it.  The host route keeps the bounds it is
 // given behind the state (A.lo, A.hi); the device route reads the caller's arrays

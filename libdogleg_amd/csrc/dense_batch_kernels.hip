@@ -37,7 +37,8 @@
 //
 // The bounded form (dogleg_amd_optimize_dense_batch_bounded and its _device twin): box bounds per problem by an active-set loop,
 // the eight steps above the prototype in dogleg.h.  BOUNDED is a template flag of batch_problem and k_batch_round beside ROBUST
-// (J form only); everything it adds lies behind the sweep, on the on-chip JtJ, g and the two cached steps, and needs no LDS of
+// (either form: dogleg_amd_optimize_dense_products_batch_bounded is the FORM_PRODUCTS instantiation of the same text); everything
+// it adds lies behind the sweep or the load of the products, on the on-chip JtJ, g and the two cached steps, and needs no LDS of
 // its own.  k_batch_clamp (behind k_batch_init) clamps the start points; k_batch_finish, or solve_locked (dense_batch.hip) on the host, forms held.
 //
 // The fit forms (dogleg_amd_dense[_products]_batch_uncertainty_fit, _query_covariance_fit and their _device twins): the two
@@ -426,13 +427,12 @@ __device__ __forceinline__ double load_products(const ProductsDev& P, int b, int
 }
 
 // one round of problem b; returns whether the problem is still live.
-// BOUNDED (J form): box bounds by an active set, the eight steps above dogleg_amd_optimize_dense_batch_bounded in dogleg.h.
-// Everything it adds lies behind the sweep, on the on-chip JtJ, g and the two cached steps; the other instantiations keep
-// their text.
+// BOUNDED (either form): box bounds by an active set, the eight steps above dogleg_amd_optimize_dense_batch_bounded in dogleg.h.
+// Everything it adds lies behind the sweep (products form: behind load_products), on the on-chip JtJ, g and the two cached
+// steps; the other instantiations keep their text.
 template <int NMAX, int FORM, bool ROBUST, bool BOUNDED>
 __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
 {
-  static_assert(!BOUNDED || FORM == FORM_J, "bounds: the J form only");
   using C = BatchCfg<NMAX>;
   const int N = A.N, M = A.M, NP = A.NP;
   double* SA = S;                      // JtJ of the point the step is taken from
@@ -1332,7 +1332,11 @@ void launch_batch_round(hipStream_t st, const BatchDev& A)
 {
   for_size_class(A.N, [&](auto c) {
     constexpr int NMAX = decltype(c)::value;
-    if(A.P.n2x)              launch_class<NMAX>(k_batch_round<NMAX, FORM_PRODUCTS, false, false>, st, A.B, A);
+    if(A.P.n2x)
+    {
+      if(A.bounded)          launch_class<NMAX>(k_batch_round<NMAX, FORM_PRODUCTS, false, true>, st, A.B, A);
+      else                   launch_class<NMAX>(k_batch_round<NMAX, FORM_PRODUCTS, false, false>, st, A.B, A);
+    }
     else if(A.bounded)
     {
       if(A.robust)           launch_class<NMAX>(k_batch_round<NMAX, FORM_J, true, true>, st, A.B, A);
