@@ -1187,6 +1187,74 @@ int dogleg_amd_numeric_stats(struct dogleg_amd_numeric* h, double* out, int n);
 int dogleg_amd_numeric_buffers(struct dogleg_amd_numeric* h, const double** p_copies_dev, const double** x_copies_dev,
                                const double** divisor_dev);
 
+/* ---- built-in fit models of the batch solver: the textbook curves "one fit per pixel or track" users fit, so that a batch can be
+ * fitted without writing device code.  The models, their parameters and the fixed order of their arithmetic: dogleg_batch_models.h
+ * (x_i = s_i (f_i(p) - y_i), J its exact derivative; EXPDECAY N = 3, GAUSS1D N = 4, GAUSS2D N = 5, GAUSS2D_ELLIPTIC N = 6).
+ *
+ * The model record is host memory; its arrays are device-accessible memory of the current device in EVERY entry point below (the
+ * host-pointer solve included) and are checked as the _device twins check their pointers, before any device work:
+ *   kind        DOGLEG_AMD_MODEL_*
+ *   Nmeas       rows per problem, > 0
+ *   width, height   the 2D kinds: the pixel window, width * height == Nmeas (row i is pixel (i mod width, i div width)); the 1D
+ *               kinds: both 0
+ *   y           [B][Nmeas] the data, required
+ *   t           the abscissae of the 1D kinds: NULL (t_i = i), [Nmeas] shared by all problems, or [B][Nmeas] with t_per_problem
+ *               != 0.  Must be NULL for the 2D kinds
+ *   scale       [B][Nmeas] s_i (for instance 1 / the standard deviation of y_i), or NULL: 1
+ * A sigma of exactly 0, a NaN datum and the like give non-finite rows: that problem ends DOGLEG_AMD_BATCH_FAILED by the rule of
+ * dogleg_amd_optimize_dense_batch, alone.
+ *
+ * 1. The model as an ordinary callback.  dogleg_amd_batch_model_callback is a dogleg_callback_device_batch_t whose cookie is a
+ * const dogleg_amd_batch_model_t* (Nstate = dogleg_amd_batch_model_nstate(kind), Nmeas = its Nmeas): one launch on the stream
+ * it is given, x and J of the live problems.  With it every batch entry point above takes a built-in model: the plain, robust and
+ * bounded solves, the uncertainty, query and _fit calls, their _device twins and dogleg_amd_check_jacobian_device_batch.  The
+ * record is not checked there: a record the fused solve would refuse makes the callback write nothing.
+ * dogleg_amd_batch_model_callback_invocations: how often it has run in this process (measurement).
+ *
+ * 2. The fused solve.  dogleg_amd_optimize_dense_batch_model[_device] have the contract of dogleg_amd_optimize_dense_batch and
+ * dogleg_amd_optimize_dense_batch_bounded (bounds != NULL) and of their _device twins in every respect but one: no callback is
+ * invoked and no x / J buffer exists.  The lane that would stage row i of J forms it in registers, through the same function as the
+ * callback above, and puts it into the on-chip tile; the sweep behind it is the J form's.  EVERY OUTPUT HAS THE BITS OF THE SAME
+ * SOLVE THROUGH dogleg_amd_batch_model_callback (with bounds: of the bounded solve through it): p, the six result fields, lambda,
+ * held.  Device memory: the state only, B (N (N + 11) / 2 + 8) doubles, plus the bounds in the host-pointer form.  A round is ONE
+ * launch and one 4-byte read-back; dogleg_amd_batch_last_stats reports the rounds and 0 ms of callback.  evaluations counts the
+ * evaluations of the model for that problem.
+ * Refused with a message and -1 before any device work, outputs untouched: what the plain or bounded twin refuses, a NULL model or
+ * a NULL y, an unknown kind, Nmeas 0, a 2D kind whose width * height != Nmeas, a 1D kind with a width or height, t given for a 2D
+ * kind, a set communicator, and arrays of the record that are not device-accessible over their span.
+ *
+ * Not provided: a loss in the fused form (the adapter route has it: dogleg_amd_optimize_dense_batch_robust / _bounded with the
+ * callback above); float or integer data; a Poisson likelihood; rotated Gaussians; fused uncertainty and query calls (take them
+ * through the adapter, with held from the fused solve in the fit record); user-defined models in the fused form (that is what a
+ * callback is). */
+#define DOGLEG_AMD_MODEL_EXPDECAY         0
+#define DOGLEG_AMD_MODEL_GAUSS1D          1
+#define DOGLEG_AMD_MODEL_GAUSS2D          2
+#define DOGLEG_AMD_MODEL_GAUSS2D_ELLIPTIC 3
+typedef struct
+{
+  int           kind;
+  unsigned int  Nmeas;
+  unsigned int  width, height;
+  const double* y;
+  const double* t;
+  const double* scale;
+  int           t_per_problem;
+} dogleg_amd_batch_model_t;
+int dogleg_amd_batch_model_nstate(int kind);
+void dogleg_amd_batch_model_callback(const double* p_dev, double* x_dev, double* J_dev, const unsigned char* live_dev,
+                                     unsigned int B, void* hip_stream, void* cookie);
+unsigned long long dogleg_amd_batch_model_callback_invocations(void);
+int dogleg_amd_optimize_dense_batch_model(double* p, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                          const dogleg_parameters2_t* parameters,
+                                          const dogleg_amd_batch_bounds_t* bounds /* NULL: none */,
+                                          dogleg_amd_batch_result_t* results);
+int dogleg_amd_optimize_dense_batch_model_device(double* p_dev, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                                 const dogleg_parameters2_t* parameters,
+                                                 const dogleg_amd_batch_bounds_t* bounds,
+                                                 dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                 const unsigned char* active_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

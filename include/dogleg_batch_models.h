@@ -1,0 +1,170 @@
+/* dogleg_batch_models.h -- the built-in fit models of the batch solver (dogleg_amd_batch_model_t in dogleg.h): one row of the
+ * residual x and of its Jacobian J, from the parameters, one datum and one abscissa.  One function for the host and the device;
+ * the adapter callback (dogleg_amd_batch_model_callback) and the fused sweep of dogleg_amd_optimize_dense_batch_model both go
+ * through it, which is why the two routes give the same bits: the order of the operations is fixed below and nothing here may be
+ * contracted into a fused multiply-add or reassociated, whatever the flags of the translation unit.  clang (hipcc: host and
+ * device) is told so by the pragma; with another compiler use -ffp-contract=off.
+ *
+ *   x_i = s_i (f_i(p) - y_i),   J_ij = s_i d f_i / d p_j,   s_i = 1 without a scale
+ *
+ *   EXPDECAY          N = 3   p = A, k, c                   f_i = A exp(-k t_i) + c
+ *   GAUSS1D           N = 4   p = A, mu, sigma, c           f_i = A exp(-(t_i - mu)^2 / (2 sigma^2)) + c
+ *   GAUSS2D           N = 5   p = A, x0, y0, sigma, c       row i is pixel (ix, iy) = (i mod width, i div width), centres on the
+ *                                                           integers: f_i = A exp(-((ix - x0)^2 + (iy - y0)^2) / (2 sigma^2)) + c
+ *   GAUSS2D_ELLIPTIC  N = 6   p = A, x0, y0, sx, sy, c      f_i = A exp(-(ix - x0)^2 / (2 sx^2) - (iy - y0)^2 / (2 sy^2)) + c
+ *
+ * The Gaussians divide once, 1 / sigma, and work on z = (t - mu) / sigma: a sigma of exactly 0 gives a non-finite row. */
+#ifndef DOGLEG_BATCH_MODELS_H
+#define DOGLEG_BATCH_MODELS_H
+
+#if defined(__HIPCC__)
+#define DOGLEG_BATCH_MODEL_FN __host__ __device__ static inline __attribute__((always_inline))
+#else
+#include <math.h>
+#define DOGLEG_BATCH_MODEL_FN static inline
+#endif
+
+#define DOGLEG_BATCH_MODEL_EXPDECAY         0     /* = DOGLEG_AMD_MODEL_EXPDECAY */
+#define DOGLEG_BATCH_MODEL_GAUSS1D          1     /* = DOGLEG_AMD_MODEL_GAUSS1D */
+#define DOGLEG_BATCH_MODEL_GAUSS2D          2     /* = DOGLEG_AMD_MODEL_GAUSS2D */
+#define DOGLEG_BATCH_MODEL_GAUSS2D_ELLIPTIC 3     /* = DOGLEG_AMD_MODEL_GAUSS2D_ELLIPTIC */
+#define DOGLEG_BATCH_MODEL_MAX_NSTATE       6
+
+/* the number of parameters of a kind, -1 for an unknown one */
+DOGLEG_BATCH_MODEL_FN int dogleg_batch_model_nstate(int kind)
+{
+  return kind == DOGLEG_BATCH_MODEL_EXPDECAY ? 3 : kind == DOGLEG_BATCH_MODEL_GAUSS1D ? 4 :
+         kind == DOGLEG_BATCH_MODEL_GAUSS2D ? 5 : kind == DOGLEG_BATCH_MODEL_GAUSS2D_ELLIPTIC ? 6 : -1;
+}
+
+/* row i of a problem: p the N parameters, t the abscissa t_i (the 1D kinds; not read by the 2D kinds), width that of the window
+ * (the 2D kinds; not read by the 1D kinds), y the datum y_i, s the scale s_i (1 without one).  *x gets x_i, J[0 .. N-1] row i of
+ * J; J has room for DOGLEG_BATCH_MODEL_MAX_NSTATE doubles whatever the kind, and those behind N - 1 are written as 0 (the six
+ * stores are unconditional, so that on the device the row stays in registers).  An unknown kind writes nothing.  Every kind
+ * evaluates one exponential, e = exp(u): what leads to u comes first, then what every kind shares (x_i and the derivative with
+ * respect to A), then the other derivatives. */
+DOGLEG_BATCH_MODEL_FN void dogleg_batch_model_row(int kind, const double* p, int i, int width, double t, double y, double s,
+                                                  double* x, double* J)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  /* A, c: amplitude and offset; z0, z1: (abscissa - centre) / width per axis (EXPDECAY: z0 = t); q0, q1: their squares */
+  double A, c, u, inv0 = 0.0, inv1 = 0.0, z0 = 0.0, z1 = 0.0, q0 = 0.0, q1 = 0.0;
+  switch(kind)
+  {
+  case DOGLEG_BATCH_MODEL_EXPDECAY:
+  {
+    const double kt = p[1] * t;
+    A = p[0]; c = p[2];
+    z0 = t;
+    u = -kt;
+    break;
+  }
+  case DOGLEG_BATCH_MODEL_GAUSS1D:
+  {
+    const double d = t - p[1];
+    A = p[0]; c = p[3];
+    inv0 = 1.0 / p[2];
+    z0 = d * inv0;
+    q0 = z0 * z0;
+    u = -0.5 * q0;
+    break;
+  }
+  case DOGLEG_BATCH_MODEL_GAUSS2D:
+  {
+    const int iy = i / width, ix = i - iy * width;
+    const double dx = (double)ix - p[1];
+    const double dy = (double)iy - p[2];
+    A = p[0]; c = p[4];
+    inv0 = 1.0 / p[3];
+    z0 = dx * inv0;
+    z1 = dy * inv0;
+    q0 = z0 * z0;
+    q1 = z1 * z1;
+    const double q = q0 + q1;
+    u = -0.5 * q;
+    break;
+  }
+  case DOGLEG_BATCH_MODEL_GAUSS2D_ELLIPTIC:
+  {
+    const int iy = i / width, ix = i - iy * width;
+    const double dx = (double)ix - p[1];
+    const double dy = (double)iy - p[2];
+    A = p[0]; c = p[5];
+    inv0 = 1.0 / p[3];
+    inv1 = 1.0 / p[4];
+    z0 = dx * inv0;
+    z1 = dy * inv1;
+    q0 = z0 * z0;
+    q1 = z1 * z1;
+    const double q = q0 + q1;
+    u = -0.5 * q;
+    break;
+  }
+  default:
+    return;
+  }
+  const double e  = exp(u);
+  const double Ae = A * e;
+  const double f  = Ae + c;
+  const double r  = f - y;
+  double j1, j2, j3 = 0.0, j4 = 0.0, j5 = 0.0;
+  switch(kind)
+  {
+  case DOGLEG_BATCH_MODEL_EXPDECAY:
+  {
+    /* d/dk = -A t e */
+    const double At = A * z0;
+    const double dk = At * e;
+    j1 = s * (-dk);
+    j2 = s;
+    break;
+  }
+  case DOGLEG_BATCH_MODEL_GAUSS1D:
+  {
+    /* d/dmu = A e z / sigma, d/dsigma = A e z^2 / sigma */
+    const double Aei = Ae * inv0;
+    const double dmu = Aei * z0;
+    const double ds  = Aei * q0;
+    j1 = s * dmu;
+    j2 = s * ds;
+    j3 = s;
+    break;
+  }
+  case DOGLEG_BATCH_MODEL_GAUSS2D:
+  {
+    /* d/dx0 = A e zx / sigma, d/dy0 = A e zy / sigma, d/dsigma = A e (zx^2 + zy^2) / sigma */
+    const double Aei = Ae * inv0;
+    const double gx  = Aei * z0;
+    const double gy  = Aei * z1;
+    const double q   = q0 + q1;
+    const double gs  = Aei * q;
+    j1 = s * gx;
+    j2 = s * gy;
+    j3 = s * gs;
+    j4 = s;
+    break;
+  }
+  default:
+  {
+    /* GAUSS2D_ELLIPTIC: d/dx0 = A e zx / sx, d/dy0 = A e zy / sy, d/dsx = A e zx^2 / sx, d/dsy = A e zy^2 / sy */
+    const double Aex = Ae * inv0;
+    const double Aey = Ae * inv1;
+    const double gx  = Aex * z0;
+    const double gy  = Aey * z1;
+    const double gsx = Aex * q0;
+    const double gsy = Aey * q1;
+    j1 = s * gx;
+    j2 = s * gy;
+    j3 = s * gsx;
+    j4 = s * gsy;
+    j5 = s;
+    break;
+  }
+  }
+  *x = s * r;
+  J[0] = s * e;
+  J[1] = j1; J[2] = j2; J[3] = j3; J[4] = j4; J[5] = j5;
+}
+#endif

@@ -7,7 +7,8 @@ import ctypes as C
 import os
 import numpy as np
 
-from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, BatchLoss, BatchBounds, BatchFit, JacobianReport, JacobianEntry,
+from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, BatchLoss, BatchBounds, BatchFit, BatchModel, MODEL_NSTATE, JacobianReport,
+                          JacobianEntry,
                           NumericOptions, NUMERIC_FORWARD, NUMERIC_CENTRAL,
                           CB_SPARSE, CB_DENSE, CB_PRODUCTS, dptr, iptr)
 
@@ -86,6 +87,8 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_batch_numeric_stats", "dogleg_amd_batch_numeric_buffers", "dogleg_amd_numeric_step",
     "dogleg_amd_numeric_plan", "dogleg_amd_numeric_create", "dogleg_amd_numeric_destroy", "dogleg_amd_numeric_callback",
     "dogleg_amd_numeric_stats", "dogleg_amd_numeric_buffers",
+    "dogleg_amd_batch_model_nstate", "dogleg_amd_batch_model_callback", "dogleg_amd_batch_model_callback_invocations",
+    "dogleg_amd_optimize_dense_batch_model", "dogleg_amd_optimize_dense_batch_model_device",
 ]
 
 _lib = None
@@ -265,6 +268,14 @@ def lib():
         BP = C.POINTER(BatchBounds)
         L.dogleg_amd_optimize_dense_products_batch_bounded.argtypes = [D, C.c_uint, C.c_uint, V, V, PP, BP, C.POINTER(BatchResult)]
         L.dogleg_amd_optimize_dense_products_batch_bounded_device.argtypes = [V, C.c_uint, C.c_uint, V, V, PP, BP, V, V, V, V]
+    if hasattr(L, "dogleg_amd_optimize_dense_batch_model"):
+        MP, BP = C.POINTER(BatchModel), C.POINTER(BatchBounds)
+        L.dogleg_amd_batch_model_nstate.argtypes = [C.c_int]
+        L.dogleg_amd_batch_model_callback.argtypes = [V, V, V, V, C.c_uint, V, V]
+        L.dogleg_amd_batch_model_callback.restype = None
+        L.dogleg_amd_batch_model_callback_invocations.restype = C.c_ulonglong
+        L.dogleg_amd_optimize_dense_batch_model.argtypes = [D, C.c_uint, MP, PP, BP, C.POINTER(BatchResult)]
+        L.dogleg_amd_optimize_dense_batch_model_device.argtypes = [V, C.c_uint, MP, PP, BP, V, V, V, V]
     if hasattr(L, "dogleg_amd_dense_batch_query_covariance"):
         U = C.c_uint
         L.dogleg_amd_dense_batch_query_covariance.argtypes = [D, U, U, U, V, V, D, D, U, U, C.c_int, D, I]
@@ -706,6 +717,61 @@ def optimize_dense_products_batch_bounded_device(p_dev, B, N, cb, cookie, params
                                                                          C.byref(params) if params is not None else None,
                                                                          C.byref(bounds), _dev(results_dev), _dev(lambda_dev),
                                                                          _dev(active_dev), _dev(stream))
+
+
+def batch_model(kind, y_dev, Nmeas, width=0, height=0, t_dev=None, t_per_problem=False, scale_dev=None):
+    """a dogleg_amd_batch_model_t: y_dev (B, Nmeas), t_dev (Nmeas,) or, with t_per_problem, (B, Nmeas), scale_dev (B, Nmeas):
+    DeviceArrays or raw device addresses, None: NULL.  The caller keeps the record (and the arrays) alive while it is used"""
+    raw = lambda a: None if a is None else _dev(a).value
+    return BatchModel(kind, Nmeas, width, height, raw(y_dev), raw(t_dev), raw(scale_dev), 1 if t_per_problem else 0)
+
+
+def batch_model_callback(model):
+    """(cb, cookie, Nstate, Nmeas) of dogleg_amd_batch_model_callback on the record `model`: what every batch entry point that takes
+    a dogleg_callback_device_batch_t is called with"""
+    cb = C.cast(lib().dogleg_amd_batch_model_callback, C.c_void_p)
+    return cb, C.c_void_p(C.addressof(model)), MODEL_NSTATE[model.kind], model.Nmeas
+
+
+def batch_model_callback_invocations():
+    """dogleg_amd_batch_model_callback_invocations: calls of the adapter callback in this process"""
+    return int(lib().dogleg_amd_batch_model_callback_invocations())
+
+
+def optimize_dense_batch_model(p0s, model, lower=None, upper=None, params=None, bounded=None, want_held=True):
+    """dogleg_amd_optimize_dense_batch_model: p0s (B, N) host start points, model a BatchModel (None: NULL) whose arrays lie in
+    device memory; lower, upper (B, N) host arrays or None.  bounded: whether a bounds record is passed at all (default: when a
+    bound is given).  Returns (rc, p (B, N), results, held (B, N) uint8 prefilled with 255, or None without a bounds record)."""
+    L = lib()
+    N = MODEL_NSTATE.get(model.kind, 1) if model is not None else 1
+    p = np.array(p0s, dtype=np.float64, copy=True).reshape(-1, N)
+    B = p.shape[0]
+    res = (BatchResult * max(B, 1))()
+    if bounded is None:
+        bounded = lower is not None or upper is not None
+    lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).reshape(B, N)
+    hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).reshape(B, N)
+    held = np.full((B, N), 255, dtype=np.uint8) if bounded and want_held else None
+    addr = lambda a: None if a is None else a.ctypes.data
+    bounds = BatchBounds(addr(lo), addr(hi), addr(held))
+    rc = L.dogleg_amd_optimize_dense_batch_model(dptr(p), B, C.byref(model) if model is not None else None,
+                                                 C.byref(params) if params is not None else None,
+                                                 C.byref(bounds) if bounded else None, res)
+    return rc, p, _batch_results(res, B), held
+
+
+def optimize_dense_batch_model_device(p_dev, B, model, params, results_dev, lower_dev=None, upper_dev=None, held_dev=None,
+                                      lambda_dev=None, active_dev=None, stream=None, bounded=None):
+    """dogleg_amd_optimize_dense_batch_model_device: the arguments as optimize_dense_batch_bounded_device without callback and
+    loss; bounded: whether a bounds record is passed at all (default: when one of its arrays is given).  Returns rc."""
+    raw = lambda a: None if a is None else _dev(a).value
+    if bounded is None:
+        bounded = lower_dev is not None or upper_dev is not None or held_dev is not None
+    bounds = BatchBounds(raw(lower_dev), raw(upper_dev), raw(held_dev))
+    return lib().dogleg_amd_optimize_dense_batch_model_device(_dev(p_dev), B, C.byref(model) if model is not None else None,
+                                                              C.byref(params) if params is not None else None,
+                                                              C.byref(bounds) if bounded else None, _dev(results_dev),
+                                                              _dev(lambda_dev), _dev(active_dev), _dev(stream))
 
 
 def batch_results_from_device(results_dev, B):

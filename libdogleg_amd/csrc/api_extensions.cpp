@@ -8,6 +8,7 @@
 #include "dense_batch.h"
 #include "gradcheck.h"
 #include "gradcheck_plan.h"
+#include "../../include/dogleg_batch_models.h"
 
 namespace {
 
@@ -147,6 +148,30 @@ template <class Req> Req with_fit(Req a, const dogleg_amd_batch_fit_t* fit)
   return a;
 }
 
+// the record of a built-in model (dogleg.h: dogleg_amd_batch_model_t), from its members alone: no pointer's target is looked at
+bool batch_model_ok(const char* who, const dogleg_amd_batch_model_t* model)
+{
+  if(!model) { MSG("%s: model must be given", who); return false; }
+  if(dogleg_batch_model_nstate(model->kind) < 0)
+  {
+    MSG("%s: model->kind = %d is none of DOGLEG_AMD_MODEL_{EXPDECAY, GAUSS1D, GAUSS2D, GAUSS2D_ELLIPTIC}", who, model->kind);
+    return false;
+  }
+  if(!model->y) { MSG("%s: model->y must be given", who); return false; }
+  if(model->Nmeas == 0) { MSG("%s: model->Nmeas = 0", who); return false; }
+  const bool two_d = model->kind == DOGLEG_AMD_MODEL_GAUSS2D || model->kind == DOGLEG_AMD_MODEL_GAUSS2D_ELLIPTIC;
+  if(two_d && (unsigned long long)model->width*model->height != model->Nmeas)
+  {
+    MSG("%s: a window of model->width x model->height = %u x %u pixels, and model->Nmeas = %u", who, model->width, model->height,
+        model->Nmeas);
+    return false;
+  }
+  if(two_d && model->t) { MSG("%s: model->t must be NULL for the 2D kinds: the abscissae are the pixels' centres", who); return false; }
+  if(!two_d && (model->width || model->height))
+  { MSG("%s: model->width = %u, model->height = %u: both are 0 for the 1D kinds", who, model->width, model->height); return false; }
+  return true;
+}
+
 // a *_dev argument of the device-resident batch entry points: memory a kernel of the current device may touch over `bytes`
 bool device_span_ok(const char* who, const char* name, const void* ptr, size_t bytes)
 {
@@ -168,7 +193,7 @@ enum SolveKind { SOLVE_PLAIN, SOLVE_ROBUST, SOLVE_BOUNDED };
 int batch_solve_entry(const char* who, SolveKind kind, DlgBatchSolve a)
 {
   const char* dev = a.device ? "_dev" : "";
-  if(!a.p || !(a.fJ || a.fP) || !a.results) { MSG("%s: p%s, the callback and results%s must be given", who, dev, dev); return -1; }
+  if(!a.p || !(a.fJ || a.fP || a.model) || !a.results) { MSG("%s: p%s, the callback and results%s must be given", who, dev, dev); return -1; }
   if(!a.prm) a.prm = &g_params;
   a.unpacked = a.fP && !a.prm->JtJ_packed;
   if(!request_shape_ok(who, a, a.prm, "a loop over dogleg_optimize_dense2")) return -1;
@@ -186,6 +211,12 @@ int batch_solve_entry(const char* who, SolveKind kind, DlgBatchSolve a)
        device_span_ok_or_null(who, "bounds->lower", bounds.lower, sizeof(double)*BN) &&
        device_span_ok_or_null(who, "bounds->upper", bounds.upper, sizeof(double)*BN) &&
        device_span_ok_or_null(who, "bounds->held", bounds.held, BN))) return -1;
+  // the arrays of a model record lie in device memory on either route
+  const size_t BM = B*a.M;
+  if(a.model &&
+     !(device_span_ok(who, "model->y", a.model->y, sizeof(double)*BM) &&
+       device_span_ok_or_null(who, "model->t", a.model->t, sizeof(double)*(a.model->t_per_problem ? BM : (size_t)a.M)) &&
+       device_span_ok_or_null(who, "model->scale", a.model->scale, sizeof(double)*BM))) return -1;
   return dlg_dense_batch_solve(a);
 }
 // featureSize: as the caller gave it; a.fs is set here
@@ -456,6 +487,29 @@ int dogleg_amd_optimize_dense_batch(double* p, unsigned int B, unsigned int Nsta
                                     const dogleg_parameters2_t* parameters, dogleg_amd_batch_result_t* results)
 {
   return batch_solve_entry(__func__, SOLVE_PLAIN, DlgBatchSolve{p, B, Nstate, Nmeas, f, nullptr, cookie, false, parameters, results});
+}
+// ---- the fused solve of a built-in model (dogleg.h: dogleg_amd_batch_model_t): the third form of the solve record, no callback.
+// The record is checked first: Nstate and Nmeas come from it
+int dogleg_amd_optimize_dense_batch_model(double* p, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                          const dogleg_parameters2_t* parameters, const dogleg_amd_batch_bounds_t* bounds,
+                                          dogleg_amd_batch_result_t* results)
+{
+  if(!batch_model_ok(__func__, model)) return -1;
+  DlgBatchSolve a{p, B, (unsigned int)dogleg_batch_model_nstate(model->kind), model->Nmeas, nullptr, nullptr, nullptr, false,
+                  parameters, results};
+  a.bounds = bounds; a.model = model;
+  return batch_solve_entry(__func__, bounds ? SOLVE_BOUNDED : SOLVE_PLAIN, a);
+}
+int dogleg_amd_optimize_dense_batch_model_device(double* p_dev, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                                 const dogleg_parameters2_t* parameters, const dogleg_amd_batch_bounds_t* bounds,
+                                                 dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                 const unsigned char* active_dev, void* hip_stream)
+{
+  if(!batch_model_ok(__func__, model)) return -1;
+  DlgBatchSolve a{p_dev, B, (unsigned int)dogleg_batch_model_nstate(model->kind), model->Nmeas, nullptr, nullptr, nullptr, false,
+                  parameters, results_dev, lambda_dev, active_dev, hip_stream};
+  a.bounds = bounds; a.device = true; a.model = model;
+  return batch_solve_entry(__func__, bounds ? SOLVE_BOUNDED : SOLVE_PLAIN, a);
 }
 int dogleg_amd_batch_last_stats(double* out, int n) { return out ? dlg_dense_batch_last_stats(out, n) : 0; }
 int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,

@@ -22,6 +22,9 @@ struct DlgBatchSolve
   const dogleg_amd_batch_loss_t* loss; double* weights;
   const dogleg_amd_batch_bounds_t* bounds;                     // the bounded form (either form; lower / upper / held may be NULL), or NULL
   bool device;
+  // the model form (dogleg_amd_optimize_dense_batch_model[_device]): a third form beside fJ / fP, both NULL then; N and M are
+  // those of the (checked) record, whose arrays lie in device memory on either route; no loss.  NULL otherwise
+  const dogleg_amd_batch_model_t* model;
 };
 int  dlg_dense_batch_solve(const DlgBatchSolve& a);
 // the fit of the ..._fit entry points (dogleg_amd_batch_fit_t, checked by the caller), the last three members of the two records

@@ -137,12 +137,13 @@ struct Segments
 
 // ---- what every call path shares ----
 // the callback of a call and what it writes: the J form (fJ: x, J of Nmeas = M rows) or the products form (fP: norm2x,
-// xtJ, JtJ; M is 0 there)
+// xtJ, JtJ; M is 0 there), or the model form of the solve (model: no callback, nothing written: the rows are formed inside the sweep)
 struct BatchForm
 {
   dogleg_callback_device_batch_t* fJ;
   dogleg_callback_device_batch_products_t* fP;
   bool unpacked;               // products: JtJ as N x N
+  const dogleg_amd_batch_model_t* model;
   bool products() const { return fP != nullptr; }
   unsigned int S(unsigned int N) const { return unpacked ? N*N : N*(N + 1)/2; }
 };
@@ -157,7 +158,12 @@ EvalBuffer eval_buffer(const BatchForm& F, unsigned int B, unsigned int N, unsig
 {
   EvalBuffer E;
   Segments S;
-  if(F.products())
+  if(F.model)
+  {
+    // the model form: an empty buffer
+    E.doubles = 0.0; E.second = 0; E.third = 0;
+  }
+  else if(F.products())
   {
     E.doubles = (double)B*(1.0 + N + F.S(N));
     S.add(sizeof(double)*(size_t)B); E.second = S.add(sizeof(double)*(size_t)B*N); E.third = S.add(sizeof(double)*(size_t)B*F.S(N));
@@ -240,6 +246,7 @@ const char* solve_who(const DlgBatchSolve& a)
     {"dogleg_amd_optimize_dense_batch_bounded", "dogleg_amd_optimize_dense_batch_bounded_device"},
     {"dogleg_amd_optimize_dense_batch_robust", "dogleg_amd_optimize_dense_batch_robust_device"},
     {"dogleg_amd_optimize_dense_batch", "dogleg_amd_optimize_dense_batch_device"}};
+  if(a.model) return a.device ? "dogleg_amd_optimize_dense_batch_model_device" : "dogleg_amd_optimize_dense_batch_model";
   return names[a.fP ? (a.bounds ? 0 : 1) : a.bounds ? 2 : a.loss ? 3 : 4][a.device ? 1 : 0];
 }
 // the cache opened and grown for the solve a, and the kernels' argument pointing into it.  The host route keeps the bounds it is
@@ -276,6 +283,8 @@ int batch_setup(const char* who, const DlgBatchSolve& a, const BatchForm& F, Bat
   A.wts = loss ? (double*)(q + o_wts) : nullptr; A.NF = (int)NF; A.robust = loss ? 1 : 0;
   A.lo = room_lo ? (const double*)(q + o_lo) : nullptr; A.hi = room_hi ? (const double*)(q + o_hi) : nullptr;
   A.held = nullptr; A.bounded = 0;
+  A.Mdl = ModelDev{0, 0, 0, nullptr, nullptr, nullptr};
+  if(a.model) A.Mdl = ModelDev{a.model->kind, (int)a.model->width, a.model->t_per_problem ? 1 : 0, a.model->y, a.model->t, a.model->scale};
   A.L.kind = loss ? loss->kind : DOGLEG_AMD_LOSS_TRIVIAL; A.L.fs = (int)fs;
   A.L.a = loss && loss->kind != DOGLEG_AMD_LOSS_TRIVIAL ? loss->scale : 1.0; A.L.c = A.L.a*A.L.a;
   A.max_iterations = prm->max_iterations; A.trustregion0 = prm->trustregion0;
@@ -286,7 +295,7 @@ int batch_setup(const char* who, const DlgBatchSolve& a, const BatchForm& F, Bat
 }
 
 // the rounds on stream st, from the initial p in A.p_trial and the initial live bytes to the round that leaves no problem
-// live: the callback, ONE launch and the 4-byte read-back of the counter per round.  Fills t_stats.
+// live: the callback (none in the model form), ONE launch and the 4-byte read-back of the counter per round.  Fills t_stats.
 int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* cookie, hipStream_t st)
 {
   BatchCache& K = g_cache;
@@ -306,7 +315,7 @@ int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* c
     }
     BHIP(hipMemsetAsync(A.counter, 0, sizeof(int), st));
     if(T.mark(who, 0, st)) return -1;
-    invoke_callback(F, A.p_trial, A, A.live, (unsigned int)A.B, st, cookie);
+    if(!F.model) invoke_callback(F, A.p_trial, A, A.live, (unsigned int)A.B, st, cookie);
     if(T.mark(who, 1, st)) return -1;
     launch_batch_round(st, A);
     BHIP(hipGetLastError());
@@ -317,7 +326,8 @@ int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* c
     if(T.read(who)) return -1;
     if(*K.h_counter == 0) break;
   }
-  t_stats[0] = (double)rounds; t_stats[1] = T.ms_callback; t_stats[2] = T.ms_library;
+  // (the model form: no callback ran between the first two marks)
+  t_stats[0] = (double)rounds; t_stats[1] = F.model ? 0.0 : T.ms_callback; t_stats[2] = T.ms_library;
   return 0;
 }
 
@@ -327,7 +337,7 @@ int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* c
 // Everything on the caller's stream if one is given.
 int solve_locked(const DlgBatchSolve& a)
 {
-  const BatchForm F{a.fJ, a.fP, a.unpacked};
+  const BatchForm F{a.fJ, a.fP, a.unpacked, a.model};
   const char* who = solve_who(a);
   const unsigned int B = a.B, N = a.N;
   const dogleg_amd_batch_bounds_t* bounds = a.bounds;
@@ -408,7 +418,7 @@ struct EvalCall
 template <class Req> EvalCall eval_call(const char* who, const Req& a)
 {
   EvalCall c{};
-  c.who = who; c.F = BatchForm{a.fJ, a.fP, a.unpacked}; c.B = a.B; c.N = a.N; c.M = a.M; c.cookie = a.cookie;
+  c.who = who; c.F = BatchForm{a.fJ, a.fP, a.unpacked, nullptr}; c.B = a.B; c.N = a.N; c.M = a.M; c.cookie = a.cookie;
   c.p = a.p; c.lambda = a.lambda; c.status = a.status; c.active = a.active; c.stream = a.stream; c.device = a.device;
   c.loss = a.loss; c.weights = a.weights; c.held = a.held;
   return c;

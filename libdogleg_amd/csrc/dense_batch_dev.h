@@ -20,6 +20,14 @@ struct ProductsDev
 // the loss of a robust solve: c = a^2, fs rows a feature
 struct LossDev { int kind, fs; double a, c; };
 
+// a built-in model (dogleg.h: dogleg_amd_batch_model_t) as the fused sweep reads it: y [B][M]; t nullptr (t_i = i), [M] or, with
+// t_each, [B][M]; scale [B][M] or nullptr.  y == nullptr: no model, and that is how the launcher tells this form from the others
+struct ModelDev
+{
+  int kind, width, t_each;
+  const double *y, *t, *scale;
+};
+
 struct BatchDev
 {
   int B, N, M, NP;
@@ -35,6 +43,7 @@ struct BatchDev
   // (no bound on that side), held [B][N] out or nullptr
   const double *lo, *hi; unsigned char* held;
   int bounded;                 // (host side: which kernel is launched)
+  ModelDev Mdl;                // FORM_MODEL (x, J, P unused there), behind everything above
 };
 
 struct UncDev

@@ -29,6 +29,11 @@
 // the same three things where sweep_point leaves them; from evaluate_step on both forms run the same functions.  The
 // kernels are templates over the form: the J-form instantiations keep their arithmetic and their order of operations.
 //
+// The model form (dogleg_amd_optimize_dense_batch_model): a built-in closed-form model (include/dogleg_batch_models.h) instead of a
+// callback.  A third front end (sweep_model) forms each row of x and J in the lane that would have staged it and puts it into the
+// tile; x and J never lie in memory, and the results have the bits of the J form on what the adapter callback (batch_models.hip)
+// would have written.  Only the class of 8 is instantiated: every model has at most 6 variables.
+//
 // The device-resident twins (dogleg_amd_*_batch_device): the same rounds and the same launch of k_batch_uncertainty with every
 // array of the caller in device memory.  The solve takes its initial p by a copy within the device and ends in k_batch_finish,
 // which writes p, the result structs and lambda where the caller has them; the uncertainty kernel's per-output pointers point
@@ -52,6 +57,7 @@
 #include <cfloat>
 #include <type_traits>
 #include "dense_batch_dev.h"
+#include "../../include/dogleg_batch_models.h"
 
 namespace {
 
@@ -60,7 +66,7 @@ constexpr double LAMBDA_INITIAL = 1e-10;       // dogleg.c:138
 
 enum { F_CAUCHY = 1, F_GN = 2, F_EDGE = 4, F_STARTED = 8 };
 
-enum { FORM_J = 0, FORM_PRODUCTS = 1 };
+enum { FORM_J = 0, FORM_PRODUCTS = 1, FORM_MODEL = 2 };
 
 template <int NMAX> struct BatchCfg
 {
@@ -72,10 +78,11 @@ template <int NMAX> struct BatchCfg
   // workgroups of any class fit a CU's 160 KB
   static constexpr int WPB = NMAX <= 32 ? 4 : NMAX <= 48 ? 2 : 1;
 };
-// the same per form: the products form has no row tile, the second region holds the factor only
+// the same per form: the products form has no row tile, the second region holds the factor only (the model form stages the J
+// form's tile)
 template <int NMAX, int FORM> struct FormCfg
 {
-  static constexpr int SCR = FORM == FORM_J ? BatchCfg<NMAX>::SCR : BatchCfg<NMAX>::NP;
+  static constexpr int SCR = FORM != FORM_PRODUCTS ? BatchCfg<NMAX>::SCR : BatchCfg<NMAX>::NP;
   static constexpr int LDSW = BatchCfg<NMAX>::NP + SCR + NMAX;
 };
 
@@ -426,6 +433,83 @@ __device__ __forceinline__ double load_products(const ProductsDev& P, int b, int
   return n2x;
 }
 
+// the front end of the model form (dogleg_amd_optimize_dense_batch_model): sweep_point<NMAX, SWEEP_PLAIN> over an x and a J that
+// never lie in memory.  Lane t of the wave forms row r0 + t of the tile from p (pb: N doubles, the same in every lane), its datum,
+// abscissa and scale through dogleg_batch_model_row -- the function the adapter callback writes x and J with, its contraction
+// switched off -- and puts it where sweep_point would have staged it: tile[t N ..] and xt[t].  The tile height, the zeros behind
+// the tile's rows, the sum for norm2(x) and the loop over the tile's rows are sweep_point's, so the results have its bits on what
+// the adapter would have written.  The loads of the next tile's y, t and scale are in flight under the loop; only the lanes that
+// hold a row evaluate the model.
+template <int NMAX>
+__device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* pb, int b, int N, int M, int NP, int lane,
+                                              double* SA, double* tile, double& gacc_out)
+{
+  using C = BatchCfg<NMAX>;
+  constexpr int NM = DOGLEG_BATCH_MODEL_MAX_NSTATE;
+  static_assert(NM <= NMAX, "every built-in model lies in the smallest size class");
+  double* xt = tile + BATCH_TILE;
+  int ei[C::NE], ej[C::NE];
+  packed_entries<NMAX>(N, NP, lane, ei, ej);
+  const int T = min(64, BATCH_TILE/N);
+  double acc[C::NE], gacc = 0.0, n2 = 0.0;
+#pragma unroll
+  for(int k = 0; k < C::NE; k++) acc[k] = 0.0;
+  double p[NM];
+#pragma unroll
+  for(int j = 0; j < NM; j++) p[j] = j < N ? pb[j] : 0.0;
+  const double* yb = Md.y + (size_t)b*M;
+  const double* tb = Md.t ? Md.t + (Md.t_each ? (size_t)b*M : (size_t)0) : nullptr;
+  const double* sb = Md.scale ? Md.scale + (size_t)b*M : nullptr;
+  double yv = 0.0, tv = 0.0, sv = 1.0;
+  if(lane < min(T, M))
+  {
+    yv = yb[lane];
+    tv = tb ? tb[lane] : (double)lane;
+    if(sb) sv = sb[lane];
+  }
+  for(int r0 = 0; r0 < M; r0 += T)
+  {
+    const int tc = min(T, M - r0);
+    double xv = 0.0, jr[NM];
+#pragma unroll
+    for(int j = 0; j < NM; j++) jr[j] = 0.0;
+    if(lane < tc) dogleg_batch_model_row(Md.kind, p, r0 + lane, Md.width, tv, yv, sv, &xv, jr);
+    wsync();
+    if(lane < T)
+    {
+#pragma unroll
+      for(int j = 0; j < NM; j++) if(j < N) tile[lane*N + j] = jr[j];
+    }
+    xt[lane] = xv;
+    wsync();
+    n2 = __builtin_fma(xv, xv, n2);
+    if(r0 + T < M)
+    {
+      const int r1 = r0 + T, tn = min(T, M - r1);
+      if(lane < tn)
+      {
+        yv = yb[r1 + lane];
+        tv = tb ? tb[r1 + lane] : (double)(r1 + lane);
+        if(sb) sv = sb[r1 + lane];
+      }
+    }
+    for(int t = 0; t < tc; t++)
+    {
+      const double* row = tile + t*N;
+#pragma unroll
+      for(int k = 0; k < C::NE; k++) acc[k] += row[ei[k]]*row[ej[k]];
+      if(lane < N) gacc += row[lane]*xt[t];
+    }
+  }
+  const double n2x = wave_sum(n2);
+  wsync();
+#pragma unroll
+  for(int k = 0; k < C::NE; k++) if(lane + 64*k < NP) SA[lane + 64*k] = acc[k];
+  wsync();
+  gacc_out = gacc;
+  return n2x;
+}
+
 // one round of problem b; returns whether the problem is still live.
 // BOUNDED (either form): box bounds by an active set, the eight steps above dogleg_amd_optimize_dense_batch_bounded in dogleg.h.
 // Everything it adds lies behind the sweep (products form: behind load_products), on the on-chip JtJ, g and the two cached
@@ -447,6 +531,14 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
     // ---- the sweep over the trial point's x and J: norm2(x), Jt x, JtJ (ROBUST: F, g, H in their places) ----
     n2x = sweep_point<NMAX, ROBUST>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc, A.L);
     // a non-finite x or J shows in norm2(x) or on the diagonal of JtJ
+    const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
+    finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
+  }
+  else if constexpr(FORM == FORM_MODEL)
+  {
+    // ---- the same sweep over rows formed on the way into the tile: no x, no J in memory ----
+    static_assert(!ROBUST, "the model form has no loss");
+    n2x = sweep_model<NMAX>(A.Mdl, A.p_trial + bN, b, N, M, NP, lane, SA, SL, gacc);
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
   }
@@ -1332,7 +1424,16 @@ void launch_batch_round(hipStream_t st, const BatchDev& A)
 {
   for_size_class(A.N, [&](auto c) {
     constexpr int NMAX = decltype(c)::value;
-    if(A.P.n2x)
+    if(A.Mdl.y)
+    {
+      // (every built-in model lies in the class of 8: the host side refuses anything else)
+      if constexpr(NMAX == 8)
+      {
+        if(A.bounded)        launch_class<NMAX>(k_batch_round<NMAX, FORM_MODEL, false, true>, st, A.B, A);
+        else                 launch_class<NMAX>(k_batch_round<NMAX, FORM_MODEL, false, false>, st, A.B, A);
+      }
+    }
+    else if(A.P.n2x)
     {
       if(A.bounded)          launch_class<NMAX>(k_batch_round<NMAX, FORM_PRODUCTS, false, true>, st, A.B, A);
       else                   launch_class<NMAX>(k_batch_round<NMAX, FORM_PRODUCTS, false, false>, st, A.B, A);

@@ -145,6 +145,16 @@ class BatchFit(C.Structure):
     _fields_ = [("loss", C.POINTER(BatchLoss)), ("weights", C.c_void_p), ("held", C.c_void_p)]
 
 
+MODEL_EXPDECAY, MODEL_GAUSS1D, MODEL_GAUSS2D, MODEL_GAUSS2D_ELLIPTIC = 0, 1, 2, 3      # dogleg_amd_batch_model_t.kind
+MODEL_NSTATE = {MODEL_EXPDECAY: 3, MODEL_GAUSS1D: 4, MODEL_GAUSS2D: 5, MODEL_GAUSS2D_ELLIPTIC: 6}
+
+
+class BatchModel(C.Structure):
+    """dogleg_amd_batch_model_t (include/dogleg.h): y, t and scale are device addresses, each 0 for NULL."""
+    _fields_ = [("kind", C.c_int), ("Nmeas", C.c_uint), ("width", C.c_uint), ("height", C.c_uint),
+                ("y", C.c_void_p), ("t", C.c_void_p), ("scale", C.c_void_p), ("t_per_problem", C.c_int)]
+
+
 class JacobianReport(C.Structure):
     """dogleg_amd_jacobian_report_t (include/dogleg.h)."""
     _fields_ = [
