@@ -1224,9 +1224,37 @@ int dogleg_amd_numeric_buffers(struct dogleg_amd_numeric* h, const double** p_co
  * kind, a set communicator, and arrays of the record that are not device-accessible over their span.
  *
  * Not provided: a loss in the fused form (the adapter route has it: dogleg_amd_optimize_dense_batch_robust / _bounded with the
- * callback above); float or integer data; a Poisson likelihood; rotated Gaussians; fused uncertainty and query calls (take them
+ * callback above); float or integer data; rotated Gaussians; fused uncertainty and query calls (take them
  * through the adapter, with held from the fused solve in the fit record); user-defined models in the fused form (that is what a
- * callback is). */
+ * callback is).
+ *
+ * 3. Maximum-likelihood fits of count data.  dogleg_amd_optimize_dense_batch_model_mle[_device] are the fused solve above with a
+ * likelihood.  DOGLEG_AMD_LIKELIHOOD_GAUSS: the fused solve above, bit for bit.  DOGLEG_AMD_LIKELIHOOD_POISSON: the data y_i >= 0
+ * are counts and the model value f_i(p) their expectation, which must be > 0:
+ *   cost   F(p) = sum_i d_i, the Poisson deviance (2 (-log L) up to a constant): d_i = 2 (r_i - y_i log(f_i / y_i)), r_i = f_i - y_i,
+ *          and d_i = 2 f_i where y_i == 0.0
+ *   rows   x~_i = r_i q_i, J~_ij = (d f_i / d p_j) q_i with q_i = 1 / sqrt(f_i): g = J~' x~ = sum (r_i / f_i) grad f_i = 1/2 grad F,
+ *          H = J~' J~ = sum grad f_i grad f_i' / f_i, the Fisher information (Fisher scoring; sum (y_i / f_i^2) grad f grad f' is
+ *          not taken: the zero counts drop out of it and H loses definiteness at low counts)
+ *   loop   that of the fused solve, plain or bounded, unchanged: F takes the place of norm2(x) in the gain ratio and in
+ *          results[b].norm2_x, g and H that of J'x and J'J everywhere else, as in the robust solve
+ * A row with !(f_i > 0) makes a point infeasible: its cost is +infinity.  An infeasible TRIAL point is a rejected step by the
+ * ordinary rule (rho = -infinity: the trust region shrinks and the loop steps again from the cached steps, down to
+ * DOGLEG_AMD_BATCH_TRUSTREGION); an infeasible START point ends DOGLEG_AMD_BATCH_FAILED, alone.  A negative or NaN datum makes the
+ * cost or the gradient NaN at the first evaluation: FAILED, alone.  The arithmetic of a row: dogleg_batch_model_row_poisson in
+ * dogleg_batch_models.h.  In every other respect the contract is that of dogleg_amd_optimize_dense_batch_model[_device]: bounds or
+ * none, held, the active mask, the stream rule, one launch and one 4-byte read-back a round, no x / J buffer.
+ * Refused with a message and -1 before any device work, outputs untouched: what the fused solve above refuses, a likelihood that
+ * is neither of the two, and model->scale != NULL with POISSON (counts carry their own variance).
+ *
+ * dogleg_amd_batch_model_fisher_callback is a dogleg_callback_device_batch_t whose cookie is the model record (scale NULL); it
+ * writes x~ and J~ of the Poisson definition, NaN in an infeasible row, in one launch.  It is there for the uncertainty, query and
+ * _fit calls: through it they return (H + lambda I)^-1, at the optimum of the Poisson solve the Cramer-Rao bound of the fit; pass
+ * held of the bounded solve in the fit record.  ITS J~ IS NOT d x~ / d p (that has the term -(f + y) / (2 f^(3/2)) grad f instead
+ * of grad f / sqrt(f)), so dogleg_amd_check_jacobian_device_batch reports it, rightly, and a solve through it would minimise
+ * Pearson's chi^2 with a wrong Jacobian: EVERY BATCH SOLVE ENTRY POINT REFUSES THIS CALLBACK with a message and -1 (the plain,
+ * robust and bounded solves and their _device twins).
+ * Not provided: a loss in this form; other likelihoods; a gain or offset per datum (EMCCD / sCMOS noise models); the products form. */
 #define DOGLEG_AMD_MODEL_EXPDECAY         0
 #define DOGLEG_AMD_MODEL_GAUSS1D          1
 #define DOGLEG_AMD_MODEL_GAUSS2D          2
@@ -1254,6 +1282,19 @@ int dogleg_amd_optimize_dense_batch_model_device(double* p_dev, unsigned int B, 
                                                  const dogleg_amd_batch_bounds_t* bounds,
                                                  dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
                                                  const unsigned char* active_dev, void* hip_stream);
+#define DOGLEG_AMD_LIKELIHOOD_GAUSS   0
+#define DOGLEG_AMD_LIKELIHOOD_POISSON 1
+int dogleg_amd_optimize_dense_batch_model_mle(double* p, unsigned int B, const dogleg_amd_batch_model_t* model, int likelihood,
+                                              const dogleg_parameters2_t* parameters,
+                                              const dogleg_amd_batch_bounds_t* bounds /* NULL: none */,
+                                              dogleg_amd_batch_result_t* results);
+int dogleg_amd_optimize_dense_batch_model_mle_device(double* p_dev, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                                     int likelihood, const dogleg_parameters2_t* parameters,
+                                                     const dogleg_amd_batch_bounds_t* bounds,
+                                                     dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                     const unsigned char* active_dev, void* hip_stream);
+void dogleg_amd_batch_model_fisher_callback(const double* p_dev, double* x_dev, double* J_dev, const unsigned char* live_dev,
+                                            unsigned int B, void* hip_stream, void* cookie);
 
 #ifdef __cplusplus
 }

@@ -167,4 +167,45 @@ DOGLEG_BATCH_MODEL_FN void dogleg_batch_model_row(int kind, const double* p, int
   J[0] = s * e;
   J[1] = j1; J[2] = j2; J[3] = j3; J[4] = j4; J[5] = j5;
 }
+
+/* row i of a problem under the Poisson likelihood (dogleg.h: DOGLEG_AMD_LIKELIHOOD_POISSON): y a count >= 0, no scale.
+ *
+ *   q_i = 1 / sqrt(f_i),   *x = (f_i - y_i) q_i,   J[j] = (d f_i / d p_j) q_i,
+ *   *d  = 2 ((f_i - y_i) - y_i log(f_i / y_i)),    2 f_i where y_i == 0.0           (the row's share of the deviance)
+ *
+ * so that J'x = sum (r / f) grad f is half the gradient of the deviance and J'J = sum grad f grad f' / f the Fisher information.
+ * f_i and its gradient come from dogleg_batch_model_row with y = 0 and s = 1, with the bits they have there; then, in this order
+ * and uncontracted: r = f - y, sqrt(f), q = 1 / sqrt(f), the products with q, f / y, one log, y log, r - y log, times 2.  The
+ * test is y == 0.0 and not y > 0: a NaN datum reaches the logarithm, a negative one makes it NaN.
+ * Returns whether the row is feasible, f_i > 0.  An infeasible row (a NaN f included) gets *x = *d = NaN and a J of NaN: what is
+ * done with it is the caller's rule (the fused sweep stages zeros and makes the cost +infinity, the Fisher callback writes the
+ * NaN).  An unknown kind writes nothing and returns 0. */
+DOGLEG_BATCH_MODEL_FN int dogleg_batch_model_row_poisson(int kind, const double* p, int i, int width, double t, double y,
+                                                         double* x, double* J, double* d)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double f = 0.0;
+  if(dogleg_batch_model_nstate(kind) < 0) return 0;
+  dogleg_batch_model_row(kind, p, i, width, t, 0.0, 1.0, &f, J);
+  const int feasible = f > 0.0;
+  const double r  = f - y;
+  const double sf = sqrt(f);
+  const double q  = feasible ? 1.0 / sf : NAN;
+  const double xq = r * q;
+  J[0] = J[0] * q; J[1] = J[1] * q; J[2] = J[2] * q; J[3] = J[3] * q; J[4] = J[4] * q; J[5] = J[5] * q;
+  double dev;
+  if(y == 0.0) dev = f;
+  else
+  {
+    const double fy = f / y;
+    const double lg = log(fy);
+    const double yl = y * lg;
+    dev = r - yl;
+  }
+  *x = xq;
+  *d = feasible ? 2.0 * dev : NAN;
+  return feasible;
+}
 #endif

@@ -89,6 +89,8 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_numeric_stats", "dogleg_amd_numeric_buffers",
     "dogleg_amd_batch_model_nstate", "dogleg_amd_batch_model_callback", "dogleg_amd_batch_model_callback_invocations",
     "dogleg_amd_optimize_dense_batch_model", "dogleg_amd_optimize_dense_batch_model_device",
+    "dogleg_amd_optimize_dense_batch_model_mle", "dogleg_amd_optimize_dense_batch_model_mle_device",
+    "dogleg_amd_batch_model_fisher_callback",
 ]
 
 _lib = None
@@ -276,6 +278,12 @@ def lib():
         L.dogleg_amd_batch_model_callback_invocations.restype = C.c_ulonglong
         L.dogleg_amd_optimize_dense_batch_model.argtypes = [D, C.c_uint, MP, PP, BP, C.POINTER(BatchResult)]
         L.dogleg_amd_optimize_dense_batch_model_device.argtypes = [V, C.c_uint, MP, PP, BP, V, V, V, V]
+    if hasattr(L, "dogleg_amd_optimize_dense_batch_model_mle"):
+        MP, BP = C.POINTER(BatchModel), C.POINTER(BatchBounds)
+        L.dogleg_amd_optimize_dense_batch_model_mle.argtypes = [D, C.c_uint, MP, C.c_int, PP, BP, C.POINTER(BatchResult)]
+        L.dogleg_amd_optimize_dense_batch_model_mle_device.argtypes = [V, C.c_uint, MP, C.c_int, PP, BP, V, V, V, V]
+        L.dogleg_amd_batch_model_fisher_callback.argtypes = [V, V, V, V, C.c_uint, V, V]
+        L.dogleg_amd_batch_model_fisher_callback.restype = None
     if hasattr(L, "dogleg_amd_dense_batch_query_covariance"):
         U = C.c_uint
         L.dogleg_amd_dense_batch_query_covariance.argtypes = [D, U, U, U, V, V, D, D, U, U, C.c_int, D, I]
@@ -772,6 +780,47 @@ def optimize_dense_batch_model_device(p_dev, B, model, params, results_dev, lowe
                                                               C.byref(params) if params is not None else None,
                                                               C.byref(bounds) if bounded else None, _dev(results_dev),
                                                               _dev(lambda_dev), _dev(active_dev), _dev(stream))
+
+
+def batch_model_fisher_callback(model):
+    """(cb, cookie, Nstate, Nmeas) of dogleg_amd_batch_model_fisher_callback on the record `model`: the rows of the Poisson
+    likelihood, for the uncertainty, query and _fit calls (the solve entry points refuse it)"""
+    cb = C.cast(lib().dogleg_amd_batch_model_fisher_callback, C.c_void_p)
+    return cb, C.c_void_p(C.addressof(model)), MODEL_NSTATE[model.kind], model.Nmeas
+
+
+def optimize_dense_batch_model_mle(p0s, model, likelihood, lower=None, upper=None, params=None, bounded=None, want_held=True):
+    """dogleg_amd_optimize_dense_batch_model_mle: optimize_dense_batch_model with a likelihood (LIKELIHOOD_GAUSS or
+    LIKELIHOOD_POISSON of ctypes_defs); the same arguments otherwise and the same return value"""
+    L = lib()
+    N = MODEL_NSTATE.get(model.kind, 1) if model is not None else 1
+    p = np.array(p0s, dtype=np.float64, copy=True).reshape(-1, N)
+    B = p.shape[0]
+    res = (BatchResult * max(B, 1))()
+    if bounded is None:
+        bounded = lower is not None or upper is not None
+    lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).reshape(B, N)
+    hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).reshape(B, N)
+    held = np.full((B, N), 255, dtype=np.uint8) if bounded and want_held else None
+    addr = lambda a: None if a is None else a.ctypes.data
+    bounds = BatchBounds(addr(lo), addr(hi), addr(held))
+    rc = L.dogleg_amd_optimize_dense_batch_model_mle(dptr(p), B, C.byref(model) if model is not None else None, likelihood,
+                                                     C.byref(params) if params is not None else None,
+                                                     C.byref(bounds) if bounded else None, res)
+    return rc, p, _batch_results(res, B), held
+
+
+def optimize_dense_batch_model_mle_device(p_dev, B, model, likelihood, params, results_dev, lower_dev=None, upper_dev=None,
+                                          held_dev=None, lambda_dev=None, active_dev=None, stream=None, bounded=None):
+    """dogleg_amd_optimize_dense_batch_model_mle_device: optimize_dense_batch_model_device with a likelihood.  Returns rc."""
+    raw = lambda a: None if a is None else _dev(a).value
+    if bounded is None:
+        bounded = lower_dev is not None or upper_dev is not None or held_dev is not None
+    bounds = BatchBounds(raw(lower_dev), raw(upper_dev), raw(held_dev))
+    return lib().dogleg_amd_optimize_dense_batch_model_mle_device(_dev(p_dev), B, C.byref(model) if model is not None else None,
+                                                                  likelihood, C.byref(params) if params is not None else None,
+                                                                  C.byref(bounds) if bounded else None, _dev(results_dev),
+                                                                  _dev(lambda_dev), _dev(active_dev), _dev(stream))
 
 
 def batch_results_from_device(results_dev, B):

@@ -149,9 +149,19 @@ template <class Req> Req with_fit(Req a, const dogleg_amd_batch_fit_t* fit)
 }
 
 // the record of a built-in model (dogleg.h: dogleg_amd_batch_model_t), from its members alone: no pointer's target is looked at
-bool batch_model_ok(const char* who, const dogleg_amd_batch_model_t* model)
+bool batch_model_ok(const char* who, const dogleg_amd_batch_model_t* model, int likelihood = DOGLEG_AMD_LIKELIHOOD_GAUSS)
 {
+  if(likelihood != DOGLEG_AMD_LIKELIHOOD_GAUSS && likelihood != DOGLEG_AMD_LIKELIHOOD_POISSON)
+  {
+    MSG("%s: likelihood = %d is neither DOGLEG_AMD_LIKELIHOOD_GAUSS nor DOGLEG_AMD_LIKELIHOOD_POISSON", who, likelihood);
+    return false;
+  }
   if(!model) { MSG("%s: model must be given", who); return false; }
+  if(likelihood == DOGLEG_AMD_LIKELIHOOD_POISSON && model->scale)
+  {
+    MSG("%s: model->scale must be NULL with DOGLEG_AMD_LIKELIHOOD_POISSON: counts carry their own variance", who);
+    return false;
+  }
   if(dogleg_batch_model_nstate(model->kind) < 0)
   {
     MSG("%s: model->kind = %d is none of DOGLEG_AMD_MODEL_{EXPDECAY, GAUSS1D, GAUSS2D, GAUSS2D_ELLIPTIC}", who, model->kind);
@@ -194,6 +204,14 @@ int batch_solve_entry(const char* who, SolveKind kind, DlgBatchSolve a)
 {
   const char* dev = a.device ? "_dev" : "";
   if(!a.p || !(a.fJ || a.fP || a.model) || !a.results) { MSG("%s: p%s, the callback and results%s must be given", who, dev, dev); return -1; }
+  // (every solve by a J callback comes through here: the plain, robust and bounded ones and their _device twins)
+  if(a.fJ == dogleg_amd_batch_model_fisher_callback)
+  {
+    MSG("%s: dogleg_amd_batch_model_fisher_callback is no callback of a solve: its J is not the derivative of its x, and a solve through "
+        "it would minimise Pearson's chi^2 with a wrong Jacobian.  The Poisson fit is dogleg_amd_optimize_dense_batch_model_mle; this "
+        "callback serves the uncertainty, query and _fit calls", who);
+    return -1;
+  }
   if(!a.prm) a.prm = &g_params;
   a.unpacked = a.fP && !a.prm->JtJ_packed;
   if(!request_shape_ok(who, a, a.prm, "a loop over dogleg_optimize_dense2")) return -1;
@@ -509,6 +527,29 @@ int dogleg_amd_optimize_dense_batch_model_device(double* p_dev, unsigned int B, 
   DlgBatchSolve a{p_dev, B, (unsigned int)dogleg_batch_model_nstate(model->kind), model->Nmeas, nullptr, nullptr, nullptr, false,
                   parameters, results_dev, lambda_dev, active_dev, hip_stream};
   a.bounds = bounds; a.device = true; a.model = model;
+  return batch_solve_entry(__func__, bounds ? SOLVE_BOUNDED : SOLVE_PLAIN, a);
+}
+// ---- the same with a likelihood: GAUSS is the record of the two above; POISSON travels in it beside the model
+int dogleg_amd_optimize_dense_batch_model_mle(double* p, unsigned int B, const dogleg_amd_batch_model_t* model, int likelihood,
+                                              const dogleg_parameters2_t* parameters, const dogleg_amd_batch_bounds_t* bounds,
+                                              dogleg_amd_batch_result_t* results)
+{
+  if(!batch_model_ok(__func__, model, likelihood)) return -1;
+  DlgBatchSolve a{p, B, (unsigned int)dogleg_batch_model_nstate(model->kind), model->Nmeas, nullptr, nullptr, nullptr, false,
+                  parameters, results};
+  a.bounds = bounds; a.model = model; a.likelihood = likelihood; a.mle = true;
+  return batch_solve_entry(__func__, bounds ? SOLVE_BOUNDED : SOLVE_PLAIN, a);
+}
+int dogleg_amd_optimize_dense_batch_model_mle_device(double* p_dev, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                                     int likelihood, const dogleg_parameters2_t* parameters,
+                                                     const dogleg_amd_batch_bounds_t* bounds,
+                                                     dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                     const unsigned char* active_dev, void* hip_stream)
+{
+  if(!batch_model_ok(__func__, model, likelihood)) return -1;
+  DlgBatchSolve a{p_dev, B, (unsigned int)dogleg_batch_model_nstate(model->kind), model->Nmeas, nullptr, nullptr, nullptr, false,
+                  parameters, results_dev, lambda_dev, active_dev, hip_stream};
+  a.bounds = bounds; a.device = true; a.model = model; a.likelihood = likelihood; a.mle = true;
   return batch_solve_entry(__func__, bounds ? SOLVE_BOUNDED : SOLVE_PLAIN, a);
 }
 int dogleg_amd_batch_last_stats(double* out, int n) { return out ? dlg_dense_batch_last_stats(out, n) : 0; }

@@ -40,6 +40,27 @@ __global__ void __launch_bounds__(256) k_model_rows(int B, int M, int N, int kin
   for(int j = 0; j < DOGLEG_BATCH_MODEL_MAX_NSTATE; j++) if(j < N) J[idx*N + j] = jr[j];
 }
 
+// the same for the rows of the Poisson likelihood (dogleg_batch_model_row_poisson): x~ and J~, NaN in an infeasible row
+__global__ void __launch_bounds__(256) k_model_rows_poisson(int B, int M, int N, int kind, int width, int t_each,
+                                                            const double* __restrict__ y, const double* __restrict__ t,
+                                                            const unsigned char* __restrict__ live, const double* __restrict__ p,
+                                                            double* __restrict__ x, double* __restrict__ J)
+{
+  const size_t idx = (size_t)blockIdx.x*256 + threadIdx.x;
+  if(idx >= (size_t)B*M) return;
+  const int b = (int)(idx/M), i = (int)(idx - (size_t)b*M);
+  if(!live[b]) return;
+  double pv[DOGLEG_BATCH_MODEL_MAX_NSTATE], jr[DOGLEG_BATCH_MODEL_MAX_NSTATE];
+#pragma unroll
+  for(int j = 0; j < DOGLEG_BATCH_MODEL_MAX_NSTATE; j++) { pv[j] = j < N ? p[(size_t)b*N + j] : 0.0; jr[j] = 0.0; }
+  const double ti = t ? t[t_each ? idx : (size_t)i] : (double)i;
+  double xv = 0.0, dv = 0.0;
+  (void)dogleg_batch_model_row_poisson(kind, pv, i, width, ti, y[idx], &xv, jr, &dv);
+  x[idx] = xv;
+#pragma unroll
+  for(int j = 0; j < DOGLEG_BATCH_MODEL_MAX_NSTATE; j++) if(j < N) J[idx*N + j] = jr[j];
+}
+
 } // namespace
 
 extern "C" {
@@ -65,6 +86,25 @@ void dogleg_amd_batch_model_callback(const double* p_dev, double* x_dev, double*
   hipLaunchKernelGGL(k_model_rows, dim3((unsigned int)((rows + 255)/256)), dim3(256), 0, (hipStream_t)hip_stream, (int)B,
                      (int)m->Nmeas, N, m->kind, (int)m->width, m->t_per_problem ? 1 : 0, m->y, m->t, m->scale, live_dev, p_dev,
                      x_dev, J_dev);
+}
+
+// a dogleg_callback_device_batch_t for the uncertainty, query and _fit calls of a Poisson fit (dogleg.h): x~ and J~.  Its J~ is not
+// the derivative of its x~, so the solve entry points refuse it (api_extensions.cpp: batch_solve_entry)
+void dogleg_amd_batch_model_fisher_callback(const double* p_dev, double* x_dev, double* J_dev, const unsigned char* live_dev,
+                                            unsigned int B, void* hip_stream, void* cookie)
+{
+  const dogleg_amd_batch_model_t* m = (const dogleg_amd_batch_model_t*)cookie;
+  const int N = m ? dogleg_batch_model_nstate(m->kind) : -1;
+  const bool two_d = m && (m->kind == DOGLEG_AMD_MODEL_GAUSS2D || m->kind == DOGLEG_AMD_MODEL_GAUSS2D_ELLIPTIC);
+  if(N < 0 || !m->y || m->scale || m->Nmeas == 0 || B == 0 || (two_d && (m->width == 0 || m->t)))
+  {
+    fprintf(stderr, "libdogleg_amd: dogleg_amd_batch_model_fisher_callback: the cookie is no dogleg_amd_batch_model_t usable with the "
+                    "Poisson likelihood (scale must be NULL): nothing written\n");
+    return;
+  }
+  const size_t rows = (size_t)B*m->Nmeas;
+  hipLaunchKernelGGL(k_model_rows_poisson, dim3((unsigned int)((rows + 255)/256)), dim3(256), 0, (hipStream_t)hip_stream, (int)B,
+                     (int)m->Nmeas, N, m->kind, (int)m->width, m->t_per_problem ? 1 : 0, m->y, m->t, live_dev, p_dev, x_dev, J_dev);
 }
 
 } // extern "C"

@@ -25,6 +25,9 @@ struct DlgBatchSolve
   // the model form (dogleg_amd_optimize_dense_batch_model[_device]): a third form beside fJ / fP, both NULL then; N and M are
   // those of the (checked) record, whose arrays lie in device memory on either route; no loss.  NULL otherwise
   const dogleg_amd_batch_model_t* model;
+  // the likelihood of a model form (DOGLEG_AMD_LIKELIHOOD_*, checked; GAUSS: least squares, the model form as it was) and whether
+  // the call came in by dogleg_amd_optimize_dense_batch_model_mle[_device] (its name in the messages)
+  int likelihood; bool mle;
 };
 int  dlg_dense_batch_solve(const DlgBatchSolve& a);
 // the fit of the ..._fit entry points (dogleg_amd_batch_fit_t, checked by the caller), the last three members of the two records

@@ -246,6 +246,7 @@ const char* solve_who(const DlgBatchSolve& a)
     {"dogleg_amd_optimize_dense_batch_bounded", "dogleg_amd_optimize_dense_batch_bounded_device"},
     {"dogleg_amd_optimize_dense_batch_robust", "dogleg_amd_optimize_dense_batch_robust_device"},
     {"dogleg_amd_optimize_dense_batch", "dogleg_amd_optimize_dense_batch_device"}};
+  if(a.model && a.mle) return a.device ? "dogleg_amd_optimize_dense_batch_model_mle_device" : "dogleg_amd_optimize_dense_batch_model_mle";
   if(a.model) return a.device ? "dogleg_amd_optimize_dense_batch_model_device" : "dogleg_amd_optimize_dense_batch_model";
   return names[a.fP ? (a.bounds ? 0 : 1) : a.bounds ? 2 : a.loss ? 3 : 4][a.device ? 1 : 0];
 }
@@ -283,8 +284,9 @@ int batch_setup(const char* who, const DlgBatchSolve& a, const BatchForm& F, Bat
   A.wts = loss ? (double*)(q + o_wts) : nullptr; A.NF = (int)NF; A.robust = loss ? 1 : 0;
   A.lo = room_lo ? (const double*)(q + o_lo) : nullptr; A.hi = room_hi ? (const double*)(q + o_hi) : nullptr;
   A.held = nullptr; A.bounded = 0;
-  A.Mdl = ModelDev{0, 0, 0, nullptr, nullptr, nullptr};
-  if(a.model) A.Mdl = ModelDev{a.model->kind, (int)a.model->width, a.model->t_per_problem ? 1 : 0, a.model->y, a.model->t, a.model->scale};
+  A.Mdl = ModelDev{0, 0, 0, 0, nullptr, nullptr, nullptr};
+  if(a.model) A.Mdl = ModelDev{a.model->kind, (int)a.model->width, a.model->t_per_problem ? 1 : 0, a.likelihood, a.model->y, a.model->t,
+                               a.model->scale};
   A.L.kind = loss ? loss->kind : DOGLEG_AMD_LOSS_TRIVIAL; A.L.fs = (int)fs;
   A.L.a = loss && loss->kind != DOGLEG_AMD_LOSS_TRIVIAL ? loss->scale : 1.0; A.L.c = A.L.a*A.L.a;
   A.max_iterations = prm->max_iterations; A.trustregion0 = prm->trustregion0;

@@ -21,10 +21,12 @@ struct ProductsDev
 struct LossDev { int kind, fs; double a, c; };
 
 // a built-in model (dogleg.h: dogleg_amd_batch_model_t) as the fused sweep reads it: y [B][M]; t nullptr (t_i = i), [M] or, with
-// t_each, [B][M]; scale [B][M] or nullptr.  y == nullptr: no model, and that is how the launcher tells this form from the others
+// t_each, [B][M]; scale [B][M] or nullptr.  y == nullptr: no model, and that is how the launcher tells this form from the others.
+// likelihood: DOGLEG_AMD_LIKELIHOOD_* (it lies where the three ints left a hole in front of the pointers, so that every other
+// member of BatchDev stays where it was); read by the launcher only: POISSON is a form of its own
 struct ModelDev
 {
-  int kind, width, t_each;
+  int kind, width, t_each, likelihood;
   const double *y, *t, *scale;
 };
 

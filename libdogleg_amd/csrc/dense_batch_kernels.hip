@@ -34,6 +34,12 @@
 // tile; x and J never lie in memory, and the results have the bits of the J form on what the adapter callback (batch_models.hip)
 // would have written.  Only the class of 8 is instantiated: every model has at most 6 variables.
 //
+// The Poisson form (dogleg_amd_optimize_dense_batch_model_mle with DOGLEG_AMD_LIKELIHOOD_POISSON): the model form's sweep with the
+// rows of dogleg_batch_model_row_poisson, x~ = (f - y) / sqrt(f) and J~ = grad f / sqrt(f), and the Poisson deviance summed where
+// the model form sums x^2: the cost the gain ratio compares is apart from the rows that form g and H, as in the robust form.  A row
+// with !(f > 0) is staged as zeros and makes the point's cost +infinity, which the finite test of this form accepts once the
+// problem has started: rho is then -infinity, an ordinary rejected step.  Everything behind the sweep is the model form's text.
+//
 // The device-resident twins (dogleg_amd_*_batch_device): the same rounds and the same launch of k_batch_uncertainty with every
 // array of the caller in device memory.  The solve takes its initial p by a copy within the device and ends in k_batch_finish,
 // which writes p, the result structs and lambda where the caller has them; the uncertainty kernel's per-output pointers point
@@ -66,7 +72,7 @@ constexpr double LAMBDA_INITIAL = 1e-10;       // dogleg.c:138
 
 enum { F_CAUCHY = 1, F_GN = 2, F_EDGE = 4, F_STARTED = 8 };
 
-enum { FORM_J = 0, FORM_PRODUCTS = 1, FORM_MODEL = 2 };
+enum { FORM_J = 0, FORM_PRODUCTS = 1, FORM_MODEL = 2, FORM_POISSON = 3 };
 
 template <int NMAX> struct BatchCfg
 {
@@ -440,7 +446,8 @@ __device__ __forceinline__ double load_products(const ProductsDev& P, int b, int
 // the tile's rows, the sum for norm2(x) and the loop over the tile's rows are sweep_point's, so the results have its bits on what
 // the adapter would have written.  The loads of the next tile's y, t and scale are in flight under the loop; only the lanes that
 // hold a row evaluate the model.
-template <int NMAX>
+// POISSON: the rows and the cost of the Poisson form (the head of this file); no scale is read there
+template <int NMAX, bool POISSON = false>
 __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* pb, int b, int N, int M, int NP, int lane,
                                               double* SA, double* tile, double& gacc_out)
 {
@@ -461,6 +468,7 @@ __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* 
   const double* tb = Md.t ? Md.t + (Md.t_each ? (size_t)b*M : (size_t)0) : nullptr;
   const double* sb = Md.scale ? Md.scale + (size_t)b*M : nullptr;
   double yv = 0.0, tv = 0.0, sv = 1.0;
+  bool infeasible = false;     // POISSON: a row of this lane had !(f > 0)
   if(lane < min(T, M))
   {
     yv = yb[lane];
@@ -473,7 +481,18 @@ __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* 
     double xv = 0.0, jr[NM];
 #pragma unroll
     for(int j = 0; j < NM; j++) jr[j] = 0.0;
-    if(lane < tc) dogleg_batch_model_row(Md.kind, p, r0 + lane, Md.width, tv, yv, sv, &xv, jr);
+    double dv = 0.0;           // POISSON: the row's share of the deviance
+    if constexpr(POISSON)
+    {
+      if(lane < tc && !dogleg_batch_model_row_poisson(Md.kind, p, r0 + lane, Md.width, tv, yv, &xv, jr, &dv))
+      {
+        infeasible = true;
+        xv = 0.0; dv = 0.0;
+#pragma unroll
+        for(int j = 0; j < NM; j++) jr[j] = 0.0;
+      }
+    }
+    else if(lane < tc) dogleg_batch_model_row(Md.kind, p, r0 + lane, Md.width, tv, yv, sv, &xv, jr);
     wsync();
     if(lane < T)
     {
@@ -482,7 +501,7 @@ __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* 
     }
     xt[lane] = xv;
     wsync();
-    n2 = __builtin_fma(xv, xv, n2);
+    if constexpr(POISSON) n2 += dv; else n2 = __builtin_fma(xv, xv, n2);
     if(r0 + T < M)
     {
       const int r1 = r0 + T, tn = min(T, M - r1);
@@ -501,7 +520,8 @@ __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* 
       if(lane < N) gacc += row[lane]*xt[t];
     }
   }
-  const double n2x = wave_sum(n2);
+  double n2x = wave_sum(n2);
+  if constexpr(POISSON) { if(__any(infeasible)) n2x = INFINITY; }
   wsync();
 #pragma unroll
   for(int k = 0; k < C::NE; k++) if(lane + 64*k < NP) SA[lane + 64*k] = acc[k];
@@ -541,6 +561,16 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
     n2x = sweep_model<NMAX>(A.Mdl, A.p_trial + bN, b, N, M, NP, lane, SA, SL, gacc);
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
+  }
+  else if constexpr(FORM == FORM_POISSON)
+  {
+    // ---- the model form's sweep over the Poisson rows; n2x is the deviance, +infinity at an infeasible point: no start point,
+    // but a trial point like any other that is worse than the point it was stepped from ----
+    static_assert(!ROBUST, "the Poisson form has no loss");
+    n2x = sweep_model<NMAX, true>(A.Mdl, A.p_trial + bN, b, N, M, NP, lane, SA, SL, gacc);
+    const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
+    const bool started = (A.st[(size_t)ST_COUNT*b + ST_FLAGS] & F_STARTED) != 0;
+    finite = __all((isfinite(n2x) || (started && n2x == INFINITY)) && isfinite(gacc) && isfinite(dg));
   }
   else
   {
@@ -764,8 +794,11 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
   return status == 0;
 }
 
+// (the Poisson form asks for the model form's 4 waves a SIMD: left alone it takes 130 VGPRs, two more than 4 waves allow; held to
+// 128 it takes 126 and no scratch.  1 is the default: the other instantiations are compiled as they were)
 template <int NMAX, int FORM, bool ROBUST, bool BOUNDED>
-__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_round(BatchDev A)
+__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) __attribute__((amdgpu_waves_per_eu(FORM == FORM_POISSON ? 4 : 1)))
+k_batch_round(BatchDev A)
 {
   constexpr int LDSW = FormCfg<NMAX, FORM>::LDSW, WPB = BatchCfg<NMAX>::WPB;
   __shared__ double lds[WPB*LDSW];
@@ -1429,7 +1462,12 @@ void launch_batch_round(hipStream_t st, const BatchDev& A)
       // (every built-in model lies in the class of 8: the host side refuses anything else)
       if constexpr(NMAX == 8)
       {
-        if(A.bounded)        launch_class<NMAX>(k_batch_round<NMAX, FORM_MODEL, false, true>, st, A.B, A);
+        if(A.Mdl.likelihood == DOGLEG_AMD_LIKELIHOOD_POISSON)
+        {
+          if(A.bounded)      launch_class<NMAX>(k_batch_round<NMAX, FORM_POISSON, false, true>, st, A.B, A);
+          else               launch_class<NMAX>(k_batch_round<NMAX, FORM_POISSON, false, false>, st, A.B, A);
+        }
+        else if(A.bounded)   launch_class<NMAX>(k_batch_round<NMAX, FORM_MODEL, false, true>, st, A.B, A);
         else                 launch_class<NMAX>(k_batch_round<NMAX, FORM_MODEL, false, false>, st, A.B, A);
       }
     }

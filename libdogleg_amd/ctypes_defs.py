@@ -147,6 +147,7 @@ class BatchFit(C.Structure):
 
 MODEL_EXPDECAY, MODEL_GAUSS1D, MODEL_GAUSS2D, MODEL_GAUSS2D_ELLIPTIC = 0, 1, 2, 3      # dogleg_amd_batch_model_t.kind
 MODEL_NSTATE = {MODEL_EXPDECAY: 3, MODEL_GAUSS1D: 4, MODEL_GAUSS2D: 5, MODEL_GAUSS2D_ELLIPTIC: 6}
+LIKELIHOOD_GAUSS, LIKELIHOOD_POISSON = 0, 1        # dogleg_amd_optimize_dense_batch_model_mle
 
 
 class BatchModel(C.Structure):
