@@ -712,7 +712,10 @@ int dogleg_amd_robust_last_stats(double* out, int n);
  *   6. Fallback, if some component was clamped and the expected improvement is <= 0 or max|s'| <= update_threshold:
  *      d = t0 Cauchy with t0 = min(1, trustregion / |Cauchy|); alpha = min(1, min_i (far_i - p_i) / d_i) over the i with d_i != 0,
  *      far_i = upper_i if d_i > 0, lower_i otherwise; the step is alpha d, clamped as in 5 (rounding only), with its own expected
- *      improvement.  The step counts as one to the edge of the trust region iff |Cauchy| >= trustregion.  A free variable on a
+ *      improvement.  In the fallback the component that sets alpha ends on its bound's bits whichever way p + alpha d rounds:
+ *      trial_i = far_i, s'_i = far_i - p_i for every i with d_i != 0 whose own ratio equals alpha (one ulp short of the bound the
+ *      variable would be neither held nor free to move, and the next fallback would be cut at alpha ~ 1e-16).
+ *      The step counts as one to the edge of the trust region iff |Cauchy| >= trustregion.  A free variable on a
  *      bound has -g pointing inwards, so alpha > 0, and JtJ is positive semidefinite, so the improvement is > 0 up to rounding:
  *      one that is <= 0 or not finite is DOGLEG_AMD_BATCH_FAILED.
  *   7. update_threshold tests the step that is applied; the trial point is `trial`; the gain ratio, the trust-region update,

@@ -755,13 +755,19 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
           if(EI <= 0.0 || smax <= A.upd_thr)
           {
             // the clipped step is no descent step of the model, or no step at all: the Cauchy step, cut at the trust region,
-            // then at the first bound a free variable meets
+            // then at the first bound a free variable meets.  The component that set alpha (its own ratio equals alpha) ends ON
+            // its bound: p + ((far - p) / d) d rounds onto the bound's bits, one ulp beyond it (which the clamp brings back) or
+            // one ulp short of it, and one ulp short the variable is on no bound, is not held at the next point, and the next
+            // fallback is cut at alpha ~ 1e-16: the solve would stop on update_threshold over a rounding.  So that component
+            // takes the clamp's form whichever way the sum rounds (k_bounds_fallback, bounds_device.hip)
             const double d_r = fmin(1.0, tr/sqrt(n2c))*ca_r;
+            const double far_r = d_r > 0.0 ? hi_r : lo_r;
             double a_r = 1.0;
-            if(lane < N && d_r != 0.0) a_r = ((d_r > 0.0 ? hi_r : lo_r) - p_r)/d_r;
+            if(lane < N && d_r != 0.0) a_r = (far_r - p_r)/d_r;
             const double alpha = fmin(1.0, wave_min(a_r));
             s_r = alpha*d_r;
-            t_r = clip_step(p_r, s_r, lo_r, hi_r, cl);
+            if(lane < N && d_r != 0.0 && a_r == alpha) { t_r = far_r; s_r = far_r - p_r; }
+            else t_r = clip_step(p_r, s_r, lo_r, hi_r, cl);
             Js2 = quad_form(SA, SV, s_r, N, lane);
             EI = -2.0*wave_sum(g_r*s_r) - Js2;
             smax = wave_max(fabs(s_r));

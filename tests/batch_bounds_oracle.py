@@ -31,17 +31,53 @@ def expected_improvement(g, H, s):
     return -2.0 * float(g @ s) - float(s @ H @ s)
 
 
-def solve_one(hp, prm, loss, lo=None, hi=None, max_rounds=100000):
+def fallback_step(p, d, lo, hi, landing="bound"):
+    """step 6 behind d = min(1, tr / |cauchy|) cauchy: (trial, the step applied, landings, margins).  The step is alpha d with
+    alpha = min(1, min_i (far_i - p_i) / d_i) over the moving components, far the bound d_i points at.  landing == "bound", the
+    rule of the library (k_bounds_fallback; batch_problem): a moving component whose own ratio equals alpha ends ON its bound,
+    trial_i = far_i and step_i = far_i - p_i, whichever way p_i + alpha d_i rounds; the others are clipped as in step 5.
+    landing == "sum": every component is p_i + alpha d_i, clipped -- what the rule replaces, kept for the tests that show what it
+    changes.  landings: per component that the rule lands, what the sum would have done: "on" the bound's bits, "beyond" it
+    (the clamp brings that back) or "short" of it.  margins: |alpha_raw - 1| relative (is the step cut at all) and, of a cut
+    step, (r2 - r1) / r2 of the two smallest ratios (which component lands: a second one within rounding of the first would
+    still land by its own sum)"""
+    assert landing in ("bound", "sum")
+    far = np.where(d > 0.0, hi, lo)
+    mv = d != 0.0
+    ratio = np.full(len(p), np.inf)
+    ratio[mv] = (far[mv] - p[mv]) / d[mv]
+    alpha_raw = float(np.min(ratio))
+    alpha = min(1.0, alpha_raw)
+    margins = [_rel(alpha_raw, 1.0)] if np.isfinite(alpha_raw) else []
+    trial, step, _ = clip(p, alpha * d, lo, hi)
+    land = mv & (ratio == alpha)
+    landings = []
+    if land.any():
+        r = np.sort(ratio)
+        if len(r) > 1 and np.isfinite(r[1]):
+            margins.append((r[1] - r[0]) / r[1] if r[1] != 0.0 else 0.0)
+        t = p + alpha * d
+        for i in np.flatnonzero(land):
+            past = t[i] > far[i] if d[i] > 0.0 else t[i] < far[i]
+            landings.append("on" if t[i] == far[i] else "beyond" if past else "short")
+        if landing == "bound":
+            trial = np.where(land, far, trial)
+            step = np.where(land, far - p, step)
+    return trial, step, landings, margins
+
+
+def solve_one(hp, prm, loss, lo=None, hi=None, max_rounds=100000, landing="bound"):
     """what batch_robust_oracle.solve_one returns, plus held (N,) at the returned point, clipped (steps with a clamped
     component), fallbacks, held_steps (steps taken with a held variable), held_resteps (of those, the ones behind a rejected
-    trial) and first_p (the first point evaluated).  margin also covers the new decisions: |g_i| against |g|_inf for variables
-    on a bound, |p_i + s_i - bound_i| against max(|s_i|, |bound_i|) per component and bound, |EI'| against |2 g's'| + s''Hs'
-    where a clip happened, the applied step against update_threshold"""
+    trial), first_p (the first point evaluated) and landings (fallback_step's, over the solve).  margin also covers the new
+    decisions: |g_i| against |g|_inf for variables on a bound, |p_i + s_i - bound_i| against max(|s_i|, |bound_i|) per
+    component and bound, |EI'| against |2 g's'| + s''Hs' where a clip happened, the applied step against update_threshold, and
+    fallback_step's two.  landing: fallback_step's"""
     N, M = hp.N, hp.M
     lo = np.full(N, -np.inf) if lo is None else np.asarray(lo, dtype=np.float64)
     hi = np.full(N, np.inf) if hi is None else np.asarray(hi, dtype=np.float64)
     p_in = np.array(hp.p0(), dtype=np.float64)
-    nothing = dict(held=np.zeros(N, dtype=np.uint8), clipped=0, fallbacks=0, held_steps=0, held_resteps=0)
+    nothing = dict(held=np.zeros(N, dtype=np.uint8), clipped=0, fallbacks=0, held_steps=0, held_resteps=0, landings=[])
     # ---- 1. a NaN bound or lo > hi: FAILED alone, nothing evaluated
     if not np.all(lo <= hi):
         return dict(p=p_in, norm2_x=-1.0, trustregion=prm.trustregion0, lambda_=0.0, iterations=0, evaluations=0,
@@ -55,7 +91,7 @@ def solve_one(hp, prm, loss, lo=None, hi=None, max_rounds=100000):
     F_b = EI = n2c = n2gn = 0.0
     p_b = g_b = H_b = w_b = cauchy = gn = held = g_F = None
     status = 0
-    step_types, margins, huber = set(), [], []
+    step_types, margins, huber, landings = set(), [], [], []
 
     def gradient_margins(p, g):
         gmax = float(np.max(np.abs(g)))
@@ -181,11 +217,9 @@ def solve_one(hp, prm, loss, lo=None, hi=None, max_rounds=100000):
             # ---- 6. the fallback
             if EI <= 0.0 or smax <= prm.update_threshold:
                 fallbacks += 1
-                d = min(1.0, tr / np.sqrt(n2c)) * cauchy
-                far = np.where(d > 0.0, hi, lo)
-                mv = d != 0.0
-                alpha = min(1.0, float(np.min((far[mv] - p_b[mv]) / d[mv]))) if mv.any() else 1.0
-                trial, step, _ = clip(p_b, alpha * d, lo, hi)
+                trial, step, landed, ms = fallback_step(p_b, min(1.0, tr / np.sqrt(n2c)) * cauchy, lo, hi, landing)
+                landings += landed
+                margins += ms
                 EI = expected_improvement(g_b, H_b, step)
                 smax = float(np.max(np.abs(step)))
                 edge = bool(n2c >= tr2)
@@ -207,4 +241,4 @@ def solve_one(hp, prm, loss, lo=None, hi=None, max_rounds=100000):
                 lambda_=lam, iterations=iters, evaluations=evals, status=status, weights=weights, last_weights=w,
                 step_types=step_types, rejected=rejected, margin=min(margins + huber) if margins else np.inf,
                 huber_gap=min(huber) if huber else np.inf, held=held_out, clipped=clipped_steps, fallbacks=fallbacks,
-                held_steps=held_steps, held_resteps=held_resteps, first_p=first_p)
+                held_steps=held_steps, held_resteps=held_resteps, first_p=first_p, landings=landings)

@@ -20,9 +20,10 @@ for both points of a gain ratio together (the leading 2).  The same allowance sa
 problem whose model nearly interpolates its data (M = 5 with N = 4 leaves one degree of freedom) can end with F ~ 1e-9 summed from
 terms of size 1, and no two evaluations of the definition agree on such an F to 1e-8 relative.  So F_err / F <= COST_TOL = 1e-9 at
 the returned point is one more condition a table's problems meet (cost_error; the seeds are chosen for it like for the margins).
-One decision of the bounded loop has margin 0 by construction and is kept out of the tables the same way: a fallback step cut at a
-bound (alpha < 1; `landings`), whose end point lies on the bound or one ulp short of it by the rounding of alpha d.  Fallbacks that
-the box does not cut (alpha = 1) stay in.
+A fallback step cut at a bound ends ON the bound by rule (batch_bounds_oracle.fallback_step, the library's rule: the component
+whose own ratio sets alpha takes the bound, however p + alpha d rounds), so it is a decision like any other, with two margins:
+is the step cut at all (|alpha_raw - 1|), and which component lands ((r2 - r1) / r2 of the two smallest ratios).  `landings` lists
+what the plain sum would have done at each: "on", "beyond" or "short".
 
 The tables.  The 14 shapes of tests/batch_models_np.CASES, B = 65, the problems of seeds SEED0 .. SEED0 + 64 of
 batch_models_np.problem with the truth and the start moved to two count levels, data drawn from the Poisson distribution at the
@@ -42,7 +43,7 @@ from libdogleg_amd.ctypes_defs import (BATCH_JTX, BATCH_SMALL_STEP, BATCH_TRUSTR
                                        MODEL_NSTATE, LIKELIHOOD_GAUSS, LIKELIHOOD_POISSON)
 from tests import batch_models_np as mz
 from tests import batch_robust_oracle as ro
-from tests.batch_bounds_oracle import FREE, held_set, clip, cholesky, expected_improvement, _rel
+from tests.batch_bounds_oracle import FREE, held_set, clip, cholesky, expected_improvement, fallback_step, _rel
 from tests.batch_robust_oracle import LAMBDA_INITIAL, EPS
 
 B = mz.B
@@ -106,10 +107,10 @@ def products_of(hp, likelihood):
 
 
 # ---------------------------------------------------------------- the loop
-def solve_one(hp, prm, likelihood, lo=None, hi=None, max_rounds=100000, products=None):
+def solve_one(hp, prm, likelihood, lo=None, hi=None, max_rounds=100000, products=None, landing="bound"):
     """what batch_bounds_oracle.solve_one returns (without the weights), plus infeasible (trial points with a row !(f > 0)) and
     cost_error (F_err / F of the returned point: the relative rounding allowance of the returned cost).
-    products: a hook p -> (F, g, H, F_err, feasibility margin, feasible), default: that of the likelihood"""
+    landing: batch_bounds_oracle.fallback_step's.  products: a hook p -> (F, g, H, F_err, feasibility margin, feasible), default: that of the likelihood"""
     N = hp.N
     products = products_of(hp, likelihood) if products is None else products
     lo = np.full(N, -np.inf) if lo is None else np.asarray(lo, dtype=np.float64)
@@ -118,16 +119,16 @@ def solve_one(hp, prm, likelihood, lo=None, hi=None, max_rounds=100000, products
     nothing = dict(held=np.zeros(N, dtype=np.uint8), clipped=0, fallbacks=0, held_steps=0, held_resteps=0, infeasible=0)
     if not np.all(lo <= hi):
         return dict(p=p_in, norm2_x=-1.0, trustregion=prm.trustregion0, lambda_=0.0, iterations=0, evaluations=0,
-                    status=BATCH_FAILED, step_types=set(), rejected=0, margin=np.inf, first_p=None, cost_error=np.inf, landings=0, **nothing)
+                    status=BATCH_FAILED, step_types=set(), rejected=0, margin=np.inf, first_p=None, cost_error=np.inf, landings=[], **nothing)
     p_trial = np.minimum(np.maximum(p_in, lo), hi)
     first_p = p_trial.copy()
     started = edge = have_cauchy = have_gn = False
-    iters = evals = rejected = clipped_steps = fallbacks = held_steps = held_resteps = infeasible = landings = 0
+    iters = evals = rejected = clipped_steps = fallbacks = held_steps = held_resteps = infeasible = 0
     tr, lam = prm.trustregion0, 0.0
     F_b = Ferr_b = EI = n2c = n2gn = 0.0
     p_b = g_b = H_b = cauchy = gn = held = g_F = None
     status = 0
-    step_types, margins = set(), []
+    step_types, margins, landings = set(), [], []
 
     def gradient_margins(p, g):
         gmax = float(np.max(np.abs(g)))
@@ -247,18 +248,10 @@ def solve_one(hp, prm, likelihood, lo=None, hi=None, max_rounds=100000, products
             margins.append(abs(EI) / (abs(2.0 * float(g_b @ step)) + float(step @ H_b @ step)))
             if EI <= 0.0 or smax <= prm.update_threshold:
                 fallbacks += 1
-                d = min(1.0, tr / np.sqrt(n2c)) * cauchy
-                far = np.where(d > 0.0, hi, lo)
-                mv = d != 0.0
-                alpha = min(1.0, float(np.min((far[mv] - p_b[mv]) / d[mv]))) if mv.any() else 1.0
-                # a fallback cut at a bound is meant to end ON it, but p + ((far - p) / d) d rounds onto the bound, beyond it (which
-                # the clamp brings back) or one ulp short of it by the last bits of d, and one ulp short the variable is not held at
-                # the next point ("The fallback's landing"): which of the three is no property of the problem, so such
-                # a step has margin 0 and the tables hold none
-                if alpha < 1.0:
-                    landings += 1
-                    margins.append(0.0)
-                trial, step, _ = clip(p_b, alpha * d, lo, hi)
+                # (the landing rule and its two margins: batch_bounds_oracle.fallback_step, the one statement of step 6)
+                trial, step, landed, ms = fallback_step(p_b, min(1.0, tr / np.sqrt(n2c)) * cauchy, lo, hi, landing)
+                landings += landed
+                margins += ms
                 EI = expected_improvement(g_b, H_b, step)
                 smax = float(np.max(np.abs(step)))
                 edge = bool(n2c >= tr2)

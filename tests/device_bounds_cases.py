@@ -17,7 +17,8 @@ beside the case and asserted to 5 % before anything is compared.
   every branch, BAProblem(5, 20, 60, eps=1.5, p0_spread=2.0), frac 0.25, trustregion0 = 1000, both thresholds 1e-5,
     max_iterations = 30: fallbacks, rejected trials that are stepped again with held variables, all three kinds of step.
     Seed 1 (branch1) has one fallback whose p + alpha d lands on the bound or one ulp short of it by the last bit of the Cauchy
-    step, which no margin here measures; the library puts the component that sets alpha on its bound either way."""
+    step: the library puts the component that sets alpha on its bound either way, and so does the oracle
+    (tests/batch_bounds_oracle.fallback_step, whose two margins -- is the step cut, which component lands -- are counted)."""
 import functools
 
 import numpy as np
