@@ -1227,8 +1227,7 @@ int dogleg_amd_numeric_buffers(struct dogleg_amd_numeric* h, const double** p_co
  * kind, a set communicator, and arrays of the record that are not device-accessible over their span.
  *
  * Not provided: a loss in the fused form (the adapter route has it: dogleg_amd_optimize_dense_batch_robust / _bounded with the
- * callback above); float or integer data; rotated Gaussians; fused uncertainty and query calls (take them
- * through the adapter, with held from the fused solve in the fit record); user-defined models in the fused form (that is what a
+ * callback above); float or integer data; rotated Gaussians; user-defined models in the fused form (that is what a
  * callback is).
  *
  * 3. Maximum-likelihood fits of count data.  dogleg_amd_optimize_dense_batch_model_mle[_device] are the fused solve above with a
@@ -1257,7 +1256,31 @@ int dogleg_amd_numeric_buffers(struct dogleg_amd_numeric* h, const double** p_co
  * of grad f / sqrt(f)), so dogleg_amd_check_jacobian_device_batch reports it, rightly, and a solve through it would minimise
  * Pearson's chi^2 with a wrong Jacobian: EVERY BATCH SOLVE ENTRY POINT REFUSES THIS CALLBACK with a message and -1 (the plain,
  * robust and bounded solves and their _device twins).
- * Not provided: a loss in this form; other likelihoods; a gain or offset per datum (EMCCD / sCMOS noise models); the products form. */
+ * Not provided: a loss in this form; other likelihoods; a gain or offset per datum (EMCCD / sCMOS noise models); the products form.
+ *
+ * 4. The fused uncertainty and query calls.  dogleg_amd_dense_batch_model_uncertainty[_device] and
+ * dogleg_amd_dense_batch_model_query_covariance[_device] are dogleg_amd_dense_batch_uncertainty_fit[_device] and
+ * dogleg_amd_dense_batch_query_covariance_fit[_device] of a built-in model with no callback and no x / J buffer: the error bars of
+ * a fused fit (with POISSON at its optimum: the Cramer-Rao bound) without the B Nmeas (Nstate + 1) doubles a callback would write.
+ * Nstate = dogleg_amd_batch_model_nstate(model->kind), Nmeas = model->Nmeas.  held: [B][Nstate] bytes as the bounded fused solve
+ * writes them (device memory in the _device twins), or NULL; it has the meaning of held in dogleg_amd_batch_fit_t.  There is no
+ * loss and there are no weights, as in the fused solve.
+ * EVERY OUTPUT HAS THE BITS OF THE CALL IT REPLACES: lambda, covariance, variances, factors, scale, status, out, the NaN of a problem
+ * that failed and the untouched outputs of one that was skipped.  With DOGLEG_AMD_LIKELIHOOD_GAUSS that call is the _fit call (held
+ * == NULL: the call without _fit) through dogleg_amd_batch_model_callback with the fit {NULL, NULL, held}; with
+ * DOGLEG_AMD_LIKELIHOOD_POISSON the same call through dogleg_amd_batch_model_fisher_callback: the covariance is the inverse Fisher
+ * information, a problem with a row of !(f_i > 0) is DOGLEG_AMD_BATCH_UNC_FAILED, alone, and a scale computed for it is NaN.  All
+ * other semantics are those of the replaced calls: featureSize, scale[b] <= 0 meaning "compute it" (from the sum of the squares of
+ * the rows, x~ with POISSON, and the free variables), the lambda loop on a failed pivot, Nobservations (the first rows of the
+ * model), the limits on Qrows and Nq, the mask and the stream.  One launch; the rows are formed in the lanes in the first sweep
+ * and, for the factors, again in the second.  Device memory of a call: the host-pointer forms keep the staged inputs and outputs
+ * (p, held, lambda, scale, status, and covariance, variances, factors or Jq and out as asked for); the _device twins B doubles
+ * where lambda_dev is NULL and nothing otherwise.  dogleg_amd_batch_uncertainty_last_stats covers them and reports 0 ms of callback.
+ * Refused with a message and -1 before any device work, outputs untouched: what the replaced call refuses, what the fused solve
+ * refuses of a model record, an unknown likelihood, model->scale with POISSON, a set communicator, and arrays of the record (and,
+ * in the _device twins, of the call) that are not device-accessible over their span.
+ * Not provided: a loss in the fused form; float or integer data; the products form; queries of more than
+ * DOGLEG_AMD_BATCH_QUERY_MAX_ROWS rows; other likelihoods. */
 #define DOGLEG_AMD_MODEL_EXPDECAY         0
 #define DOGLEG_AMD_MODEL_GAUSS1D          1
 #define DOGLEG_AMD_MODEL_GAUSS2D          2
@@ -1298,6 +1321,23 @@ int dogleg_amd_optimize_dense_batch_model_mle_device(double* p_dev, unsigned int
                                                      const unsigned char* active_dev, void* hip_stream);
 void dogleg_amd_batch_model_fisher_callback(const double* p_dev, double* x_dev, double* J_dev, const unsigned char* live_dev,
                                             unsigned int B, void* hip_stream, void* cookie);
+int dogleg_amd_dense_batch_model_uncertainty(const double* p, unsigned int B, const dogleg_amd_batch_model_t* model, int likelihood,
+                                             double* lambda, double* covariance, double* variances, double* factors,
+                                             double* scale, int featureSize, int* status, const unsigned char* held /* or NULL */);
+int dogleg_amd_dense_batch_model_uncertainty_device(const double* p_dev, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                                    int likelihood, double* lambda_dev, double* covariance_dev,
+                                                    double* variances_dev, double* factors_dev, double* scale_dev, int featureSize,
+                                                    int* status_dev, const unsigned char* held_dev,
+                                                    const unsigned char* active_dev, void* hip_stream);
+int dogleg_amd_dense_batch_model_query_covariance(const double* p, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                                  int likelihood, double* lambda, const double* Jq, unsigned int Nq,
+                                                  unsigned int Qrows, int Nobservations, double* out, int* status,
+                                                  const unsigned char* held /* or NULL */);
+int dogleg_amd_dense_batch_model_query_covariance_device(const double* p_dev, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                                         int likelihood, double* lambda_dev, const double* Jq_dev, unsigned int Nq,
+                                                         unsigned int Qrows, int Nobservations, double* out_dev, int* status_dev,
+                                                         const unsigned char* held_dev, const unsigned char* active_dev,
+                                                         void* hip_stream);
 
 #ifdef __cplusplus
 }

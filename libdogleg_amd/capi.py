@@ -91,6 +91,8 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_optimize_dense_batch_model", "dogleg_amd_optimize_dense_batch_model_device",
     "dogleg_amd_optimize_dense_batch_model_mle", "dogleg_amd_optimize_dense_batch_model_mle_device",
     "dogleg_amd_batch_model_fisher_callback",
+    "dogleg_amd_dense_batch_model_uncertainty", "dogleg_amd_dense_batch_model_uncertainty_device",
+    "dogleg_amd_dense_batch_model_query_covariance", "dogleg_amd_dense_batch_model_query_covariance_device",
 ]
 
 _lib = None
@@ -284,6 +286,12 @@ def lib():
         L.dogleg_amd_optimize_dense_batch_model_mle_device.argtypes = [V, C.c_uint, MP, C.c_int, PP, BP, V, V, V, V]
         L.dogleg_amd_batch_model_fisher_callback.argtypes = [V, V, V, V, C.c_uint, V, V]
         L.dogleg_amd_batch_model_fisher_callback.restype = None
+    if hasattr(L, "dogleg_amd_dense_batch_model_uncertainty"):
+        MP, U = C.POINTER(BatchModel), C.c_uint
+        L.dogleg_amd_dense_batch_model_uncertainty.argtypes = [D, U, MP, C.c_int, D, D, D, D, D, C.c_int, I, V]
+        L.dogleg_amd_dense_batch_model_uncertainty_device.argtypes = [V, U, MP, C.c_int, V, V, V, V, V, C.c_int, V, V, V, V]
+        L.dogleg_amd_dense_batch_model_query_covariance.argtypes = [D, U, MP, C.c_int, D, D, U, U, C.c_int, D, I, V]
+        L.dogleg_amd_dense_batch_model_query_covariance_device.argtypes = [V, U, MP, C.c_int, V, V, U, U, C.c_int, V, V, V, V, V]
     if hasattr(L, "dogleg_amd_dense_batch_query_covariance"):
         U = C.c_uint
         L.dogleg_amd_dense_batch_query_covariance.argtypes = [D, U, U, U, V, V, D, D, U, U, C.c_int, D, I]
@@ -821,6 +829,74 @@ def optimize_dense_batch_model_mle_device(p_dev, B, model, likelihood, params, r
                                                                   likelihood, C.byref(params) if params is not None else None,
                                                                   C.byref(bounds) if bounded else None, _dev(results_dev),
                                                                   _dev(lambda_dev), _dev(active_dev), _dev(stream))
+
+
+def _held_addr(held, keep):
+    """the address of a held array: a numpy array by its host address (kept alive in `keep`), a DeviceArray or a raw address"""
+    if held is None:
+        return None
+    if isinstance(held, np.ndarray):
+        keep.append(np.ascontiguousarray(held, dtype=np.uint8))
+        return keep[-1].ctypes.data
+    return _dev(held)
+
+
+def dense_batch_model_uncertainty(p, model, likelihood, lam=None, want=("cov", "var", "factors"), fs=1, scale=None, held=None):
+    """dogleg_amd_dense_batch_model_uncertainty at the points p (B, N): dense_batch_uncertainty with a BatchModel (None: NULL)
+    and a likelihood instead of N, M, cb and cookie; held: (B, N) uint8 or None instead of a fit.  The same dict."""
+    L = lib()
+    N = MODEL_NSTATE.get(model.kind, 1) if model is not None else 1
+    M = model.Nmeas if model is not None else 1
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, N)
+    B = p.shape[0]
+    out = dict(lam=None if lam is None else np.array(lam, dtype=np.float64, copy=True).reshape(B))
+    out["status"] = np.full(B, -1, dtype=np.int32)
+    if "cov" in want:
+        out["cov"] = np.zeros((B, N, N))
+    if "var" in want:
+        out["var"] = np.zeros((B, N))
+    if "factors" in want:
+        out["factors"] = np.zeros((B, M // max(fs, 1)))
+        out["scale"] = np.full(B, -1.0) if scale is None else np.array(np.broadcast_to(scale, (B,)), dtype=np.float64)
+    opt = lambda k: dptr(out[k]) if out.get(k) is not None else None
+    keep = []
+    out["rc"] = L.dogleg_amd_dense_batch_model_uncertainty(dptr(p), B, C.byref(model) if model is not None else None, likelihood,
+                                                           opt("lam"), opt("cov"), opt("var"), opt("factors"), opt("scale"), fs,
+                                                           iptr(out["status"]), _held_addr(held, keep))
+    return out
+
+
+def dense_batch_model_uncertainty_device(p_dev, B, model, likelihood, status_dev, lambda_dev=None, cov_dev=None, var_dev=None,
+                                         factors_dev=None, scale_dev=None, fs=1, held_dev=None, active_dev=None, stream=None):
+    """dogleg_amd_dense_batch_model_uncertainty_device: every array a DeviceArray or a raw device address (None: NULL).
+    Returns rc."""
+    return lib().dogleg_amd_dense_batch_model_uncertainty_device(_dev(p_dev), B, C.byref(model) if model is not None else None,
+                                                                 likelihood, _dev(lambda_dev), _dev(cov_dev), _dev(var_dev),
+                                                                 _dev(factors_dev), _dev(scale_dev), fs, _dev(status_dev),
+                                                                 _dev(held_dev), _dev(active_dev), _dev(stream))
+
+
+def dense_batch_model_query_covariance(p, model, likelihood, Jq, lam=None, nobs=-1, held=None):
+    """dogleg_amd_dense_batch_model_query_covariance at the points p (B, N): dense_batch_query_covariance with a BatchModel and a
+    likelihood instead of N, M, cb and cookie; held: (B, N) uint8 or None instead of a fit.  The same dict."""
+    N = MODEL_NSTATE.get(model.kind, 1) if model is not None else np.shape(Jq)[-1]
+    p, Jq, out = _query_arrays(p, N, Jq, lam)
+    keep = []
+    out["rc"] = lib().dogleg_amd_dense_batch_model_query_covariance(dptr(p), p.shape[0], C.byref(model) if model is not None else None,
+                                                                    likelihood, dptr(out["lam"]) if lam is not None else None,
+                                                                    dptr(Jq), Jq.shape[1], Jq.shape[2], nobs, dptr(out["out"]),
+                                                                    iptr(out["status"]), _held_addr(held, keep))
+    return out
+
+
+def dense_batch_model_query_covariance_device(p_dev, B, model, likelihood, Jq_dev, Nq, Q, out_dev, status_dev, nobs=-1,
+                                              lambda_dev=None, held_dev=None, active_dev=None, stream=None):
+    """dogleg_amd_dense_batch_model_query_covariance_device: every array a DeviceArray or a raw device address (None: NULL).
+    Returns rc."""
+    return lib().dogleg_amd_dense_batch_model_query_covariance_device(_dev(p_dev), B, C.byref(model) if model is not None else None,
+                                                                      likelihood, _dev(lambda_dev), _dev(Jq_dev), Nq, Q, nobs,
+                                                                      _dev(out_dev), _dev(status_dev), _dev(held_dev),
+                                                                      _dev(active_dev), _dev(stream))
 
 
 def batch_results_from_device(results_dev, B):

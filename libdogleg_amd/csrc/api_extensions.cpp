@@ -147,6 +147,13 @@ template <class Req> Req with_fit(Req a, const dogleg_amd_batch_fit_t* fit)
   if(fit) { a.loss = fit->loss; a.weights = fit->weights; a.held = fit->held; }
   return a;
 }
+// a (checked) model into a request record of the uncertainty or query kind: its shape, the likelihood and, of a fit, held alone
+template <class Req> Req with_model(Req a, const dogleg_amd_batch_model_t* model, int likelihood, const unsigned char* held)
+{
+  a.N = (unsigned int)dogleg_batch_model_nstate(model->kind); a.M = model->Nmeas;
+  a.held = held; a.model = model; a.likelihood = likelihood;
+  return a;
+}
 
 // the record of a built-in model (dogleg.h: dogleg_amd_batch_model_t), from its members alone: no pointer's target is looked at
 bool batch_model_ok(const char* who, const dogleg_amd_batch_model_t* model, int likelihood = DOGLEG_AMD_LIKELIHOOD_GAUSS)
@@ -195,6 +202,15 @@ bool device_span_ok_or_null(const char* who, const char* name, const void* ptr, 
 {
   return !ptr || device_span_ok(who, name, ptr, bytes);
 }
+// the arrays of a (checked) model record of B problems, which lie in device memory on either route; no model: nothing to check
+bool model_spans_ok(const char* who, const dogleg_amd_batch_model_t* model, size_t B)
+{
+  if(!model) return true;
+  const size_t BM = B*model->Nmeas;
+  return device_span_ok(who, "model->y", model->y, sizeof(double)*BM) &&
+         device_span_ok_or_null(who, "model->t", model->t, sizeof(double)*(model->t_per_problem ? BM : (size_t)model->Nmeas)) &&
+         device_span_ok_or_null(who, "model->scale", model->scale, sizeof(double)*BM);
+}
 
 // ---- the three kinds of batch request (dense_batch.h), each behind one function that makes every check of its entry points in
 // one order: the required pointers, the shape, what the kind adds, one rank only; then, and only on the device route, the spans
@@ -229,19 +245,14 @@ int batch_solve_entry(const char* who, SolveKind kind, DlgBatchSolve a)
        device_span_ok_or_null(who, "bounds->lower", bounds.lower, sizeof(double)*BN) &&
        device_span_ok_or_null(who, "bounds->upper", bounds.upper, sizeof(double)*BN) &&
        device_span_ok_or_null(who, "bounds->held", bounds.held, BN))) return -1;
-  // the arrays of a model record lie in device memory on either route
-  const size_t BM = B*a.M;
-  if(a.model &&
-     !(device_span_ok(who, "model->y", a.model->y, sizeof(double)*BM) &&
-       device_span_ok_or_null(who, "model->t", a.model->t, sizeof(double)*(a.model->t_per_problem ? BM : (size_t)a.M)) &&
-       device_span_ok_or_null(who, "model->scale", a.model->scale, sizeof(double)*BM))) return -1;
+  if(!model_spans_ok(who, a.model, B)) return -1;
   return dlg_dense_batch_solve(a);
 }
 // featureSize: as the caller gave it; a.fs is set here
 int batch_unc_entry(const char* who, DlgBatchUnc a, const dogleg_parameters2_t* parameters, int featureSize)
 {
   const char* dev = a.device ? "_dev" : "";
-  if(!a.p || !(a.fJ || a.fP) || !a.status) { MSG("%s: p%s, the callback and status%s must be given", who, dev, dev); return -1; }
+  if(!a.p || !(a.fJ || a.fP || a.model) || !a.status) { MSG("%s: p%s, the callback and status%s must be given", who, dev, dev); return -1; }
   const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
   a.unpacked = a.fP && !prm->JtJ_packed;
   if(!request_shape_ok(who, a, prm, "a loop over dogleg_optimize_dense2")) return -1;
@@ -289,14 +300,15 @@ int batch_unc_entry(const char* who, DlgBatchUnc a, const dogleg_parameters2_t* 
                        device_span_ok(who, "scale_dev", a.scale, sizeof(double)*B))) &&
        device_span_ok_or_null(who, "active_dev", a.active, B) &&
        device_span_ok_or_null(who, "fit->weights", a.weights, sizeof(double)*B*loss_features(a.loss, a.M)) &&
-       device_span_ok_or_null(who, "fit->held", a.held, BN))) return -1;
+       device_span_ok_or_null(who, a.model ? "held_dev" : "fit->held", a.held, BN))) return -1;
+  if(!model_spans_ok(who, a.model, B)) return -1;
   return dlg_dense_batch_uncertainty(a);
 }
 // Nq queries of Qrows rows per problem, Nobservations of the J form's Nmeas
 int batch_query_entry(const char* who, DlgBatchQuery a, const dogleg_parameters2_t* parameters)
 {
   const char* dev = a.device ? "_dev" : "";
-  if(!a.p || !(a.fJ || a.fP) || !a.Jq || !a.out || !a.status)
+  if(!a.p || !(a.fJ || a.fP || a.model) || !a.Jq || !a.out || !a.status)
   { MSG("%s: p%s, the callback, Jq%s, out%s and status%s must be given", who, dev, dev, dev, dev); return -1; }
   const dogleg_parameters2_t* prm = parameters ? parameters : &g_params;
   a.unpacked = a.fP && !prm->JtJ_packed;
@@ -321,7 +333,8 @@ int batch_query_entry(const char* who, DlgBatchQuery a, const dogleg_parameters2
        device_span_ok(who, "Jq_dev", a.Jq, sizeof(double)*rows*a.N) && device_span_ok(who, "out_dev", a.out, sizeof(double)*rows*a.Qrows) &&
        device_span_ok_or_null(who, "active_dev", a.active, B) &&
        device_span_ok_or_null(who, "fit->weights", a.weights, sizeof(double)*B*loss_features(a.loss, a.M)) &&
-       device_span_ok_or_null(who, "fit->held", a.held, B*a.N))) return -1;
+       device_span_ok_or_null(who, a.model ? "held_dev" : "fit->held", a.held, B*a.N))) return -1;
+  if(!model_spans_ok(who, a.model, B)) return -1;
   return dlg_dense_batch_query(a);
 }
 
@@ -551,6 +564,47 @@ int dogleg_amd_optimize_dense_batch_model_mle_device(double* p_dev, unsigned int
                   parameters, results_dev, lambda_dev, active_dev, hip_stream};
   a.bounds = bounds; a.device = true; a.model = model; a.likelihood = likelihood; a.mle = true;
   return batch_solve_entry(__func__, bounds ? SOLVE_BOUNDED : SOLVE_PLAIN, a);
+}
+// ---- the fused uncertainty and query calls of a built-in model: the records of the J form's calls with the model as their third
+// form and held as their fit; the record is checked first, as in the fused solve
+int dogleg_amd_dense_batch_model_uncertainty(const double* p, unsigned int B, const dogleg_amd_batch_model_t* model, int likelihood,
+                                             double* lambda, double* covariance, double* variances, double* factors,
+                                             double* scale, int featureSize, int* status, const unsigned char* held)
+{
+  if(!batch_model_ok(__func__, model, likelihood)) return -1;
+  return batch_unc_entry(__func__, with_model(DlgBatchUnc{p, B, 0, 0, nullptr, nullptr, nullptr, false, lambda, covariance, variances,
+                                                         factors, scale, 0, status}, model, likelihood, held), nullptr, featureSize);
+}
+int dogleg_amd_dense_batch_model_uncertainty_device(const double* p_dev, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                                    int likelihood, double* lambda_dev, double* covariance_dev,
+                                                    double* variances_dev, double* factors_dev, double* scale_dev, int featureSize,
+                                                    int* status_dev, const unsigned char* held_dev,
+                                                    const unsigned char* active_dev, void* hip_stream)
+{
+  if(!batch_model_ok(__func__, model, likelihood)) return -1;
+  return batch_unc_entry(__func__, with_model(DlgBatchUnc{p_dev, B, 0, 0, nullptr, nullptr, nullptr, false, lambda_dev, covariance_dev,
+                                                         variances_dev, factors_dev, scale_dev, 0, status_dev, active_dev, hip_stream,
+                                                         true}, model, likelihood, held_dev), nullptr, featureSize);
+}
+int dogleg_amd_dense_batch_model_query_covariance(const double* p, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                                  int likelihood, double* lambda, const double* Jq, unsigned int Nq,
+                                                  unsigned int Qrows, int Nobservations, double* out, int* status,
+                                                  const unsigned char* held)
+{
+  if(!batch_model_ok(__func__, model, likelihood)) return -1;
+  return batch_query_entry(__func__, with_model(DlgBatchQuery{p, B, 0, 0, nullptr, nullptr, nullptr, false, lambda, Jq, Nq, Qrows,
+                                                               Nobservations, out, status}, model, likelihood, held), nullptr);
+}
+int dogleg_amd_dense_batch_model_query_covariance_device(const double* p_dev, unsigned int B, const dogleg_amd_batch_model_t* model,
+                                                         int likelihood, double* lambda_dev, const double* Jq_dev, unsigned int Nq,
+                                                         unsigned int Qrows, int Nobservations, double* out_dev, int* status_dev,
+                                                         const unsigned char* held_dev, const unsigned char* active_dev,
+                                                         void* hip_stream)
+{
+  if(!batch_model_ok(__func__, model, likelihood)) return -1;
+  return batch_query_entry(__func__, with_model(DlgBatchQuery{p_dev, B, 0, 0, nullptr, nullptr, nullptr, false, lambda_dev, Jq_dev, Nq,
+                                                               Qrows, Nobservations, out_dev, status_dev, active_dev, hip_stream,
+                                                               true}, model, likelihood, held_dev), nullptr);
 }
 int dogleg_amd_batch_last_stats(double* out, int n) { return out ? dlg_dense_batch_last_stats(out, n) : 0; }
 int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,

@@ -33,6 +33,10 @@ int  dlg_dense_batch_solve(const DlgBatchSolve& a);
 // the fit of the ..._fit entry points (dogleg_amd_batch_fit_t, checked by the caller), the last three members of the two records
 // below: loss (a featureSize <= 4 that divides M; kind and scale checked where weights is NULL), weights [B][M / featureSize],
 // held [B][N]; all NULL: the call without _fit.  Host or device arrays as the record's other arrays
+// The model form of the two (dogleg_amd_dense_batch_model_uncertainty, _query_covariance and their _device twins), a third form
+// beside fJ / fP, both NULL then: model, the (checked) record whose arrays lie in device memory on either route, N and M those of
+// the record, and its likelihood (DOGLEG_AMD_LIKELIHOOD_*, checked).  No callback runs and no x / J buffer exists; of the fit only
+// held is taken.  model NULL otherwise
 // dogleg_amd_dense[_products]_batch_uncertainty[_fit][_device]; fs is 1 or 2 here
 struct DlgBatchUnc
 {
@@ -42,6 +46,7 @@ struct DlgBatchUnc
   const unsigned char* active; void* stream;
   bool device;
   const dogleg_amd_batch_loss_t* loss; const double* weights; const unsigned char* held;
+  const dogleg_amd_batch_model_t* model; int likelihood;
 };
 int  dlg_dense_batch_uncertainty(const DlgBatchUnc& a);
 // dogleg_amd_dense[_products]_batch_query_covariance[_fit][_device]; the products form has no Nobservations (< 0: the plain form)
@@ -53,6 +58,7 @@ struct DlgBatchQuery
   const unsigned char* active; void* stream;
   bool device;
   const dogleg_amd_batch_loss_t* loss; const double* weights; const unsigned char* held;
+  const dogleg_amd_batch_model_t* model; int likelihood;
 };
 int  dlg_dense_batch_query(const DlgBatchQuery& a);
 #pragma GCC visibility pop

@@ -1,7 +1,8 @@
 // dense_batch.hip -- the host side of the batch solver: what is kept between calls (the cache), and one call path per kind of
 // request of dense_batch.h -- the solve (solve_locked: the rounds), and the uncertainty and query calls (evaluate_at: one
 // callback and ONE launch; with the fit of the ..._fit entry points, whose weights and held set travel with the inputs).  Each
-// path serves the J and the products form, host arrays and the caller's device arrays.  The
+// path serves the J and the products form, host arrays and the caller's device arrays; the solve and the evaluation calls also
+// the model form, which has no callback and no evaluation buffer.  The
 // kernels and what they compute: dense_batch_kernels.hip; their arguments and launchers: dense_batch_dev.h.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -137,7 +138,7 @@ struct Segments
 
 // ---- what every call path shares ----
 // the callback of a call and what it writes: the J form (fJ: x, J of Nmeas = M rows) or the products form (fP: norm2x,
-// xtJ, JtJ; M is 0 there), or the model form of the solve (model: no callback, nothing written: the rows are formed inside the sweep)
+// xtJ, JtJ; M is 0 there), or the model form (model: no callback, nothing written: the rows are formed inside the sweep)
 struct BatchForm
 {
   dogleg_callback_device_batch_t* fJ;
@@ -416,11 +417,12 @@ struct EvalCall
   const dogleg_amd_batch_loss_t* loss; const double* weights; const unsigned char* held;
   size_t o_wts, o_held, wts_bytes, held_bytes;
   bool fit() const { return loss || weights || held; }
+  int likelihood;              // of the model form (F.model)
 };
 template <class Req> EvalCall eval_call(const char* who, const Req& a)
 {
   EvalCall c{};
-  c.who = who; c.F = BatchForm{a.fJ, a.fP, a.unpacked, nullptr}; c.B = a.B; c.N = a.N; c.M = a.M; c.cookie = a.cookie;
+  c.who = who; c.F = BatchForm{a.fJ, a.fP, a.unpacked, a.model}; c.likelihood = a.likelihood; c.B = a.B; c.N = a.N; c.M = a.M; c.cookie = a.cookie;
   c.p = a.p; c.lambda = a.lambda; c.status = a.status; c.active = a.active; c.stream = a.stream; c.device = a.device;
   c.loss = a.loss; c.weights = a.weights; c.held = a.held;
   return c;
@@ -457,12 +459,22 @@ FitDev fit_dev(const EvalCall& c, char* d)
   F.fit = c.fit() ? 1 : 0;
   return F;
 }
+// the kernels' argument of a call's model and its points (d_p: p in device memory), empty without a model
+ModelEvalDev model_dev(const EvalCall& c, const double* d_p)
+{
+  ModelEvalDev E{ModelDev{0, 0, 0, 0, nullptr, nullptr, nullptr}, nullptr};
+  if(const dogleg_amd_batch_model_t* m = c.F.model)
+    E = ModelEvalDev{ModelDev{m->kind, (int)m->width, m->t_per_problem ? 1 : 0, c.likelihood, m->y, m->t, m->scale}, d_p};
+  return E;
+}
 // U: the kernel's argument (of a query: its front half), its shape filled in.  bind(d): the kind's own pointers into the
-// kernel's argument (placed); gather(h): its inputs into the staging buffer h; launch(st, fit): with the call's fit as the kernels
-// take it (weights and held are staged and placed here, for both kinds); scatter(h): its outputs from h into the caller's arrays.  gather and scatter: the host route only.  Counted into t_unc_stats where they happen: kernel launches,
+// kernel's argument (placed); gather(h): its inputs into the staging buffer h; launch(st, fit, model): with the call's fit and model as the kernels
+// take them (weights and held are staged and placed here, for both kinds); scatter(h): its outputs from h into the caller's arrays.  gather and scatter: the host route only.  Counted into t_unc_stats where they happen: kernel launches,
 // synchronisations, copies + fills.
 // The device route keeps of the cache x / J (or the products) and at most two small arrays: a zeroed lambda where the caller
-// gives none and the live bytes, all 1, where no mask is given (the mask itself is the callback's live_dev otherwise)
+// gives none and the live bytes, all 1, where no mask is given (the mask itself is the callback's live_dev otherwise).
+// The model form: no callback, an empty x / J buffer (the cache's is neither grown nor read) and no live bytes, which only a
+// callback reads; ms_callback is 0
 template <class Bind, class Gather, class Launch, class Scatter>
 int evaluate_at(const EvalCall& c, UncDev& U, Bind bind, Gather gather, Launch launch, Scatter scatter)
 {
@@ -476,7 +488,8 @@ int evaluate_at(const EvalCall& c, UncDev& U, Bind bind, Gather gather, Launch l
   if(cache_open(who)) return -1;
   BatchCache& K = g_cache;
   const size_t b_bytes = align256(sizeof(double)*(size_t)B), io_bytes = c.device ? b_bytes : c.stage.bytes;
-  if(!cache_ensure(who, B, N, M, E.bytes, io_bytes + align256(B)) || (!c.device && !stage_ensure(who, B, N, M, io_bytes))) return -1;
+  const bool model = c.F.model != nullptr;
+  if(!cache_ensure(who, B, N, M, E.bytes, io_bytes + (model ? 0 : align256(B))) || (!c.device && !stage_ensure(who, B, N, M, io_bytes))) return -1;
   char* d = (char*)K.d_state; char* h = (char*)K.h_stage;
   unsigned char* own_live = (unsigned char*)(d + io_bytes);
   point_at_eval(U, c.F, E, K.d_eval);
@@ -503,17 +516,17 @@ int evaluate_at(const EvalCall& c, UncDev& U, Bind bind, Gather gather, Launch l
     if(c.held) memcpy(h + c.o_held, c.held, c.held_bytes);
     BHIP(hipMemcpyAsync(d, h, c.o_st, hipMemcpyHostToDevice, st)); ts[2] += 1.0;
   }
-  if(!c.active) { BHIP(hipMemsetAsync(own_live, 1, B, st)); ts[2] += 1.0; }
+  if(!c.active && !model) { BHIP(hipMemsetAsync(own_live, 1, B, st)); ts[2] += 1.0; }
   if(T.mark(who, 0, st)) return -1;
-  invoke_callback(c.F, d_p, U, d_live, B, st, c.cookie);
+  if(!model) invoke_callback(c.F, d_p, U, d_live, B, st, c.cookie);
   if(T.mark(who, 1, st)) return -1;
-  launch(st, fit);
+  launch(st, fit, model_dev(c, d_p));
   BHIP(hipGetLastError()); ts[0] += 1.0;
   if(T.mark(who, 2, st)) return -1;
   if(!c.device) { BHIP(hipMemcpyAsync(h + c.o_lam, d + c.o_lam, io_bytes - c.o_lam, hipMemcpyDeviceToHost, st)); ts[2] += 1.0; }
   BHIP(hipStreamSynchronize(st)); ts[1] += 1.0;
   if(T.read(who)) return -1;
-  ts[3] = T.ms_callback; ts[4] = T.ms_library;
+  ts[3] = model ? 0.0 : T.ms_callback; ts[4] = T.ms_library;
   if(c.device) return 0;
   if(c.lambda) memcpy(c.lambda, h + c.o_lam, sizeof(double)*B);
   memcpy(c.status, h + c.o_st, sizeof(int)*B);
@@ -529,7 +542,8 @@ int unc_locked(const DlgBatchUnc& a)
      {"dogleg_amd_dense_products_batch_uncertainty", "dogleg_amd_dense_products_batch_uncertainty_device"}},
     {{"dogleg_amd_dense_batch_uncertainty_fit", "dogleg_amd_dense_batch_uncertainty_fit_device"},
      {"dogleg_amd_dense_products_batch_uncertainty_fit", "dogleg_amd_dense_products_batch_uncertainty_fit_device"}}};
-  EvalCall c = eval_call(names[a.loss || a.weights || a.held ? 1 : 0][a.fP ? 1 : 0][a.device ? 1 : 0], a);
+  static const char* const model_names[2] = {"dogleg_amd_dense_batch_model_uncertainty", "dogleg_amd_dense_batch_model_uncertainty_device"};
+  EvalCall c = eval_call(a.model ? model_names[a.device ? 1 : 0] : names[a.loss || a.weights || a.held ? 1 : 0][a.fP ? 1 : 0][a.device ? 1 : 0], a);
   const unsigned int B = a.B, N = a.N, NF = a.M/(unsigned int)a.fs;
   const size_t vec_bytes = sizeof(double)*(size_t)B*N, fac_bytes = sizeof(double)*(size_t)B*NF;
   c.stage.add(vec_bytes);
@@ -548,7 +562,7 @@ int unc_locked(const DlgBatchUnc& a)
       A.var = placed(d, o_var, a.variances); A.cov = placed(d, o_cov, a.covariance); A.fac = placed(d, o_fac, a.factors);
     },
     [&](char* h) { if(a.factors) memcpy(h + o_scale, a.scale, sizeof(double)*B); },
-    [&](hipStream_t st, const FitDev& fit) { launch_batch_uncertainty(st, A, fit); },
+    [&](hipStream_t st, const FitDev& fit, const ModelEvalDev& mdl) { launch_batch_uncertainty(st, A, fit, mdl); },
     [&](const char* h) {
       if(a.factors) { memcpy(a.scale, h + o_scale, sizeof(double)*B); memcpy(a.factors, h + o_fac, fac_bytes); }
       if(a.variances) memcpy(a.variances, h + o_var, vec_bytes);
@@ -564,7 +578,9 @@ int query_locked(const DlgBatchQuery& a)
      {"dogleg_amd_dense_products_batch_query_covariance", "dogleg_amd_dense_products_batch_query_covariance_device"}},
     {{"dogleg_amd_dense_batch_query_covariance_fit", "dogleg_amd_dense_batch_query_covariance_fit_device"},
      {"dogleg_amd_dense_products_batch_query_covariance_fit", "dogleg_amd_dense_products_batch_query_covariance_fit_device"}}};
-  EvalCall c = eval_call(names[a.loss || a.weights || a.held ? 1 : 0][a.fP ? 1 : 0][a.device ? 1 : 0], a);
+  static const char* const model_names[2] = {"dogleg_amd_dense_batch_model_query_covariance",
+                                             "dogleg_amd_dense_batch_model_query_covariance_device"};
+  EvalCall c = eval_call(a.model ? model_names[a.device ? 1 : 0] : names[a.loss || a.weights || a.held ? 1 : 0][a.fP ? 1 : 0][a.device ? 1 : 0], a);
   const unsigned int B = a.B, N = a.N;
   const size_t rows = (size_t)B*a.Nq*a.Qrows, Jq_bytes = sizeof(double)*rows*N, out_bytes = sizeof(double)*rows*a.Qrows;
   c.stage.add(sizeof(double)*(size_t)B*N);
@@ -583,7 +599,7 @@ int query_locked(const DlgBatchQuery& a)
   return evaluate_at(c, U,
     [&](char* d) { A.Jq = placed(d, o_Jq, a.Jq); A.out = placed(d, o_out, a.out); },
     [&](char* h) { memcpy(h + o_Jq, a.Jq, Jq_bytes); },
-    [&](hipStream_t st, const FitDev& fit) { launch_batch_query(st, A, fit); },
+    [&](hipStream_t st, const FitDev& fit, const ModelEvalDev& mdl) { launch_batch_query(st, A, fit, mdl); },
     [&](const char* h) { memcpy(a.out, h + o_out, out_bytes); });
 }
 

@@ -66,6 +66,15 @@ struct FitDev
   int fit;                     // (host side: which kernel is launched)
 };
 
+// the built-in model of the fused uncertainty and query calls (dogleg_amd_dense_batch_model_uncertainty, _query_covariance): the
+// record and the points p [B][N] the rows are formed at, a kernel argument of its own behind FitDev, so that UncDev, QueryDev and
+// FitDev lie where they did.  Mdl.y == nullptr: no model (the J and the products form, which do not read this argument); that is
+// how the launchers tell the forms apart
+struct ModelEvalDev
+{
+  ModelDev Mdl; const double* p;
+};
+
 struct QueryDev
 {
   UncDev U;                    // B, N, M, NP, x, J, P, lam, status, active; cov, var, fac, scale: nullptr
@@ -84,8 +93,8 @@ __host__ __device__ inline unsigned char held_code(double p, double g, double lo
 // size class of N, the form, robust, bounded, fit).  The caller asks hipGetLastError
 #pragma GCC visibility push(hidden)
 void launch_batch_round(hipStream_t st, const BatchDev& A);
-void launch_batch_uncertainty(hipStream_t st, const UncDev& A, const FitDev& F);
-void launch_batch_query(hipStream_t st, const QueryDev& A, const FitDev& F);
+void launch_batch_uncertainty(hipStream_t st, const UncDev& A, const FitDev& F, const ModelEvalDev& E);
+void launch_batch_query(hipStream_t st, const QueryDev& A, const FitDev& F, const ModelEvalDev& E);
 // active: [B] or nullptr (all): the initial live bytes
 void launch_batch_init(hipStream_t st, const BatchDev& A, const unsigned char* active);
 void launch_batch_clamp(hipStream_t st, const BatchDev& A);

@@ -40,6 +40,12 @@
 // with !(f > 0) is staged as zeros and makes the point's cost +infinity, which the finite test of this form accepts once the
 // problem has started: rho is then -infinity, an ordinary rejected step.  Everything behind the sweep is the model form's text.
 //
+// The fused uncertainty and query calls of a built-in model (dogleg_amd_dense_batch_model_uncertainty, _query_covariance): the forms
+// FORM_MODEL and FORM_POISSON of k_batch_uncertainty and k_batch_query.  Their sweeps -- the first, the second for the outlierness
+// factors and the one for G -- form the rows in the lanes as the fused solve does; with POISSON the rows are those of
+// dogleg_amd_batch_model_fisher_callback (ROWS_FISHER of sweep_model: NaN in an infeasible row, the squares of x~ summed).  Every
+// output has the bits of the J form's call behind the respective callback; no x, no J in memory.
+//
 // The device-resident twins (dogleg_amd_*_batch_device): the same rounds and the same launch of k_batch_uncertainty with every
 // array of the caller in device memory.  The solve takes its initial p by a copy within the device and ends in k_batch_finish,
 // which writes p, the result structs and lambda where the caller has them; the uncertainty kernel's per-output pointers point
@@ -446,11 +452,17 @@ __device__ __forceinline__ double load_products(const ProductsDev& P, int b, int
 // the tile's rows, the sum for norm2(x) and the loop over the tile's rows are sweep_point's, so the results have its bits on what
 // the adapter would have written.  The loads of the next tile's y, t and scale are in flight under the loop; only the lanes that
 // hold a row evaluate the model.
-// POISSON: the rows and the cost of the Poisson form (the head of this file); no scale is read there
-template <int NMAX, bool POISSON = false>
-__device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* pb, int b, int N, int M, int NP, int lane,
+// ROWS_POISSON: the rows and the cost of the Poisson form (the head of this file); no scale is read there.
+// ROWS_FISHER: the rows of the Poisson form as dogleg_amd_batch_model_fisher_callback writes them, for the uncertainty and query
+// kernels, which stand in for that callback and a J-form launch: an infeasible row is staged as the header function returns it (NaN,
+// so the problem fails the finiteness test alone), and the sum is that of the squares of the staged x~, not the deviance.
+// M rows are swept (the query kernel's G: the first Nobservations); the problem's data lie Ms apart
+enum { ROWS_GAUSS = 0, ROWS_POISSON = 1, ROWS_FISHER = 2 };
+template <int NMAX, int MODE = ROWS_GAUSS>
+__device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* pb, int b, int N, int M, int Ms, int NP, int lane,
                                               double* SA, double* tile, double& gacc_out)
 {
+  constexpr bool POISSON = MODE == ROWS_POISSON;
   using C = BatchCfg<NMAX>;
   constexpr int NM = DOGLEG_BATCH_MODEL_MAX_NSTATE;
   static_assert(NM <= NMAX, "every built-in model lies in the smallest size class");
@@ -464,9 +476,9 @@ __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* 
   double p[NM];
 #pragma unroll
   for(int j = 0; j < NM; j++) p[j] = j < N ? pb[j] : 0.0;
-  const double* yb = Md.y + (size_t)b*M;
-  const double* tb = Md.t ? Md.t + (Md.t_each ? (size_t)b*M : (size_t)0) : nullptr;
-  const double* sb = Md.scale ? Md.scale + (size_t)b*M : nullptr;
+  const double* yb = Md.y + (size_t)b*Ms;
+  const double* tb = Md.t ? Md.t + (Md.t_each ? (size_t)b*Ms : (size_t)0) : nullptr;
+  const double* sb = Md.scale ? Md.scale + (size_t)b*Ms : nullptr;
   double yv = 0.0, tv = 0.0, sv = 1.0;
   bool infeasible = false;     // POISSON: a row of this lane had !(f > 0)
   if(lane < min(T, M))
@@ -491,6 +503,10 @@ __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* 
 #pragma unroll
         for(int j = 0; j < NM; j++) jr[j] = 0.0;
       }
+    }
+    else if constexpr(MODE == ROWS_FISHER)
+    {
+      if(lane < tc) (void)dogleg_batch_model_row_poisson(Md.kind, p, r0 + lane, Md.width, tv, yv, &xv, jr, &dv);
     }
     else if(lane < tc) dogleg_batch_model_row(Md.kind, p, r0 + lane, Md.width, tv, yv, sv, &xv, jr);
     wsync();
@@ -558,7 +574,7 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
   {
     // ---- the same sweep over rows formed on the way into the tile: no x, no J in memory ----
     static_assert(!ROBUST, "the model form has no loss");
-    n2x = sweep_model<NMAX>(A.Mdl, A.p_trial + bN, b, N, M, NP, lane, SA, SL, gacc);
+    n2x = sweep_model<NMAX>(A.Mdl, A.p_trial + bN, b, N, M, M, NP, lane, SA, SL, gacc);
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
   }
@@ -567,7 +583,7 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
     // ---- the model form's sweep over the Poisson rows; n2x is the deviance, +infinity at an infeasible point: no start point,
     // but a trial point like any other that is worse than the point it was stepped from ----
     static_assert(!ROBUST, "the Poisson form has no loss");
-    n2x = sweep_model<NMAX, true>(A.Mdl, A.p_trial + bN, b, N, M, NP, lane, SA, SL, gacc);
+    n2x = sweep_model<NMAX, ROWS_POISSON>(A.Mdl, A.p_trial + bN, b, N, M, M, NP, lane, SA, SL, gacc);
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     const bool started = (A.st[(size_t)ST_COUNT*b + ST_FLAGS] & F_STARTED) != 0;
     finite = __all((isfinite(n2x) || (started && n2x == INFINITY)) && isfinite(gacc) && isfinite(dg));
@@ -887,9 +903,14 @@ __device__ inline double feature2(const double* SA, const double* ra, int NS, in
 // the matrix that is factorised are the identity's, as in the bounded solve, so the factor and X have unit vectors there; and the
 // held diagonal entries of X are cleared: X' X, X q and X' z then have exact zeros in the held places and the inverse of the free
 // block in the others.  hm stays 0 otherwise.
+//
+// FORM_MODEL, FORM_POISSON (dogleg_amd_dense_batch_model_uncertainty, _query_covariance; E: the model and the points): the sweep is
+// sweep_model over rows formed in the lanes, which leaves in SA and gacc what sweep_point leaves on the rows of
+// dogleg_amd_batch_model_callback (FORM_MODEL) or dogleg_amd_batch_model_fisher_callback (FORM_POISSON: ROWS_FISHER).  No loss and
+// no weights, so FIT adds the held set only; a weight of exactly 1 would change no bit of a row
 template <int NMAX, int FORM, bool FIT, class Report>
-__device__ __forceinline__ bool factor_and_invert(const UncDev& A, const FitDev& F, int b, int lane, double* SA, double* SL,
-                                                  unsigned long long& hm, Report report)
+__device__ __forceinline__ bool factor_and_invert(const UncDev& A, const FitDev& F, const ModelEvalDev& E, int b, int lane,
+                                                  double* SA, double* SL, unsigned long long& hm, Report report)
 {
   const int N = A.N, M = A.M, NP = A.NP;
   double gacc, n2x;
@@ -904,6 +925,12 @@ __device__ __forceinline__ bool factor_and_invert(const UncDev& A, const FitDev&
       if(bad) n2x = __builtin_nan("");
     }
     else n2x = sweep_point<NMAX>(A.J + (size_t)b*M*N, A.x + (size_t)b*M, N, M, NP, lane, SA, SL, gacc);
+    const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
+    ok = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
+  }
+  else if constexpr(FORM == FORM_MODEL || FORM == FORM_POISSON)
+  {
+    n2x = sweep_model<NMAX, FORM == FORM_POISSON ? ROWS_FISHER : ROWS_GAUSS>(E.Mdl, E.p + (size_t)b*N, b, N, M, M, NP, lane, SA, SL, gacc);
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     ok = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
   }
@@ -984,8 +1011,10 @@ __device__ __forceinline__ double fit_sqrt_w(const FitDev& F, const double* wb, 
 
 // FIT: the leverage blocks and x of the second sweep are those of the weighted rows, against a Sigma with zero held rows and
 // columns; a computed scale counts the free variables only
+//
+// FORM_MODEL, FORM_POISSON: the second sweep forms its rows again, as the first did
 template <int NMAX, int FORM, bool FIT>
-__device__ void unc_problem(const UncDev& A, const FitDev& F, int b, int lane, double* S)
+__device__ void unc_problem(const UncDev& A, const FitDev& F, const ModelEvalDev& E, int b, int lane, double* S)
 {
   using C = BatchCfg<NMAX>;
   const int N = A.N, M = A.M, NP = A.NP;
@@ -1002,7 +1031,7 @@ __device__ void unc_problem(const UncDev& A, const FitDev& F, int b, int lane, d
 
   double scale = 0.0;
   unsigned long long hm = 0;
-  const bool stands = factor_and_invert<NMAX, FORM, FIT>(A, F, b, lane, SA, SL, hm, [&](bool ok, double lam, double n2x)
+  const bool stands = factor_and_invert<NMAX, FORM, FIT>(A, F, E, b, lane, SA, SL, hm, [&](bool ok, double lam, double n2x)
   {
     if(A.fac)
     {
@@ -1052,6 +1081,77 @@ __device__ void unc_problem(const UncDev& A, const FitDev& F, int b, int lane, d
       const int i = e/N;
       A.cov[(size_t)b*N*N + e] = sym_at(SA, i, e - i*N, N);
     }
+  if constexpr(FORM == FORM_MODEL || FORM == FORM_POISSON)
+  {
+    // ---- the second sweep of the model forms: the J form's tiles (T rows at the stride N | 1, lane t takes feature t), the rows
+    // formed where the J form copies them.  Lane t evaluates row r0 + t, as in sweep_model, and stores it at t (N | 1); its x stays
+    // in the lane: the x of feature t's rows is this lane's (fs = 1) or comes by two shuffles (fs = 2).  The loads of the next
+    // tile's y, t and scale are in flight under the features' loop
+    if(!A.fac) return;
+    constexpr int NM = DOGLEG_BATCH_MODEL_MAX_NSTATE;
+    const int fs = A.fs, NF = A.NF, NS = N | 1, Mc = NF*fs;
+    int T = min(min(64, BATCH_TILE/N), (BATCH_TILE + 64)/NS);
+    if(fs == 2) T &= ~1;
+    const double kf = scale/8.0;
+    double* tile = SL;
+    const ModelDev& Md = E.Mdl;
+    double p[NM];
+#pragma unroll
+    for(int j = 0; j < NM; j++) p[j] = j < N ? E.p[(size_t)b*N + j] : 0.0;
+    const double* yb = Md.y + (size_t)b*M;
+    const double* tb = Md.t ? Md.t + (Md.t_each ? (size_t)b*M : (size_t)0) : nullptr;
+    const double* sb = Md.scale ? Md.scale + (size_t)b*M : nullptr;
+    double yv = 0.0, tv = 0.0, sv = 1.0;
+    if(lane < min(T, Mc))
+    {
+      yv = yb[lane];
+      tv = tb ? tb[lane] : (double)lane;
+      if(sb) sv = sb[lane];
+    }
+    for(int r0 = 0; r0 < Mc; r0 += T)
+    {
+      const int tc = min(T, Mc - r0);
+      double xv = 0.0, jr[NM];
+#pragma unroll
+      for(int j = 0; j < NM; j++) jr[j] = 0.0;
+      if(lane < tc)
+      {
+        if constexpr(FORM == FORM_POISSON)
+        {
+          double dv;
+          (void)dogleg_batch_model_row_poisson(Md.kind, p, r0 + lane, Md.width, tv, yv, &xv, jr, &dv);
+        }
+        else dogleg_batch_model_row(Md.kind, p, r0 + lane, Md.width, tv, yv, sv, &xv, jr);
+      }
+      wsync();
+      if(lane < tc)
+      {
+#pragma unroll
+        for(int j = 0; j < NM; j++) if(j < N) tile[lane*NS + j] = jr[j];
+      }
+      wsync();
+      if(r0 + T < Mc)
+      {
+        const int r1 = r0 + T, tn = min(T, Mc - r1);
+        if(lane < tn)
+        {
+          yv = yb[r1 + lane];
+          tv = tb ? tb[r1 + lane] : (double)(r1 + lane);
+          if(sb) sv = sb[r1 + lane];
+        }
+      }
+      // (every lane makes the shuffles, so that they find their sources)
+      const double x0 = fs == 1 ? xv : __shfl(xv, (2*lane) & 63, 64);
+      const double x1 = fs == 1 ? 0.0 : __shfl(xv, (2*lane + 1) & 63, 64);
+      if(lane*fs < tc)
+      {
+        const size_t f = (size_t)(r0/fs + lane);
+        if(fs == 1) A.fac[(size_t)b*NF + f] = feature1(SA, tile + lane*NS, N, x0, kf);
+        else        A.fac[(size_t)b*NF + f] = feature2(SA, tile + 2*lane*NS, NS, N, x0, x1, kf);
+      }
+    }
+    return;
+  }
   if(FORM != FORM_J || !A.fac) return;
 
   // ---- the second sweep over J: tiles of T rows, row stride N | 1 in LDS (lanes read different rows: an odd stride keeps
@@ -1191,7 +1291,7 @@ __device__ void unc_problem(const UncDev& A, const FitDev& F, int b, int lane, d
 }
 
 template <int NMAX, int FORM, bool FIT>
-__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_uncertainty(UncDev A, FitDev F)
+__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_uncertainty(UncDev A, FitDev F, ModelEvalDev E)
 {
   constexpr int LDSW = BatchCfg<NMAX>::NP + FormCfg<NMAX, FORM>::SCR, WPB = BatchCfg<NMAX>::WPB;
   __shared__ double lds[WPB*LDSW];
@@ -1204,7 +1304,7 @@ __global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_uncertainty(Un
     if(lane == 0) A.status[b] = DOGLEG_AMD_BATCH_UNC_SKIPPED;
     return;
   }
-  unc_problem<NMAX, FORM, FIT>(A, F, b, lane, lds + w*LDSW);
+  unc_problem<NMAX, FORM, FIT>(A, F, E, b, lane, lds + w*LDSW);
 }
 
 // a . b over the wave, every lane ending with the same bits: the products are rounded before the butterfly.  (An FMA that took
@@ -1229,7 +1329,7 @@ template <int NMAX, int FORM> struct QueryCfg
 {
   using C = BatchCfg<NMAX>;
   static constexpr int SCR = FormCfg<NMAX, FORM>::SCR;
-  static constexpr int GB = FORM == FORM_J ? C::NP : 0;
+  static constexpr int GB = FORM != FORM_PRODUCTS ? C::NP : 0;
   static constexpr int ZROWS = DOGLEG_AMD_BATCH_QUERY_MAX_ROWS*NMAX;
   static constexpr int ZOWN = C::NP >= ZROWS ? 0 : ZROWS;
   static constexpr int LDSW = C::NP + SCR + NMAX + GB + ZOWN;
@@ -1237,8 +1337,9 @@ template <int NMAX, int FORM> struct QueryCfg
 };
 
 // FIT: G is that of the weighted rows, X that of the free block (factor_and_invert); everything behind them is the same text
+// FORM_MODEL, FORM_POISSON: G is sweep_model's JtJ over the first nobs rows, the data Nmeas apart
 template <int NMAX, int FORM, bool FIT>
-__device__ void query_problem(const QueryDev& A, const FitDev& F, int b, int lane, double* S)
+__device__ void query_problem(const QueryDev& A, const FitDev& F, const ModelEvalDev& E, int b, int lane, double* S)
 {
   using C = BatchCfg<NMAX>;
   using QC = QueryCfg<NMAX, FORM>;
@@ -1268,8 +1369,18 @@ __device__ void query_problem(const QueryDev& A, const FitDev& F, int b, int lan
         (void)sweep_point<NMAX>(U.J + (size_t)b*U.M*N, U.x + (size_t)b*U.M, N, A.nobs, U.NP, lane, SG, SL, g);
     }
   }
+  else if constexpr(FORM == FORM_MODEL || FORM == FORM_POISSON)
+  {
+    sandwich = A.nobs >= 0;
+    if(sandwich)
+    {
+      double g;
+      (void)sweep_model<NMAX, FORM == FORM_POISSON ? ROWS_FISHER : ROWS_GAUSS>(E.Mdl, E.p + (size_t)b*N, b, N, A.nobs, U.M, U.NP, lane,
+                                                                             SG, SL, g);
+    }
+  }
   unsigned long long hm = 0;
-  const bool stands = factor_and_invert<NMAX, FORM, FIT>(U, F, b, lane, SA, SL, hm, [&](bool ok, double lam, double)
+  const bool stands = factor_and_invert<NMAX, FORM, FIT>(U, F, E, b, lane, SA, SL, hm, [&](bool ok, double lam, double)
   {
     if(lane == 0) { U.lam[b] = lam; U.status[b] = ok ? DOGLEG_AMD_BATCH_UNC_OK : DOGLEG_AMD_BATCH_UNC_FAILED; }
     if(!ok)
@@ -1345,7 +1456,7 @@ __device__ void query_problem(const QueryDev& A, const FitDev& F, int b, int lan
 }
 
 template <int NMAX, int FORM, bool FIT>
-__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_query(QueryDev A, FitDev F)
+__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_query(QueryDev A, FitDev F, ModelEvalDev E)
 {
   constexpr int LDSW = QueryCfg<NMAX, FORM>::LDSW, WPB = BatchCfg<NMAX>::WPB;
   __shared__ double lds[WPB*LDSW];
@@ -1358,7 +1469,7 @@ __global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) k_batch_query(QueryDev
     if(lane == 0) A.U.status[b] = DOGLEG_AMD_BATCH_UNC_SKIPPED;
     return;
   }
-  query_problem<NMAX, FORM, FIT>(A, F, b, lane, lds + w*LDSW);
+  query_problem<NMAX, FORM, FIT>(A, F, E, b, lane, lds + w*LDSW);
 }
 
 // active: [B] or nullptr (all); a problem with active[b] == 0 starts, and stays, not live
@@ -1491,30 +1602,50 @@ void launch_batch_round(hipStream_t st, const BatchDev& A)
     else                     launch_class<NMAX>(k_batch_round<NMAX, FORM_J, false, false>, st, A.B, A);
   });
 }
-void launch_batch_uncertainty(hipStream_t st, const UncDev& A, const FitDev& F)
+// (the model forms: the class of 8 only, as in launch_batch_round, and one instantiation with FIT for both: without a held set hm
+// is 0 and NFree is N, which leaves the text without FIT)
+void launch_batch_uncertainty(hipStream_t st, const UncDev& A, const FitDev& F, const ModelEvalDev& E)
 {
   for_size_class(A.N, [&](auto c) {
     constexpr int NMAX = decltype(c)::value;
-    if(F.fit)
+    if(E.Mdl.y)
     {
-      if(A.P.n2x) launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_PRODUCTS, true>, st, A.B, A, F);
-      else        launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_J, true>, st, A.B, A, F);
+      if constexpr(NMAX == 8)
+      {
+        if(E.Mdl.likelihood == DOGLEG_AMD_LIKELIHOOD_POISSON)
+             launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_POISSON, true>, st, A.B, A, F, E);
+        else launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_MODEL, true>, st, A.B, A, F, E);
+      }
     }
-    else if(A.P.n2x) launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_PRODUCTS, false>, st, A.B, A, F);
-    else             launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_J, false>, st, A.B, A, F);
+    else if(F.fit)
+    {
+      if(A.P.n2x) launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_PRODUCTS, true>, st, A.B, A, F, E);
+      else        launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_J, true>, st, A.B, A, F, E);
+    }
+    else if(A.P.n2x) launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_PRODUCTS, false>, st, A.B, A, F, E);
+    else             launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_J, false>, st, A.B, A, F, E);
   });
 }
-void launch_batch_query(hipStream_t st, const QueryDev& A, const FitDev& F)
+void launch_batch_query(hipStream_t st, const QueryDev& A, const FitDev& F, const ModelEvalDev& E)
 {
   for_size_class(A.U.N, [&](auto c) {
     constexpr int NMAX = decltype(c)::value;
-    if(F.fit)
+    if(E.Mdl.y)
     {
-      if(A.U.P.n2x) launch_class<NMAX>(k_batch_query<NMAX, FORM_PRODUCTS, true>, st, A.U.B, A, F);
-      else          launch_class<NMAX>(k_batch_query<NMAX, FORM_J, true>, st, A.U.B, A, F);
+      if constexpr(NMAX == 8)
+      {
+        if(E.Mdl.likelihood == DOGLEG_AMD_LIKELIHOOD_POISSON)
+             launch_class<NMAX>(k_batch_query<NMAX, FORM_POISSON, true>, st, A.U.B, A, F, E);
+        else launch_class<NMAX>(k_batch_query<NMAX, FORM_MODEL, true>, st, A.U.B, A, F, E);
+      }
     }
-    else if(A.U.P.n2x) launch_class<NMAX>(k_batch_query<NMAX, FORM_PRODUCTS, false>, st, A.U.B, A, F);
-    else               launch_class<NMAX>(k_batch_query<NMAX, FORM_J, false>, st, A.U.B, A, F);
+    else if(F.fit)
+    {
+      if(A.U.P.n2x) launch_class<NMAX>(k_batch_query<NMAX, FORM_PRODUCTS, true>, st, A.U.B, A, F, E);
+      else          launch_class<NMAX>(k_batch_query<NMAX, FORM_J, true>, st, A.U.B, A, F, E);
+    }
+    else if(A.U.P.n2x) launch_class<NMAX>(k_batch_query<NMAX, FORM_PRODUCTS, false>, st, A.U.B, A, F, E);
+    else               launch_class<NMAX>(k_batch_query<NMAX, FORM_J, false>, st, A.U.B, A, F, E);
   });
 }
 void launch_batch_init(hipStream_t st, const BatchDev& A, const unsigned char* active)
