@@ -1227,8 +1227,8 @@ int dogleg_amd_numeric_buffers(struct dogleg_amd_numeric* h, const double** p_co
  * kind, a set communicator, and arrays of the record that are not device-accessible over their span.
  *
  * Not provided: a loss in the fused form (the adapter route has it: dogleg_amd_optimize_dense_batch_robust / _bounded with the
- * callback above); float or integer data; rotated Gaussians; user-defined models in the fused form (that is what a
- * callback is).
+ * callback above); float or integer data in this record (item 5 takes them); rotated Gaussians; user-defined models in the fused
+ * form (that is what a callback is).
  *
  * 3. Maximum-likelihood fits of count data.  dogleg_amd_optimize_dense_batch_model_mle[_device] are the fused solve above with a
  * likelihood.  DOGLEG_AMD_LIKELIHOOD_GAUSS: the fused solve above, bit for bit.  DOGLEG_AMD_LIKELIHOOD_POISSON: the data y_i >= 0
@@ -1256,7 +1256,8 @@ int dogleg_amd_numeric_buffers(struct dogleg_amd_numeric* h, const double** p_co
  * of grad f / sqrt(f)), so dogleg_amd_check_jacobian_device_batch reports it, rightly, and a solve through it would minimise
  * Pearson's chi^2 with a wrong Jacobian: EVERY BATCH SOLVE ENTRY POINT REFUSES THIS CALLBACK with a message and -1 (the plain,
  * robust and bounded solves and their _device twins).
- * Not provided: a loss in this form; other likelihoods; a gain or offset per datum (EMCCD / sCMOS noise models); the products form.
+ * Not provided: a loss in this form; other likelihoods; a gain or offset per datum in this record (item 5 has the sCMOS model; no
+ * EMCCD excess-noise model); the products form.
  *
  * 4. The fused uncertainty and query calls.  dogleg_amd_dense_batch_model_uncertainty[_device] and
  * dogleg_amd_dense_batch_model_query_covariance[_device] are dogleg_amd_dense_batch_uncertainty_fit[_device] and
@@ -1279,8 +1280,43 @@ int dogleg_amd_numeric_buffers(struct dogleg_amd_numeric* h, const double** p_co
  * Refused with a message and -1 before any device work, outputs untouched: what the replaced call refuses, what the fused solve
  * refuses of a model record, an unknown likelihood, model->scale with POISSON, a set communicator, and arrays of the record (and,
  * in the _device twins, of the call) that are not device-accessible over their span.
- * Not provided: a loss in the fused form; float or integer data; the products form; queries of more than
- * DOGLEG_AMD_BATCH_QUERY_MAX_ROWS rows; other likelihoods. */
+ * Not provided: a loss in the fused form; float or integer data in this record (item 5 takes them); the products form; queries of
+ * more than DOGLEG_AMD_BATCH_QUERY_MAX_ROWS rows; other likelihoods.
+ *
+ * 5. Raw camera frames.  dogleg_amd_batch_camera_t is the model record with the data as the camera delivers them: readings of
+ * uint16 ADU, float or double, and, for an sCMOS sensor, the per-pixel calibration maps.  Every call of items 1 to 4 has a camera
+ * twin that forms the datum in the lane that forms the row, so that the only per-problem stream is the raw one (2 bytes a pixel
+ * where the model record reads 8) and no kernel of the caller cuts windows out of the maps:
+ *   model       the record above with y == NULL; all else as in the fused solve
+ *   dtype, raw  DOGLEG_AMD_DATA_F64 / _F32 / _U16 and [B][Nmeas] readings of that type, aligned to the element
+ *   calibration either none (every member below NULL / 0) or sensor_width, sensor_height, offset, gain_inv and origin together,
+ *               the 2D kinds only.  offset (ADU), gain_inv (photoelectrons per ADU) and readvar (photoelectrons^2, or NULL: 0) are
+ *               float maps [sensor_height][sensor_width]; origin [B][2] ints: the sensor column and row of pixel (0, 0) of problem
+ *               b's window.  Row i is window pixel (ix, iy) = (i mod width, i div width), sensor pixel (ox + ix, oy + iy)
+ *   datum       without calibration y = (double)raw, v = 0; with it y = ((double)raw - (double)offset) * (double)gain_inv,
+ *               v = (double)readvar, uncontracted (dogleg_batch_camera_datum in dogleg_batch_models.h)
+ * All arrays are device-accessible memory of the current device, as those of the model record.
+ * DOGLEG_AMD_LIKELIHOOD_GAUSS reads y alone (readvar may be given and is not read; model.scale stays available, for instance
+ * 1 / sqrt(variance)).  DOGLEG_AMD_LIKELIHOOD_POISSON without calibration is item 3 on y (a negative float datum fails its problem
+ * as there); with calibration it is the sCMOS estimator of Huang et al. 2013, the Poisson fit of y + v against f + v, y + v clamped
+ * at 0: dogleg_batch_model_row_poisson_v.  With readvar NULL or 0 and no negative y that is item 3 on y, bit for bit.
+ * A window that leaves the sensor (ox < 0, oy < 0, ox + width > sensor_width or oy + height > sensor_height) reads nothing from
+ * the maps; its data are NaN, so that problem ends DOGLEG_AMD_BATCH_FAILED (DOGLEG_AMD_BATCH_UNC_FAILED), alone.  The test is made
+ * in the kernel, once a problem: origin is device memory.
+ * dogleg_amd_optimize_dense_batch_camera[_device] have the contract of dogleg_amd_optimize_dense_batch_model_mle[_device],
+ * dogleg_amd_dense_batch_camera_uncertainty[_device] and dogleg_amd_dense_batch_camera_query_covariance[_device] that of the
+ * _model_ calls of item 4: bounds, held, the active mask, the stream rule, one launch and one 4-byte read-back a round, what the
+ * host-pointer forms stage.  On data that are exactly representable EVERY OUTPUT HAS THE BITS OF THE _model_ CALL ON THE y ABOVE.
+ * dogleg_amd_batch_camera_callback and dogleg_amd_batch_camera_fisher_callback are the adapter route: dogleg_callback_device_batch_t
+ * whose cookie is the camera record, one launch each; the first writes x and J of the GAUSS definition, the second x~ and J~ of
+ * the Poisson definition (with read noise under calibration).  EVERY BATCH SOLVE ENTRY POINT REFUSES THE SECOND as it refuses
+ * dogleg_amd_batch_model_fisher_callback.
+ * Refused with a message and -1 before any device work, outputs untouched: what the mirrored call refuses of camera->model, a NULL
+ * camera, model.y != NULL, raw NULL or misaligned for its dtype, an unknown dtype, calibration given in part (readvar without the
+ * rest included), calibration with a 1D kind, a sensor smaller than the window, model.scale with POISSON, and arrays that are not
+ * device-accessible over their span (the maps: sensor_width sensor_height floats, origin: 2 B ints).
+ * Not provided: calibration for the 1D kinds; uint8 / int32 data; EMCCD excess-noise models; a loss in the fused form; the
+ * products form. */
 #define DOGLEG_AMD_MODEL_EXPDECAY         0
 #define DOGLEG_AMD_MODEL_GAUSS1D          1
 #define DOGLEG_AMD_MODEL_GAUSS2D          2
@@ -1338,6 +1374,53 @@ int dogleg_amd_dense_batch_model_query_covariance_device(const double* p_dev, un
                                                          unsigned int Qrows, int Nobservations, double* out_dev, int* status_dev,
                                                          const unsigned char* held_dev, const unsigned char* active_dev,
                                                          void* hip_stream);
+#define DOGLEG_AMD_DATA_F64 0
+#define DOGLEG_AMD_DATA_F32 1
+#define DOGLEG_AMD_DATA_U16 2
+typedef struct
+{
+  dogleg_amd_batch_model_t model;   /* model.y must be NULL; all else as in the fused solve */
+  int           dtype;              /* DOGLEG_AMD_DATA_* */
+  const void*   raw;                /* [B][Nmeas] readings of dtype, aligned to the element */
+  /* calibration: none (all of the below NULL / 0) or offset, gain_inv and origin together; 2D kinds only */
+  unsigned int  sensor_width, sensor_height;
+  const float*  offset;             /* [sensor_height][sensor_width], ADU */
+  const float*  gain_inv;           /* same shape, photoelectrons per ADU */
+  const float*  readvar;            /* same shape, photoelectrons^2, or NULL: 0 */
+  const int*    origin;             /* [B][2]: sensor column, row of pixel (0,0) of problem b's window */
+} dogleg_amd_batch_camera_t;
+void dogleg_amd_batch_camera_callback(const double* p_dev, double* x_dev, double* J_dev, const unsigned char* live_dev,
+                                      unsigned int B, void* hip_stream, void* cookie);
+void dogleg_amd_batch_camera_fisher_callback(const double* p_dev, double* x_dev, double* J_dev, const unsigned char* live_dev,
+                                             unsigned int B, void* hip_stream, void* cookie);
+int dogleg_amd_optimize_dense_batch_camera(double* p, unsigned int B, const dogleg_amd_batch_camera_t* camera, int likelihood,
+                                           const dogleg_parameters2_t* parameters,
+                                           const dogleg_amd_batch_bounds_t* bounds /* NULL: none */,
+                                           dogleg_amd_batch_result_t* results);
+int dogleg_amd_optimize_dense_batch_camera_device(double* p_dev, unsigned int B, const dogleg_amd_batch_camera_t* camera,
+                                                  int likelihood, const dogleg_parameters2_t* parameters,
+                                                  const dogleg_amd_batch_bounds_t* bounds,
+                                                  dogleg_amd_batch_result_t* results_dev, double* lambda_dev,
+                                                  const unsigned char* active_dev, void* hip_stream);
+int dogleg_amd_dense_batch_camera_uncertainty(const double* p, unsigned int B, const dogleg_amd_batch_camera_t* camera,
+                                              int likelihood, double* lambda, double* covariance, double* variances,
+                                              double* factors, double* scale, int featureSize, int* status,
+                                              const unsigned char* held /* or NULL */);
+int dogleg_amd_dense_batch_camera_uncertainty_device(const double* p_dev, unsigned int B, const dogleg_amd_batch_camera_t* camera,
+                                                     int likelihood, double* lambda_dev, double* covariance_dev,
+                                                     double* variances_dev, double* factors_dev, double* scale_dev, int featureSize,
+                                                     int* status_dev, const unsigned char* held_dev,
+                                                     const unsigned char* active_dev, void* hip_stream);
+int dogleg_amd_dense_batch_camera_query_covariance(const double* p, unsigned int B, const dogleg_amd_batch_camera_t* camera,
+                                                   int likelihood, double* lambda, const double* Jq, unsigned int Nq,
+                                                   unsigned int Qrows, int Nobservations, double* out, int* status,
+                                                   const unsigned char* held /* or NULL */);
+int dogleg_amd_dense_batch_camera_query_covariance_device(const double* p_dev, unsigned int B,
+                                                          const dogleg_amd_batch_camera_t* camera, int likelihood,
+                                                          double* lambda_dev, const double* Jq_dev, unsigned int Nq,
+                                                          unsigned int Qrows, int Nobservations, double* out_dev, int* status_dev,
+                                                          const unsigned char* held_dev, const unsigned char* active_dev,
+                                                          void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -208,4 +208,70 @@ DOGLEG_BATCH_MODEL_FN int dogleg_batch_model_row_poisson(int kind, const double*
   *d = feasible ? 2.0 * dev : NAN;
   return feasible;
 }
+
+/* one datum of a camera record (dogleg.h: dogleg_amd_batch_camera_t) from a raw reading already converted to double (the
+ * conversions of float and of a 16-bit integer are exact) and the three calibration values of its sensor pixel:
+ *
+ *   *y = (raw - (double)offset) * (double)gain_inv   photoelectrons,   *v = (double)readvar   photoelectrons^2
+ *
+ * one subtraction and one product, uncontracted.  Without calibration pass offset = 0, gain_inv = 1, readvar = 0: *y has the bits of
+ * raw then (a -0.0 becomes +0.0 under the subtraction, which no later comparison tells apart). */
+DOGLEG_BATCH_MODEL_FN void dogleg_batch_camera_datum(double raw, float offset, float gain_inv, float readvar, double* y, double* v)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double o = (double)offset;
+  const double g = (double)gain_inv;
+  const double e = raw - o;
+  *y = e * g;
+  *v = (double)readvar;
+}
+
+/* row i of a problem under the Poisson likelihood with read noise (the sCMOS estimator of Huang et al. 2013: the variance v of the
+ * Gaussian read noise, in photoelectrons^2, added to the datum and to the model, so that y + v is again nearly Poisson with the
+ * expectation f + v).  With f' = f_i + v and y' = max(y_i + v, 0):
+ *
+ *   q_i = 1 / sqrt(f'),   *x = (f' - y') q_i,   J[j] = (d f_i / d p_j) q_i,
+ *   *d  = 2 ((f' - y') - y' log(f' / y')),      2 f' where y' == 0.0
+ *
+ * f_i and its gradient come from dogleg_batch_model_row with y = 0 and s = 1; then, in this order and uncontracted: f' = f + v,
+ * y' = y + v, the clamp y' = y' < 0.0 ? 0.0 : y' (a comparison, not fmax: a NaN datum stays NaN and fails the problem as it does
+ * without read noise; a reading below the offset by more than v counts as no photon), the test f' > 0, r = f' - y', sqrt(f'),
+ * q = 1 / sqrt(f'), the products with q, f' / y', one log, y' log, r - y' log, times 2.
+ * Returns whether the row is feasible, f' > 0; an infeasible row gets *x = *d = NaN and a J of NaN, as in
+ * dogleg_batch_model_row_poisson.  With v == 0 and a y that is >= 0 or NaN every output has the bits of that function: f + 0 and
+ * y + 0 change no bit that is read later (-0.0 becomes +0.0, equal in every comparison and under f - y; an f of -0.0 is infeasible
+ * either way).  An unknown kind writes nothing and returns 0. */
+DOGLEG_BATCH_MODEL_FN int dogleg_batch_model_row_poisson_v(int kind, const double* p, int i, int width, double t, double y, double v,
+                                                           double* x, double* J, double* d)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double f = 0.0;
+  if(dogleg_batch_model_nstate(kind) < 0) return 0;
+  dogleg_batch_model_row(kind, p, i, width, t, 0.0, 1.0, &f, J);
+  const double fv = f + v;
+  const double ys = y + v;
+  const double yv = ys < 0.0 ? 0.0 : ys;
+  const int feasible = fv > 0.0;
+  const double r  = fv - yv;
+  const double sf = sqrt(fv);
+  const double q  = feasible ? 1.0 / sf : NAN;
+  const double xq = r * q;
+  J[0] = J[0] * q; J[1] = J[1] * q; J[2] = J[2] * q; J[3] = J[3] * q; J[4] = J[4] * q; J[5] = J[5] * q;
+  double dev;
+  if(yv == 0.0) dev = fv;
+  else
+  {
+    const double fy = fv / yv;
+    const double lg = log(fy);
+    const double yl = yv * lg;
+    dev = r - yl;
+  }
+  *x = xq;
+  *d = feasible ? 2.0 * dev : NAN;
+  return feasible;
+}
 #endif

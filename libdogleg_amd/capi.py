@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, BatchLoss, BatchBounds, BatchFit, BatchModel, MODEL_NSTATE, JacobianReport,
+from .ctypes_defs import (Parameters2, CholmodSparse, Trace, TraceBuffer, BatchResult, BatchLoss, BatchBounds, BatchFit, BatchModel, BatchCamera, MODEL_NSTATE, JacobianReport,
                           JacobianEntry,
                           NumericOptions, NUMERIC_FORWARD, NUMERIC_CENTRAL,
                           CB_SPARSE, CB_DENSE, CB_PRODUCTS, dptr, iptr)
@@ -93,6 +93,10 @@ DOGLEG_SYMBOLS = [
     "dogleg_amd_batch_model_fisher_callback",
     "dogleg_amd_dense_batch_model_uncertainty", "dogleg_amd_dense_batch_model_uncertainty_device",
     "dogleg_amd_dense_batch_model_query_covariance", "dogleg_amd_dense_batch_model_query_covariance_device",
+    "dogleg_amd_batch_camera_callback", "dogleg_amd_batch_camera_fisher_callback",
+    "dogleg_amd_optimize_dense_batch_camera", "dogleg_amd_optimize_dense_batch_camera_device",
+    "dogleg_amd_dense_batch_camera_uncertainty", "dogleg_amd_dense_batch_camera_uncertainty_device",
+    "dogleg_amd_dense_batch_camera_query_covariance", "dogleg_amd_dense_batch_camera_query_covariance_device",
 ]
 
 _lib = None
@@ -292,6 +296,17 @@ def lib():
         L.dogleg_amd_dense_batch_model_uncertainty_device.argtypes = [V, U, MP, C.c_int, V, V, V, V, V, C.c_int, V, V, V, V]
         L.dogleg_amd_dense_batch_model_query_covariance.argtypes = [D, U, MP, C.c_int, D, D, U, U, C.c_int, D, I, V]
         L.dogleg_amd_dense_batch_model_query_covariance_device.argtypes = [V, U, MP, C.c_int, V, V, U, U, C.c_int, V, V, V, V, V]
+    if hasattr(L, "dogleg_amd_optimize_dense_batch_camera"):
+        CP, PP, BP, U = C.POINTER(BatchCamera), C.POINTER(Parameters2), C.POINTER(BatchBounds), C.c_uint
+        L.dogleg_amd_optimize_dense_batch_camera.argtypes = [D, U, CP, C.c_int, PP, BP, C.POINTER(BatchResult)]
+        L.dogleg_amd_optimize_dense_batch_camera_device.argtypes = [V, U, CP, C.c_int, PP, BP, V, V, V, V]
+        L.dogleg_amd_dense_batch_camera_uncertainty.argtypes = [D, U, CP, C.c_int, D, D, D, D, D, C.c_int, I, V]
+        L.dogleg_amd_dense_batch_camera_uncertainty_device.argtypes = [V, U, CP, C.c_int, V, V, V, V, V, C.c_int, V, V, V, V]
+        L.dogleg_amd_dense_batch_camera_query_covariance.argtypes = [D, U, CP, C.c_int, D, D, U, U, C.c_int, D, I, V]
+        L.dogleg_amd_dense_batch_camera_query_covariance_device.argtypes = [V, U, CP, C.c_int, V, V, U, U, C.c_int, V, V, V, V, V]
+        for n in ("dogleg_amd_batch_camera_callback", "dogleg_amd_batch_camera_fisher_callback"):
+            getattr(L, n).argtypes = [V, V, V, V, C.c_uint, V, V]
+            getattr(L, n).restype = None
     if hasattr(L, "dogleg_amd_dense_batch_query_covariance"):
         U = C.c_uint
         L.dogleg_amd_dense_batch_query_covariance.argtypes = [D, U, U, U, V, V, D, D, U, U, C.c_int, D, I]
@@ -897,6 +912,117 @@ def dense_batch_model_query_covariance_device(p_dev, B, model, likelihood, Jq_de
                                                                       likelihood, _dev(lambda_dev), _dev(Jq_dev), Nq, Q, nobs,
                                                                       _dev(out_dev), _dev(status_dev), _dev(held_dev),
                                                                       _dev(active_dev), _dev(stream))
+
+
+def batch_camera(model, dtype, raw_dev, sensor=(0, 0), offset_dev=None, gain_inv_dev=None, readvar_dev=None, origin_dev=None):
+    """a dogleg_amd_batch_camera_t: model a BatchModel with y NULL (batch_model(kind, None, ...)), dtype a DATA_* of ctypes_defs,
+    raw_dev (B, Nmeas) readings of that type; sensor = (width, height), the three float maps (height, width) and origin_dev (B, 2)
+    int32: DeviceArrays or raw device addresses, None: NULL.  The caller keeps the record (and the arrays) alive while it is used"""
+    raw = lambda a: None if a is None else _dev(a).value
+    return BatchCamera(model, dtype, raw(raw_dev), sensor[0], sensor[1], raw(offset_dev), raw(gain_inv_dev), raw(readvar_dev),
+                       raw(origin_dev))
+
+
+def batch_camera_callback(camera, fisher=False):
+    """(cb, cookie, Nstate, Nmeas) of dogleg_amd_batch_camera_callback (fisher: of dogleg_amd_batch_camera_fisher_callback, which
+    the solve entry points refuse) on the record `camera`"""
+    L = lib()
+    cb = C.cast(L.dogleg_amd_batch_camera_fisher_callback if fisher else L.dogleg_amd_batch_camera_callback, C.c_void_p)
+    return cb, C.c_void_p(C.addressof(camera)), MODEL_NSTATE[camera.model.kind], camera.model.Nmeas
+
+
+def _camera_shape(camera):
+    if camera is None:
+        return 1, 1, None
+    return MODEL_NSTATE.get(camera.model.kind, 1), camera.model.Nmeas, C.byref(camera)
+
+
+def optimize_dense_batch_camera(p0s, camera, likelihood, lower=None, upper=None, params=None, bounded=None, want_held=True):
+    """dogleg_amd_optimize_dense_batch_camera: optimize_dense_batch_model_mle with a BatchCamera (None: NULL) instead of the model;
+    the same arguments otherwise and the same return value"""
+    N, _, cam = _camera_shape(camera)
+    p = np.array(p0s, dtype=np.float64, copy=True).reshape(-1, N)
+    B = p.shape[0]
+    res = (BatchResult * max(B, 1))()
+    if bounded is None:
+        bounded = lower is not None or upper is not None
+    lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).reshape(B, N)
+    hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).reshape(B, N)
+    held = np.full((B, N), 255, dtype=np.uint8) if bounded and want_held else None
+    addr = lambda a: None if a is None else a.ctypes.data
+    bounds = BatchBounds(addr(lo), addr(hi), addr(held))
+    rc = lib().dogleg_amd_optimize_dense_batch_camera(dptr(p), B, cam, likelihood, C.byref(params) if params is not None else None,
+                                                      C.byref(bounds) if bounded else None, res)
+    return rc, p, _batch_results(res, B), held
+
+
+def optimize_dense_batch_camera_device(p_dev, B, camera, likelihood, params, results_dev, lower_dev=None, upper_dev=None,
+                                       held_dev=None, lambda_dev=None, active_dev=None, stream=None, bounded=None):
+    """dogleg_amd_optimize_dense_batch_camera_device: optimize_dense_batch_model_mle_device with a BatchCamera.  Returns rc."""
+    raw = lambda a: None if a is None else _dev(a).value
+    if bounded is None:
+        bounded = lower_dev is not None or upper_dev is not None or held_dev is not None
+    bounds = BatchBounds(raw(lower_dev), raw(upper_dev), raw(held_dev))
+    return lib().dogleg_amd_optimize_dense_batch_camera_device(_dev(p_dev), B, _camera_shape(camera)[2], likelihood,
+                                                               C.byref(params) if params is not None else None,
+                                                               C.byref(bounds) if bounded else None, _dev(results_dev),
+                                                               _dev(lambda_dev), _dev(active_dev), _dev(stream))
+
+
+def dense_batch_camera_uncertainty(p, camera, likelihood, lam=None, want=("cov", "var", "factors"), fs=1, scale=None, held=None):
+    """dogleg_amd_dense_batch_camera_uncertainty at the points p (B, N): dense_batch_model_uncertainty with a BatchCamera (None:
+    NULL) instead of the model.  The same dict."""
+    N, M, cam = _camera_shape(camera)
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, N)
+    B = p.shape[0]
+    out = dict(lam=None if lam is None else np.array(lam, dtype=np.float64, copy=True).reshape(B))
+    out["status"] = np.full(B, -1, dtype=np.int32)
+    if "cov" in want:
+        out["cov"] = np.zeros((B, N, N))
+    if "var" in want:
+        out["var"] = np.zeros((B, N))
+    if "factors" in want:
+        out["factors"] = np.zeros((B, M // max(fs, 1)))
+        out["scale"] = np.full(B, -1.0) if scale is None else np.array(np.broadcast_to(scale, (B,)), dtype=np.float64)
+    opt = lambda k: dptr(out[k]) if out.get(k) is not None else None
+    keep = []
+    out["rc"] = lib().dogleg_amd_dense_batch_camera_uncertainty(dptr(p), B, cam, likelihood, opt("lam"), opt("cov"), opt("var"),
+                                                                opt("factors"), opt("scale"), fs, iptr(out["status"]),
+                                                                _held_addr(held, keep))
+    return out
+
+
+def dense_batch_camera_uncertainty_device(p_dev, B, camera, likelihood, status_dev, lambda_dev=None, cov_dev=None, var_dev=None,
+                                          factors_dev=None, scale_dev=None, fs=1, held_dev=None, active_dev=None, stream=None):
+    """dogleg_amd_dense_batch_camera_uncertainty_device: every array a DeviceArray or a raw device address (None: NULL).
+    Returns rc."""
+    return lib().dogleg_amd_dense_batch_camera_uncertainty_device(_dev(p_dev), B, _camera_shape(camera)[2], likelihood,
+                                                                  _dev(lambda_dev), _dev(cov_dev), _dev(var_dev), _dev(factors_dev),
+                                                                  _dev(scale_dev), fs, _dev(status_dev), _dev(held_dev),
+                                                                  _dev(active_dev), _dev(stream))
+
+
+def dense_batch_camera_query_covariance(p, camera, likelihood, Jq, lam=None, nobs=-1, held=None):
+    """dogleg_amd_dense_batch_camera_query_covariance at the points p (B, N): dense_batch_model_query_covariance with a BatchCamera
+    instead of the model.  The same dict."""
+    N = MODEL_NSTATE.get(camera.model.kind, 1) if camera is not None else np.shape(Jq)[-1]
+    p, Jq, out = _query_arrays(p, N, Jq, lam)
+    keep = []
+    out["rc"] = lib().dogleg_amd_dense_batch_camera_query_covariance(dptr(p), p.shape[0], _camera_shape(camera)[2], likelihood,
+                                                                     dptr(out["lam"]) if lam is not None else None, dptr(Jq),
+                                                                     Jq.shape[1], Jq.shape[2], nobs, dptr(out["out"]),
+                                                                     iptr(out["status"]), _held_addr(held, keep))
+    return out
+
+
+def dense_batch_camera_query_covariance_device(p_dev, B, camera, likelihood, Jq_dev, Nq, Q, out_dev, status_dev, nobs=-1,
+                                               lambda_dev=None, held_dev=None, active_dev=None, stream=None):
+    """dogleg_amd_dense_batch_camera_query_covariance_device: every array a DeviceArray or a raw device address (None: NULL).
+    Returns rc."""
+    return lib().dogleg_amd_dense_batch_camera_query_covariance_device(_dev(p_dev), B, _camera_shape(camera)[2], likelihood,
+                                                                       _dev(lambda_dev), _dev(Jq_dev), Nq, Q, nobs, _dev(out_dev),
+                                                                       _dev(status_dev), _dev(held_dev), _dev(active_dev),
+                                                                       _dev(stream))
 
 
 def batch_results_from_device(results_dev, B):

@@ -189,6 +189,53 @@ bool batch_model_ok(const char* who, const dogleg_amd_batch_model_t* model, int 
   return true;
 }
 
+// a (checked) camera record into a request record of the uncertainty or query kind: its model, whose y is NULL, and the record
+template <class Req> Req with_camera(Req a, const dogleg_amd_batch_camera_t* camera, int likelihood, const unsigned char* held)
+{
+  a = with_model(a, &camera->model, likelihood, held);
+  a.camera = camera;
+  return a;
+}
+// bytes of one reading of a camera record; 0 for an unknown dtype
+size_t camera_element(int dtype)
+{
+  return dtype == DOGLEG_AMD_DATA_F64 ? 8 : dtype == DOGLEG_AMD_DATA_F32 ? 4 : dtype == DOGLEG_AMD_DATA_U16 ? 2 : 0;
+}
+// the camera record (dogleg.h: dogleg_amd_batch_camera_t), from its members alone: no pointer's target is looked at.  Its model is
+// checked as the fused solve checks a model record, with raw in the place of y
+bool batch_camera_ok(const char* who, const dogleg_amd_batch_camera_t* camera, int likelihood)
+{
+  if(!camera) { MSG("%s: camera must be given", who); return false; }
+  if(camera->model.y) { MSG("%s: camera->model.y must be NULL: the data of a camera record are camera->raw", who); return false; }
+  if(!camera->raw) { MSG("%s: camera->raw must be given", who); return false; }
+  dogleg_amd_batch_model_t m = camera->model;
+  m.y = (const double*)camera->raw;
+  if(!batch_model_ok(who, &m, likelihood)) return false;
+  const size_t el = camera_element(camera->dtype);
+  if(!el) { MSG("%s: camera->dtype = %d is none of DOGLEG_AMD_DATA_{F64, F32, U16}", who, camera->dtype); return false; }
+  if((size_t)camera->raw % el) { MSG("%s: camera->raw = %p is not aligned to its element of %zu bytes", who, camera->raw, el); return false; }
+  const bool any = camera->offset || camera->gain_inv || camera->origin || camera->sensor_width || camera->sensor_height;
+  const bool all = camera->offset && camera->gain_inv && camera->origin && camera->sensor_width && camera->sensor_height;
+  if((any || camera->readvar) && !all)
+  {
+    MSG("%s: calibration is given in part: camera->offset, gain_inv, origin, sensor_width and sensor_height go together (readvar only "
+        "with them), or all of them are NULL / 0", who);
+    return false;
+  }
+  if(!all) return true;
+  const bool two_d = m.kind == DOGLEG_AMD_MODEL_GAUSS2D || m.kind == DOGLEG_AMD_MODEL_GAUSS2D_ELLIPTIC;
+  if(!two_d) { MSG("%s: calibration maps go with the 2D kinds only: model.kind = %d has no window on the sensor", who, m.kind); return false; }
+  if(camera->sensor_width < m.width || camera->sensor_height < m.height)
+  {
+    MSG("%s: a sensor of %u x %u pixels is smaller than the window of %u x %u", who, camera->sensor_width, camera->sensor_height, m.width,
+        m.height);
+    return false;
+  }
+  if((unsigned long long)camera->sensor_width*camera->sensor_height > 2147483647ull)
+  { MSG("%s: a sensor of %u x %u pixels: more than 2^31 - 1 are not supported", who, camera->sensor_width, camera->sensor_height); return false; }
+  return true;
+}
+
 // a *_dev argument of the device-resident batch entry points: memory a kernel of the current device may touch over `bytes`
 bool device_span_ok(const char* who, const char* name, const void* ptr, size_t bytes)
 {
@@ -202,13 +249,23 @@ bool device_span_ok_or_null(const char* who, const char* name, const void* ptr, 
 {
   return !ptr || device_span_ok(who, name, ptr, bytes);
 }
-// the arrays of a (checked) model record of B problems, which lie in device memory on either route; no model: nothing to check
-bool model_spans_ok(const char* who, const dogleg_amd_batch_model_t* model, size_t B)
+// the arrays of a (checked) model record of B problems, which lie in device memory on either route; no model: nothing to check.
+// camera: the (checked) record the model lies in, or NULL: its raw stands for y, and its maps and origins are checked too
+bool model_spans_ok(const char* who, const dogleg_amd_batch_model_t* model, size_t B, const dogleg_amd_batch_camera_t* camera = nullptr)
 {
   if(!model) return true;
   const size_t BM = B*model->Nmeas;
-  return device_span_ok(who, "model->y", model->y, sizeof(double)*BM) &&
-         device_span_ok_or_null(who, "model->t", model->t, sizeof(double)*(model->t_per_problem ? BM : (size_t)model->Nmeas)) &&
+  if(camera)
+  {
+    const size_t px = sizeof(float)*(size_t)camera->sensor_width*camera->sensor_height;
+    if(!(device_span_ok(who, "camera->raw", camera->raw, camera_element(camera->dtype)*BM) &&
+         device_span_ok_or_null(who, "camera->offset", camera->offset, px) &&
+         device_span_ok_or_null(who, "camera->gain_inv", camera->gain_inv, px) &&
+         device_span_ok_or_null(who, "camera->readvar", camera->readvar, px) &&
+         device_span_ok_or_null(who, "camera->origin", camera->origin, sizeof(int)*2*B))) return false;
+  }
+  else if(!device_span_ok(who, "model->y", model->y, sizeof(double)*BM)) return false;
+  return device_span_ok_or_null(who, "model->t", model->t, sizeof(double)*(model->t_per_problem ? BM : (size_t)model->Nmeas)) &&
          device_span_ok_or_null(who, "model->scale", model->scale, sizeof(double)*BM);
 }
 
@@ -225,6 +282,13 @@ int batch_solve_entry(const char* who, SolveKind kind, DlgBatchSolve a)
   {
     MSG("%s: dogleg_amd_batch_model_fisher_callback is no callback of a solve: its J is not the derivative of its x, and a solve through "
         "it would minimise Pearson's chi^2 with a wrong Jacobian.  The Poisson fit is dogleg_amd_optimize_dense_batch_model_mle; this "
+        "callback serves the uncertainty, query and _fit calls", who);
+    return -1;
+  }
+  if(a.fJ == dogleg_amd_batch_camera_fisher_callback)
+  {
+    MSG("%s: dogleg_amd_batch_camera_fisher_callback is no callback of a solve: its J is not the derivative of its x, and a solve through "
+        "it would minimise Pearson's chi^2 with a wrong Jacobian.  The Poisson fit is dogleg_amd_optimize_dense_batch_camera; this "
         "callback serves the uncertainty, query and _fit calls", who);
     return -1;
   }
@@ -245,7 +309,7 @@ int batch_solve_entry(const char* who, SolveKind kind, DlgBatchSolve a)
        device_span_ok_or_null(who, "bounds->lower", bounds.lower, sizeof(double)*BN) &&
        device_span_ok_or_null(who, "bounds->upper", bounds.upper, sizeof(double)*BN) &&
        device_span_ok_or_null(who, "bounds->held", bounds.held, BN))) return -1;
-  if(!model_spans_ok(who, a.model, B)) return -1;
+  if(!model_spans_ok(who, a.model, B, a.camera)) return -1;
   return dlg_dense_batch_solve(a);
 }
 // featureSize: as the caller gave it; a.fs is set here
@@ -301,7 +365,7 @@ int batch_unc_entry(const char* who, DlgBatchUnc a, const dogleg_parameters2_t* 
        device_span_ok_or_null(who, "active_dev", a.active, B) &&
        device_span_ok_or_null(who, "fit->weights", a.weights, sizeof(double)*B*loss_features(a.loss, a.M)) &&
        device_span_ok_or_null(who, a.model ? "held_dev" : "fit->held", a.held, BN))) return -1;
-  if(!model_spans_ok(who, a.model, B)) return -1;
+  if(!model_spans_ok(who, a.model, B, a.camera)) return -1;
   return dlg_dense_batch_uncertainty(a);
 }
 // Nq queries of Qrows rows per problem, Nobservations of the J form's Nmeas
@@ -334,7 +398,7 @@ int batch_query_entry(const char* who, DlgBatchQuery a, const dogleg_parameters2
        device_span_ok_or_null(who, "active_dev", a.active, B) &&
        device_span_ok_or_null(who, "fit->weights", a.weights, sizeof(double)*B*loss_features(a.loss, a.M)) &&
        device_span_ok_or_null(who, a.model ? "held_dev" : "fit->held", a.held, B*a.N))) return -1;
-  if(!model_spans_ok(who, a.model, B)) return -1;
+  if(!model_spans_ok(who, a.model, B, a.camera)) return -1;
   return dlg_dense_batch_query(a);
 }
 
@@ -365,6 +429,12 @@ bool tolerances_ok(const char* who, double rtol, double atol)
 }
 
 } // namespace
+
+bool dlg_batch_camera_ok(const char* who, const dogleg_amd_batch_camera_t* camera, int likelihood)
+{
+  return batch_camera_ok(who, camera, likelihood);
+}
+
 
 extern "C" {
 
@@ -605,6 +675,68 @@ int dogleg_amd_dense_batch_model_query_covariance_device(const double* p_dev, un
   return batch_query_entry(__func__, with_model(DlgBatchQuery{p_dev, B, 0, 0, nullptr, nullptr, nullptr, false, lambda_dev, Jq_dev, Nq,
                                                                Qrows, Nobservations, out_dev, status_dev, active_dev, hip_stream,
                                                                true}, model, likelihood, held_dev), nullptr);
+}
+// ---- the same calls on a camera record: the model forms with camera->raw, and the calibration maps, as the source of the data
+int dogleg_amd_optimize_dense_batch_camera(double* p, unsigned int B, const dogleg_amd_batch_camera_t* camera, int likelihood,
+                                           const dogleg_parameters2_t* parameters, const dogleg_amd_batch_bounds_t* bounds,
+                                           dogleg_amd_batch_result_t* results)
+{
+  if(!batch_camera_ok(__func__, camera, likelihood)) return -1;
+  DlgBatchSolve a{p, B, (unsigned int)dogleg_batch_model_nstate(camera->model.kind), camera->model.Nmeas, nullptr, nullptr, nullptr, false,
+                  parameters, results};
+  a.bounds = bounds; a.model = &camera->model; a.likelihood = likelihood; a.mle = true; a.camera = camera;
+  return batch_solve_entry(__func__, bounds ? SOLVE_BOUNDED : SOLVE_PLAIN, a);
+}
+int dogleg_amd_optimize_dense_batch_camera_device(double* p_dev, unsigned int B, const dogleg_amd_batch_camera_t* camera,
+                                                  int likelihood, const dogleg_parameters2_t* parameters,
+                                                  const dogleg_amd_batch_bounds_t* bounds, dogleg_amd_batch_result_t* results_dev,
+                                                  double* lambda_dev, const unsigned char* active_dev, void* hip_stream)
+{
+  if(!batch_camera_ok(__func__, camera, likelihood)) return -1;
+  DlgBatchSolve a{p_dev, B, (unsigned int)dogleg_batch_model_nstate(camera->model.kind), camera->model.Nmeas, nullptr, nullptr, nullptr,
+                  false, parameters, results_dev, lambda_dev, active_dev, hip_stream};
+  a.bounds = bounds; a.device = true; a.model = &camera->model; a.likelihood = likelihood; a.mle = true; a.camera = camera;
+  return batch_solve_entry(__func__, bounds ? SOLVE_BOUNDED : SOLVE_PLAIN, a);
+}
+int dogleg_amd_dense_batch_camera_uncertainty(const double* p, unsigned int B, const dogleg_amd_batch_camera_t* camera, int likelihood,
+                                              double* lambda, double* covariance, double* variances, double* factors, double* scale,
+                                              int featureSize, int* status, const unsigned char* held)
+{
+  if(!batch_camera_ok(__func__, camera, likelihood)) return -1;
+  return batch_unc_entry(__func__, with_camera(DlgBatchUnc{p, B, 0, 0, nullptr, nullptr, nullptr, false, lambda, covariance, variances,
+                                                          factors, scale, 0, status}, camera, likelihood, held), nullptr, featureSize);
+}
+int dogleg_amd_dense_batch_camera_uncertainty_device(const double* p_dev, unsigned int B, const dogleg_amd_batch_camera_t* camera,
+                                                     int likelihood, double* lambda_dev, double* covariance_dev,
+                                                     double* variances_dev, double* factors_dev, double* scale_dev, int featureSize,
+                                                     int* status_dev, const unsigned char* held_dev,
+                                                     const unsigned char* active_dev, void* hip_stream)
+{
+  if(!batch_camera_ok(__func__, camera, likelihood)) return -1;
+  return batch_unc_entry(__func__, with_camera(DlgBatchUnc{p_dev, B, 0, 0, nullptr, nullptr, nullptr, false, lambda_dev, covariance_dev,
+                                                          variances_dev, factors_dev, scale_dev, 0, status_dev, active_dev, hip_stream,
+                                                          true}, camera, likelihood, held_dev), nullptr, featureSize);
+}
+int dogleg_amd_dense_batch_camera_query_covariance(const double* p, unsigned int B, const dogleg_amd_batch_camera_t* camera,
+                                                   int likelihood, double* lambda, const double* Jq, unsigned int Nq,
+                                                   unsigned int Qrows, int Nobservations, double* out, int* status,
+                                                   const unsigned char* held)
+{
+  if(!batch_camera_ok(__func__, camera, likelihood)) return -1;
+  return batch_query_entry(__func__, with_camera(DlgBatchQuery{p, B, 0, 0, nullptr, nullptr, nullptr, false, lambda, Jq, Nq, Qrows,
+                                                                Nobservations, out, status}, camera, likelihood, held), nullptr);
+}
+int dogleg_amd_dense_batch_camera_query_covariance_device(const double* p_dev, unsigned int B,
+                                                          const dogleg_amd_batch_camera_t* camera, int likelihood,
+                                                          double* lambda_dev, const double* Jq_dev, unsigned int Nq,
+                                                          unsigned int Qrows, int Nobservations, double* out_dev, int* status_dev,
+                                                          const unsigned char* held_dev, const unsigned char* active_dev,
+                                                          void* hip_stream)
+{
+  if(!batch_camera_ok(__func__, camera, likelihood)) return -1;
+  return batch_query_entry(__func__, with_camera(DlgBatchQuery{p_dev, B, 0, 0, nullptr, nullptr, nullptr, false, lambda_dev, Jq_dev, Nq,
+                                                                Qrows, Nobservations, out_dev, status_dev, active_dev, hip_stream,
+                                                                true}, camera, likelihood, held_dev), nullptr);
 }
 int dogleg_amd_batch_last_stats(double* out, int n) { return out ? dlg_dense_batch_last_stats(out, n) : 0; }
 int dogleg_amd_dense_batch_uncertainty(const double* p, unsigned int B, unsigned int Nstate, unsigned int Nmeas,

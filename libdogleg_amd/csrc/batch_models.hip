@@ -8,6 +8,7 @@
 #include <cstdio>
 #include "../../include/dogleg.h"
 #include "../../include/dogleg_batch_models.h"
+#include "dense_batch.h"
 
 static_assert(DOGLEG_BATCH_MODEL_EXPDECAY == DOGLEG_AMD_MODEL_EXPDECAY && DOGLEG_BATCH_MODEL_GAUSS1D == DOGLEG_AMD_MODEL_GAUSS1D &&
               DOGLEG_BATCH_MODEL_GAUSS2D == DOGLEG_AMD_MODEL_GAUSS2D &&
@@ -61,6 +62,73 @@ __global__ void __launch_bounds__(256) k_model_rows_poisson(int B, int M, int N,
   for(int j = 0; j < DOGLEG_BATCH_MODEL_MAX_NSTATE; j++) if(j < N) J[idx*N + j] = jr[j];
 }
 
+// the same two for a camera record (dogleg.h: dogleg_amd_batch_camera_t): the datum is formed from the reading and, with
+// calibration (offset != nullptr), from the maps at the row's sensor pixel; a window that leaves the sensor reads nothing from the
+// maps and its data are NaN.  FISHER: the Poisson rows, with the read-noise variance under calibration
+// (dogleg_batch_model_row_poisson_v), else those of the GAUSS definition
+struct CameraArgs
+{
+  int kind, width, height, t_each, dtype, sw, sh;
+  const void* raw; const float *offset, *gain_inv, *readvar; const int* origin;
+  const double *t, *scale;
+};
+template <bool FISHER>
+__global__ void __launch_bounds__(256) k_camera_rows(int B, int M, int N, CameraArgs C, const unsigned char* __restrict__ live,
+                                                     const double* __restrict__ p, double* __restrict__ x, double* __restrict__ J)
+{
+  const size_t idx = (size_t)blockIdx.x*256 + threadIdx.x;
+  if(idx >= (size_t)B*M) return;
+  const int b = (int)(idx/M), i = (int)(idx - (size_t)b*M);
+  if(!live[b]) return;
+  double pv[DOGLEG_BATCH_MODEL_MAX_NSTATE], jr[DOGLEG_BATCH_MODEL_MAX_NSTATE];
+#pragma unroll
+  for(int j = 0; j < DOGLEG_BATCH_MODEL_MAX_NSTATE; j++) { pv[j] = j < N ? p[(size_t)b*N + j] : 0.0; jr[j] = 0.0; }
+  const double ti = C.t ? C.t[C.t_each ? idx : (size_t)i] : (double)i;
+  const double raw = C.dtype == DOGLEG_AMD_DATA_U16 ? (double)((const unsigned short*)C.raw)[idx] :
+                     C.dtype == DOGLEG_AMD_DATA_F32 ? (double)((const float*)C.raw)[idx] : ((const double*)C.raw)[idx];
+  double yv = raw, vv = 0.0;
+  if(C.offset)
+  {
+    const int ox = C.origin[2*(size_t)b], oy = C.origin[2*(size_t)b + 1];
+    if(ox >= 0 && oy >= 0 && ox <= C.sw - C.width && oy <= C.sh - C.height)
+    {
+      const int iy = i/C.width, ix = i - iy*C.width;
+      const size_t px = (size_t)(oy + iy)*C.sw + (ox + ix);
+      dogleg_batch_camera_datum(raw, C.offset[px], C.gain_inv[px], C.readvar ? C.readvar[px] : 0.0f, &yv, &vv);
+    }
+    else yv = __builtin_nan("");
+  }
+  double xv = 0.0, dv = 0.0;
+  if constexpr(FISHER)
+  {
+    if(C.offset) (void)dogleg_batch_model_row_poisson_v(C.kind, pv, i, C.width, ti, yv, vv, &xv, jr, &dv);
+    else         (void)dogleg_batch_model_row_poisson(C.kind, pv, i, C.width, ti, yv, &xv, jr, &dv);
+  }
+  else dogleg_batch_model_row(C.kind, pv, i, C.width, ti, yv, C.scale ? C.scale[idx] : 1.0, &xv, jr);
+  x[idx] = xv;
+#pragma unroll
+  for(int j = 0; j < DOGLEG_BATCH_MODEL_MAX_NSTATE; j++) if(j < N) J[idx*N + j] = jr[j];
+}
+
+template <bool FISHER>
+void camera_rows(const char* who, const double* p_dev, double* x_dev, double* J_dev, const unsigned char* live_dev, unsigned int B,
+                 void* hip_stream, void* cookie)
+{
+  const dogleg_amd_batch_camera_t* c = (const dogleg_amd_batch_camera_t*)cookie;
+  // (the rules of the fused camera calls, stated once: api_extensions.cpp; FISHER: the Poisson rows, which take no scale)
+  if(B == 0 || !dlg_batch_camera_ok(who, c, FISHER ? DOGLEG_AMD_LIKELIHOOD_POISSON : DOGLEG_AMD_LIKELIHOOD_GAUSS))
+  {
+    fprintf(stderr, "libdogleg_amd: %s: the cookie is no usable dogleg_amd_batch_camera_t: nothing written\n", who);
+    return;
+  }
+  const dogleg_amd_batch_model_t& m = c->model;
+  const CameraArgs C{m.kind, (int)m.width, (int)m.height, m.t_per_problem ? 1 : 0, c->dtype, (int)c->sensor_width, (int)c->sensor_height,
+                     c->raw, c->offset, c->gain_inv, c->readvar, c->origin, m.t, m.scale};
+  const size_t rows = (size_t)B*m.Nmeas;
+  hipLaunchKernelGGL(k_camera_rows<FISHER>, dim3((unsigned int)((rows + 255)/256)), dim3(256), 0, (hipStream_t)hip_stream, (int)B,
+                     (int)m.Nmeas, dogleg_batch_model_nstate(m.kind), C, live_dev, p_dev, x_dev, J_dev);
+}
+
 } // namespace
 
 extern "C" {
@@ -105,6 +173,19 @@ void dogleg_amd_batch_model_fisher_callback(const double* p_dev, double* x_dev, 
   const size_t rows = (size_t)B*m->Nmeas;
   hipLaunchKernelGGL(k_model_rows_poisson, dim3((unsigned int)((rows + 255)/256)), dim3(256), 0, (hipStream_t)hip_stream, (int)B,
                      (int)m->Nmeas, N, m->kind, (int)m->width, m->t_per_problem ? 1 : 0, m->y, m->t, live_dev, p_dev, x_dev, J_dev);
+}
+
+// the two callbacks of a camera record (dogleg.h, item 5 of the built-in models): a dogleg_callback_device_batch_t each, one launch.
+// The second writes rows whose J~ is not the derivative of their x~: the solve entry points refuse it as they refuse the one above
+void dogleg_amd_batch_camera_callback(const double* p_dev, double* x_dev, double* J_dev, const unsigned char* live_dev,
+                                      unsigned int B, void* hip_stream, void* cookie)
+{
+  camera_rows<false>(__func__, p_dev, x_dev, J_dev, live_dev, B, hip_stream, cookie);
+}
+void dogleg_amd_batch_camera_fisher_callback(const double* p_dev, double* x_dev, double* J_dev, const unsigned char* live_dev,
+                                             unsigned int B, void* hip_stream, void* cookie)
+{
+  camera_rows<true>(__func__, p_dev, x_dev, J_dev, live_dev, B, hip_stream, cookie);
 }
 
 } // extern "C"

@@ -28,6 +28,9 @@ struct DlgBatchSolve
   // the likelihood of a model form (DOGLEG_AMD_LIKELIHOOD_*, checked; GAUSS: least squares, the model form as it was) and whether
   // the call came in by dogleg_amd_optimize_dense_batch_model_mle[_device] (its name in the messages)
   int likelihood; bool mle;
+  // a model form whose data are those of a camera record (dogleg_amd_optimize_dense_batch_camera[_device]): the (checked) record,
+  // model = &camera->model, whose y is NULL.  NULL otherwise.  The same in the two records below
+  const dogleg_amd_batch_camera_t* camera;
 };
 int  dlg_dense_batch_solve(const DlgBatchSolve& a);
 // the fit of the ..._fit entry points (dogleg_amd_batch_fit_t, checked by the caller), the last three members of the two records
@@ -47,6 +50,7 @@ struct DlgBatchUnc
   bool device;
   const dogleg_amd_batch_loss_t* loss; const double* weights; const unsigned char* held;
   const dogleg_amd_batch_model_t* model; int likelihood;
+  const dogleg_amd_batch_camera_t* camera;
 };
 int  dlg_dense_batch_uncertainty(const DlgBatchUnc& a);
 // dogleg_amd_dense[_products]_batch_query_covariance[_fit][_device]; the products form has no Nobservations (< 0: the plain form)
@@ -59,6 +63,7 @@ struct DlgBatchQuery
   bool device;
   const dogleg_amd_batch_loss_t* loss; const double* weights; const unsigned char* held;
   const dogleg_amd_batch_model_t* model; int likelihood;
+  const dogleg_amd_batch_camera_t* camera;
 };
 int  dlg_dense_batch_query(const DlgBatchQuery& a);
 #pragma GCC visibility pop
@@ -66,6 +71,10 @@ int  dlg_dense_batch_query(const DlgBatchQuery& a);
 // the span, managed memory or registered / page-locked host memory.  Exported: the one place both pointer checks are made,
 // so that they can be tested without a launch on a bad pointer
 extern "C" int dlg_batch_device_span_ok(const void* ptr, size_t bytes);
+// whether a camera record (dogleg.h: dogleg_amd_batch_camera_t) is one the camera calls take with this likelihood, from its members
+// alone; a message under `who` where it is not.  The one statement of these rules (api_extensions.cpp), for the entry points and
+// for the two camera callbacks (batch_models.hip)
+bool dlg_batch_camera_ok(const char* who, const dogleg_amd_batch_camera_t* camera, int likelihood);
 // the last uncertainty or query call
 int  dlg_dense_batch_uncertainty_last_stats(double* out, int n);
 // the device buffers, the stream, the page-locked counter and staging kept between calls (dogleg_amd_release_cache)

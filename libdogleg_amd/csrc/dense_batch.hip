@@ -145,6 +145,7 @@ struct BatchForm
   dogleg_callback_device_batch_products_t* fP;
   bool unpacked;               // products: JtJ as N x N
   const dogleg_amd_batch_model_t* model;
+  const dogleg_amd_batch_camera_t* camera;     // the model form on a camera record's data (model: its model), or nullptr
   bool products() const { return fP != nullptr; }
   unsigned int S(unsigned int N) const { return unpacked ? N*N : N*(N + 1)/2; }
 };
@@ -238,6 +239,20 @@ struct BatchTimer
   }
 };
 
+// the kernels' records of a call's (checked) model and of the camera record it may lie in; empty without a model.  A camera
+// record of doubles without calibration is the model form itself: its raw is the model's y
+void model_records(const dogleg_amd_batch_model_t* m, const dogleg_amd_batch_camera_t* cam, int likelihood, ModelDev& Md, CameraDev& Cd)
+{
+  Md = ModelDev{0, 0, 0, 0, nullptr, nullptr, nullptr};
+  Cd = CameraDev{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
+  if(!m) return;
+  Md = ModelDev{m->kind, (int)m->width, m->t_per_problem ? 1 : 0, likelihood, m->y, m->t, m->scale};
+  if(!cam) return;
+  if(!cam->offset && cam->dtype == DOGLEG_AMD_DATA_F64) { Md.y = (const double*)cam->raw; return; }
+  Cd = CameraDev{cam->raw, cam->offset, cam->gain_inv, cam->readvar, cam->origin, cam->dtype, (int)cam->sensor_width,
+                 (int)(cam->sensor_width - m->width), (int)(cam->sensor_height - m->height), cam->offset ? 1 : 0};
+}
+
 // ---- the solve ----
 const char* solve_who(const DlgBatchSolve& a)
 {
@@ -247,6 +262,7 @@ const char* solve_who(const DlgBatchSolve& a)
     {"dogleg_amd_optimize_dense_batch_bounded", "dogleg_amd_optimize_dense_batch_bounded_device"},
     {"dogleg_amd_optimize_dense_batch_robust", "dogleg_amd_optimize_dense_batch_robust_device"},
     {"dogleg_amd_optimize_dense_batch", "dogleg_amd_optimize_dense_batch_device"}};
+  if(a.camera) return a.device ? "dogleg_amd_optimize_dense_batch_camera_device" : "dogleg_amd_optimize_dense_batch_camera";
   if(a.model && a.mle) return a.device ? "dogleg_amd_optimize_dense_batch_model_mle_device" : "dogleg_amd_optimize_dense_batch_model_mle";
   if(a.model) return a.device ? "dogleg_amd_optimize_dense_batch_model_device" : "dogleg_amd_optimize_dense_batch_model";
   return names[a.fP ? (a.bounds ? 0 : 1) : a.bounds ? 2 : a.loss ? 3 : 4][a.device ? 1 : 0];
@@ -285,9 +301,7 @@ int batch_setup(const char* who, const DlgBatchSolve& a, const BatchForm& F, Bat
   A.wts = loss ? (double*)(q + o_wts) : nullptr; A.NF = (int)NF; A.robust = loss ? 1 : 0;
   A.lo = room_lo ? (const double*)(q + o_lo) : nullptr; A.hi = room_hi ? (const double*)(q + o_hi) : nullptr;
   A.held = nullptr; A.bounded = 0;
-  A.Mdl = ModelDev{0, 0, 0, 0, nullptr, nullptr, nullptr};
-  if(a.model) A.Mdl = ModelDev{a.model->kind, (int)a.model->width, a.model->t_per_problem ? 1 : 0, a.likelihood, a.model->y, a.model->t,
-                               a.model->scale};
+  model_records(a.model, a.camera, a.likelihood, A.Mdl, A.Cam);
   A.L.kind = loss ? loss->kind : DOGLEG_AMD_LOSS_TRIVIAL; A.L.fs = (int)fs;
   A.L.a = loss && loss->kind != DOGLEG_AMD_LOSS_TRIVIAL ? loss->scale : 1.0; A.L.c = A.L.a*A.L.a;
   A.max_iterations = prm->max_iterations; A.trustregion0 = prm->trustregion0;
@@ -340,7 +354,7 @@ int batch_rounds(const char* who, const BatchForm& F, const BatchDev& A, void* c
 // Everything on the caller's stream if one is given.
 int solve_locked(const DlgBatchSolve& a)
 {
-  const BatchForm F{a.fJ, a.fP, a.unpacked, a.model};
+  const BatchForm F{a.fJ, a.fP, a.unpacked, a.model, a.camera};
   const char* who = solve_who(a);
   const unsigned int B = a.B, N = a.N;
   const dogleg_amd_batch_bounds_t* bounds = a.bounds;
@@ -422,7 +436,7 @@ struct EvalCall
 template <class Req> EvalCall eval_call(const char* who, const Req& a)
 {
   EvalCall c{};
-  c.who = who; c.F = BatchForm{a.fJ, a.fP, a.unpacked, a.model}; c.likelihood = a.likelihood; c.B = a.B; c.N = a.N; c.M = a.M; c.cookie = a.cookie;
+  c.who = who; c.F = BatchForm{a.fJ, a.fP, a.unpacked, a.model, a.camera}; c.likelihood = a.likelihood; c.B = a.B; c.N = a.N; c.M = a.M; c.cookie = a.cookie;
   c.p = a.p; c.lambda = a.lambda; c.status = a.status; c.active = a.active; c.stream = a.stream; c.device = a.device;
   c.loss = a.loss; c.weights = a.weights; c.held = a.held;
   return c;
@@ -462,9 +476,9 @@ FitDev fit_dev(const EvalCall& c, char* d)
 // the kernels' argument of a call's model and its points (d_p: p in device memory), empty without a model
 ModelEvalDev model_dev(const EvalCall& c, const double* d_p)
 {
-  ModelEvalDev E{ModelDev{0, 0, 0, 0, nullptr, nullptr, nullptr}, nullptr};
-  if(const dogleg_amd_batch_model_t* m = c.F.model)
-    E = ModelEvalDev{ModelDev{m->kind, (int)m->width, m->t_per_problem ? 1 : 0, c.likelihood, m->y, m->t, m->scale}, d_p};
+  ModelEvalDev E{};
+  model_records(c.F.model, c.F.camera, c.likelihood, E.Mdl, E.Cam);
+  E.p = c.F.model ? d_p : nullptr;
   return E;
 }
 // U: the kernel's argument (of a query: its front half), its shape filled in.  bind(d): the kind's own pointers into the
@@ -543,7 +557,9 @@ int unc_locked(const DlgBatchUnc& a)
     {{"dogleg_amd_dense_batch_uncertainty_fit", "dogleg_amd_dense_batch_uncertainty_fit_device"},
      {"dogleg_amd_dense_products_batch_uncertainty_fit", "dogleg_amd_dense_products_batch_uncertainty_fit_device"}}};
   static const char* const model_names[2] = {"dogleg_amd_dense_batch_model_uncertainty", "dogleg_amd_dense_batch_model_uncertainty_device"};
-  EvalCall c = eval_call(a.model ? model_names[a.device ? 1 : 0] : names[a.loss || a.weights || a.held ? 1 : 0][a.fP ? 1 : 0][a.device ? 1 : 0], a);
+  static const char* const camera_names[2] = {"dogleg_amd_dense_batch_camera_uncertainty", "dogleg_amd_dense_batch_camera_uncertainty_device"};
+  EvalCall c = eval_call(a.camera ? camera_names[a.device ? 1 : 0] : a.model ? model_names[a.device ? 1 : 0] :
+                         names[a.loss || a.weights || a.held ? 1 : 0][a.fP ? 1 : 0][a.device ? 1 : 0], a);
   const unsigned int B = a.B, N = a.N, NF = a.M/(unsigned int)a.fs;
   const size_t vec_bytes = sizeof(double)*(size_t)B*N, fac_bytes = sizeof(double)*(size_t)B*NF;
   c.stage.add(vec_bytes);
@@ -580,7 +596,10 @@ int query_locked(const DlgBatchQuery& a)
      {"dogleg_amd_dense_products_batch_query_covariance_fit", "dogleg_amd_dense_products_batch_query_covariance_fit_device"}}};
   static const char* const model_names[2] = {"dogleg_amd_dense_batch_model_query_covariance",
                                              "dogleg_amd_dense_batch_model_query_covariance_device"};
-  EvalCall c = eval_call(a.model ? model_names[a.device ? 1 : 0] : names[a.loss || a.weights || a.held ? 1 : 0][a.fP ? 1 : 0][a.device ? 1 : 0], a);
+  static const char* const camera_names[2] = {"dogleg_amd_dense_batch_camera_query_covariance",
+                                              "dogleg_amd_dense_batch_camera_query_covariance_device"};
+  EvalCall c = eval_call(a.camera ? camera_names[a.device ? 1 : 0] : a.model ? model_names[a.device ? 1 : 0] :
+                         names[a.loss || a.weights || a.held ? 1 : 0][a.fP ? 1 : 0][a.device ? 1 : 0], a);
   const unsigned int B = a.B, N = a.N;
   const size_t rows = (size_t)B*a.Nq*a.Qrows, Jq_bytes = sizeof(double)*rows*N, out_bytes = sizeof(double)*rows*a.Qrows;
   c.stage.add(sizeof(double)*(size_t)B*N);

@@ -30,6 +30,18 @@ struct ModelDev
   const double *y, *t, *scale;
 };
 
+// the data source of a camera record (dogleg.h: dogleg_amd_batch_camera_t) beside the ModelDev of its model, whose y is nullptr
+// then: raw [B][M] readings of dtype (DOGLEG_AMD_DATA_*).  cal != 0: offset, gain_inv, readvar (or nullptr: 0) maps of sw floats a
+// row, origin [B][2] ints, and the largest origin at which the window lies on the sensor: xmax = sw - width, ymax = sh - height,
+// both >= 0.  raw == nullptr: no camera.  A record of its own behind ModelDev (BatchDev) and behind the points (ModelEvalDev), so
+// that every member the other forms read lies where it did.  A camera record of doubles without calibration is no camera here: its
+// raw is the model's y
+struct CameraDev
+{
+  const void* raw; const float *offset, *gain_inv, *readvar; const int* origin;
+  int dtype, sw, xmax, ymax, cal;
+};
+
 struct BatchDev
 {
   int B, N, M, NP;
@@ -46,6 +58,7 @@ struct BatchDev
   const double *lo, *hi; unsigned char* held;
   int bounded;                 // (host side: which kernel is launched)
   ModelDev Mdl;                // FORM_MODEL (x, J, P unused there), behind everything above
+  CameraDev Cam;               // the camera forms, behind everything above
 };
 
 struct UncDev
@@ -73,6 +86,7 @@ struct FitDev
 struct ModelEvalDev
 {
   ModelDev Mdl; const double* p;
+  CameraDev Cam;
 };
 
 struct QueryDev

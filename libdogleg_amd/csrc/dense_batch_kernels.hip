@@ -46,6 +46,13 @@
 // dogleg_amd_batch_model_fisher_callback (ROWS_FISHER of sweep_model: NaN in an infeasible row, the squares of x~ summed).  Every
 // output has the bits of the J form's call behind the respective callback; no x, no J in memory.
 //
+// The camera forms (dogleg_amd_optimize_dense_batch_camera, dogleg_amd_dense_batch_camera_uncertainty, _query_covariance): the model
+// and the Poisson form with the data of a camera record (dogleg.h: dogleg_amd_batch_camera_t) -- readings of uint16, float or
+// double, as they are (FORM_MODEL_RAW, FORM_POISSON_RAW) or calibrated by sensor-sized maps at the window's origin (FORM_MODEL_CAL,
+// FORM_POISSON_CAL; FORM_POISSON_CALV with the read-noise variance v: the Poisson fit of y + v against f + v).  The lane that forms
+// a row loads its own reading and gathers its pixel's map values (CamSrc, CamLane above sweep_model); everything behind the sweep
+// is the model forms' text, and FORM_MODEL and FORM_POISSON themselves are compiled as they were.
+//
 // The device-resident twins (dogleg_amd_*_batch_device): the same rounds and the same launch of k_batch_uncertainty with every
 // array of the caller in device memory.  The solve takes its initial p by a copy within the device and ends in k_batch_finish,
 // which writes p, the result structs and lambda where the caller has them; the uncertainty kernel's per-output pointers point
@@ -78,7 +85,19 @@ constexpr double LAMBDA_INITIAL = 1e-10;       // dogleg.c:138
 
 enum { F_CAUCHY = 1, F_GN = 2, F_EDGE = 4, F_STARTED = 8 };
 
-enum { FORM_J = 0, FORM_PRODUCTS = 1, FORM_MODEL = 2, FORM_POISSON = 3 };
+// (the camera forms: the model and the Poisson form with another source of the data, see the head of this file)
+enum { FORM_J = 0, FORM_PRODUCTS = 1, FORM_MODEL = 2, FORM_POISSON = 3, FORM_MODEL_RAW = 4, FORM_POISSON_RAW = 5, FORM_MODEL_CAL = 6,
+       FORM_POISSON_CAL = 7, FORM_POISSON_CALV = 8 };
+// where the rows' data come from: the model record's y; a camera record's raw readings as they are; those calibrated by the offset
+// and gain maps; and with the read-noise map beside them (the Poisson form alone reads it: least squares has no use for v)
+enum { SRC_F64 = 0, SRC_RAW = 1, SRC_CAL = 2, SRC_CALV = 3 };
+constexpr bool form_gauss(int F)   { return F == FORM_MODEL || F == FORM_MODEL_RAW || F == FORM_MODEL_CAL; }
+constexpr bool form_poisson(int F) { return F == FORM_POISSON || F == FORM_POISSON_RAW || F == FORM_POISSON_CAL || F == FORM_POISSON_CALV; }
+constexpr bool form_rows(int F)    { return form_gauss(F) || form_poisson(F); }      // rows formed in the lanes
+constexpr int  form_src(int F)     { return F == FORM_MODEL_RAW || F == FORM_POISSON_RAW ? SRC_RAW :
+                                            F == FORM_MODEL_CAL || F == FORM_POISSON_CAL ? SRC_CAL :
+                                            F == FORM_POISSON_CALV ? SRC_CALV : SRC_F64; }
+constexpr bool src_cal(int S)      { return S == SRC_CAL || S == SRC_CALV; }
 
 template <int NMAX> struct BatchCfg
 {
@@ -445,6 +464,77 @@ __device__ __forceinline__ double load_products(const ProductsDev& P, int b, int
   return n2x;
 }
 
+// the data source of the camera forms (dense_batch_dev.h: CameraDev; dogleg.h: dogleg_amd_batch_camera_t).
+// CamLane: what a lane holds of one row while its loads are in flight: the reading's bits as loaded (a uint16 zero-extended, a
+// float's or a double's bits) and, with calibration, the two or three map values of its sensor pixel.  SRC_CALV: a read-noise map
+// is given and read; it is an instantiation of its own because the test for a null map, kept live across the sweep, cost the
+// bounded Poisson kernel the scalar registers it had left.
+// CamSrc: made ONCE a problem -- the problem's readings and, with calibration, the window's origin and the index of its first sensor
+// pixel, or -1 where the window does not lie on the sensor as a whole; such a window reads nothing (its origin apart) and every
+// datum of it is NaN.  That test is all that keeps the gather inside the maps: ox >= 0, oy >= 0, ox <= xmax = sw - width and
+// oy <= ymax = sh - height, both >= 0 (formed and checked on the host), so no sum overflows and (oy + iy) sw + ox + ix < sw sh for
+// every pixel of the window.
+// The type of the readings is a switch that is uniform over the launch, around one load and one conversion: a template parameter
+// would triple the instantiations for one instruction each
+template <int SRC> struct CamLane { unsigned long long bits; };
+template <> struct CamLane<SRC_F64> {};
+template <> struct CamLane<SRC_CAL> { unsigned long long bits; float off, gi; };
+template <> struct CamLane<SRC_CALV> { unsigned long long bits; float off, gi, rv; };
+template <int SRC> struct CamSrc
+{
+  const char* rb; int dtype;
+  const float *off, *gi, *rv; int width, sw, first;
+  // (b is the same in every lane of the wave, which the compiler cannot see: what follows from it is made scalar by hand)
+  __device__ __forceinline__ CamSrc(const CameraDev& Cm, int b, int Ms, int w)
+  {
+    const int bu = __builtin_amdgcn_readfirstlane(b);
+    dtype = Cm.dtype;
+    rb = (const char*)Cm.raw + (size_t)b*Ms*(dtype == DOGLEG_AMD_DATA_U16 ? 2 : dtype == DOGLEG_AMD_DATA_F32 ? 4 : 8);
+    off = gi = rv = nullptr; width = w; sw = 0; first = 0;
+    if constexpr(src_cal(SRC))
+    {
+      const int ox = __builtin_amdgcn_readfirstlane(Cm.origin[2*(size_t)bu]), oy = __builtin_amdgcn_readfirstlane(Cm.origin[2*(size_t)bu + 1]);
+      off = Cm.offset; gi = Cm.gain_inv; rv = Cm.readvar; sw = Cm.sw;
+      // the first sensor pixel of the window (the host has checked that sw sh fits an int), -1: the window leaves the sensor
+      first = ox >= 0 && oy >= 0 && ox <= Cm.xmax && oy <= Cm.ymax ? oy*Cm.sw + ox : -1;
+    }
+  }
+  __device__ __forceinline__ bool inside() const { return first >= 0; }
+  // the loads of row i
+  __device__ __forceinline__ void load(int i, CamLane<SRC>& r) const
+  {
+    if constexpr(src_cal(SRC))
+    {
+      if(!inside()) return;
+      const int iy = i/width, ix = i - iy*width;
+      const int px = first + iy*sw + ix;
+      r.off = off[px]; r.gi = gi[px];
+      if constexpr(SRC == SRC_CALV) r.rv = rv[px];
+    }
+    if(dtype == DOGLEG_AMD_DATA_U16)      r.bits = ((const unsigned short*)rb)[i];
+    else if(dtype == DOGLEG_AMD_DATA_F32) r.bits = ((const unsigned int*)rb)[i];
+    else                                  r.bits = ((const unsigned long long*)rb)[i];
+  }
+  // y and v of what was loaded
+  __device__ __forceinline__ void datum(const CamLane<SRC>& r, double& y, double& v) const
+  {
+    const double raw = dtype == DOGLEG_AMD_DATA_U16 ? (double)(unsigned int)r.bits :
+                       dtype == DOGLEG_AMD_DATA_F32 ? (double)__uint_as_float((unsigned int)r.bits) : __longlong_as_double((long long)r.bits);
+    if constexpr(src_cal(SRC))
+    {
+      float rvv = 0.0f;
+      if constexpr(SRC == SRC_CALV) rvv = r.rv;
+      if(inside()) dogleg_batch_camera_datum(raw, r.off, r.gi, rvv, &y, &v);
+      else { y = __builtin_nan(""); v = 0.0; }
+    }
+    else { y = raw; v = 0.0; }
+  }
+};
+template <> struct CamSrc<SRC_F64>
+{
+  __device__ __forceinline__ CamSrc(const CameraDev&, int, int, int) {}
+};
+
 // the front end of the model form (dogleg_amd_optimize_dense_batch_model): sweep_point<NMAX, SWEEP_PLAIN> over an x and a J that
 // never lie in memory.  Lane t of the wave forms row r0 + t of the tile from p (pb: N doubles, the same in every lane), its datum,
 // abscissa and scale through dogleg_batch_model_row -- the function the adapter callback writes x and J with, its contraction
@@ -457,12 +547,27 @@ __device__ __forceinline__ double load_products(const ProductsDev& P, int b, int
 // kernels, which stand in for that callback and a J-form launch: an infeasible row is staged as the header function returns it (NaN,
 // so the problem fails the finiteness test alone), and the sum is that of the squares of the staged x~, not the deviance.
 // M rows are swept (the query kernel's G: the first Nobservations); the problem's data lie Ms apart
-enum { ROWS_GAUSS = 0, ROWS_POISSON = 1, ROWS_FISHER = 2 };
-template <int NMAX, int MODE = ROWS_GAUSS>
-__device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* pb, int b, int N, int M, int Ms, int NP, int lane,
-                                              double* SA, double* tile, double& gacc_out)
+// ROWS_POISSON_V, ROWS_FISHER_V: the two with the read-noise variance of a calibrated camera record
+// (dogleg_batch_model_row_poisson_v).
+// SRC: where the data come from.  SRC_F64: Md.y, the text as it was.  SRC_RAW, SRC_CAL: a camera record (CamSrc above): the lane
+// loads its own reading, 2, 4 or 8 bytes, and with calibration gathers its sensor pixel's three map values; what was loaded stays
+// as it came (CamLane) while the loads are in flight under the row loop and becomes y and v at the head of the next tile
+enum { ROWS_GAUSS = 0, ROWS_POISSON = 1, ROWS_FISHER = 2, ROWS_POISSON_V = 3, ROWS_FISHER_V = 4 };
+constexpr int rows_solve(int F) { return form_poisson(F) ? (src_cal(form_src(F)) ? ROWS_POISSON_V : ROWS_POISSON) : ROWS_GAUSS; }
+constexpr int rows_eval(int F)  { return form_poisson(F) ? (src_cal(form_src(F)) ? ROWS_FISHER_V : ROWS_FISHER) : ROWS_GAUSS; }
+// a Poisson row of either kind
+template <int MODE>
+__device__ __forceinline__ int poisson_row(int kind, const double* p, int i, int width, double t, double y, double v, double* x,
+                                           double* J, double* d)
 {
-  constexpr bool POISSON = MODE == ROWS_POISSON;
+  if constexpr(MODE == ROWS_POISSON_V || MODE == ROWS_FISHER_V) return dogleg_batch_model_row_poisson_v(kind, p, i, width, t, y, v, x, J, d);
+  else return dogleg_batch_model_row_poisson(kind, p, i, width, t, y, x, J, d);
+}
+template <int NMAX, int MODE = ROWS_GAUSS, int SRC = SRC_F64>
+__device__ __forceinline__ double sweep_model(const ModelDev& Md, const CameraDev& Cm, const double* pb, int b, int N, int M, int Ms,
+                                              int NP, int lane, double* SA, double* tile, double& gacc_out)
+{
+  constexpr bool POISSON = MODE == ROWS_POISSON || MODE == ROWS_POISSON_V;
   using C = BatchCfg<NMAX>;
   constexpr int NM = DOGLEG_BATCH_MODEL_MAX_NSTATE;
   static_assert(NM <= NMAX, "every built-in model lies in the smallest size class");
@@ -476,14 +581,17 @@ __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* 
   double p[NM];
 #pragma unroll
   for(int j = 0; j < NM; j++) p[j] = j < N ? pb[j] : 0.0;
-  const double* yb = Md.y + (size_t)b*Ms;
+  const double* yb = SRC == SRC_F64 ? Md.y + (size_t)b*Ms : nullptr;
   const double* tb = Md.t ? Md.t + (Md.t_each ? (size_t)b*Ms : (size_t)0) : nullptr;
   const double* sb = Md.scale ? Md.scale + (size_t)b*Ms : nullptr;
   double yv = 0.0, tv = 0.0, sv = 1.0;
+  [[maybe_unused]] double vv = 0.0;      // the read-noise variance of the row (SRC_CAL)
+  const CamSrc<SRC> cs(Cm, b, Ms, Md.width);
+  CamLane<SRC> cl{};
   bool infeasible = false;     // POISSON: a row of this lane had !(f > 0)
   if(lane < min(T, M))
   {
-    yv = yb[lane];
+    if constexpr(SRC == SRC_F64) yv = yb[lane]; else cs.load(lane, cl);
     tv = tb ? tb[lane] : (double)lane;
     if(sb) sv = sb[lane];
   }
@@ -494,9 +602,10 @@ __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* 
 #pragma unroll
     for(int j = 0; j < NM; j++) jr[j] = 0.0;
     double dv = 0.0;           // POISSON: the row's share of the deviance
+    if constexpr(SRC != SRC_F64) cs.datum(cl, yv, vv);
     if constexpr(POISSON)
     {
-      if(lane < tc && !dogleg_batch_model_row_poisson(Md.kind, p, r0 + lane, Md.width, tv, yv, &xv, jr, &dv))
+      if(lane < tc && !poisson_row<MODE>(Md.kind, p, r0 + lane, Md.width, tv, yv, vv, &xv, jr, &dv))
       {
         infeasible = true;
         xv = 0.0; dv = 0.0;
@@ -504,9 +613,9 @@ __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* 
         for(int j = 0; j < NM; j++) jr[j] = 0.0;
       }
     }
-    else if constexpr(MODE == ROWS_FISHER)
+    else if constexpr(MODE == ROWS_FISHER || MODE == ROWS_FISHER_V)
     {
-      if(lane < tc) (void)dogleg_batch_model_row_poisson(Md.kind, p, r0 + lane, Md.width, tv, yv, &xv, jr, &dv);
+      if(lane < tc) (void)poisson_row<MODE>(Md.kind, p, r0 + lane, Md.width, tv, yv, vv, &xv, jr, &dv);
     }
     else if(lane < tc) dogleg_batch_model_row(Md.kind, p, r0 + lane, Md.width, tv, yv, sv, &xv, jr);
     wsync();
@@ -523,7 +632,7 @@ __device__ __forceinline__ double sweep_model(const ModelDev& Md, const double* 
       const int r1 = r0 + T, tn = min(T, M - r1);
       if(lane < tn)
       {
-        yv = yb[r1 + lane];
+        if constexpr(SRC == SRC_F64) yv = yb[r1 + lane]; else cs.load(r1 + lane, cl);
         tv = tb ? tb[r1 + lane] : (double)(r1 + lane);
         if(sb) sv = sb[r1 + lane];
       }
@@ -570,20 +679,20 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
   }
-  else if constexpr(FORM == FORM_MODEL)
+  else if constexpr(form_gauss(FORM))
   {
     // ---- the same sweep over rows formed on the way into the tile: no x, no J in memory ----
     static_assert(!ROBUST, "the model form has no loss");
-    n2x = sweep_model<NMAX>(A.Mdl, A.p_trial + bN, b, N, M, M, NP, lane, SA, SL, gacc);
+    n2x = sweep_model<NMAX, ROWS_GAUSS, form_src(FORM)>(A.Mdl, A.Cam, A.p_trial + bN, b, N, M, M, NP, lane, SA, SL, gacc);
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     finite = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
   }
-  else if constexpr(FORM == FORM_POISSON)
+  else if constexpr(form_poisson(FORM))
   {
     // ---- the model form's sweep over the Poisson rows; n2x is the deviance, +infinity at an infeasible point: no start point,
     // but a trial point like any other that is worse than the point it was stepped from ----
     static_assert(!ROBUST, "the Poisson form has no loss");
-    n2x = sweep_model<NMAX, ROWS_POISSON>(A.Mdl, A.p_trial + bN, b, N, M, M, NP, lane, SA, SL, gacc);
+    n2x = sweep_model<NMAX, rows_solve(FORM), form_src(FORM)>(A.Mdl, A.Cam, A.p_trial + bN, b, N, M, M, NP, lane, SA, SL, gacc);
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     const bool started = (A.st[(size_t)ST_COUNT*b + ST_FLAGS] & F_STARTED) != 0;
     finite = __all((isfinite(n2x) || (started && n2x == INFINITY)) && isfinite(gacc) && isfinite(dg));
@@ -819,7 +928,7 @@ __device__ bool batch_problem(const BatchDev& A, int b, int lane, double* S)
 // (the Poisson form asks for the model form's 4 waves a SIMD: left alone it takes 130 VGPRs, two more than 4 waves allow; held to
 // 128 it takes 126 and no scratch.  1 is the default: the other instantiations are compiled as they were)
 template <int NMAX, int FORM, bool ROBUST, bool BOUNDED>
-__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) __attribute__((amdgpu_waves_per_eu(FORM == FORM_POISSON ? 4 : 1)))
+__global__ void __launch_bounds__(64*BatchCfg<NMAX>::WPB) __attribute__((amdgpu_waves_per_eu(form_poisson(FORM) ? 4 : 1)))
 k_batch_round(BatchDev A)
 {
   constexpr int LDSW = FormCfg<NMAX, FORM>::LDSW, WPB = BatchCfg<NMAX>::WPB;
@@ -928,9 +1037,9 @@ __device__ __forceinline__ bool factor_and_invert(const UncDev& A, const FitDev&
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     ok = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
   }
-  else if constexpr(FORM == FORM_MODEL || FORM == FORM_POISSON)
+  else if constexpr(form_rows(FORM))
   {
-    n2x = sweep_model<NMAX, FORM == FORM_POISSON ? ROWS_FISHER : ROWS_GAUSS>(E.Mdl, E.p + (size_t)b*N, b, N, M, M, NP, lane, SA, SL, gacc);
+    n2x = sweep_model<NMAX, rows_eval(FORM), form_src(FORM)>(E.Mdl, E.Cam, E.p + (size_t)b*N, b, N, M, M, NP, lane, SA, SL, gacc);
     const double dg = lane < N ? SA[col_off(lane, N)] : 0.0;
     ok = __all(isfinite(n2x) && isfinite(gacc) && isfinite(dg));
   }
@@ -1081,7 +1190,7 @@ __device__ void unc_problem(const UncDev& A, const FitDev& F, const ModelEvalDev
       const int i = e/N;
       A.cov[(size_t)b*N*N + e] = sym_at(SA, i, e - i*N, N);
     }
-  if constexpr(FORM == FORM_MODEL || FORM == FORM_POISSON)
+  if constexpr(form_rows(FORM))
   {
     // ---- the second sweep of the model forms: the J form's tiles (T rows at the stride N | 1, lane t takes feature t), the rows
     // formed where the J form copies them.  Lane t evaluates row r0 + t, as in sweep_model, and stores it at t (N | 1); its x stays
@@ -1098,13 +1207,17 @@ __device__ void unc_problem(const UncDev& A, const FitDev& F, const ModelEvalDev
     double p[NM];
 #pragma unroll
     for(int j = 0; j < NM; j++) p[j] = j < N ? E.p[(size_t)b*N + j] : 0.0;
-    const double* yb = Md.y + (size_t)b*M;
+    constexpr int SRC = form_src(FORM);
+    const double* yb = SRC == SRC_F64 ? Md.y + (size_t)b*M : nullptr;
     const double* tb = Md.t ? Md.t + (Md.t_each ? (size_t)b*M : (size_t)0) : nullptr;
     const double* sb = Md.scale ? Md.scale + (size_t)b*M : nullptr;
     double yv = 0.0, tv = 0.0, sv = 1.0;
+    [[maybe_unused]] double vv = 0.0;
+    const CamSrc<SRC> cs(E.Cam, b, M, Md.width);
+    CamLane<SRC> cl{};
     if(lane < min(T, Mc))
     {
-      yv = yb[lane];
+      if constexpr(SRC == SRC_F64) yv = yb[lane]; else cs.load(lane, cl);
       tv = tb ? tb[lane] : (double)lane;
       if(sb) sv = sb[lane];
     }
@@ -1114,12 +1227,13 @@ __device__ void unc_problem(const UncDev& A, const FitDev& F, const ModelEvalDev
       double xv = 0.0, jr[NM];
 #pragma unroll
       for(int j = 0; j < NM; j++) jr[j] = 0.0;
+      if constexpr(SRC != SRC_F64) cs.datum(cl, yv, vv);
       if(lane < tc)
       {
-        if constexpr(FORM == FORM_POISSON)
+        if constexpr(form_poisson(FORM))
         {
           double dv;
-          (void)dogleg_batch_model_row_poisson(Md.kind, p, r0 + lane, Md.width, tv, yv, &xv, jr, &dv);
+          (void)poisson_row<rows_eval(FORM)>(Md.kind, p, r0 + lane, Md.width, tv, yv, vv, &xv, jr, &dv);
         }
         else dogleg_batch_model_row(Md.kind, p, r0 + lane, Md.width, tv, yv, sv, &xv, jr);
       }
@@ -1135,7 +1249,7 @@ __device__ void unc_problem(const UncDev& A, const FitDev& F, const ModelEvalDev
         const int r1 = r0 + T, tn = min(T, Mc - r1);
         if(lane < tn)
         {
-          yv = yb[r1 + lane];
+          if constexpr(SRC == SRC_F64) yv = yb[r1 + lane]; else cs.load(r1 + lane, cl);
           tv = tb ? tb[r1 + lane] : (double)(r1 + lane);
           if(sb) sv = sb[r1 + lane];
         }
@@ -1369,14 +1483,13 @@ __device__ void query_problem(const QueryDev& A, const FitDev& F, const ModelEva
         (void)sweep_point<NMAX>(U.J + (size_t)b*U.M*N, U.x + (size_t)b*U.M, N, A.nobs, U.NP, lane, SG, SL, g);
     }
   }
-  else if constexpr(FORM == FORM_MODEL || FORM == FORM_POISSON)
+  else if constexpr(form_rows(FORM))
   {
     sandwich = A.nobs >= 0;
     if(sandwich)
     {
       double g;
-      (void)sweep_model<NMAX, FORM == FORM_POISSON ? ROWS_FISHER : ROWS_GAUSS>(E.Mdl, E.p + (size_t)b*N, b, N, A.nobs, U.M, U.NP, lane,
-                                                                             SG, SL, g);
+      (void)sweep_model<NMAX, rows_eval(FORM), form_src(FORM)>(E.Mdl, E.Cam, E.p + (size_t)b*N, b, N, A.nobs, U.M, U.NP, lane, SG, SL, g);
     }
   }
   unsigned long long hm = 0;
@@ -1574,7 +1687,38 @@ void launch_batch_round(hipStream_t st, const BatchDev& A)
 {
   for_size_class(A.N, [&](auto c) {
     constexpr int NMAX = decltype(c)::value;
-    if(A.Mdl.y)
+    if(A.Cam.raw)
+    {
+      // (a camera record: the model forms with the readings as their data; calibrated or not is the instantiation, the type of
+      // the readings a switch inside it)
+      if constexpr(NMAX == 8)
+      {
+        const bool poisson = A.Mdl.likelihood == DOGLEG_AMD_LIKELIHOOD_POISSON;
+        if(A.Cam.cal)
+        {
+          if(poisson)
+          {
+            if(A.Cam.readvar)
+            {
+              if(A.bounded)  launch_class<NMAX>(k_batch_round<NMAX, FORM_POISSON_CALV, false, true>, st, A.B, A);
+              else           launch_class<NMAX>(k_batch_round<NMAX, FORM_POISSON_CALV, false, false>, st, A.B, A);
+            }
+            else if(A.bounded) launch_class<NMAX>(k_batch_round<NMAX, FORM_POISSON_CAL, false, true>, st, A.B, A);
+            else             launch_class<NMAX>(k_batch_round<NMAX, FORM_POISSON_CAL, false, false>, st, A.B, A);
+          }
+          else if(A.bounded) launch_class<NMAX>(k_batch_round<NMAX, FORM_MODEL_CAL, false, true>, st, A.B, A);
+          else               launch_class<NMAX>(k_batch_round<NMAX, FORM_MODEL_CAL, false, false>, st, A.B, A);
+        }
+        else if(poisson)
+        {
+          if(A.bounded)      launch_class<NMAX>(k_batch_round<NMAX, FORM_POISSON_RAW, false, true>, st, A.B, A);
+          else               launch_class<NMAX>(k_batch_round<NMAX, FORM_POISSON_RAW, false, false>, st, A.B, A);
+        }
+        else if(A.bounded)   launch_class<NMAX>(k_batch_round<NMAX, FORM_MODEL_RAW, false, true>, st, A.B, A);
+        else                 launch_class<NMAX>(k_batch_round<NMAX, FORM_MODEL_RAW, false, false>, st, A.B, A);
+      }
+    }
+    else if(A.Mdl.y)
     {
       // (every built-in model lies in the class of 8: the host side refuses anything else)
       if constexpr(NMAX == 8)
@@ -1608,7 +1752,22 @@ void launch_batch_uncertainty(hipStream_t st, const UncDev& A, const FitDev& F, 
 {
   for_size_class(A.N, [&](auto c) {
     constexpr int NMAX = decltype(c)::value;
-    if(E.Mdl.y)
+    if(E.Cam.raw)
+    {
+      if constexpr(NMAX == 8)
+      {
+        const bool poisson = E.Mdl.likelihood == DOGLEG_AMD_LIKELIHOOD_POISSON;
+        if(E.Cam.cal)
+        {
+          if(poisson && E.Cam.readvar) launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_POISSON_CALV, true>, st, A.B, A, F, E);
+          else if(poisson) launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_POISSON_CAL, true>, st, A.B, A, F, E);
+          else        launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_MODEL_CAL, true>, st, A.B, A, F, E);
+        }
+        else if(poisson) launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_POISSON_RAW, true>, st, A.B, A, F, E);
+        else             launch_class<NMAX>(k_batch_uncertainty<NMAX, FORM_MODEL_RAW, true>, st, A.B, A, F, E);
+      }
+    }
+    else if(E.Mdl.y)
     {
       if constexpr(NMAX == 8)
       {
@@ -1630,7 +1789,22 @@ void launch_batch_query(hipStream_t st, const QueryDev& A, const FitDev& F, cons
 {
   for_size_class(A.U.N, [&](auto c) {
     constexpr int NMAX = decltype(c)::value;
-    if(E.Mdl.y)
+    if(E.Cam.raw)
+    {
+      if constexpr(NMAX == 8)
+      {
+        const bool poisson = E.Mdl.likelihood == DOGLEG_AMD_LIKELIHOOD_POISSON;
+        if(E.Cam.cal)
+        {
+          if(poisson && E.Cam.readvar) launch_class<NMAX>(k_batch_query<NMAX, FORM_POISSON_CALV, true>, st, A.U.B, A, F, E);
+          else if(poisson) launch_class<NMAX>(k_batch_query<NMAX, FORM_POISSON_CAL, true>, st, A.U.B, A, F, E);
+          else        launch_class<NMAX>(k_batch_query<NMAX, FORM_MODEL_CAL, true>, st, A.U.B, A, F, E);
+        }
+        else if(poisson) launch_class<NMAX>(k_batch_query<NMAX, FORM_POISSON_RAW, true>, st, A.U.B, A, F, E);
+        else             launch_class<NMAX>(k_batch_query<NMAX, FORM_MODEL_RAW, true>, st, A.U.B, A, F, E);
+      }
+    }
+    else if(E.Mdl.y)
     {
       if constexpr(NMAX == 8)
       {

@@ -156,6 +156,18 @@ class BatchModel(C.Structure):
                 ("y", C.c_void_p), ("t", C.c_void_p), ("scale", C.c_void_p), ("t_per_problem", C.c_int)]
 
 
+DATA_F64, DATA_F32, DATA_U16 = 0, 1, 2        # dogleg_amd_batch_camera_t.dtype
+DATA_NUMPY = {DATA_F64: "float64", DATA_F32: "float32", DATA_U16: "uint16"}
+
+
+class BatchCamera(C.Structure):
+    """dogleg_amd_batch_camera_t (include/dogleg.h): the model record (y 0) and the camera's data; raw, the three maps and origin
+    are device addresses, each 0 for NULL."""
+    _fields_ = [("model", BatchModel), ("dtype", C.c_int), ("raw", C.c_void_p),
+                ("sensor_width", C.c_uint), ("sensor_height", C.c_uint),
+                ("offset", C.c_void_p), ("gain_inv", C.c_void_p), ("readvar", C.c_void_p), ("origin", C.c_void_p)]
+
+
 class JacobianReport(C.Structure):
     """dogleg_amd_jacobian_report_t (include/dogleg.h)."""
     _fields_ = [
